@@ -9,6 +9,12 @@ independent replicas per rank (weak scaling), RCCL only for the broadcast of the
 the gather of summary statistics -- no data-path collective.
 
 Prints ONE JSON line on rank 0 (see the contract in the task description).
+
+A plain run sets up, relaxes (--equil), warms up, times --steps steps and prints the line: `value`, `ms_per_step`, the farm's
+summary rows and the roofline of the timed launches.  --full adds everything else the line has carried: the steady-state window,
+the rate at the reference's observation cadence, the oracle check of the timed state with the CPU baselines (--no-cpu-baseline
+leaves them out) and the other workloads (--no-extra leaves them out).  --dump-outputs DIR writes what the timed steps left for a
+caller of gd_run (rank 0's replicas) as DIR/<name>.npy, before anything else runs on the handle.
 """
 import argparse
 import importlib
@@ -126,6 +132,35 @@ def check_against_oracle(g, wl, sys_, n_beads, replica):
     return {"replica": replica, "max_rel_force_err": err, "tolerance": FORCE_RTOL, "max_abs_force": scale,
             "what": "forces of one replica of the timed handle after the timed steps vs oracle/liboracle.so (fp64), |dF|max / |F|max",
             "list_path": {0: "none", 1: "generic", 2: "tiled"}[sys_.context(0).list_path], "ok": err <= FORCE_RTOL}
+
+
+DUMP_LIMIT_BYTES = 60 << 20     # all files of --dump-outputs together
+DUMP_SAMPLE_SEED = 20220101
+
+
+def dump_outputs(out_dir, sys_):
+    """--dump-outputs: the state the last timed step left, as a caller of gd_run reads it -- positions of every replica (float32,
+    the device's own precision; a fixed, seeded sample of bead rows when they would not fit DUMP_LIMIT_BYTES, with the sampled row
+    indices of the flattened (R * N, 3) array in positions_index.npy) and each replica's context."""
+    os.makedirs(out_dir, exist_ok=True)
+    ctx = [sys_.context(r) for r in range(sys_.R)]
+    arrays = {
+        "step_time": np.array([[c.step, c.time] for c in ctx], dtype=np.float64),
+        "bead_bond_scale": np.array([[c.bead_scale, c.bond_scale] for c in ctx], dtype=np.float64),
+        "semiaxes": np.array([list(c.semiaxes) for c in ctx], dtype=np.float64),
+        "axial_reaction": np.array([list(c.axial_reaction) for c in ctx], dtype=np.float64),
+    }
+    x = sys_.positions().astype(np.float32).reshape(-1, 3)
+    room = DUMP_LIMIT_BYTES - sum(v.nbytes for v in arrays.values())
+    if x.nbytes > room:
+        rows = room // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(len(x), size=rows, replace=False))
+        arrays["positions_index"] = idx.astype(np.float64)
+        x = x[idx]
+    arrays["positions"] = x if "positions_index" in arrays else x.reshape(sys_.R, sys_.N, 3)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return sorted(arrays)
 
 
 def _kernel_source_sha():
@@ -262,8 +297,11 @@ def main():
     ap.add_argument("--replicas", type=int, default=128, help="replicas batched per GPU (64: -5 %%, 256: -7 %% on one MI355X)")
     ap.add_argument("--equil", type=int, default=20000,
                     help="untimed relaxation steps before warmup (SURVEY 8d cfg3: 20 000 from the random-walk start)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other workloads of the measurement row (config.other_workloads)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: steady-state window, reference-cadence rate, oracle check "
+                    "+ CPU baselines, other workloads (off: a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the state the timed steps left (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle check and the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other workloads of the measurement row (config.other_workloads)")
     ap.add_argument("--save-state", default="", help="write the relaxed positions (after --equil) to this .npy and exit")
     ap.add_argument("--load-state", default="", help="start from relaxed positions saved by --save-state (no relaxation "
                     "launches: used for the committed rocprof summaries, so that kernel averages cover the timed state only)")
@@ -359,35 +397,38 @@ def main():
     farm.barrier()
     el = farm.max_over_ranks(time.perf_counter() - t0, device=tdev)
     rollbacks_timed = sys_.context(0).rollbacks - rb0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, sys_)
 
-    # steady-state rate: a window of at least 40 rebuild intervals (the timed region of a short run holds one build or two by
-    # chance), time-boxed; reported beside `value`, never instead of it
-    K_now = max(int(sys_.context(0).rebuild_interval), 1)
-    n_ss = min(max(40 * K_now, 400), 4000)
-    # (ten intervals untimed first: with --warmup 5 the wall dynamics were switched on 25 steps ago, and the interval adaptation has
-    # not seen a complete interval of this phase yet -- the window below is the STEADY state)
-    sys_.run(10 * K_now, dt, kT, seed=seed, flags=flags)
-    farm.barrier(); torch.cuda.synchronize()
-    t_ss = time.perf_counter()
-    sys_.run(n_ss, dt, kT, seed=seed, flags=flags)
-    torch.cuda.synchronize(); farm.barrier()
-    el_ss = farm.max_over_ranks(time.perf_counter() - t_ss, device=tdev)
+    if a.full:
+        # steady-state rate: a window of at least 40 rebuild intervals (the timed region of a short run holds one build or two by
+        # chance), time-boxed; reported beside `value`, never instead of it
+        K_now = max(int(sys_.context(0).rebuild_interval), 1)
+        n_ss = min(max(40 * K_now, 400), 4000)
+        # (ten intervals untimed first: with --warmup 5 the wall dynamics were switched on 25 steps ago, and the interval adaptation has
+        # not seen a complete interval of this phase yet -- the window below is the STEADY state)
+        sys_.run(10 * K_now, dt, kT, seed=seed, flags=flags)
+        farm.barrier(); torch.cuda.synchronize()
+        t_ss = time.perf_counter()
+        sys_.run(n_ss, dt, kT, seed=seed, flags=flags)
+        torch.cuda.synchronize(); farm.barrier()
+        el_ss = farm.max_over_ranks(time.perf_counter() - t_ss, device=tdev)
 
-    # second figure: the same stepping with the reference's observation cadence -- mean energy every
-    # interphase_logging_interval = 100 steps, a quantised snapshot every interphase_sampling_interval = 1000 steps
-    # (config_entries.inc:81-82); 1000 extra steps, not part of `value`
-    farm.barrier()
-    sys_.positions_f32(quantize=True)      # (a driver takes thousands of snapshots: not the first, cold one)
-    t1 = time.perf_counter()
-    for k in range(10):
-        # as the drivers do it: stop where the reference's callback observes (before its state updates), observe, apply them
-        sys_.run(100, dt, kT, seed=seed, flags=flags | g.RUN_DEFER_CALLBACK)
-        e_obs = sys_.energy()
-        if k == 9:
-            snap = sys_.positions_f32(quantize=True)
-        sys_.apply_callback()
-    obs_rate = N * R * 1000 / (time.perf_counter() - t1)
-    del snap, e_obs
+        # second figure: the same stepping with the reference's observation cadence -- mean energy every
+        # interphase_logging_interval = 100 steps, a quantised snapshot every interphase_sampling_interval = 1000 steps
+        # (config_entries.inc:81-82); 1000 extra steps, not part of `value`
+        farm.barrier()
+        sys_.positions_f32(quantize=True)      # (a driver takes thousands of snapshots: not the first, cold one)
+        t1 = time.perf_counter()
+        for k in range(10):
+            # as the drivers do it: stop where the reference's callback observes (before its state updates), observe, apply them
+            sys_.run(100, dt, kT, seed=seed, flags=flags | g.RUN_DEFER_CALLBACK)
+            e_obs = sys_.energy()
+            if k == 9:
+                snap = sys_.positions_f32(quantize=True)
+            sys_.apply_callback()
+        obs_rate = N * R * 1000 / (time.perf_counter() - t1)
+        del snap, e_obs
 
     ctx = sys_.context(0)
     e_mean = float(sys_.energy().mean() / N)
@@ -433,8 +474,6 @@ def main():
                        "rebuild_interval": int(ctx.rebuild_interval), "list_radius": ctx.list_radius, "list_GB": ctx.list_bytes / 1e9,
                        "row_repairs_last_chunk": int(ctx.row_repairs),
                        "rollbacks": int(ctx.rollbacks), "rollbacks_in_timed_steps": int(rollbacks_timed), "equil_steps": a.equil,
-                       "steady_state_bead_steps_per_s": N * R * world * n_ss / el_ss, "steady_state_steps": n_ss,
-                       "bead_steps_per_s_with_reference_cadence_rank0": obs_rate,
                        "mean_energy_per_bead": [float(v[0]) for v in gathered], "wall_semiaxis": [float(v[1]) for v in gathered]},
             # frac = measured HBM bytes of the dominant kernel / its launch time / 8 TB/s (<= 1 by construction).
             # whole_step_counter_frac: the same counters over the WHOLE step -- k_step's bytes + the list build's bytes (every kernel of
@@ -456,19 +495,22 @@ def main():
         # reference only -- NOT a roofline claim: the tiled kernel does not move those bytes
         out["config"]["survey_pricing_non_credit"] = {"bytes_per_launch": alg_bytes, "k_step_frac": alg_gbs / HBM_PEAK_GBS,
                                                       "whole_step_frac": 204.0 * N * R * a.steps / el / 1e9 / HBM_PEAK_GBS}
+        if a.full:
+            out["config"].update({"steady_state_bead_steps_per_s": N * R * world * n_ss / el_ss, "steady_state_steps": n_ss,
+                                  "bead_steps_per_s_with_reference_cadence_rank0": obs_rate})
         rp = _cached_replay(N, R)
         if rp:
             # what actually bounds k_step: VALU issue.  Its arithmetic alone (operands resident, same grid and LDS class) takes t_alu,
             # its memory pattern alone t_mem; the product kernel overlaps the two almost completely (profiles/README.md)
             out["roofline"]["issue_bound"] = {"t_alu_us": rp["t_alu_us"], "t_mem_us": rp["t_mem_us"], "t_kstep_fresh_list_us": rp["t_kstep_us"],
                                               "overlap": rp["overlap"], "kstep_over_alu_bound": rp["t_alu_us"] / rp["t_kstep_us"], "source": rp["source"]}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["checked"] = check_against_oracle(g, wl, sys_, N, R // 2)
             out["cpu_baseline"], farm_cpu = cpu_baseline(g, wl, sys_.positions()[0], N)
             out["config"]["gpu_over_cpu_1core"] = out["value"] / out["cpu_baseline"]["value"]
             if farm_cpu is not None:
                 out["config"]["cpu_farm_one_replica_per_core"] = farm_cpu      # `cores` = the cores this process may run on (affinity)
-        if not a.no_extra and world == 1:
+        if a.full and not a.no_extra and world == 1:
             sys_.close()
             out["config"]["other_workloads"] = other_workloads(g, wl, hip, dev_index)
         print(json.dumps(out), flush=True)
@@ -479,7 +521,7 @@ def main():
                 sys.stderr.write(f"bench.py: {out['rccl_ranks']} RCCL rank(s) for a world of {world}\n"); status = 5
             if not out["cpu_shares_disjoint"] and not os.environ.get("GDYN_NO_BIND") and len(cpu_share) < ncpu:
                 sys.stderr.write("bench.py: the ranks' CPU shares overlap\n"); status = 5
-        if traffic is None and "source hash" in why_not and "list length" not in why_not and not a.lib and not a.allow_stale_traffic:
+        if a.full and traffic is None and "source hash" in why_not and "list length" not in why_not and not a.lib and not a.allow_stale_traffic:
             # the headline's roofline needs the counter traffic: a committed PMC pass of THIS kernel source (profiles/r*_traffic.json is
             # keyed by the hash of gdyn_kernels.hip + gdyn_types.h and by the list length).  After a kernel edit: tools/profile_round.sh
             sys.stderr.write("bench.py: the committed PMC traffic of this workload was taken from another kernel source (roofline.traffic is null): "

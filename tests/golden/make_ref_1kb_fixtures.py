@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/ref_1kb_kinetics.npz by running the scenarios of tests/kinetics_util.py through the
+"""Generates tests/golden/ref_1kb_kinetics.npz (the named scenarios) and tests/golden/ref_1kb_random.npz (random_cases)
+by running the scenarios of tests/kinetics_util.py through the
 REFERENCE's loop simulator and reservoir sampler, compiled in place into oracle/_ref/libref1kb.so
 (`make -C oracle ref`; needs /root/reference).  The fixture holds outputs only: loop records per step, the
 reservoir contents, and the generator's next draw (which pins the number of random draws consumed)."""
@@ -26,3 +27,15 @@ for k, (cap, n, seed) in enumerate(ku.RESERVOIR_CASES):
     out[f"reservoir_{k}_next"] = np.uint64(nxt)
 np.savez_compressed(os.path.join(HERE, "ref_1kb_kinetics.npz"), **out)
 print("wrote", len(out), "arrays")
+rnd = {}
+loop_cases, reservoir_cases = ku.random_cases()
+for k, sc in enumerate(loop_cases):
+    loops, nxt = ref.loops(sc)
+    rnd[f"loops_{k}"] = loops
+    rnd[f"loops_{k}_next"] = np.uint64(nxt)
+for k, (cap, n, seed) in enumerate(reservoir_cases):
+    items, nxt = ref.reservoir(cap, n, seed)
+    rnd[f"reservoir_{k}"] = items
+    rnd[f"reservoir_{k}_next"] = np.uint64(nxt)
+np.savez_compressed(os.path.join(HERE, "ref_1kb_random.npz"), **rnd)
+print("wrote", len(rnd), "arrays")

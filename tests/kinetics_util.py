@@ -74,3 +74,26 @@ LOOP_SCENARIOS = {
     "static": dict(length=50, max_loops=3, forward=0.0, backward=0.0, seed=8, steps=5, dt=0.1, handcuffs=[5, 20]),
 }
 RESERVOIR_CASES = [(5, 3, 11), (5, 5, 12), (5, 6, 13), (8, 1000, 14), (1, 50, 15), (64, 5000, 16), (3, 0, 17)]
+
+
+def random_cases(n_loops=40, n_reservoir=30, seed=5):
+    """Random loop scenarios and reservoir cases (fixed seed): the reference's outputs for them are stored in
+    tests/golden/ref_1kb_random.npz and compared live where oracle/_ref/libref1kb.so exists."""
+    rng = np.random.default_rng(seed)
+    loops = []
+    for k in range(n_loops):
+        length = int(rng.integers(20, 400))
+        sc = dict(length=length, max_loops=int(rng.integers(1, 20)), loading=float(rng.uniform(0, 30)), unloading=float(rng.uniform(0.05, 2)),
+                  forward=float(rng.uniform(0, 80)), backward=float(rng.uniform(0, 20)), seed=int(rng.integers(1, 2**31)), steps=25,
+                  dt=float(rng.uniform(0.005, 0.05)), preload=bool(rng.integers(0, 2)),
+                  boundaries=rng.choice(length, size=int(rng.integers(0, 6)), replace=False).tolist(),
+                  attach=[(int(p), float(rng.uniform(0, 1))) for p in rng.choice(length, size=3, replace=False)],
+                  detach=[(int(p), float(rng.uniform(0, 1))) for p in rng.choice(length, size=3, replace=False)],
+                  handcuffs=rng.integers(0, length, size=int(rng.integers(0, 4))).tolist())
+        if k % 3 == 0:
+            sc["crossing"] = float(rng.uniform(0, 20))
+        elif k % 3 == 1:
+            sc["crossing"] = float("inf")
+        loops.append(sc)
+    reservoir = [(int(rng.integers(1, 50)), int(rng.integers(0, 3000)), int(rng.integers(1, 2**31))) for _ in range(n_reservoir)]
+    return loops, reservoir

@@ -295,7 +295,7 @@ def test_every_entry_point_makes_its_device_current_before_its_first_hip_call():
 
 
 def test_committed_pmc_traffic_describes_the_kernel_source_in_the_tree():
-    """bench.py exits with status 4 when the committed PMC traffic of the headline workload was taken from another kernel source
+    """bench.py --full exits with status 4 when the committed PMC traffic of the headline workload was taken from another kernel source
     (hash of gdyn_kernels.hip + gdyn_types.h): a kernel edit without a new profile round must fail HERE, on the CPU, not in the
     driver's bench run."""
     import glob

@@ -34,7 +34,7 @@ if [ -f 2022a-genome-dynamics_amd/csrc/libgdyn_abl41.so ]; then
   [ -x tools/ubench/valu_rate ] && ./tools/ubench/valu_rate > $out/${tag}_valu_rate.txt 2>&1
   echo "[profile] replay done"
 fi
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --allow-stale-traffic > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --allow-stale-traffic > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 echo "[profile] driver-line bench done"
-python3 bench.py --no-cpu-baseline --no-extra --allow-stale-traffic > $out/${tag}_bench_2000steps.json 2> $out/${tag}_bench_2000steps.err
+python3 bench.py --full --no-cpu-baseline --no-extra --allow-stale-traffic > $out/${tag}_bench_2000steps.json 2> $out/${tag}_bench_2000steps.err
 tail -c 300 $out/${tag}_bench_2000steps.json

@@ -12,4 +12,4 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p
 python3 $root/tools/kstats.py /tmp/prof_a > $out/kstats.txt; cat $out/kstats.txt
 cp $(find /tmp/prof_a -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 cd $root
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extra --allow-stale-traffic > $out/bench_short.json 2> $out/bench_short.err; tail -c 900 $out/bench_short.json
+timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extra --allow-stale-traffic > $out/bench_short.json 2> $out/bench_short.err; tail -c 900 $out/bench_short.json

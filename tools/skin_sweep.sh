@@ -5,7 +5,7 @@ out=$1; shift
 cd "$(dirname "$0")/.."
 python bench.py --save-state /tmp/state.npy > /dev/null 2>&1
 for sk in "$@"; do
-  GDYN_DEBUG=1 GDYN_SKIN=$sk python bench.py --lib libgdyn_dev.so --load-state /tmp/state.npy --warmup 600 --steps 2000 --no-cpu-baseline --no-extra 2> /tmp/sweep.err | python -c "
+  GDYN_DEBUG=1 GDYN_SKIN=$sk python bench.py --lib libgdyn_dev.so --load-state /tmp/state.npy --warmup 600 --steps 2000 --full --no-cpu-baseline --no-extra 2> /tmp/sweep.err | python -c "
 import json,sys,re
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 t=[int(m.group(1)) for m in re.finditer(r'largest tile (\d+)', open('/tmp/sweep.err').read())]
