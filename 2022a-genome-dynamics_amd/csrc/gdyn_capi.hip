@@ -47,6 +47,8 @@ static int fail(int code, const char *fmt, ...)
     } while (0)
 
 extern "C" const char *gd_last_error(void) { return g_err; }
+// the flow analyses (gdyn_flow.hip, include/gdyn_flow.h) report through the same message
+int gd_report_error(int code, const char *msg) { return fail(code, "%s", msg); }
 
 // Experiment hooks (environment variables, debug prints, the kernel micro-benchmark) exist in developer builds only
 // (make dev -> libgdyn_dev.so, -DGD_DEV); the product library reads no environment variable.

@@ -7,6 +7,8 @@
 //        nucleolus_bonds.i32 (M,2)
 //   gd_h5tool dump-metadata <file> <dir>               the same tables back out of a file (+ enum.tsv, keys_*.json)
 //   gd_h5tool put-positions-f64 <file> <phase> <step> <in.f64>   replaces the snapshot with a float64 positions dataset (refine/run.py:41-46)
+//   gd_h5tool put-positions <file> <phase> <step> <in.f64>   a float32 snapshot quantised to 2^-16 (trajectory_store::save_positions);
+//        creates the file if it does not exist
 //   gd_h5tool steps <file> <phase>                     numerically ordered step list
 //   gd_h5tool positions <file> <phase> <step> <out.f64>
 //   gd_h5tool context <file> <phase> <step>            prints the JSON context fields
@@ -146,6 +148,15 @@ int main(int argc, char **argv)
             store.replace_positions_f64(std::stol(argv[4]), reinterpret_cast<double const *>(raw.data()), raw.size() / (3 * sizeof(double)));
             return 0;
         }
+        if (cmd == "put-positions" && argc == 6) {
+            auto const raw = slurp(argv[5]);
+            if (raw.size() % (3 * sizeof(double))) throw std::runtime_error("positions file is not (N,3) float64");
+            bool const create = !std::ifstream(argv[2]).good();
+            gd::trajectory_store store(argv[2], create);
+            store.set_phase(argv[3]);
+            store.save_positions(std::stol(argv[4]), reinterpret_cast<double const *>(raw.data()), raw.size() / (3 * sizeof(double)));
+            return 0;
+        }
         if (cmd == "steps" && argc == 4) {
             gd::trajectory_store store(argv[2]);
             store.set_phase(argv[3]);
@@ -283,7 +294,7 @@ int main(int argc, char **argv)
             else for (auto const &s : gd::h5::read_string_list(loc, name)) std::cout << s << '\n';
             return 0;
         }
-        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions-f64|steps|positions|context|contacts|dataset|strings ...\n";
+        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|steps|positions|context|contacts|dataset|strings ...\n";
         return 1;
     } catch (std::exception const &e) {
         std::cerr << "error: " << e.what() << '\n';

@@ -199,6 +199,24 @@ inline void write_string_list(hid_t loc, std::string const &name, std::vector<st
     if (n) check(H5Dwrite(ds, type, H5S_ALL, H5S_ALL, H5P_DEFAULT, p.data()) >= 0, "cannot write " + name);
 }
 
+// a 1-d list of fixed-length strings as h5py stores a list of bytes (NULLPAD ASCII, the length of the longest item)
+inline void write_fixed_string_list(hid_t loc, std::string const &name, std::vector<std::string> const &items)
+{
+    unlink_if_present(loc, name);
+    std::size_t len = 1;
+    for (auto const &s : items) len = std::max(len, s.size());
+    hsize_t n = items.size();
+    std::vector<char> buf(n * len, 0);
+    for (std::size_t k = 0; k < items.size(); k++) std::memcpy(buf.data() + k * len, items[k].data(), items[k].size());
+    hid type(H5Tcopy(H5T_C_S1)), space(H5Screate_simple(1, &n, nullptr));
+    H5Tset_size(type, len);
+    H5Tset_strpad(type, H5T_STR_NULLPAD);
+    H5Tset_cset(type, H5T_CSET_ASCII);
+    hid ds(H5Dcreate2(loc, name.c_str(), type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT));
+    check(ds >= 0, "cannot create " + name);
+    if (n) check(H5Dwrite(ds, type, H5S_ALL, H5S_ALL, H5P_DEFAULT, buf.data()) >= 0, "cannot write " + name);
+}
+
 inline std::vector<std::string> read_string_list(hid_t loc, std::string const &name)
 {
     std::vector<std::string> out;
@@ -206,6 +224,17 @@ inline std::vector<std::string> read_string_list(hid_t loc, std::string const &n
     hid ds(H5Dopen2(loc, name.c_str(), H5P_DEFAULT)), space(H5Dget_space(ds)), type(vlen_string_type());
     hssize_t n = H5Sget_simple_extent_npoints(space);
     if (n <= 0) return out;
+    hid ftype(H5Dget_type(ds));
+    if (H5Tis_variable_str(ftype) <= 0) {      // fixed-length items (write_fixed_string_list)
+        std::size_t const len = H5Tget_size(ftype);
+        std::vector<char> buf((std::size_t)n * len + 1, 0);
+        check(H5Dread(ds, ftype, H5S_ALL, H5S_ALL, H5P_DEFAULT, buf.data()) >= 0, "cannot read " + name);
+        for (hssize_t k = 0; k < n; k++) {
+            char const *p = buf.data() + (std::size_t)k * len;
+            out.emplace_back(p, strnlen(p, len));
+        }
+        return out;
+    }
     std::vector<char *> p((std::size_t)n, nullptr);
     check(H5Dread(ds, type, H5S_ALL, H5S_ALL, H5P_DEFAULT, p.data()) >= 0, "cannot read " + name);
     for (auto q : p) out.emplace_back(q ? q : "");
