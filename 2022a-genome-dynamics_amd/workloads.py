@@ -145,7 +145,8 @@ def genome_interphase(lib, n_beads=30000, n_replicas=1, device=0, second_bond_sp
 def spindle(lib, n_beads=300, n_replicas=1, device=0, seed=MASTER_SEED, bend_energy=1.0):
     """cfg2 / S-spindle: coarse ana/telophase model, forces of
     5-sim-genome/src/simulation_spindle/simulation_driver.cc:90-172 with the init_* defaults
-    (config_entries.inc:46-66) and init_bend_energy 1.0 so the angle kernel is exercised."""
+    (config_entries.inc:46-66) and init_bend_energy 1.0.  The initial rods are straight with every bond at its rest
+    length, so bending and bonds do not act at this state; tests/stressed_states.py jitters it so that they do."""
     rng = np.random.default_rng(seed)
     lens = chain_lengths(n_beads)
     s = System(lib, n_beads, n_replicas, device=device)

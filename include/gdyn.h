@@ -131,6 +131,9 @@ typedef struct {
     double  k_a, k_b, l_a, l_b;
     int32_t scale_by_bond_scale; /* K/=s^2, l*=s  (simulation_driver_forcefield.cc:72-77) */
     int32_t p, q;                /* GD_POT_SOFTCORE only */
+    /* GD_POT_SOFTCORE bonds are evaluated with k_a, l_a exactly as given (the glue of glue_forcefield.cpp:12 sets
+       neither flag): gd_add_bond_range, gd_add_bond_pairs and gd_set_dynamic_pairs reject mix or
+       scale_by_bond_scale on them with GD_EINVAL. */
     int32_t minimum_image;       /* periodic_box::shortest_displacement (glue_forcefield.cpp:38) */
 } gd_bond_params;
 

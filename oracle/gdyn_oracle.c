@@ -344,6 +344,9 @@ static int check_bond_params(const gd_bond_params *p)
 {
     if (p->kind < GD_POT_HARMONIC || p->kind > GD_POT_SOFTCORE) return fail(GD_EINVAL, "bond params: bad kind %d", p->kind);
     if (p->kind == GD_POT_SOFTCORE && !valid_pq(p->p, p->q)) return fail(GD_EINVAL, "bond params: unsupported softcore powers");
+    /* a softcore bond is k_a (1 - (r/l_a)^p)^q as given (gdyn.h): mixing and bond_scale scaling are not defined for it */
+    if (p->kind == GD_POT_SOFTCORE && (p->mix || p->scale_by_bond_scale))
+        return fail(GD_EINVAL, "bond params: a softcore bond takes neither mix nor scale_by_bond_scale");
     return GD_OK;
 }
 

@@ -1,0 +1,223 @@
+"""The stressed states of tests/stressed_states.py on the CPU oracle (no GPU needed).
+
+1. Coverage: each state reaches what the device comparisons at it rely on -- every configured term is a sizeable part of the total
+   force in every replica, and the branches kernels get wrong (both sides of rest lengths and radii, tiny and folded bending angles,
+   both sides of the wall, pair distances from 0 to the cutoff, images across the box faces) are populated.  These keep
+   tests/test_term_parity_gpu.py from going vacuous the way the golden states are (test_golden_states_leave_terms_idle).
+2. Per-term finite differences of the fp64 oracle at those states: the reference the device is held to is -grad U term by term.
+3. The softcore-bond rule (include/gdyn.h): mix / scale_by_bond_scale are rejected; the accepted form is k_a (1-(r/l_a)^p)^q."""
+import numpy as np
+import pytest
+
+import stressed_states as ss
+from util import CASES, build, g
+
+
+def _assert_covered(s, configured):
+    assert ss.idle_terms(s, configured) == [], ss.term_ratios(s)
+
+
+# ------------------------------------------------------------------------------------------------ coverage
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_golden_states_leave_terms_idle(oracle, name):
+    """Why the stressed states exist: at the workloads' initial states (the golden states) spindle bonds and bending and the 1 kb
+    springs do not act at all -- a per-term comparison there cannot see an error in them."""
+    s, *_ = build(oracle, name)
+    idle = ss.idle_terms(s, ss.CONFIGURED[name])
+    assert idle == {"genome": [], "spindle": ["bend", "bond"], "ab_box": [], "chromatin_1kb": ["bond"]}[name]
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_perturbed_workloads_cover_every_term(oracle, name):
+    s = ss.perturbed(oracle, name)
+    _assert_covered(s, ss.CONFIGURED[name])
+    x = s.positions()
+    assert x.shape[0] == 2 and np.abs(x[0] - x[1]).max() > 0.05                      # the replicas hold different states
+    assert np.array_equal(x, ss.f32(x))
+    if name == "genome":
+        assert (s.context(0).bead_scale, s.context(0).bond_scale) != (s.context(1).bead_scale, s.context(1).bond_scale)
+    if name == "spindle":
+        info = ss.g_wl().spindle(oracle, n_beads=300)[1]
+        r = ss.separations(x, ss.chain_bonds(info["ranges"])) / 0.2 - 1
+        assert (r < -0.01).any() and (r > 0.01).any()                                # the semispring bonds: both sides of 0.2
+        first = [i for b0, b1 in info["ranges"] for i in range(b0, b1 - 2)]
+        th, _, _ = ss.bend_geometry(x, first)
+        assert th.max() > 0.3                                                         # the rods are bent
+    if name == "chromatin_1kb":
+        r = ss.separations(x, ss.chain_bonds([(0, s.N)])) - 1.0
+        assert (r < -0.01).any() and (r > 0.01).any()                                # the springs: compressed and stretched
+
+
+def test_composite_model_reaches_every_branch(oracle):
+    s = ss.composite(oracle)
+    _assert_covered(s, ss.TERM_NAMES)
+    x = s.positions()
+    assert np.array_equal(x, ss.f32(x)) and np.abs(x[0] - x[1]).max() > 0.1
+    scales = [(s.context(r).bead_scale, s.context(r).bond_scale) for r in range(2)]
+    assert scales == list(ss.COMPOSITE_SCALES) and scales[0] != scales[1]
+    for r in range(2):
+        xr = x[r:r + 1]
+        # semispring chains: both sides of the rest length, some within 1 % of it on either side
+        u = ss.separations(xr, ss.chain_bonds([ss._chain_range(k) for k in ss.SEMISPRING_CHAINS])) / ss.BOND_L - 1
+        assert (u < -0.01).any() and (u > 0.01).any()
+        assert ((u > -0.01) & (u < 0)).any() and ((u > 0) & (u < 0.01)).any()
+        # spring chains: compressed and stretched
+        u = ss.separations(xr, ss.chain_bonds([ss._chain_range(k) for k in ss.SPRING_CHAINS])) / ss.BOND_L - 1
+        assert (u < -0.01).any() and (u > 0.01).any()
+        # softcore bonds: some inside their range l_a, some beyond
+        u = ss.separations(xr, ss.softcore_bond_pairs().astype(np.int64)) / ss.SOFTCORE_BOND.l_a
+        assert (u < 0.9).any() and (u > 1).any()
+        # bending: angles under 1e-3 rad and over 3.1 rad, with unequal bond lengths in those triplets
+        th, l1, l2 = ss.bend_geometry(xr, ss.composite_triplets())
+        th, unequal = th[0], np.abs(l1 - l2)[0] > 0.05 * ss.BOND_L
+        assert (th < 1e-3).any() and (th > 3.1).any() and th.min() > 0
+        assert (unequal & (th < 1e-3)).any() and (unequal & (th > 3.1)).any()
+        # point sources: targets inside and outside the semispring radius and the spring's rest radius
+        for kind, _, b, pt, tg in ss.POINT_SOURCES:
+            if kind == g.POT_HARMONIC:
+                continue
+            idx = slice(None) if tg is None else ss.source_targets(tg)
+            dist = np.linalg.norm(x[r][idx] - np.array(pt), axis=-1)
+            assert (dist < b).any() and (dist > b).any(), (kind, b)
+        # the wall: beads on both sides of the surface where it acts, the outside ones within 0.02 of it
+        Fw = np.linalg.norm(s.forces(g.TERM_WALL)[r], axis=-1)
+        C = np.sum((x[r] / np.array(ss.SEMI)) ** 2, axis=-1) - 1
+        assert ((C < 0) & (Fw > 0)).sum() >= 5 and ((C > 0) & (Fw > 0)).sum() >= 5
+        assert Fw[C > 0].max() <= ss.PACKING * 0.025
+        assert ((C < 0) & (Fw == 0)).sum() > 100                                     # and most of the beads away from it
+        # pairs: one coincident pair; AA, BB and AB pairs from 1e-3 or closer to within 3 % of the cutoff
+        cut = ss.PAIR["sigma_a"] * scales[r][0]
+        pairs = s.search_pairs(cut, replica=r).astype(np.int64)
+        dist = ss.separations(xr, pairs)[0]
+        assert (dist == 0).sum() == 1
+        a, b, _ = ss._types(s.N)
+        ss._composite_free_types(a, b)
+        for ta, tb in (((1, 0), (1, 0)), ((0, 1), (0, 1)), ((1, 0), (0, 1))):
+            ti, tj = np.stack([a, b], 1)[pairs[:, 0]], np.stack([a, b], 1)[pairs[:, 1]]
+            sel = (np.all(ti == ta, 1) & np.all(tj == tb, 1)) | (np.all(ti == tb, 1) & np.all(tj == ta, 1))
+            assert dist[sel].min() <= 1.001e-3 and dist[sel].max() > 0.97 * cut, (ta, tb)
+
+
+@pytest.mark.parametrize("shape", [(1.0, 1.0, 1.0), (0.8, 1.0, 1.25)])
+def test_1kb_images_straddle_the_box_faces(oracle, shape):
+    base = ss.chromatin_1kb_images(oracle, shifted=False, shape=shape)
+    _assert_covered(base, ss.CONFIGURED["1kb_images"])
+    s = ss.chromatin_1kb_images(oracle, shifted=True, shape=shape)
+    L = np.array(s.box)
+    assert len(set(s.box)) == len(set(shape))
+    x, x0 = s.positions(), base.positions()
+    assert np.array_equal(x, ss.f32(x)) and np.array_equal(np.rint((x - x0) / L), (x - x0) / L)     # shifts by whole periods, exact
+    assert ((x < 0) | (x >= L)).any(axis=-1).mean() > 0.2                             # many beads outside [0, L) in raw coordinates
+    loops, glues = ss.kb_pairs(s.N, 5)
+    for r in range(2):
+        # pair-term neighbours and glue pairs whose raw separation spans a box face: the minimum image is what makes them act
+        nb = s.search_pairs(1.5, replica=r).astype(np.int64)
+        raw = x[r, nb[:, 0]] - x[r, nb[:, 1]]
+        assert (np.abs(raw) > L / 2).any(axis=-1).sum() > 100
+        gl = glues.astype(np.int64)
+        graw = np.linalg.norm(x[r, gl[:, 0]] - x[r, gl[:, 1]], axis=-1)
+        gimg = ss.separations(x[r:r + 1], gl, box=s.box)[0]
+        assert ((graw > 1.5) & (gimg < 1.5)).sum() >= 5                              # glues acting only through the image
+        # unflagged chain bonds that are long in raw coordinates (and short through the image)
+        cb = ss.chain_bonds([(0, s.N)])
+        assert (ss.separations(x[r:r + 1], cb)[0] > L.min() / 2).sum() > 100
+    # the oracle: pair and glue forces are those of the unshifted state; the springs see the raw separations
+    for term in (g.TERM_PAIR,):
+        assert np.abs(s.forces(term) - base.forces(term)).max() <= 1e-9 * np.abs(base.forces(term)).max()
+    assert np.abs(s.forces(g.TERM_BOND)).max() > 100 * np.abs(base.forces(g.TERM_BOND)).max()
+
+
+# ------------------------------------------------------------------------------------------------ per-term finite differences
+
+def _fd_check(s, mask, beads, h=1e-6):
+    x0 = s.positions()
+    F = s.forces(mask)
+    scale = np.abs(F).max()
+    for r in range(s.R):
+        for i in beads:
+            for k in range(3):
+                xp = x0.copy(); xp[r, i, k] += h; s.set_positions(xp); ep = s.energy(mask)[r]
+                xm = x0.copy(); xm[r, i, k] -= h; s.set_positions(xm); em = s.energy(mask)[r]
+                assert F[r, i, k] == pytest.approx(-(ep - em) / (2 * h), rel=2e-5, abs=1e-6 * scale + 1e-9), (mask, r, i, k)
+    s.set_positions(x0)
+
+
+def _composite_probe_beads():
+    beads = set()
+    for k in range(ss.N_CHAINS):
+        b0, _ = ss._chain_range(k)
+        for j in list(ss._SPECIAL_ANGLES) + [2, 3, 6, 7, 12, 13, 46, 47]:         # folded / straight triplets, near-rest bonds, ends
+            beads |= {b0 + j, b0 + j + 1, b0 + j + 2} if j + 2 < ss.CHAIN_LEN else {b0 + j}
+    beads |= set(range(ss.N_CHAINS * ss.CHAIN_LEN, ss.N_COMPOSITE))                   # wall band and close pairs
+    return sorted(b for b in beads if b < ss.N_COMPOSITE)
+
+
+@pytest.mark.parametrize("term", ss.TERM_NAMES)
+def test_composite_force_is_minus_gradient_per_term(oracle, term):
+    s = ss.composite(oracle)
+    if term == "wall":
+        # the wall's force is -grad U only where the second-order nearest-surface construction is exact, on a sphere (the ellipsoid's
+        # construction is pinned against the reference's own geometry module: test_wall_distance_matches_the_reference_geometry_module)
+        for r, (bs, os_) in enumerate(ss.COMPOSITE_SCALES):
+            s.set_context(r, 0, bs, os_, semiaxes=(ss.SEMI[1],) * 3)
+        Fw, C = s.forces(g.TERM_WALL), np.sum(s.positions() ** 2, axis=-1) - ss.SEMI[1] ** 2
+        assert ((np.abs(Fw).max(-1) > 0) & (C < 0)).sum() >= 5 and ((np.abs(Fw).max(-1) > 0) & (C > 0)).sum() >= 5
+    _fd_check(s, ss.TERM_BITS[term], _composite_probe_beads())
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_perturbed_force_is_minus_gradient_per_term(oracle, name):
+    s = ss.perturbed(oracle, name)
+    beads = np.random.default_rng(4).choice(s.N, 16, replace=False)
+    for t in ss.CONFIGURED[name]:
+        _fd_check(s, ss.TERM_BITS[t], beads)
+
+
+def test_1kb_images_force_is_minus_gradient_per_term(oracle):
+    s = ss.chromatin_1kb_images(oracle, shape=(0.8, 1.0, 1.25))
+    loops, glues = ss.kb_pairs(s.N, 5)
+    beads = sorted(set(glues[:8].ravel()) | set(loops[:4].ravel()) | set(np.random.default_rng(6).choice(s.N, 8, replace=False)))
+    for t in ss.CONFIGURED["1kb_images"]:
+        _fd_check(s, ss.TERM_BITS[t], beads)
+
+
+# ------------------------------------------------------------------------------------------------ the softcore-bond rule
+
+def _glue(**kw):
+    return g.System.bond_params(g.POT_SOFTCORE, k_a=-1.0, l_a=0.5, p=8, q=3, **kw)
+
+
+@pytest.mark.parametrize("flags", [dict(mix=True), dict(scale_by_bond_scale=True), dict(mix=True, scale_by_bond_scale=True)])
+def test_softcore_bond_rejects_mix_and_scale(oracle, flags):
+    s = g.System(oracle, 4, 1)
+    pairs = np.array([[0, 2]], dtype=np.uint32)
+    for call in (lambda: s.add_bond_range(_glue(**flags), 0, 4, 1), lambda: s.add_bond_pairs(_glue(**flags), pairs),
+                 lambda: s.set_dynamic_pairs(1, _glue(**flags), pairs)):
+        with pytest.raises(g.GdynError) as e:
+            call()
+        assert e.value.code == 1 and "softcore" in str(e.value)
+    s.add_bond_range(g.System.bond_params(g.POT_SEMISPRING, k_a=5.0, l_a=0.2, **flags), 0, 4, 1)   # the other kinds keep both flags
+    s.add_bond_pairs(_glue(), pairs)
+    s.set_dynamic_pairs(1, _glue(minimum_image=True), pairs)
+
+
+@pytest.mark.parametrize("bond_scale", [1.0, 0.8])
+def test_softcore_bond_is_the_documented_formula(oracle, bond_scale):
+    """U = k_a (1 - (r/l_a)^p)^q with k_a, l_a as given, at any bond_scale and next to bond sets that do scale."""
+    k, l, P, Q = -1.3, 0.5, 8, 3
+    for r in (0.1, 0.3, 0.45, 0.499, 0.6):
+        s = g.System(oracle, 4, 1)
+        s.set_bead_params(a=np.array([1.0, 0.0, 0.5, 1.0]), b=np.array([0.0, 1.0, 0.5, 0.0]))
+        s.add_bond_pairs(g.System.bond_params(g.POT_SOFTCORE, k_a=k, l_a=l, p=P, q=Q), np.array([[0, 1]]))
+        s.add_bond_pairs(g.System.bond_params(g.POT_SPRING, k_a=3.0, l_a=0.3, k_b=1.0, l_b=0.2, mix=True, scale_by_bond_scale=True),
+                         np.array([[2, 3]]))
+        s.set_scaling(1.0, 1.0, bond_scale, 1.0)
+        s.set_positions(np.array([[0.0, 0, 0], [r, 0, 0], [5.0, 0, 0], [5.0, 0, 0.25]]))
+        u = r / l
+        e = k * (1 - u ** P) ** Q if u < 1 else 0.0
+        f = k * P * Q / l * (1 - u ** P) ** (Q - 1) * u ** (P - 1) if u < 1 else 0.0      # -dU/dr on bead 1
+        F = s.forces(g.TERM_BOND)[0]
+        Kb, lb = (0.75 * 3.0 + 0.25 * 1.0) / bond_scale ** 2, (0.75 * 0.3 + 0.25 * 0.2) * bond_scale
+        assert F[1, 0] == pytest.approx(f, rel=1e-12, abs=1e-14) and F[0, 0] == pytest.approx(-f, rel=1e-12, abs=1e-14)
+        assert s.energy(g.TERM_BOND)[0] == pytest.approx(e + 0.5 * Kb * (0.25 - lb) ** 2, rel=1e-12, abs=1e-15)

@@ -19,7 +19,7 @@ TERMS = {"pair": g.TERM_PAIR, "bond": g.TERM_BOND, "bend": g.TERM_BEND, "point":
          "wall": g.TERM_WALL, "dynamic": g.TERM_DYNAMIC, "all": g.TERM_ALL}
 
 # fp32 tolerances of the device path against the fp64 oracle (stated in DESIGN.md)
-FORCE_RTOL = 5e-5      # |dF| <= FORCE_RTOL * max|F_all|   (per-term forces are compared on the all-terms scale)
+FORCE_RTOL = 5e-5      # |dF| <= FORCE_RTOL * max|F|  (test_parity_gpu: per-term forces on the all-terms scale; test_term_parity_gpu: on each term's own)
 ENERGY_RTOL = 2e-6     # |dE| <= ENERGY_RTOL * sum of |term energies|
 POS_ATOL_1STEP = 2e-6  # |dx| after one step
 POS_ATOL_20STEP = 3e-5 # |dx| after 20 steps (trajectories of dense soft-sphere systems diverge exponentially)
