@@ -20,6 +20,7 @@
 
 #include "gdyn_types.h"
 #include "gdyn_once.hpp"
+#include "gdyn_policy.hpp"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
 #endif
@@ -104,13 +105,11 @@ struct gd_system {
 
     bool topo_dirty = true, list_valid = false, ctx_dirty = true;
     bool has_bend = false, has_bonds = false;
-    uint32_t WB = 0, W = 0, ncell_cap = 0;
-    uint32_t list_W = 0;           // row width the list in use was built with (W may change for the next build)
-    uint32_t tiled_off = 0;        // why the tiled path is off: 0 on, 1 a tile overflowed (dense transient: retried later), 2 by design
-    uint32_t tiled_wait = 0, tiled_backoff = 8;     // accepted chunks since / until the next retry of the tiled path
+    uint32_t WB = 0, ncell_cap = 0;
+    uint32_t list_W = 0;           // row width the list in use was built with (pol.W may change for the next build)
     int pcur = 0, ccur = 0;
     uint32_t kernel_path = 0;      // 0 auto, 1 generic, 2 tiled
-    bool packed_ab = false, tiled_ok = true, list_tiled = false;
+    bool packed_ab = false, list_tiled = false;
     bool w_packed = false;         // pos.w of the current positions holds the packed (a,b) factors (set by a build, reset by gd_set_positions / a new topology)
     bool has_inner = false; gd_inner_sphere inner{};
     bool has_softcore_bonds = false;
@@ -121,27 +120,9 @@ struct gd_system {
     float *h_stage = nullptr;      // pinned host staging for snapshot downloads (R*N*3 floats)
     char *h_chunk = nullptr;       // pinned host block for the per-chunk readback (flags, contexts, list counts): copies into pageable
                                    // memory are staged by the runtime and cost ~20 us each
-    uint32_t tile_hold = 0;        // chunks to stay in the larger tile class after an overflow
-    uint32_t last_need_t = 0;      // largest tile of the last build that reported one (entries)
     uint32_t list_tile_cap = 0;    // tile capacity the current list was built with (fixes its entry encoding and LDS need)
-    uint32_t cpb = 1, tile_cap = 3312;
-
-    // tuning / cadence
-    double skin = 0.75;   // relative to the pair cutoff; 0.65..0.8 are within 3% of each other on S-genome-30k, smaller tiles leave more LDS margin
-    // Width by tile class (class_skin): the wider list (0.9: a third fewer builds) is used wherever its largest tile still fits the
-    // three-block LDS class -- a rule on the state, not on measured times, so a given state always selects the same width.
-    bool skin_fixed = false;       // the caller chose a skin (gd_tuning.skin > 0): keep it
-    uint32_t skin_streak = 0, skin_hold = 0;
-    double skin_next = 0;          // width the next list build moves to (the list in use serves out its interval; 0: none pending)
-    double skin_dense_from = 0;    // > 0: the width was narrowed because a build met a dense state (dense_guard); the width to return to
-    uint32_t last_need_w = 0;      // longest list (entries, padded) the last build reported
-    uint32_t ncell_seen = 0;       // largest cell grid of the last build that reported one (sizes k_scan's launch)
-    uint32_t dense_budget = 0;     // dense_guard: longest list (entries) the memory budget admits
-    bool dense_by_tile = false;    // the width was narrowed because the largest tile did not fit the LDS (handle_overflow): returns by tile size
-    bool all_near = false;         // single-class lists (near radius = list radius): a build met a far class beyond the tiled record's
-                                   // 504 entries; two classes again once the longest list is below that
-    uint32_t K = 4, adapt = 1;
-    uint32_t K_bad = 0, K_bad_ttl = 0;   // interval that violated the skin recently: stay below it for a while
+    uint32_t cpb = 1;
+    gd::ListPolicy pol;            // list width, rebuild interval, tile class, list path of the builds to come (gdyn_policy.hpp)
     uint32_t steps_since_build = 0;
     float rv = 0;
     uint64_t rebuilds = 0, rollbacks = 0;
@@ -167,7 +148,6 @@ struct gd_system {
     float need_rv = 0; bool need_all_near = false;      // list radius / class mode need_prev was counted at
     uint32_t pool_used = 0;        // KiB the last build took (its cursor's final value: the need, when the pool was full)
     uint32_t repairs = 0;          // k_step waves the last build read back had to repair (diagnostics)
-    uint32_t repair_wide = 0;      // > 0: accepted chunks still to run with a repair block for EVERY wave (a build queued more than GD_REPAIR_GRID)
     DevBuf<float> bbox;
     DevBuf<float2> ab; DevBuf<float> mobs; DevBuf<float4> bendE; DevBuf<int4> chain;
     float mob_uniform = -1.f;
@@ -176,22 +156,9 @@ struct gd_system {
     DevBuf<unsigned long long> seeds_d;     // gd_run_desc.replica_seeds of the run in progress
     DevBuf<unsigned> dmax;          // [R] largest squared displacement since the list build (k_step keeps it; zeroed by the build)
     float rn = 0;                   // near-class radius of the tiled list in use
-    double a2_ema = 0;              // running mean of (largest displacement)^2 per step of an interval (interval adaptation; 0: none yet)
     double last_dt = 0, last_kT = -1;
     int last_flags = 0;             // flags of the last gd_run (the look-ahead of a list built between runs, gd_search_pairs)
     bool search_list = false;       // the list in use was built by gd_search_pairs at a radius beyond the force list's
-    // Skin selection by measured cost (per workload): a few candidate widths are each run for a few verified chunks once the
-    // rebuild interval has settled, the device time per step decides (gd_run, tune_skin).  Results do not depend on the skin
-    // (verified lists + rollback), only the cost does.
-    struct SkinTuner {
-        bool enabled = false, done = false;     // opt-in: gd_tuning.auto_skin
-        std::vector<double> cand, cost;
-        size_t idx = 0;
-        int settle = 0, measured = 0, wait = 4, rounds = 0;      // wait: accepted chunks before the (next) sweep may start
-        uint32_t K_ref = 0;                                      // rebuild interval when the last sweep ended
-        uint32_t cap_ref = 0;                                    // tile class when the last sweep ended
-        double acc_ms = 0; uint64_t acc_steps = 0;
-    } tuner;
     double pend_dt = 0; int pend_flags = 0;      // timestep and flags of the run that left its last callback pending (GD_RUN_DEFER_CALLBACK)
     double near_frac = 0.65;        // near-class radius = cutoff + near_frac x (list radius - cutoff)
     // gd_search_pairs: device output, counters, and the cached result of the last call
@@ -258,8 +225,13 @@ extern "C" int gd_create_abi(int abi_version, const gd_desc *d, gd_system **out)
     s->lcount.assign(2 * (size_t)s->R, 0ull);      // per replica: directed entries, then the near entries (in fours) of tiled lists
     s->ncell_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(8ull * s->N, 4096ull), 262144ull);
     if (const char *e = dev_env("GDYN_NEAR_FRAC")) s->near_frac = atof(e);
-    if (const char *e = dev_env("GDYN_SKIN")) { s->skin = atof(e); s->skin_fixed = true; }
-    if (dev_env("GDYN_AUTO_SKIN")) s->tuner.enabled = true;
+    if (const char *e = dev_env("GDYN_SKIN")) { s->pol.skin = atof(e); s->pol.skin_fixed = true; }
+    if (dev_env("GDYN_AUTO_SKIN")) s->pol.tuner.enabled = true;
+    if (const char *e = dev_env("GDYN_TILE_CAPS")) { auto &c = s->pol.tile_caps; c.clear(); for (const char *q = e; *q;) { c.push_back((unsigned)strtoul(q, (char **)&q, 10)); if (*q == ',') q++; } }
+    if (const char *e = dev_env("GDYN_K_TARGET")) s->pol.k_target = atof(e);
+    if (dev_env("GDYN_DEBUG")) s->pol.trace = stderr;
+    size_t free_b = 0, total_b = 0;      // the list policy's memory guard (off when the query fails)
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) s->pol.mem_total = total_b;
     hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete s; return fail(GD_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e)); }
     const size_t RNp = (size_t)s->R * s->Np, RN = (size_t)s->R * s->N;
@@ -562,12 +534,12 @@ extern "C" int gd_get_context(gd_system *s, uint32_t r, gd_context *o)
     o->step = c.step; o->time = c.time; o->bead_scale = c.bead_scale; o->bond_scale = c.bond_scale;
     memcpy(o->semiaxes, c.semi, sizeof c.semi); memcpy(o->axial_reaction, c.react, sizeof c.react);
     o->list_entries = s->lcount[r]; o->rebuilds = s->rebuilds; o->rollbacks = s->rollbacks;
-    o->rebuild_interval = s->K; o->list_radius = s->rv;
+    o->rebuild_interval = s->pol.K; o->list_radius = s->rv;
     o->list_path = !s->list_valid && s->rebuilds == 0 ? 0u : (s->list_tiled ? 2u : 1u);
     o->callback_pending = c.pending ? 1u : 0u;
     o->tile_capacity = (s->list_valid && s->list_tiled) ? s->list_tile_cap : 0u;
     o->compensated = s->comp_last ? 1u : 0u;
-    o->largest_tile = (s->list_valid && s->list_tiled) ? s->last_need_t : 0u;
+    o->largest_tile = (s->list_valid && s->list_tiled) ? s->pol.last_need_t : 0u;
     o->row_repairs = s->list_tiled ? s->repairs : 0u;
     o->near_entries = s->list_tiled ? s->lcount[(size_t)s->R + r] : 0ull;
     o->list_bytes = !s->list_valid ? 0ull : s->list_tiled ? 1024ull * s->pool_used : (uint64_t)s->list_W * s->R * s->Np * 4ull;
@@ -605,17 +577,10 @@ extern "C" int gd_set_tuning(gd_system *s, const gd_tuning *t)
     if (t->kernel_path > 2) return fail(GD_EINVAL, "gd_set_tuning: kernel_path must be 0..2");      // (validated before any state changes)
     if (t->near_fraction < 0 || t->near_fraction > 1) return fail(GD_EINVAL, "gd_set_tuning: near_fraction must be in [0,1]");
     HIPCHK(hipSetDevice(s->device));
-    if (t->skin > 0) { s->skin = t->skin; s->skin_fixed = true; }
-    else if (t->skin < 0) { s->skin = 0.75; s->skin_fixed = false; s->skin_dense_from = 0; s->dense_by_tile = false; }      // back to the library's own choice
-    s->skin_streak = 0; s->skin_hold = 0; s->skin_next = 0;
-    if (t->rebuild_interval > 0) s->K = t->rebuild_interval;
-    s->tuner = gd_system::SkinTuner{};
-    s->tuner.enabled = (t->auto_skin != 0 || dev_env("GDYN_AUTO_SKIN")) && t->adapt_interval != 0;          // (a fixed cadence: nothing to select for)
+    if (s->pol.set_tuning(t->skin, t->rebuild_interval, t->adapt_interval, t->list_width, t->auto_skin != 0 || dev_env("GDYN_AUTO_SKIN")))
+        (void)s->nbr.resize(0);
     if (t->near_fraction > 0) s->near_frac = t->near_fraction;
-    s->a2_ema = 0;
-    s->adapt = t->adapt_interval;
-    if (t->list_width > 0 && t->list_width != s->W) { (void)s->nbr.resize(0); s->W = t->list_width; }
-    s->kernel_path = t->kernel_path; s->tiled_ok = true; s->tiled_off = 0;
+    s->kernel_path = t->kernel_path;
     s->list_valid = false;
     return GD_OK;
 }
@@ -760,9 +725,10 @@ static int finalize_topology(gd_system *s)
 
 static double scale_at(const gd_system *s, double init, double tau, double time) { (void)s; return 1.0 - (1.0 - init) * std::exp(-time / tau); }
 
-// bead_scale bound over the next `ahead` steps (monotone in time)
-static double bead_scale_bound(const gd_system *s, const gd_run_desc *run, uint32_t ahead)
+// Factor of the pair cutoff over the next `ahead` steps: the bead_scale bound (monotone in time) when the pair term scales with it
+static double cut_scale(const gd_system *s, const gd_run_desc *run, uint32_t ahead)
 {
+    if (!s->pair.scale_by_bead_scale) return 1.0;
     double m = 0;
     for (auto &c : s->hctx) {
         m = std::max(m, c.bead_scale);
@@ -781,7 +747,7 @@ static void fill_common(gd_system *s, StepParams &p)
     p.pos_in = s->pos[s->pcur].p; p.pos_out = s->pos[s->pcur ^ 1].p; p.xb = s->xb.p; p.orig = s->orig[s->ocur].p;
     p.ab = s->ab.p; p.mob = s->mobs.p; p.bendE = s->bendE.p; p.mob_uniform = s->mob_uniform; p.WB = s->WB;
     p.nbr = s->nbr.p; p.nbr16 = s->nbr16.p; p.wtab = s->wtab.p; p.tiles = s->tiles.p; p.tiled = s->list_tiled ? 1 : 0; p.packed_ab = s->packed_ab ? 1 : 0;
-    p.cpb = s->cpb; p.tile_cap = s->list_tiled ? s->list_tile_cap : s->tile_cap;   // as at the build of the list in use
+    p.cpb = s->cpb; p.tile_cap = s->list_tiled ? s->list_tile_cap : s->pol.tile_cap;   // as at the build of the list in use
     p.pk = (s->has_pair && s->pair.p_a == 2 && s->pair.q_a == 3 && s->pair.p_b == 8 && s->pair.q_b == 3) ? (s->pair.mix ? 1 : 2) : 0;
     p.meta = s->meta.p; p.rec_x0 = s->rec_x0.p; p.rec_mo = s->rec_mo.p; p.W = s->list_W; p.badj = s->badj.p; p.chain = s->chain.p;
     p.ctx_in = s->ctx[s->ccur].p; p.ctx_out = s->ctx[s->ccur ^ 1].p; p.flags = s->flags.p;
@@ -827,23 +793,19 @@ static void fill_common(gd_system *s, StepParams &p)
 }
 
 // Enqueue one list build (counting sort into slot order + ELL fill) with radius rv.
-static bool want_tiled(const gd_system *s)
-{
-    return s->kernel_path != 1 && s->tiled_ok && s->packed_ab && s->W <= GD_TILED_MAX_W;      // open and periodic boxes alike
-}
-
 static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tiled = true)
 {
-    const bool tiled = with_list && allow_tiled && want_tiled(s);
+    gd::ListPolicy &pol = s->pol;
+    const bool tiled = with_list && allow_tiled && pol.want_tiled(s->kernel_path != 1 && s->packed_ab);
     if (with_list) {
-        if (s->W == 0) s->W = 96;
-        s->W = (s->W + GD_UNROLL - 1) & ~(GD_UNROLL - 1);
+        if (pol.W == 0) pol.W = 96;
+        pol.W = (pol.W + GD_UNROLL - 1) & ~(GD_UNROLL - 1);
         // generic lists: uniform rows of W entries (chunked wave-interleaved layout, k_step), grown on demand -- with an eighth to spare
         // once the rows are long -- and given back when a dense transient has passed.  Tiled lists: ragged rows from a pool, below.
-        const size_t need = (size_t)s->W * s->R * s->Np;
-        const size_t grow = s->W >= 512 ? need + need / 8 : need;
+        const size_t need = (size_t)pol.W * s->R * s->Np;
+        const size_t grow = pol.W >= 512 ? need + need / 8 : need;
         if (!tiled && (s->nbr.n < need || s->nbr.n > 4 * need)) HIPCHK(s->nbr.resize(grow, false));
-        s->list_W = s->W;
+        s->list_W = pol.W;
     }
     BuildParams b;
     memset(&b, 0, sizeof b);
@@ -853,10 +815,10 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
     b.rv = rv; b.ncell_cap = s->ncell_cap; b.dmax = s->dmax.p;
     b.kx = b.periodic ? 1 : 2;
     if (const char *e = dev_env("GDYN_KX")) b.kx = b.periodic ? 1 : std::max(1, atoi(e));      // (experiments: cells per list radius in x)
-    b.scan_segments = std::min((s->ncell_seen + s->ncell_seen / 4 + 8191u) / 8192u, (s->ncell_cap + 8191u) / 8192u);      // (0 before the first build: one block per replica)
+    b.scan_segments = std::min((pol.ncell_seen + pol.ncell_seen / 4 + 8191u) / 8192u, (s->ncell_cap + 8191u) / 8192u);      // (0 before the first build: one block per replica)
     {   // near-class radius: the (look-ahead) cutoff the list radius was derived from, plus a share of the skin
-        const float cutb = rv - (float)(pair_cutoff(s) * s->skin);
-        b.rn = (cutb > 0.f && cutb < rv && !s->all_near) ? cutb + (float)s->near_frac * (rv - cutb) : rv;
+        const float cutb = rv - (float)(pair_cutoff(s) * pol.skin);
+        b.rn = (cutb > 0.f && cutb < rv && !pol.all_near) ? cutb + (float)s->near_frac * (rv - cutb) : rv;
     }
     b.pos_in = s->pos[s->pcur].p; b.pos_out = s->pos[s->pcur ^ 1].p; b.xb = s->xb.p;
     b.orig_in = s->orig[s->ocur].p; b.orig_out = s->orig[s->ocur ^ 1].p; b.slot_of = s->slot_of.p;
@@ -869,11 +831,11 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
     b.ab = s->ab.p; b.mob = s->mobs.p; b.bendE = s->bendE.p; b.badj = s->badj.p; b.has_bend = s->has_bend ? 1 : 0;
     b.mob_is_uniform = s->mob_uniform >= 0.f ? 1 : 0;
     b.chain = s->chain.p; b.nbr = (with_list && !tiled) ? s->nbr.p : nullptr; b.nbr16 = tiled ? s->nbr16.p : nullptr;
-    b.meta = s->meta.p; b.rec_x0 = s->rec_x0.p; b.rec_mo = s->rec_mo.p; b.len_prev = s->len_prev.p; b.W = s->W; b.tiles = s->tiles.p; b.tiled = tiled ? 1 : 0;
-    b.packed_ab = s->packed_ab ? 1 : 0; b.cpb = s->cpb; b.tile_cap = s->tile_cap;
+    b.meta = s->meta.p; b.rec_x0 = s->rec_x0.p; b.rec_mo = s->rec_mo.p; b.len_prev = s->len_prev.p; b.W = pol.W; b.tiles = s->tiles.p; b.tiled = tiled ? 1 : 0;
+    b.packed_ab = s->packed_ab ? 1 : 0; b.cpb = s->cpb; b.tile_cap = pol.tile_cap;
     b.w_valid = (s->packed_ab && s->w_packed) ? 1 : 0;
     b.flags = s->flags.p; b.lcount = s->lcount_d.p; b.dbg = (unsigned long long *)s->fout.p;
-    b.wtab = s->wtab.p; b.need_prev = s->need_prev.p; b.pool = s->pool.p; b.rqueue = s->rqueue.p; b.rq_cap = (unsigned)s->rqueue.n; b.rq_grid = s->repair_wide > 0 ? b.rq_cap : std::min(GD_REPAIR_GRID, b.rq_cap);
+    b.wtab = s->wtab.p; b.need_prev = s->need_prev.p; b.pool = s->pool.p; b.rqueue = s->rqueue.p; b.rq_cap = (unsigned)s->rqueue.n; b.rq_grid = pol.repair_wide > 0 ? b.rq_cap : std::min(GD_REPAIR_GRID, b.rq_cap);
     if (tiled) {
         // Ragged rows (BuildParams): every k_step wave's rows are as wide as its longest list, predicted from what each bead needed at
         // the build before (no history -- first build, positions from the caller, another list radius or class mode: W entries per
@@ -881,20 +843,20 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
         // build with an eighth + a KiB per wave to spare (the use is read back with every chunk; the builds in between grow with the
         // lists); a pool that turns out too small is flagged, its cursor has counted the need, and the chunk is rolled back.
         const size_t waves = (size_t)s->R * s->Np / 64;
-        const bool predict = s->need_valid && s->need_all_near == s->all_near && s->need_rv > 0 && std::fabs(rv / s->need_rv - 1.f) <= 0.02f;
+        const bool predict = s->need_valid && s->need_all_near == pol.all_near && s->need_rv > 0 && std::fabs(rv / s->need_rv - 1.f) <= 0.02f;
         auto pool_kib = [&]() { return (size_t)(s->nbr16.n / 512); };
-        const size_t used = predict ? std::max<size_t>(s->pool_used, waves) : std::max<size_t>(s->pool_used, waves * (s->W / 8));
+        const size_t used = predict ? std::max<size_t>(s->pool_used, waves) : std::max<size_t>(s->pool_used, waves * (pol.W / 8));
         const size_t want = used + used / 8 + 2 * waves;
         if (pool_kib() < want || pool_kib() > 2 * want + 4 * waves) HIPCHK(s->nbr16.resize((want + want / 16) * 512, false));      // (not preserved: the list in it is about to be rebuilt)
         if (dev_env("GDYN_DEBUG") && dev_env("GDYN_DEBUG")[0] == '2')
             fprintf(stderr, "[gdyn] build %llu: %s, rows used %u KiB, pool %zu KiB, rv %.4f\n", (unsigned long long)s->rebuilds, predict ? "predicted" : "no history", s->pool_used, pool_kib(), rv);
         if (!predict) s->pool_used = (uint32_t)std::min<size_t>(used, 0xffffffffu);      // (the guess stands in until a chunk's readback brings the real use)
         b.predict = predict ? 1 : 0; b.nbr16 = s->nbr16.p; b.pool_cap = (unsigned)std::min<size_t>(pool_kib(), 0xffffffffu);
-        s->need_valid = true; s->need_rv = rv; s->need_all_near = s->all_near;
+        s->need_valid = true; s->need_rv = rv; s->need_all_near = pol.all_near;
     }
     gd_launch_build(b, s->stream);
     s->bbox_cur ^= 1; s->bbox_valid = tiled;      // (the box of the positions this build sorted, reduced by k_tiles: the next build's grid)
-    s->list_tiled = tiled; s->list_tile_cap = s->tile_cap;
+    s->list_tiled = tiled; s->list_tile_cap = pol.tile_cap;
     s->w_packed = s->packed_ab;
     s->pcur ^= 1; s->ocur ^= 1;
     s->rv = rv; s->rn = b.rn; s->steps_since_build = 0; s->rebuilds++;
@@ -902,17 +864,6 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
     return GD_OK;
 }
 
-static int read_flags(gd_system *s, std::vector<unsigned> &f)
-{
-    HIPCHK(hipGetLastError());
-    f.resize((size_t)s->R * GD_NFLAGS);
-    HIPCHK(hipMemcpyAsync(f.data(), s->flags.p, f.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-    unsigned used[4] = {0u, 0u, 0u, 0u};
-    HIPCHK(hipMemcpyAsync(used, s->pool.p, sizeof used, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->list_tiled && used[0] > 0) { s->pool_used = std::max(used[0], used[1]); s->repairs = used[2]; }
-    return GD_OK;
-}
 static int clear_flags(gd_system *s)
 {
     HIPCHK(hipMemsetAsync(s->flags.p, 0, (size_t)s->R * GD_NFLAGS * sizeof(unsigned), s->stream));
@@ -920,189 +871,67 @@ static int clear_flags(gd_system *s)
     return GD_OK;
 }
 
-// Tile capacities (float4 entries) at which k_step still fits 3, 2, 1 blocks into the 160 KB of LDS of a CU
-// (1.2 KB static LDS per block on top of the tile).
-static unsigned pick_tile_cap(unsigned need)
+// The list in use and the handle, as the list policy sees them
+static gd::ListState list_state(const gd_system *s)
 {
-    // LDS is granted in 1280-byte granules (measured with 1184 B of static LDS: 3264 entries fit 3 blocks, 3318 do not; 720 B now)
-    static const std::vector<unsigned> caps = [] {      // (initialised once, thread-safe; experiment hook of developer builds: GDYN_TILE_CAPS=a,b,c)
-        std::vector<unsigned> c = {3312u, 4080u, 5072u, 8192u};      // (4080: the largest tile with byte-offset list entries)
-        if (const char *e = dev_env("GDYN_TILE_CAPS")) { c.clear(); for (const char *q = e; *q;) { c.push_back((unsigned)strtoul(q, (char **)&q, 10)); if (*q == ',') q++; } }
-        return c;
-    }();
-    for (unsigned c : caps) if (need <= c) return c;
-    return need;     // > 8192: the caller falls back to the generic path
+    return {pair_cutoff(s), s->rv, s->list_tiled, s->list_tile_cap, s->list_W, s->pool_used, s->nbr16.n / 512, (double)s->R * (double)s->Np,
+            s->sw_n != 0, s->kernel_path != 1 && s->packed_ab};
 }
 
-// A build that meets a dense state -- the spline-refined start of the pipeline is a globule in which some beads have 1 500
-// neighbours inside the default list radius.  Tiled lists have ragged rows: the pool holds what the waves need, not the longest list
-// times every bead (uniform rows took 18-20 GB at 128 x 30 000 beads there; the pool a fifth of it), so this guard is a safety net:
-// only when the rows exceed a sixteenth of the device memory is the list width narrowed so that they fit (lists grow with the cube of
-// the radius; at least a skin of 0.15 x cutoff), and class_skin returns to the width it left once the longest list, scaled back, fits
-// again.  Not with a caller-chosen skin.
-static void dense_guard(gd_system *s, unsigned need_w)
-{
-    if (s->skin_fixed || need_w <= 512u || !(s->rv > 0)) return;
-    const double cut = pair_cutoff(s);
-    if (!(cut > 0)) return;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) return;
-    // what the rows of the build take: tiled lists the pool's use (ragged rows: the sum of what the waves need), generic lists uniform
-    // rows of the longest list at four bytes per entry
-    const double rows = (double)s->R * (double)s->Np, budget_b = (double)(total_b / 16);
-    const double bytes = s->list_tiled ? 1024.0 * (double)s->pool_used : (double)need_w * 4.0 * rows;
-    if (bytes <= budget_b) return;
-    const double shrink = 0.9 * budget_b / bytes;                 // lists grow with the cube of the radius
-    s->dense_budget = (uint32_t)std::max(64.0, (double)need_w * budget_b / bytes);
-    const double sc = s->rv / cut - s->skin;                       // bead-scale part of the radius the build used
-    const double r_new = s->rv * std::cbrt(shrink);
-    const double skin_new = std::max(0.15, r_new / cut - sc);
-    if (skin_new < s->skin - 1e-9) {
-        if (!(s->skin_dense_from > 0)) s->skin_dense_from = s->skin;
-        s->skin = skin_new; s->skin_next = 0; s->a2_ema = 0;
-        if (s->adapt) s->K = std::max(1u, std::min(s->K, 4u));      // (a caller-fixed interval stays the caller's)
-        if (!s->list_tiled) s->W = std::max(64u, s->dense_budget & ~7u);      // (the narrowed list is predicted at 0.9 of the budget; a miss is one more exactly sized build)
-        if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] dense state (longest list %u, rows %.1f GB): skin %.3f\n", need_w, bytes / 1e9, skin_new);
-    }
-}
+// A build or a chunk of gd_run: what it ran and the state before it (gd_run), what the device reported (read_chunk)
+struct Chunk {
+    int64_t steps = 0;
+    bool full_interval = false, on_search_list = false;      // it holds the last step of a complete K-step interval / began on a search list
+    std::vector<DevCtx> snap_ctx; bool snap_w_packed = false;      // the context before it, what pos.w carried then
+    std::vector<std::pair<size_t, int>> spans; size_t ev_end = 0;      // (end event, kind: 0 step, 1 build) of each span; the chunk's end event
+    gd::BuildReport rep; std::vector<DevCtx> ctx; float dmax2 = 0;      // flags, contexts and largest displacement bound read back
+};
 
-// (class_skin, below: the handle runs at the wider of its two list widths)
-static bool class_skin_wide(const gd_system *s)
+// One round trip for everything the host wants from a build or a chunk: flags, contexts, list counts, the running displacement bound
+// of every replica (tiled path, one word per 128-byte line: it covers the positions the last step WROTE, which no step has checked
+// yet) and the row pool's use (the list counts and the pool's use go to the handle)
+static int read_chunk(gd_system *s, Chunk &c)
 {
-    return !s->skin_fixed && s->adapt && !s->tuner.enabled && !(s->skin_dense_from > 0) && !s->sw_n && s->skin >= 0.9 - 1e-9 && s->skin <= 0.9 + 1e-9;
-}
-
-// React to list-width / tile-capacity overflow flags: widen the list, enlarge the LDS tile or
-// fall back to the generic path. Returns true when a build has to be redone.
-static bool handle_overflow(gd_system *s, const std::vector<unsigned> &f)
-{
-    unsigned need_w = 0, need_t = 0; bool over = false, tover = false, class_over = false;
-    for (uint32_t r = 0; r < s->R; r++) {
-        over |= f[r * GD_NFLAGS + GD_FLAG_OVERFLOW] != 0; need_w = std::max(need_w, f[r * GD_NFLAGS + GD_FLAG_NEED_W]);
-        class_over |= (f[r * GD_NFLAGS + GD_FLAG_OVERFLOW] & 2u) != 0;
-        tover |= f[r * GD_NFLAGS + GD_FLAG_TILE_OVERFLOW] != 0; need_t = std::max(need_t, f[r * GD_NFLAGS + GD_FLAG_NEED_TILE]);
-    }
-    if (need_t > 0 && need_t < (1u << 20)) s->last_need_t = need_t;
-    if (need_w > 0) s->last_need_w = need_w;
-    {
-        unsigned nc = 0;
-        for (uint32_t r = 0; r < s->R; r++) nc = std::max(nc, f[r * GD_NFLAGS + GD_FLAG_NCELL]);
-        if (nc > 0) s->ncell_seen = nc;
-    }
-    if (!tover && !over && s->list_tiled && need_t > 0) {
-        // size the LDS tile to what the builds actually need (more resident blocks per CU)
-        // LDS capacity is a step function of the tile size: k_step keeps 3 / 2 / 1 blocks (6 / 4 / 2 waves per SIMD)
-        // resident per CU up to these tile capacities, so the capacity is always the largest one of its occupancy class
-        // (the tiles of consecutive builds differ by a few entries; an overflow costs one rolled-back chunk and then
-        // keeps the larger class for a while, so the margin for the smaller class can be thin)
-        unsigned want = pick_tile_cap(need_t + 24);
-        if (want < s->tile_cap && s->tile_hold > 0) { s->tile_hold--; want = s->tile_cap; }
-        // at the width class_skin selected the tiles are about to leave the three-block class: class_skin (called after this) takes
-        // the narrower list back at the next build, where they fit it -- no detour through the two-block class
-        if (want > 3312u && s->tile_cap <= 3312u && class_skin_wide(s)) want = s->tile_cap;
-        if (want != s->tile_cap && want <= 8192u) {
-            if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] tile capacity %u -> %u (largest tile %u)\n", s->tile_cap, want, need_t);
-            s->tile_cap = want;
-        }
-    }
-    if (tover) {
-        const unsigned cap = pick_tile_cap(need_t + need_t / 32 + 32);
-        // 128 KB dynamic + static part < 160 KB of LDS per CU (one resident block per CU at the largest class: still ahead of the
-        // generic path's global gathers -- S-1kb-250k x 16: 471 us per step generic, 239 us tiled at two blocks per CU)
-        const unsigned cap_max = 8192u;
-        if (cap <= cap_max) { s->tile_cap = cap; s->tile_hold = 4; }
-        else {
-            // Too dense for one tile at this list width (the spline-refined start of the pipeline: a globule whose core holds thousands
-            // of beads per list sphere).  A tile is the block's own cells plus their neighbour cells: it shrinks about with the square of
-            // the list radius -- so the width is narrowed until the largest tile fits the LDS (at least a skin of 0.15 x cutoff; builds
-            // get more frequent, but the state stays on the tiled path: global-gather lists cost 2-2.4 x per step there and uniform rows
-            // of the longest list), and class_skin returns to the width it left once the largest tile, scaled back, fits again.  Only
-            // when that is not enough -- or the caller pinned the width -- the generic path takes over (retried later with back-off).
-            const double cut = pair_cutoff(s);
-            bool narrowed = false;
-            if (!s->skin_fixed && cut > 0 && s->rv > 0 && need_t < (1u << 20)) {
-                const double sc = s->rv / cut - s->skin;
-                const double ratio = std::min(0.97, std::max(0.5, std::sqrt(0.85 * (double)cap_max / (double)need_t)));
-                const double skin_new = std::max(0.15, s->rv * ratio / cut - sc);
-                if (skin_new < s->skin - 1e-9) {
-                    if (!(s->skin_dense_from > 0)) s->skin_dense_from = s->skin;
-                    s->skin = skin_new; s->skin_next = 0; s->a2_ema = 0; s->dense_by_tile = true;
-                    if (s->adapt) s->K = std::max(1u, std::min(s->K, 4u));
-                    s->tile_cap = cap_max; s->tile_hold = 4;
-                    narrowed = true;
-                    if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] dense state (largest tile %u): skin %.3f\n", need_t, skin_new);
-                }
-            }
-            if (!narrowed) { s->tiled_ok = false; s->tiled_off = 1; }
-        }
-    }
-    if (over) {
-        // Tiled lists (ragged rows): the pool was full -- its cursor counted on, pool_used is the need and the next build sizes the pool
-        // from it -- or a build queued more waves for repair than the repair launch has blocks: the next chunks launch one per wave
-        // (a list that outgrows its predicted row is repaired on the device and never gets here).  Generic lists (uniform
-        // rows): the overflowing build has counted the longest list exactly (a row keeps counting past its width): the next build
-        // gets that width with 6 % to spare.
-        {
-            unsigned bits = 0;
-            for (uint32_t r = 0; r < s->R; r++) bits |= f[r * GD_NFLAGS + GD_FLAG_OVERFLOW];
-            if (s->list_tiled && (bits & 4u) && (size_t)s->pool_used <= s->nbr16.n / 512) s->repair_wide = 16;      // (bit 4 with room in the pool: the repair queue)
-        }
-        if (!s->list_tiled) {
-            unsigned w = need_w + need_w / 16 + 8;
-            s->W = std::max(w, s->W + 8);
-        }
-        if (class_over) {
-            // a class beyond its field of the tiled record: single-class lists while that is the far class; a near class beyond
-            // 8 184 entries is beyond tiled rows
-            if (!s->all_near && need_w <= GD_TILED_MAX_NEAR) s->all_near = true;
-            else s->W = std::max(s->W, GD_TILED_MAX_W + 8u);
-        }
-        dense_guard(s, need_w);
-    }
-    else if (!tover && need_w > 0) {
-        if (s->list_tiled && (size_t)s->pool_used * 1024u > ((size_t)4 << 30)) dense_guard(s, need_w);      // (rows of several GB: within the budget?)
-        if (s->all_near && need_w <= GD_TILED_MAX_FAR) s->all_near = false;      // (no far class can overflow its field any more; from the next build)
-        // the longest list is reported by every build: generic lists give the row width back when a dense transient has passed
-        const unsigned want_w = std::max(64u, (need_w + need_w / 4 + 16 + GD_UNROLL - 1) & ~(GD_UNROLL - 1));
-        if (!s->list_tiled && 2 * want_w <= s->W) s->W = want_w;       // (takes effect at the next build; the list in use keeps list_W)
-        else if (s->list_tiled && s->W > GD_TILED_MAX_W && need_w <= GD_TILED_MAX_NEAR) s->W = 96;      // (a near class beyond the tiled record has passed)
-    }
-    if (tover && dev_env("GDYN_DEBUG")) {
+    HIPCHK(hipGetLastError());
+    const size_t nf = (size_t)s->R * GD_NFLAGS * sizeof(unsigned), nc = s->R * sizeof(DevCtx), nl = 2 * (size_t)s->R * sizeof(unsigned long long), nd = s->R * sizeof(float);
+    if (!s->h_chunk) HIPCHK(hipHostMalloc((void **)&s->h_chunk, nf + nc + nl + nd + 16, hipHostMallocDefault));
+    HIPCHK(hipMemcpyAsync(s->h_chunk + nf + nc + nl + nd, s->pool.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_chunk, s->flags.p, nf, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_chunk + nf, s->ctx[s->ccur].p, nc, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_chunk + nf + nc, s->lcount_d.p, nl, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpy2DAsync(s->h_chunk + nf + nc + nl, sizeof(float), s->dmax.p, GD_DMAX_STRIDE * sizeof(unsigned), sizeof(float), s->R,
+                            hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    c.rep = gd::summarize((const unsigned *)s->h_chunk, s->R);
+    c.ctx.resize(s->R); memcpy(c.ctx.data(), s->h_chunk + nf, nc); memcpy(s->lcount.data(), s->h_chunk + nf + nc, nl);
+    c.dmax2 = 0; for (uint32_t r = 0; r < s->R; r++) { float d2; memcpy(&d2, s->h_chunk + nf + nc + nl + r * sizeof(float), 4); c.dmax2 = std::max(c.dmax2, d2); }
+    unsigned used[4]; memcpy(used, s->h_chunk + nf + nc + nl + nd, 16);
+    if (s->list_tiled && used[0] > 0) { s->pool_used = std::max(used[0], used[1]); s->repairs = used[2]; }
+    if (c.rep.tile_over && dev_env("GDYN_DEBUG")) {      // (developer builds: the grids of a tile overflow)
         std::vector<GridP> gp(s->R);
         (void)hipMemcpy(gp.data(), s->grid.p, s->R * sizeof(GridP), hipMemcpyDeviceToHost);
         for (uint32_t r = 0; r < std::min(s->R, 3u); r++)
             fprintf(stderr, "[gdyn] grid r%u: nc %d %d %d ncell %d org %g %g %g inv %g flags need_t %u\n", r, gp[r].nc[0], gp[r].nc[1], gp[r].nc[2],
-                    gp[r].ncell, gp[r].org[0], gp[r].org[1], gp[r].org[2], gp[r].inv[0], f[r * GD_NFLAGS + GD_FLAG_NEED_TILE]);
+                    gp[r].ncell, gp[r].org[0], gp[r].org[1], gp[r].org[2], gp[r].inv[0], ((const unsigned *)s->h_chunk)[r * GD_NFLAGS + GD_FLAG_NEED_TILE]);
     }
-    if ((over || tover) && dev_env("GDYN_DEBUG"))
-    {
-        unsigned bits = 0;
-        for (uint32_t r = 0; r < s->R; r++) bits |= f[r * GD_NFLAGS + GD_FLAG_OVERFLOW];
-        fprintf(stderr, "[gdyn] overflow: list %d (bits %u, need %u -> W %u; rows %u KiB of a pool of %zu), tile %d (need %u -> cap %u, tiled_ok %d)\n", (int)over, bits,
-                need_w, s->W, s->pool_used, (size_t)(s->nbr16.n / 512), (int)tover, need_t, s->tile_cap, (int)s->tiled_ok);
-    }
-    return over || tover;
+    return GD_OK;
 }
 
 // Synchronous build used outside gd_run: grows the list width until nothing overflows.
 static int build_now(gd_system *s, float rv, bool with_list, bool allow_tiled = true, float rv_min = 0.f)
 {
-    const double skin0 = s->skin;
+    const double skin0 = s->pol.skin;
+    Chunk c;
     for (int attempt = 0; attempt < 10; attempt++) {
         GDCHK(clear_flags(s));
         // (a retry after the dense guard has narrowed the width builds at the narrowed radius -- not below what the caller needs
         // the list to cover, rv_min: a pair search at a contact distance beyond the force cutoff)
-        const float rv_try = std::max(rv_min, rv - (float)(pair_cutoff(s) * (skin0 - s->skin)));
+        const float rv_try = std::max(rv_min, rv - (float)(pair_cutoff(s) * (skin0 - s->pol.skin)));
         GDCHK(enqueue_build(s, rv_try, with_list, allow_tiled));
-        std::vector<unsigned> f;
-        GDCHK(read_flags(s, f));
-        if (!handle_overflow(s, f)) {
-            HIPCHK(hipMemcpy(s->lcount.data(), s->lcount_d.p, 2 * (size_t)s->R * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            GDCHK(clear_flags(s));
-            return GD_OK;
-        }
+        GDCHK(read_chunk(s, c));
+        if (!s->pol.on_report(list_state(s), c.rep)) return clear_flags(s);
     }
-    return fail(GD_ENOMEM, "neighbour list width did not converge (W=%u)", s->W);
+    return fail(GD_ENOMEM, "neighbour list width did not converge (W=%u)", s->pol.W);
 }
 
 static int prepare(gd_system *s)
@@ -1117,32 +946,17 @@ static float list_radius(gd_system *s, const gd_run_desc *run, uint32_t ahead)
 {
     const float cut = pair_cutoff(s);
     if (!(cut > 0)) return 1.0f;
-    const double sc = s->pair.scale_by_bead_scale ? bead_scale_bound(s, run, ahead) : 1.0;
+    const double sc = cut_scale(s, run, ahead);
     // the skin is an absolute width, `skin` x the NOMINAL cutoff: with a scaled-down cutoff (bead_scale < 1 early in the
     // interphase run, simulation_driver_forcefield.cc:47-49) the displacement budget (rv - cutoff) / 2, and with it the
     // rebuild interval, stays what it is at full scale
-    return (float)(cut * (sc + s->skin));
-}
-
-// The width selected by tile class (class_skin) takes over at a list build: interval and radius change together
-static uint32_t interval_for_skin(const gd_system *s, double skin);
-static void take_pending_skin(gd_system *s)
-{
-    if (!(s->skin_next > 0)) return;
-    // the interval follows the square of the skin (diffusive displacements) from the interval the handle had adapted to at the old width --
-    // a tenth off on the way up -- and not beyond what the measured displacement rate admits: the rate alone, averaged over a few
-    // intervals of a state that had just changed its regime, put S-genome-30k without second bonds at 23 steps where 19-20 hold
-    // (one rolled-back chunk in the timed steps of that line)
-    const double ratio = s->skin > 0 ? s->skin_next / s->skin : 1.0;
-    const uint32_t k_scaled = (uint32_t)std::max(1.0, std::floor((double)s->K * ratio * ratio * (ratio > 1.0 ? 0.9 : 1.0)));
-    s->skin = s->skin_next; s->skin_next = 0;
-    s->K = std::min(interval_for_skin(s, s->skin), std::max(k_scaled, 1u)); s->K_bad_ttl = 0;
+    return (float)(cut * (sc + s->pol.skin));
 }
 
 static int ensure_fresh_list(gd_system *s)
 {
     if (s->list_valid && (s->steps_since_build == 0 || s->verified_serial == s->state_serial)) return GD_OK;
-    take_pending_skin(s);
+    s->pol.take_pending_skin(pair_cutoff(s));
     GDCHK(build_now(s, list_radius(s, nullptr, 0), pair_cutoff(s) > 0));
     s->list_valid = true; s->search_list = false;
     return GD_OK;
@@ -1185,78 +999,6 @@ static int apply_pending(gd_system *s)
     return GD_OK;
 }
 
-// Interval the skin admits at the measured displacement rate (the adaptation formula of gd_run)
-static uint32_t interval_for_skin(const gd_system *s, double skin)
-{
-    if (!(s->a2_ema > 0)) return s->K;
-    const double lim = 0.5 * pair_cutoff(s) * skin, k = 0.90 * lim * 0.90 * lim / s->a2_ema;
-    return (uint32_t)std::max(1.0, std::min(200.0, std::floor(k)));
-}
-
-// One accepted chunk of `steps` steps took `ms` on the device.  Candidates: the width in use, 1.2 x it (fewer builds: what a small
-// launch-latency-bound system wants) and 0.7 / 0.5 / 0.35 of it (shorter lists and smaller LDS tiles against more frequent builds;
-// a periodic box whose tiles did not fit may fit them at a smaller width).  Each candidate: one chunk to settle (tile class, list width, interval), three measured.  The width the sweep
-// started from is left only for a gain of 6 % or more (chunk times scatter by a few per cent).
-static void tune_skin(gd_system *s, double ms, int64_t steps, bool full_interval, bool rolled_back)
-{
-    auto &t = s->tuner;
-    if (!t.enabled || s->sw_n) return;
-    if (s->skin_dense_from > 0 || s->skin_next > 0) return;      // a dense transient at its narrow width (dense_guard): the selection starts once it has passed
-    if (rolled_back) { t.settle = std::max(t.settle, 1); t.acc_ms = 0; t.acc_steps = 0; t.measured = 0; return; }
-    if (!full_interval || !(s->a2_ema > 0)) return;
-    if (t.done) {      // conditions drift (a relaxation, a growing bead scale): look again, around the width in use, once the
-                       // rebuild interval -- the displacement rate -- has moved by a third since the last sweep
-        // ... or the tiles have outgrown the class the width was selected in (fewer resident blocks per CU: another width may
-        // fit the smaller class)
-        if (t.wait > 0) t.wait--;
-        if (t.cap_ref == 0 && t.wait <= 45 && s->list_tiled) t.cap_ref = std::max(s->list_tile_cap, 3312u);
-        const double k = (double)s->K, k0 = (double)std::max(t.K_ref, 1u);
-        const bool outgrown = s->list_tiled && t.cap_ref > 0 && s->list_tile_cap > t.cap_ref;
-        if (!(outgrown && t.wait <= 40) && (t.wait > 0 || (k < 1.33 * k0 && k0 < 1.33 * k))) return;
-        t.done = false; t.cand.clear();
-    }
-    if (t.cand.empty()) {
-        if (t.wait > 0 && t.rounds == 0) { t.wait--; return; }
-        if (t.rounds == 0) t.cand = {s->skin, std::min(1.2 * s->skin, 1.0), 0.7 * s->skin, 0.5 * s->skin, 0.35 * s->skin};
-        else t.cand = {s->skin, std::min(1.2 * s->skin, 1.0), 0.85 * s->skin, 0.7 * s->skin};      // (finer steps around the width in use)
-        t.cost.assign(t.cand.size(), 0.0);
-        t.idx = 0; t.settle = 0; t.measured = 0; t.acc_ms = 0; t.acc_steps = 0; t.rounds++;
-    }
-    if (t.settle > 0) { t.settle--; return; }
-    t.acc_ms += ms; t.acc_steps += (uint64_t)steps; t.measured++;
-    if (t.measured < 3) return;
-    t.cost[t.idx] = t.acc_ms / (double)t.acc_steps;
-    if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] skin %.3f: %.4f ms per step (K %u, %s, W %u, tile %u)\n", t.cand[t.idx], t.cost[t.idx], s->K,
-                                       s->list_tiled ? "tiled" : "generic", s->list_W, s->list_tile_cap);
-    size_t next = t.idx + 1;
-    while (next < t.cand.size() && (t.cand[next] == s->skin || interval_for_skin(s, t.cand[next]) < 2)) next++;
-    if (next >= t.cand.size()) {      // sweep complete: the cheapest, but the width the sweep started from unless the gain is 6 % or more
-        size_t best = 0;
-        for (size_t k = 1; k < t.cand.size(); k++) if (t.cost[k] > 0 && t.cost[k] < 0.94 * t.cost[0] && t.cost[k] < t.cost[best]) best = k;
-        next = best; t.done = true; t.wait = 50; t.K_ref = interval_for_skin(s, t.cand[best]);
-        t.cap_ref = 0;      // (taken a few chunks on, once the selected width has found its class)
-    }
-    if (t.cand[next] != s->skin) {
-        // the tile class for the new width: tiles scale about with the square of the list radius (rows of cells x their
-        // neighbour rows); sized from the last build's largest tile so that the candidate is not measured in a class it does
-        // not need (or found by overflow and rollback)
-        if (s->last_need_t > 0 && s->rv > 0) {
-            const double cut = pair_cutoff(s), r0 = cut * (1.0 + s->skin), r1 = cut * (1.0 + t.cand[next]);
-            const unsigned est = (unsigned)(1.08 * s->last_need_t * (r1 / r0) * (r1 / r0)) + 32u;
-            s->tile_cap = std::min(pick_tile_cap(est), 8192u); s->tile_hold = 0;
-        }
-        {      // (the interval as in take_pending_skin: from the one adapted to at the width in use, not beyond the measured rate)
-            const double ratio = s->skin > 0 ? t.cand[next] / s->skin : 1.0;
-            const uint32_t k_scaled = (uint32_t)std::max(1.0, std::floor((double)s->K * ratio * ratio * (ratio > 1.0 ? 0.9 : 1.0)));
-            s->skin = t.cand[next];
-            s->K = std::min(interval_for_skin(s, s->skin), k_scaled); s->K_bad_ttl = 0;
-        }
-        s->list_valid = false;
-        if (s->kernel_path != 1 && s->packed_ab) { s->tiled_ok = true; s->tiled_off = 0; }      // smaller tiles may fit now
-    }
-    t.idx = next; t.settle = 1; t.measured = 0; t.acc_ms = 0; t.acc_steps = 0;
-}
-
 // Whether a run steps with the compensated position update (k_step's p.comp).  The increment of a step is mu F dt + sigma xi with
 // sigma = sqrt(2 mu kT dt); once sigma is within a few dozen ulp of an fp32 coordinate -- always at T = 0 -- the rounding of x + dx is no
 // longer small against what a step adds, and summed over a run it is a systematic loss (simulation_fine_sampling: T = 0, dt = 1e-7; an
@@ -1274,67 +1016,129 @@ static bool want_compensated(const gd_system *s, const gd_run_desc *run)
     return sigma < 64.0 * ulp;
 }
 
-// List width by tile class.  On S-genome-30k x 128 the steady-state cost is flat to 1 % over skins 0.7 ... 0.85 and 2.5 % lower at
-// 0.9 ... 0.95 (interval 20-22 instead of 14: a third fewer builds; `tools/skin_sweep.sh`, profiles/r04_skin_sweep.txt) -- as long as
-// the largest tile stays inside the three-block LDS class (3 312 entries); one class up every block loses a third of its occupancy
-// (S-genome-62k at 0.9: -15 %).  So: the handle starts at 0.75 and moves to 0.9 once the largest tile of the builds, scaled to the
-// wider list (the halo part of a tile grows with the square of the list radius), has fitted the class for three accepted
-// chunks in a row; it moves back when the largest tile of a build at 0.9 comes within 24 entries of the class (the next build is
-// already at 0.75: no build in the two-block class in between), and waits 64 chunks before it looks again.  The rule reads
-// the state only (tile sizes are cell counts), never a clock: the same state selects the same width.  Not with a caller-chosen skin
-// (gd_tuning.skin), not while the timing-based selection (gd_tuning.auto_skin) is on.
-static void class_skin(gd_system *s, const gd_run_desc *run)
-{
-    if (s->skin_dense_from > 0 && !s->skin_fixed) {
-        // back from the narrow width of a dense state (dense_guard) once the longest list, scaled to the width it left, is short
-        // again; the timing-based selection, when enabled, starts from there
-        const unsigned need_w = s->last_need_w;
-        const double cut = pair_cutoff(s), sc0 = s->rv / cut - s->skin, ratio = (sc0 + s->skin_dense_from) / (sc0 + s->skin);
-        // (narrowed for the memory of the rows: back when the longest list, scaled with the cube of the radius, fits the budget again;
-        // narrowed for the LDS tile: back -- in steps of at most a quarter of the width, the densest tile decides -- when the largest
-        // tile, scaled with the square of the radius, fits 0.85 of the LDS)
-        if (s->dense_by_tile) {
-            if (s->list_tiled && s->last_need_t > 0 && !(s->skin_next > 0)) {
-                const double target = std::min(s->skin_dense_from, s->skin * 1.35 + 0.02);
-                const double rt = (sc0 + target) / (sc0 + s->skin);
-                if ((double)s->last_need_t * rt * rt <= 0.85 * 8192.0) {      // (a decondensing globule: the tiles shrink from build to build; a miss costs one rolled-back chunk)
-                    s->skin_next = target;
-                    if (target >= s->skin_dense_from - 1e-9) { s->skin_dense_from = 0; s->dense_by_tile = false; }
-                    if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] dense state eases (largest tile %u): skin %.3f at the next build\n", s->last_need_t, s->skin_next);
-                }
-            }
-            return;
-        }
-        if (need_w > 0 && (double)need_w * ratio * ratio * ratio <= 0.8 * (double)s->dense_budget && !(s->skin_next > 0)) {
-            s->skin_next = s->skin_dense_from; s->skin_dense_from = 0;
-            { const bool on = s->tuner.enabled; s->tuner = gd_system::SkinTuner{}; s->tuner.enabled = on; }      // (a fresh selection from the default width)
-            if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] dense state has passed (longest list %u): skin %.3f at the next build\n", need_w, s->skin_next);
-        }
-        return;
-    }
-    if (s->skin_fixed || !s->adapt || s->tuner.enabled || !s->list_tiled || !s->last_need_t || s->sw_n) return;
-    const double lo = 0.75, hi = 0.9;
-    const double sc = s->pair.scale_by_bead_scale ? bead_scale_bound(s, run, s->K) : 1.0;
-    auto move_to = [&](double skin) {      // takes effect at the next build (take_pending_skin): the list in use stays valid until then
-        s->skin_next = skin; s->skin_streak = 0;
-        if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] list width by tile class: skin %.2f at the next build (largest tile %u)\n", skin, s->last_need_t);
-    };
-    if (s->skin_next > 0) return;
-    if (s->skin < hi - 1e-9) {
-        if (s->skin_hold > 0) { s->skin_hold--; return; }
-        const double ratio = (sc + hi) / (sc + s->skin);
-        // a tile = the block's own slots under three (dz) planes + the halo rows around them: only the halo grows with the cell
-        // cross-section (measured on S-genome-30k: 2 930 entries at 0.75, 3 074 at 0.9)
-        const double own = 3.0 * GD_BLOCK, est = own + std::max(0.0, (double)s->last_need_t - own) * ratio * ratio + 24.0;
-        if (est <= 3312.0 - 24.0 && s->list_tile_cap <= 3312u) { if (++s->skin_streak >= 3) move_to(hi); }
-        else s->skin_streak = 0;
-    } else if (s->skin <= hi + 1e-9 && (s->list_tile_cap > 3312u || s->last_need_t + 24u > 3312u)) { move_to(lo); s->skin_hold = 64; }
-}
-
 extern "C" int gd_apply_callback(gd_system *s)
 {
     if (!s) return fail(GD_EINVAL, "gd_apply_callback: NULL system");
     return apply_pending(s);
+}
+
+static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, bool comp, bool host_noise, Chunk &c)
+{
+    const size_t RN = (size_t)s->R * s->N;
+    const bool with_list = pair_cutoff(s) > 0;
+    const int64_t chunk = c.steps = s->pol.chunk_steps(run->steps - done);
+    // snapshot for rollback: positions in bead order + context
+    gd_launch_gather_positions(s->pos[s->pcur].p, s->slot_of.p, s->snap.p, s->N, s->Np, s->R, 0, s->stream);
+    if (comp) HIPCHK(hipMemcpyAsync(s->snap_lo.p, s->lo.p, RN * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    c.snap_ctx = s->hctx; c.snap_w_packed = s->w_packed;
+    GDCHK(clear_flags(s));
+    StepParams p;
+    // The scales a callback sets are pure functions of the step index (simulation_driver_interphase.cc:42-43): when every
+    // replica is at the same step (the usual case) the host evaluates them and passes them with the launch
+    bool common_step = s->has_scaling && (run->flags & GD_RUN_UPDATE_SCALES);
+    const long long step0 = s->hctx[0].step;
+    for (uint32_t r = 1; r < s->R && common_step; r++) common_step = s->hctx[r].step == step0;
+    auto host_scales = [&](StepParams &q, int64_t launch) {      // launch: index within the chunk of the launch that applies the callback
+        if (!common_step) return;
+        const double time = (double)(step0 + launch) * run->timestep;
+        q.scaling.from_host = 1;
+        q.scaling.bead_next = scale_at(s, s->bs_init, s->bs_tau, time);
+        q.scaling.bond_next = scale_at(s, s->bo_init, s->bo_tau, time);
+    };
+    size_t nev = 0;
+    // Spans of step launches and of builds share their boundary events: the end of one is the start of the next (an event in the
+    // stream costs the device ~5 us between two kernels: 10-12 us across the two that used to separate a build from the steps)
+    HIPCHK(hipEventRecord(get_event(s, nev++), s->stream));
+    int64_t k = 0;
+    // (an interval that runs on a contact-search list has a wider skin than the force lists: its displacement is no measure
+    // for the interval of those)
+    c.on_search_list = s->list_valid && s->search_list;
+    while (k < chunk) {
+        if (!s->list_valid || s->steps_since_build >= s->pol.K) {
+            s->pol.take_pending_skin(pair_cutoff(s));
+            hipEvent_t e1 = get_event(s, nev++);
+            GDCHK(enqueue_build(s, list_radius(s, run, (uint32_t)(k + s->pol.K)), with_list));
+            s->search_list = false;
+            HIPCHK(hipEventRecord(e1, s->stream));
+            c.spans.push_back({nev - 1, 1});
+            s->list_valid = true;
+        }
+        const int64_t n = std::min<int64_t>((int64_t)s->pol.K - s->steps_since_build, chunk - k);
+        hipEvent_t e1 = get_event(s, nev++);
+        for (int64_t q = 0; q < n; q++) {
+            fill_common(s, p);
+            p.dt_d = run->timestep; p.dt = (float)run->timestep; p.kT = (float)run->temperature; p.seed = run->seed;
+            p.seeds = run->replica_seeds ? s->seeds_d.p : nullptr;
+            p.noise_mode = run->noise_mode; p.run_flags = run->flags; p.comp = comp ? 1 : 0;
+            p.host_noise = host_noise ? s->noise.p + (size_t)(done + k + q) * RN * 3 : nullptr;
+            host_scales(p, k + q);
+            // the interval adaptation needs the displacement at K steps since the build: recorded at the last force
+            // evaluation of a COMPLETE interval only (a chunk that ends mid-interval records nothing and adapts nothing)
+            p.record_disp = (s->steps_since_build + (uint32_t)q + 1u == s->pol.K);
+            c.full_interval |= p.record_disp != 0;
+            gd_launch_step(p, GD_MODE_STEP, s->stream);
+            if (s->sw_n) launch_softwell(s, p, 0);
+            s->pcur ^= 1; s->ccur ^= 1;
+        }
+        HIPCHK(hipEventRecord(e1, s->stream));
+        c.spans.push_back({nev - 1, 0});
+        s->timing.step_launches += (uint64_t)n;
+        s->steps_since_build += (uint32_t)n;
+        k += n;
+    }
+    // apply the callback of the last step (unless the caller wants to observe the state its callback sees first)
+    const bool defer = (run->flags & GD_RUN_DEFER_CALLBACK) && done + chunk == run->steps;
+    if (!defer) {
+        fill_common(s, p);
+        p.dt_d = run->timestep; p.dt = (float)run->timestep; p.run_flags = run->flags;
+        host_scales(p, chunk);
+        gd_launch_finalize(p, 0, s->stream);
+        s->ccur ^= 1;
+    } else { s->pend_dt = run->timestep; s->pend_flags = run->flags; }
+    c.ev_end = nev;
+    HIPCHK(hipEventRecord(get_event(s, nev++), s->stream));
+    return GD_OK;
+}
+
+// Roll a chunk back to the positions, residuals and context before it, without a list.  Every cause of a rollback changes what the
+// retry runs with, so a chunk converges in a few attempts; one that does not is a defect, reported from the restored state.
+static int rollback_chunk(gd_system *s, const Chunk &c, bool over, bool comp, int retries)
+{
+    const size_t RN = (size_t)s->R * s->N;
+    s->rollbacks++;
+    HIPCHK(hipMemcpy2DAsync(s->pos[s->pcur].p, (size_t)s->Np * sizeof(float4), s->snap.p, (size_t)s->N * sizeof(float4),
+                            (size_t)s->N * sizeof(float4), s->R, hipMemcpyDeviceToDevice, s->stream));
+    gd_launch_identity(s->orig[s->ocur].p, s->slot_of.p, s->N, s->Np, s->R, s->stream);
+    if (comp) HIPCHK(hipMemcpyAsync(s->lo.p, s->snap_lo.p, RN * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
+    s->hctx = c.snap_ctx; s->ctx_dirty = true; s->w_packed = c.snap_w_packed;
+    GDCHK(upload_ctx(s));
+    s->list_valid = false; s->bbox_valid = false;      // (the box the abandoned builds recorded may be that of positions stepped on incomplete lists)
+    if (retries > 24) return fail(GD_ESTATE, "gd_run: a chunk of %lld steps at step %lld was rolled back %d times (%s): giving up",
+                                  (long long)c.steps, (long long)s->hctx[0].step, retries, over ? "list / tile / pool overflow" : "skin violation");
+    if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] rollback %llu: %s, K %u, skin %.3f, chunk of %lld steps at step %lld\n", (unsigned long long)s->rollbacks,
+                                       over ? "overflow" : "skin violation", s->pol.K, s->pol.skin, (long long)c.steps, (long long)s->hctx[0].step);
+    if (c.rep.violated && !over && !s->pol.on_violation()) return fail(GD_ESTATE, "gd_run: Verlet skin cannot cover one step (timestep too large?)");
+    s->timing.step_launches -= std::min<uint64_t>(s->timing.step_launches, (uint64_t)c.steps);
+    s->pol.on_rollback(s->sw_n != 0);
+    return GD_OK;
+}
+
+// Accept a chunk: timing, context mirror, then the policy (tiled-path back-off, interval adaptation, skin, repair width)
+static int accept_chunk(gd_system *s, const gd_run_desc *run, const Chunk &c)
+{
+    float ms = 0, step_ms = 0, build_ms = 0;
+    for (auto &sp : c.spans) {
+        HIPCHK(hipEventElapsedTime(&ms, s->events[sp.first - 1], s->events[sp.first]));
+        (sp.second ? build_ms : step_ms) += ms;
+    }
+    HIPCHK(hipEventElapsedTime(&ms, s->events[0], s->events[c.ev_end]));
+    s->timing.total_ms += ms; s->timing.step_kernel_ms += step_ms; s->timing.rebuild_ms += build_ms;
+    s->hctx = c.ctx;
+    unsigned long long L = 0; for (uint32_t r = 0; r < s->R; r++) L += s->lcount[r];
+    s->timing.list_entries_visited += L * (uint64_t)c.steps;   // L of the last build, per step
+    const gd::Accepted a{ms, c.steps, c.rep.maxd2, cut_scale(s, nullptr, 0), c.full_interval, c.on_search_list};
+    if (s->pol.on_accepted(list_state(s), a, [&](uint32_t ahead) { return cut_scale(s, run, ahead); })) s->list_valid = false;
+    return GD_OK;
 }
 
 extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
@@ -1350,13 +1154,13 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
     GDCHK(prepare(s));
     GDCHK(apply_pending(s));
     s->state_serial++;
-    if (run->timestep != s->last_dt || run->temperature != s->last_kT) { s->a2_ema = 0; s->last_dt = run->timestep; s->last_kT = run->temperature; }   // another regime: measure afresh
+    if (run->timestep != s->last_dt || run->temperature != s->last_kT) { s->pol.a2_ema = 0; s->last_dt = run->timestep; s->last_kT = run->temperature; }   // another regime: measure afresh
     // The wall or the scales start (or stop) moving with this run -- a relaxation is followed by the production phase: the
     // displacement statistics the interval was adapted on are those of the other regime, and the first intervals of the new one used
     // to end in a rolled-back chunk every few runs (bench.py: flags 0 for the relaxation, wall dynamics + scale updates after it).
     // A fifth off the interval until complete intervals of the new regime have been measured.
-    if (s->adapt && s->K > 4 && ((run->flags ^ s->last_flags) & (GD_RUN_WALL_DYNAMICS | GD_RUN_UPDATE_SCALES)) != 0 && s->rebuilds > 0)
-        s->K -= s->K / 5;
+    if (s->pol.adapt && s->pol.K > 4 && ((run->flags ^ s->last_flags) & (GD_RUN_WALL_DYNAMICS | GD_RUN_UPDATE_SCALES)) != 0 && s->rebuilds > 0)
+        s->pol.K -= s->pol.K / 5;
     s->last_flags = run->flags;
     const bool with_list = pair_cutoff(s) > 0;
     const size_t RN = (size_t)s->R * s->N;
@@ -1388,200 +1192,24 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
     }
 
     int64_t done = 0;
-    int chunk_retries = 0;     // consecutive rollbacks of the chunk in progress
+    int retries = 0;           // consecutive rollbacks of the chunk in progress
     float last_dmax2 = 0;      // largest bound, over the replicas, of the squared displacement since the build of the positions the last accepted chunk WROTE
     while (done < run->steps) {
-        // ---- one verified chunk
-        // (while the skin sweep is measuring candidates the chunks are shorter -- four rebuild intervals -- so that a sweep costs
-        // a few thousand steps, not tens of thousands)
-        const bool sweeping = s->tuner.enabled && !s->tuner.done && !s->tuner.cand.empty();
-        const int64_t chunk = std::min<int64_t>(run->steps - done, sweeping ? std::min<int64_t>(128, std::max<int64_t>(32, 4ll * s->K))
-                                                                            : std::min<int64_t>(256, std::max<int64_t>(32, 12ll * s->K)));
-        // snapshot for rollback: positions in bead order + context
-        gd_launch_gather_positions(s->pos[s->pcur].p, s->slot_of.p, s->snap.p, s->N, s->Np, s->R, 0, s->stream);
-        if (comp) HIPCHK(hipMemcpyAsync(s->snap_lo.p, s->lo.p, RN * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-        const std::vector<DevCtx> snap_ctx = s->hctx;
-        const bool snap_w_packed = s->w_packed;      // (the snapshot's w is what the positions carried at this point)
-        GDCHK(clear_flags(s));
-
-        StepParams p;
-        // The scales a callback sets are pure functions of the step index (simulation_driver_interphase.cc:42-43): when every
-        // replica is at the same step (the usual case) the host evaluates them and passes them with the launch
-        bool common_step = s->has_scaling && (run->flags & GD_RUN_UPDATE_SCALES);
-        const long long step0 = s->hctx[0].step;
-        for (uint32_t r = 1; r < s->R && common_step; r++) common_step = s->hctx[r].step == step0;
-        auto host_scales = [&](StepParams &q, int64_t launch) {      // launch: index within the chunk of the launch that applies the callback
-            if (!common_step) return;
-            const double time = (double)(step0 + launch) * run->timestep;
-            q.scaling.from_host = 1;
-            q.scaling.bead_next = scale_at(s, s->bs_init, s->bs_tau, time);
-            q.scaling.bond_next = scale_at(s, s->bo_init, s->bo_tau, time);
-        };
-        size_t nev = 0;
-        float step_ms = 0, build_ms = 0;
-        // Spans of step launches and of builds share their boundary events: the end of one is the start of the next (an event in the
-        // stream costs the device ~5 us between two kernels -- kernel trace of one 30 000-bead replica: 0.3 us between two steps,
-        // 10-12 us across the two events that used to separate a build from the steps on either side)
-        std::vector<std::pair<size_t, int>> spans;   // index of the span's end event (its start: the event before it), kind (0 step, 1 build)
-        hipEvent_t ev_begin = get_event(s, nev++);
-        HIPCHK(hipEventRecord(ev_begin, s->stream));
-        int64_t k = 0;
-        bool full_interval = false;      // the chunk contains the last step of a complete K-step interval
-        // (an interval that runs on a contact-search list has a wider skin than the force lists: its displacement is no measure
-        // for the interval of those)
-        bool on_search_list = s->list_valid && s->search_list;
-        while (k < chunk) {
-            if (!s->list_valid || s->steps_since_build >= s->K) {
-                take_pending_skin(s);
-                hipEvent_t e1 = get_event(s, nev++);
-                GDCHK(enqueue_build(s, list_radius(s, run, (uint32_t)(k + s->K)), with_list));
-                s->search_list = false;
-                HIPCHK(hipEventRecord(e1, s->stream));
-                spans.push_back({nev - 1, 1});
-                s->list_valid = true;
-            }
-            const int64_t n = std::min<int64_t>((int64_t)s->K - s->steps_since_build, chunk - k);
-            hipEvent_t e1 = get_event(s, nev++);
-            for (int64_t q = 0; q < n; q++) {
-                fill_common(s, p);
-                p.dt_d = run->timestep; p.dt = (float)run->timestep; p.kT = (float)run->temperature; p.seed = run->seed;
-                p.seeds = run->replica_seeds ? s->seeds_d.p : nullptr;
-                p.noise_mode = run->noise_mode; p.run_flags = run->flags; p.comp = comp ? 1 : 0;
-                p.host_noise = host_noise ? s->noise.p + (size_t)(done + k + q) * RN * 3 : nullptr;
-                host_scales(p, k + q);
-                // the interval adaptation needs the displacement at K steps since the build: recorded at the last force
-                // evaluation of a COMPLETE interval only (a chunk that ends mid-interval records nothing and adapts nothing)
-                p.record_disp = (s->steps_since_build + (uint32_t)q + 1u == s->K);
-                full_interval |= p.record_disp != 0;
-                gd_launch_step(p, GD_MODE_STEP, s->stream);
-                if (s->sw_n) launch_softwell(s, p, 0);
-                s->pcur ^= 1; s->ccur ^= 1;
-            }
-            HIPCHK(hipEventRecord(e1, s->stream));
-            spans.push_back({nev - 1, 0});
-            s->timing.step_launches += (uint64_t)n;
-            s->steps_since_build += (uint32_t)n;
-            k += n;
-        }
-        // apply the callback of the last step (unless the caller wants to observe the state its callback sees first), then
-        // check the chunk
-        const bool defer = (run->flags & GD_RUN_DEFER_CALLBACK) && done + chunk == run->steps;
-        if (!defer) {
-            fill_common(s, p);
-            p.dt_d = run->timestep; p.dt = (float)run->timestep; p.run_flags = run->flags;
-            host_scales(p, chunk);
-            gd_launch_finalize(p, 0, s->stream);
-            s->ccur ^= 1;
-        } else { s->pend_dt = run->timestep; s->pend_flags = run->flags; }
-        hipEvent_t ev_end = get_event(s, nev++);
-        HIPCHK(hipEventRecord(ev_end, s->stream));
-        // one round trip for everything the host wants from the chunk: flags, contexts, list counts
-        std::vector<unsigned> f((size_t)s->R * GD_NFLAGS);
-        std::vector<DevCtx> ctx_new(s->R);
-        HIPCHK(hipGetLastError());
-        {
-            const size_t nf = f.size() * sizeof(unsigned), nc = s->R * sizeof(DevCtx), nl = 2 * (size_t)s->R * sizeof(unsigned long long), nd = s->R * sizeof(float);
-            if (!s->h_chunk) HIPCHK(hipHostMalloc((void **)&s->h_chunk, nf + nc + nl + nd + 16, hipHostMallocDefault));
-            HIPCHK(hipMemcpyAsync(s->h_chunk + nf + nc + nl + nd, s->pool.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));      // the row pool's use
-            HIPCHK(hipMemcpyAsync(s->h_chunk, s->flags.p, nf, hipMemcpyDeviceToHost, s->stream));
-            HIPCHK(hipMemcpyAsync(s->h_chunk + nf, s->ctx[s->ccur].p, nc, hipMemcpyDeviceToHost, s->stream));
-            HIPCHK(hipMemcpyAsync(s->h_chunk + nf + nc, s->lcount_d.p, nl, hipMemcpyDeviceToHost, s->stream));
-            // the running displacement bound of every replica (tiled path; one word per 128-byte line): it covers the positions the
-            // last step WROTE, which no step has checked yet
-            HIPCHK(hipMemcpy2DAsync(s->h_chunk + nf + nc + nl, sizeof(float), s->dmax.p, GD_DMAX_STRIDE * sizeof(unsigned), sizeof(float), s->R,
-                                    hipMemcpyDeviceToHost, s->stream));
-            HIPCHK(hipStreamSynchronize(s->stream));
-            memcpy(f.data(), s->h_chunk, nf); memcpy(ctx_new.data(), s->h_chunk + nf, nc); memcpy(s->lcount.data(), s->h_chunk + nf + nc, nl);
-            last_dmax2 = 0;
-            for (uint32_t r = 0; r < s->R; r++) { float d2; memcpy(&d2, s->h_chunk + nf + nc + nl + r * sizeof(float), 4); last_dmax2 = std::max(last_dmax2, d2); }
-            { unsigned used[4]; memcpy(used, s->h_chunk + nf + nc + nl + nd, 16); if (s->list_tiled && used[0] > 0) { s->pool_used = std::max(used[0], used[1]); s->repairs = used[2]; } }
-        }
-        bool violated = false; float maxd2 = 0;
-        for (uint32_t r = 0; r < s->R; r++) {
-            violated |= f[r * GD_NFLAGS + GD_FLAG_VIOLATION] != 0;
-            float d2; memcpy(&d2, &f[r * GD_NFLAGS + GD_FLAG_MAXDISP2], 4); maxd2 = std::max(maxd2, d2);
-        }
-        const bool over = handle_overflow(s, f);
-        if (violated || over) {
-            // roll the chunk back: restore bead-order positions + context, shorten the interval / widen the list
-            s->rollbacks++;
-            // (every cause of a rollback changes what the retry runs with -- interval, skin, pool, tile class, list path -- so a chunk
-            // converges in a few attempts; a chunk that does not is a defect, reported instead of retried for ever)
-            if (++chunk_retries > 24) return fail(GD_ESTATE, "gd_run: a chunk of %lld steps at step %lld was rolled back %d times (%s): giving up",
-                                                  (long long)chunk, (long long)s->hctx[0].step, chunk_retries, over ? "list / tile / pool overflow" : "skin violation");
-            if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] rollback %llu: %s, K %u, skin %.3f, chunk of %lld steps at step %lld\n", (unsigned long long)s->rollbacks,
-                                               over ? "overflow" : "skin violation", s->K, s->skin, (long long)chunk, (long long)s->hctx[0].step);
-            HIPCHK(hipMemcpy2DAsync(s->pos[s->pcur].p, (size_t)s->Np * sizeof(float4), s->snap.p, (size_t)s->N * sizeof(float4),
-                                    (size_t)s->N * sizeof(float4), s->R, hipMemcpyDeviceToDevice, s->stream));
-            gd_launch_identity(s->orig[s->ocur].p, s->slot_of.p, s->N, s->Np, s->R, s->stream);
-            if (comp) HIPCHK(hipMemcpyAsync(s->lo.p, s->snap_lo.p, RN * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-            s->hctx = snap_ctx; s->ctx_dirty = true; s->w_packed = snap_w_packed;
-            GDCHK(upload_ctx(s));
-            s->list_valid = false;
-            s->bbox_valid = false;      // (the box the abandoned builds recorded may be that of positions stepped on incomplete lists)
-            if (violated && !over) {
-                if (s->K == 1) {
-                    if (s->skin > 8) return fail(GD_ESTATE, "gd_run: Verlet skin cannot cover one step (timestep too large?)");
-                    s->skin *= 1.5;
-                } else { s->K_bad = s->K; s->K_bad_ttl = 64; s->K = std::max(1u, s->K - std::max(1u, s->K / 4)); s->a2_ema = 0; }   // (a gentler cut, K/8 for 32 chunks, violates again sooner: measured 1% slower)
-            }
-            s->timing.step_launches -= std::min<uint64_t>(s->timing.step_launches, (uint64_t)chunk);
-            tune_skin(s, 0.0, 0, false, true);
-            continue;
-        }
-        // accepted: timing, context mirror, cadence adaptation
-        if (s->list_tiled) { s->tiled_backoff = 8; s->tiled_wait = 0; }
-        else if (!s->tiled_ok && s->tiled_off == 1 && ++s->tiled_wait >= s->tiled_backoff) {
-            // the tiled path was left because one tile did not fit (a dense transient, e.g. the start of a relaxation):
-            // try it again at the next build, with the largest tile class; a new overflow costs one rolled-back chunk
-            // and doubles the waiting time
-            s->tiled_ok = true; s->tiled_off = 0; s->tiled_wait = 0; s->tiled_backoff = std::min(2 * s->tiled_backoff, 1024u);
-            s->tile_cap = 8192u;
-        }
-        float ms = 0;
-        for (auto &sp : spans) {
-            HIPCHK(hipEventElapsedTime(&ms, s->events[sp.first - 1], s->events[sp.first]));
-            (sp.second ? build_ms : step_ms) += ms;
-        }
-        HIPCHK(hipEventElapsedTime(&ms, ev_begin, ev_end));
-        s->timing.total_ms += ms; s->timing.step_kernel_ms += step_ms; s->timing.rebuild_ms += build_ms;
-        s->hctx = ctx_new;
-        unsigned long long L = 0;
-        for (uint32_t r = 0; r < s->R; r++) L += s->lcount[r];
-        s->timing.list_entries_visited += L * (uint64_t)chunk;   // L of the last build, per step
-        if (s->adapt && with_list && full_interval && !on_search_list) {
-            const double cut_now = pair_cutoff(s) * (s->pair.scale_by_bead_scale ? bead_scale_bound(s, nullptr, 0) : 1.0);
-            const double lim = 0.5 * (s->rv - cut_now), d = std::sqrt((double)maxd2);
-            if (lim > 0 && d > 0) {
-                // displacement grows ~ sqrt(steps): aim at 90% of the skin at the end of an interval. The maximum over ~2e6 beads
-                // fluctuates by only ~3.5% between intervals (sigma / sqrt(2 ln n)) and the measurement is the largest of a chunk's
-                // (up to 12) intervals, averaged over chunks, i.e. already biased upwards: measured on the benchmark state no rollback
-                // in 40 000 steps at 0.90, the first ones at 0.92; a violation costs one rolled-back chunk and is remembered (K_bad)
-                // (the squared displacement per step of an interval, d^2 / K, is averaged over the chunks -- weight 0.4 for the newest --
-                // so that the interval does not jitter with the single measurement: 12 ... 15 on the benchmark state otherwise)
-                const double a2 = d * d / (double)s->K;
-                s->a2_ema = s->a2_ema > 0 ? 0.6 * s->a2_ema + 0.4 * a2 : a2;
-                static const double target = dev_env("GDYN_K_TARGET") ? atof(dev_env("GDYN_K_TARGET")) : 0.90;
-                double knew = target * lim * target * lim / s->a2_ema;
-                knew = std::min(knew, 2.0 * s->K + 1);
-                s->K = (uint32_t)std::max(1.0, std::min(200.0, std::floor(knew)));
-            } else if (d == 0) s->K = std::min(200u, s->K * 2);
-            if (s->K_bad_ttl > 0) { s->K_bad_ttl--; if (s->K >= s->K_bad) s->K = std::max(1u, s->K_bad - 1); }
-        }
-        if (with_list) tune_skin(s, ms, chunk, full_interval, false);
-        if (with_list && full_interval) class_skin(s, run);
-        done += chunk; chunk_retries = 0;
-        if (s->repair_wide > 0) s->repair_wide--;
+        Chunk c;
+        GDCHK(enqueue_chunk(s, run, done, comp, host_noise, c));
+        GDCHK(read_chunk(s, c));
+        const bool over = s->pol.on_report(list_state(s), c.rep);
+        if (c.rep.violated || over) { GDCHK(rollback_chunk(s, c, over, comp, ++retries)); continue; }
+        GDCHK(accept_chunk(s, run, c));
+        done += c.steps; retries = 0; last_dmax2 = c.dmax2;
     }
-    // The last chunk was accepted: every bead is within the margin the list in use was built for, at the cutoff of the last step.
-    // That is still the cutoff an observation sees when the scales did not move behind that step (callback deferred, or no scale
-    // updates in this run) -- the resident list then serves gd_compute_energy as it is.
-    // (Not with the droplet term: its kernel moves beads behind k_step's check.)
-    // The checks of a step cover the positions it READ; the positions the last step wrote are covered by the running bound of the
-    // tiled path (dmax: triangle bound of the written positions, read back with the chunk): the list serves an observation only if that
-    // bound is inside the margin too.  The generic path keeps no such bound: its observations build a list.
+    // The last chunk was accepted: every bead is within the margin the list in use was built for, at the cutoff of the last step --
+    // still the cutoff an observation sees when the scales did not move behind that step (callback deferred, or no scale updates):
+    // the resident list then serves gd_compute_energy as it is (not with the droplet term: its kernel moves beads behind k_step's
+    // check).  The positions the last step WROTE are covered by the running bound of the tiled path (dmax, read back with the chunk)
+    // only: the list serves an observation if that bound is inside the margin too.  The generic path's observations build a list.
     if (run->steps > 0 && with_list && s->list_valid && !s->sw_n && (!(run->flags & GD_RUN_UPDATE_SCALES) || (run->flags & GD_RUN_DEFER_CALLBACK))) {
-        const double cut_obs = pair_cutoff(s) * (s->pair.scale_by_bead_scale ? bead_scale_bound(s, nullptr, 0) : 1.0);
+        const double cut_obs = pair_cutoff(s) * cut_scale(s, nullptr, 0);
         const double lim = 0.5 * ((double)s->rv - cut_obs);
         if (s->list_tiled && lim > 0 && (double)last_dmax2 <= lim * lim) s->verified_serial = s->state_serial;
     }
@@ -1654,8 +1282,8 @@ static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, 
             // scale over the rest of an interval), like the builds inside gd_run
             gd_run_desc ahead{};
             ahead.timestep = s->last_dt; ahead.flags = s->last_flags;
-            take_pending_skin(s);
-            const float rv_force = with_list ? list_radius(s, s->last_dt > 0 ? &ahead : nullptr, s->K) : 0.f;
+            s->pol.take_pending_skin(pair_cutoff(s));
+            const float rv_force = with_list ? list_radius(s, s->last_dt > 0 ? &ahead : nullptr, s->pol.K) : 0.f;
             const float rv_search = (float)(dcut * (1.0 + 1e-6));
             GDCHK(build_now(s, std::max(rv_force, rv_search), true, true, rv_search));
             s->list_valid = true; s->search_list = rv_search > rv_force;

@@ -1173,7 +1173,7 @@ def test_fp64_positions_survive_the_boundary_and_compensated_runs_on_both_paths(
 
 
 def test_list_width_follows_the_tile_class(hip, oracle):
-    """The default list width is a rule on the state (gdyn_capi.hip, class_skin): 0.9 x cutoff where the largest tile of the wider
+    """The default list width is a rule on the state (gdyn_policy.hpp, ListPolicy::class_skin): 0.9 x cutoff where the largest tile of the wider
     list fits the three-block LDS class (S-genome-30k), 0.75 where it does not (S-genome-62k); a caller-chosen skin stays.  The
     width changes cost only: forces on the state that the wide list produced match the oracle."""
     cut = 0.30
