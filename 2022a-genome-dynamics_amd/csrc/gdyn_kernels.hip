@@ -354,6 +354,198 @@ __device__ __forceinline__ void fill_ctxf(CtxF &o, const DevCtx &c, const StepPa
     }
 }
 
+// ------------------------------------------------------------- k_step terms
+// Force terms of k_step, one function each, in the order the kernel calls them; each adds its force to F (and in energy mode its
+// energy to E).  They are inlined: the kernel is one body as before.
+
+// The thread's bead as the term functions read it, set up by the prologue of k_step
+struct StepBead {
+    float3 xi;              // position
+    float4 xi4;             // position record as read (w: the packed a / b weights)
+    float2 abi;             // a / b weights
+    unsigned meta;          // degree | point-source mask << 8 (generic path: | list length << 16)
+    unsigned oid;           // bead id
+    unsigned local;         // tiled: block-local slot of the bead
+    size_t rbase, g;        // first slot of the replica; the bead's slot in the replica-major arrays
+    const float4 *rpos;     // positions of the replica
+};
+
+// ---- cosine bending over the (up to) three triplets this bead belongs to (a7)
+template <int MODE, bool TILED>
+__device__ __forceinline__ void bending_forces(const StepParams &p, const float4 *s_tile, const StepBead &bead, float3 &F, float &E)
+{
+    const float3 xi = bead.xi;
+    const float4 *__restrict__ rpos = bead.rpos;
+    const float4 be = p.bendE[bead.g];
+    if (be.x != 0.f || be.y != 0.f || be.z != 0.f) {
+        const int4 c4 = p.chain[bead.g];
+        float3 xm2 = xi, xm1 = xi, xp1 = xi, xp2 = xi;
+        auto fetch = [&](int c) -> float3 {
+            float4 t;
+            if (TILED && (c & GD_CHAIN_LOCAL)) t = s_tile[c & 0xffff]; else t = rpos[c];
+            return make_float3(t.x, t.y, t.z);
+        };
+        if (c4.x >= 0) xm2 = fetch(c4.x);
+        if (c4.y >= 0) xm1 = fetch(c4.y);
+        if (c4.z >= 0) xp1 = fetch(c4.z);
+        if (c4.w >= 0) xp2 = fetch(c4.w);
+        float3 fi, fk; float cs;
+        if (be.x != 0.f) {   // (i-2, i-1, i): this bead is the last one
+            const float3 d1 = make_float3(xm1.x - xm2.x, xm1.y - xm2.y, xm1.z - xm2.z);
+            const float3 d2 = make_float3(xi.x - xm1.x, xi.y - xm1.y, xi.z - xm1.z);
+            if (bend_forces(d1, d2, be.x, fi, fk, cs)) { F.x += fk.x; F.y += fk.y; F.z += fk.z; }
+        }
+        if (be.y != 0.f) {   // (i-1, i, i+1): middle
+            const float3 d1 = make_float3(xi.x - xm1.x, xi.y - xm1.y, xi.z - xm1.z);
+            const float3 d2 = make_float3(xp1.x - xi.x, xp1.y - xi.y, xp1.z - xi.z);
+            if (bend_forces(d1, d2, be.y, fi, fk, cs)) {
+                F.x -= fi.x + fk.x; F.y -= fi.y + fk.y; F.z -= fi.z + fk.z;
+                if (MODE == GD_MODE_ENERGY) E += be.y * (1.0f - cs);
+            }
+        }
+        if (be.z != 0.f) {   // (i, i+1, i+2): first
+            const float3 d1 = make_float3(xp1.x - xi.x, xp1.y - xi.y, xp1.z - xi.z);
+            const float3 d2 = make_float3(xp2.x - xp1.x, xp2.y - xp1.y, xp2.z - xp1.z);
+            if (bend_forces(d1, d2, be.z, fi, fk, cs)) { F.x += fi.x; F.y += fi.y; F.z += fi.z; }
+        }
+    }
+}
+
+// ---- point sources (a8)
+template <int MODE>
+__device__ __forceinline__ void point_source_forces(const StepParams &p, const StepBead &bead, float3 &F, float &E)
+{
+    const float3 xi = bead.xi;
+    const unsigned pm = (bead.meta >> 8) & 0xffu;
+    for (int s = 0; s < p.nps; s++) {
+        if (!((pm >> s) & 1u)) continue;
+        const float3 d = make_float3(xi.x - p.ps[s].p[0], xi.y - p.ps[s].p[1], xi.z - p.ps[s].p[2]);
+        const float r2 = d.x * d.x + d.y * d.y + d.z * d.z;
+        float e, fr;
+        bond_pot(p.ps[s].kind, p.ps[s].k, p.ps[s].b, 2, 1, r2, e, fr);
+        F.x += fr * d.x; F.y += fr * d.y; F.z += fr * d.z;
+        if (MODE == GD_MODE_ENERGY) E += e;
+    }
+}
+
+// ---- ellipsoid wall (a9): second-order nearest-surface construction
+// (5-sim-genome/src/analyze_lamina/geometry.py:13-28), conjugate form u = C/(B+sqrt(B^2-AC)).  react receives the bead's share of
+// the axial reaction on the wall.
+template <int MODE>
+__device__ __forceinline__ void ellipsoid_wall_force(const StepParams &p, const CtxF &s_ctx, const StepBead &bead, float3 &F, float &E, float3 &react)
+{
+#ifdef GD_REPLAY
+    if (RP_MEM) return;
+#endif
+    const float3 xi = bead.xi;
+    const float2 abi = bead.abi;
+    const float ia = s_ctx.inv_semi2[0], ib = s_ctx.inv_semi2[1], ic = s_ctx.inv_semi2[2];
+    const float3 s1 = make_float3(xi.x * ia, xi.y * ib, xi.z * ic);
+    const float C1 = xi.x * s1.x + xi.y * s1.y + xi.z * s1.z;
+    // waves of interior beads (the slots are cell-sorted) skip the nearest-point construction altogether
+    if (__builtin_amdgcn_ballot_w64(C1 >= s_ctx.near2) == 0ull) return;
+    // C = C1 - 1 is a difference of two numbers near 1 for every bead the wall acts on (|C| < 0.05): its numerator in fp64
+    // (full-rate on this chip) from the fp64 semiaxes; everything downstream is a product, fp32 is enough there
+    const double xd = (double)xi.x, yd = (double)xi.y, zd = (double)xi.z;
+    const float C = (float)fma(xd * xd, s_ctx.w_q[0], fma(yd * yd, s_ctx.w_q[1], fma(zd * zd, s_ctx.w_q[2], -s_ctx.w_q[3]))) * s_ctx.w_inv_q3;
+    const float B = s1.x * s1.x + s1.y * s1.y + s1.z * s1.z;
+    const float A = s1.x * s1.x * ia + s1.y * s1.y * ib + s1.z * s1.z * ic;
+    // (hardware sqrt / rcp, 1 ulp: the IEEE-exact sequences are ~10 instructions each)
+    const float den = B + __builtin_amdgcn_sqrtf(fmaxf(B * B - A * C, 0.f));
+    if (den > 0.f && C != 0.f) {
+        const float u = C * __builtin_amdgcn_rcpf(den);
+        const float3 dl = make_float3(u * s1.x, u * s1.y, u * s1.z);
+        const float r2 = dl.x * dl.x + dl.y * dl.y + dl.z * dl.z;
+        float e = 0.f, fr = 0.f;
+        if (C < 0.f) {
+            const float wa = 0.5f * (abi.x + p.wall.wall_a), wb = 0.5f * (abi.y + p.wall.wall_b);
+            if (p.wall.fast2383 && MODE != GD_MODE_ENERGY) {
+                // the wall's soft cores are the pair family (<2,3> + <8,3>, half diameters): branch-free form
+                fr = softcore_2383(r2, s_ctx.w_inv_sa2, s_ctx.w_inv_sb2, wa * s_ctx.w_ca, wb * s_ctx.w_cb);
+            } else {
+                float ea, fa, eb, fb;
+                softcore(p.wall.eps_a, s_ctx.w_inv_sa2, p.wall.p_a, p.wall.q_a, r2, ea, fa);
+                softcore(p.wall.eps_b, s_ctx.w_inv_sb2, p.wall.p_b, p.wall.q_b, r2, eb, fb);
+                e = wa * ea + wb * eb; fr = wa * fa + wb * fb;
+            }
+        } else {
+            e = 0.5f * p.wall.packing_spring * r2; fr = -p.wall.packing_spring;
+        }
+        if (fr != 0.f) {
+            const float3 fw = make_float3(fr * dl.x, fr * dl.y, fr * dl.z);
+            F.x += fw.x; F.y += fw.y; F.z += fw.z;
+            // axial_reaction_k = -F_k q_k / a_k, q = contact point on the surface
+            react.x = -fw.x * (xi.x - dl.x) * s_ctx.inv_semi[0];
+            react.y = -fw.y * (xi.y - dl.y) * s_ctx.inv_semi[1];
+            react.z = -fw.z * (xi.z - dl.z) * s_ctx.inv_semi[2];
+        }
+        if (MODE == GD_MODE_ENERGY) E += e;
+    }
+}
+
+// ---- inner spherical wall (excluded core of the 4-sim-ab sphere model): soft repulsion outside, harmonic inside
+template <int MODE>
+__device__ __forceinline__ void inner_wall_force(const StepParams &p, const StepBead &bead, float3 &F, float &E)
+{
+    const float3 xi = bead.xi;
+    const float2 abi = bead.abi;
+    const float rr2 = xi.x * xi.x + xi.y * xi.y + xi.z * xi.z;
+    const float reach = p.wall.in_radius + 0.5f * fmaxf(p.wall.in_sigma_a, p.wall.in_sigma_b);
+    if (__builtin_amdgcn_ballot_w64(rr2 < reach * reach) != 0ull && rr2 > 0.f) {
+        const float inv_r = rsqrtf(rr2), rad = rr2 * inv_r, gap = rad - p.wall.in_radius;
+        const float r2 = gap * gap, gs = gap * inv_r;          // delta = gs * x
+        float e = 0.f, fr = 0.f;
+        if (gap > 0.f) {
+            const float sa = 0.5f * p.wall.in_sigma_a, sb = 0.5f * p.wall.in_sigma_b;
+            const float wa = 0.5f * (abi.x + p.wall.in_wall_a), wb = 0.5f * (abi.y + p.wall.in_wall_b);
+            float ea, fa, eb, fb;
+            softcore(p.wall.in_eps_a, sa > 0.f ? 1.0f / (sa * sa) : 0.f, p.wall.in_p_a, p.wall.in_q_a, r2, ea, fa);
+            softcore(p.wall.in_eps_b, sb > 0.f ? 1.0f / (sb * sb) : 0.f, p.wall.in_p_b, p.wall.in_q_b, r2, eb, fb);
+            e = wa * ea + wb * eb; fr = wa * fa + wb * fb;
+        } else if (gap < 0.f) {
+            e = 0.5f * p.wall.in_spring * r2; fr = -p.wall.in_spring;
+        }
+        F.x += fr * gs * xi.x; F.y += fr * gs * xi.y; F.z += fr * gs * xi.z;
+        if (MODE == GD_MODE_ENERGY) E += e;
+    }
+}
+
+// ---- overdamped Langevin / Euler-Maruyama (a1): x += mu F dt + sqrt(2 mu kT dt) z, stored to pos_out.  Returns (tiled path) the
+// bound on the new position's squared displacement since the build, for the far-class test of the next step; disp2 is the old one.
+template <bool TILED>
+__device__ __forceinline__ float integrate(const StepParams &p, const CtxF &s_ctx, const StepBead &bead, unsigned r, unsigned blk,
+                                           float mu, const float3 &z, const float3 &F, float disp2)
+{
+    const float3 xi = bead.xi;
+    const float mu_dt = mu * p.dt;
+    const float sg = s_ctx.sg_uniform >= 0.f ? s_ctx.sg_uniform : sqrtf(2.0f * p.kT * mu_dt);
+    const float ex = mu_dt * F.x + sg * z.x, ey = mu_dt * F.y + sg * z.y, ez = mu_dt * F.z + sg * z.z;
+    float nx = xi.x + ex, ny = xi.y + ey, nz = xi.z + ez;
+    if (p.comp) {
+        // Compensated update (uniform branch; gd_run selects it when the increment of a step is within a few ulp of an
+        // fp32 coordinate: the reference's deterministic fine-sampling run, T = 0 and dt = 1e-7,
+        // simulation_fine_sampling/simulation_driver.cc:30-34, moves a bead by 1e-7 ... 2e-6 per step at |x| of 3 ... 8,
+        // i.e. by 0.1 ... 4 ulp).  The bead's true position is x + lo; the increment is added to the residual first and
+        // the pair is re-normalised by a two-sum (Knuth; exact in round-to-nearest whatever the magnitudes), so that no
+        // part of mu F dt is lost.  Forces are evaluated on x alone: |lo| <= ulp(x) / 2, the rounding every fp32
+        // position carries anyway.  The residual lives by BEAD index, outside the cell sort.
+        float4 *lp = p.lo + ((size_t)r * p.N + bead.oid);
+        const float4 l = *lp;
+        const float tx = l.x + ex, ty = l.y + ey, tz = l.z + ez;
+        nx = xi.x + tx; ny = xi.y + ty; nz = xi.z + tz;
+        const float bx = nx - xi.x, by = ny - xi.y, bz = nz - xi.z;
+        *lp = make_float4((xi.x - (nx - bx)) + (tx - bx), (xi.y - (ny - by)) + (ty - by), (xi.z - (nz - bz)) + (tz - bz), 0.f);
+    }
+    if (TILED) *(float4 *)((char *)(p.pos_out + bead.rbase + (size_t)blk * GD_BLOCK) + bead.local * 16u) = make_float4(nx, ny, nz, bead.xi4.w);
+    else p.pos_out[bead.g] = make_float4(nx, ny, nz, bead.xi4.w);
+    // displacement of the NEW position since the build, bounded by the triangle inequality (the build position
+    // need not stay in registers): |x + dx - x0| <= |x - x0| + |dx|
+    // ((d + e)^2 = d^2 + e^2 + 2 sqrt(d^2 e^2): one square root)
+    float dnew2 = 0.f;
+    if (TILED) { const float e2 = ex * ex + ey * ey + ez * ez; dnew2 = (disp2 + e2 + 2.0f * __builtin_amdgcn_sqrtf(disp2 * e2)) * 1.000002f; }
+    return dnew2;
+}
+
 // ------------------------------------------------------------------- k_step
 // TILED: the block first stages its LDS tile (its own 256 slots + all slots of the adjacent
 // cells, 9 contiguous slot ranges, TileDesc) with coalesced loads; pair-list entries are 16-bit
@@ -580,6 +772,7 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
         const float3 xi = make_float3(xi4.x, xi4.y, xi4.z);
         const float2 *__restrict__ rab = p.ab + rbase;
         const float2 abi = p.packed_ab ? unpack_ab(xi4.w) : p.ab[g];
+        const StepBead bead = {xi, xi4, abi, meta, oid, local, rbase, g, rpos};
 
         // ---- non-bonded pairs over the Verlet list (a3, a5)
         if (p.pair.enabled && (mask & TERM_PAIR)) {
@@ -798,10 +991,7 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     xjs[u] = xi4;
-                    if (k0 + u < deg) {
-                        const unsigned j = ents[u] & GD_ADJ_MASK;
-                        if (TILED && (ents[u] & GD_ADJ_LOCAL)) xjs[u] = s_tile[j]; else xjs[u] = rpos[j];
-                    }
+                    if (k0 + u < deg) xjs[u] = rpos[ents[u] & GD_ADJ_MASK];
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
@@ -816,7 +1006,7 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
                     const float r2 = d.x * d.x + d.y * d.y + d.z * d.z;
                     float K = bt.ka, l = bt.la;
                     if (bt.flags & 1) {
-                        const float2 abj = (TILED || p.packed_ab) ? unpack_ab(xj.w) : rab[j];
+                        const float2 abj = p.packed_ab ? unpack_ab(xj.w) : rab[j];
                         const float a = 0.5f * (abi.x + abj.x), b = 0.5f * (abi.y + abj.y);
                         K = a * bt.ka + b * bt.kb; l = a * bt.la + b * bt.lb;
                     }
@@ -838,160 +1028,16 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
         }
 
         GD_STAMP(3);  // bonds
-        // ---- cosine bending over the (up to) three triplets this bead belongs to (a7)
-        if (p.has_bend && (mask & TERM_BEND)) {
-            const float4 be = p.bendE[g];
-            if (be.x != 0.f || be.y != 0.f || be.z != 0.f) {
-                const int4 c4 = p.chain[g];
-                float3 xm2 = xi, xm1 = xi, xp1 = xi, xp2 = xi;
-                auto fetch = [&](int c) -> float3 {
-                    float4 t;
-                    if (TILED && (c & GD_CHAIN_LOCAL)) t = s_tile[c & 0xffff]; else t = rpos[c];
-                    return make_float3(t.x, t.y, t.z);
-                };
-                if (c4.x >= 0) xm2 = fetch(c4.x);
-                if (c4.y >= 0) xm1 = fetch(c4.y);
-                if (c4.z >= 0) xp1 = fetch(c4.z);
-                if (c4.w >= 0) xp2 = fetch(c4.w);
-                float3 fi, fk; float cs;
-                if (be.x != 0.f) {   // (i-2, i-1, i): this bead is the last one
-                    const float3 d1 = make_float3(xm1.x - xm2.x, xm1.y - xm2.y, xm1.z - xm2.z);
-                    const float3 d2 = make_float3(xi.x - xm1.x, xi.y - xm1.y, xi.z - xm1.z);
-                    if (bend_forces(d1, d2, be.x, fi, fk, cs)) { F.x += fk.x; F.y += fk.y; F.z += fk.z; }
-                }
-                if (be.y != 0.f) {   // (i-1, i, i+1): middle
-                    const float3 d1 = make_float3(xi.x - xm1.x, xi.y - xm1.y, xi.z - xm1.z);
-                    const float3 d2 = make_float3(xp1.x - xi.x, xp1.y - xi.y, xp1.z - xi.z);
-                    if (bend_forces(d1, d2, be.y, fi, fk, cs)) {
-                        F.x -= fi.x + fk.x; F.y -= fi.y + fk.y; F.z -= fi.z + fk.z;
-                        if (MODE == GD_MODE_ENERGY) E += be.y * (1.0f - cs);
-                    }
-                }
-                if (be.z != 0.f) {   // (i, i+1, i+2): first
-                    const float3 d1 = make_float3(xp1.x - xi.x, xp1.y - xi.y, xp1.z - xi.z);
-                    const float3 d2 = make_float3(xp2.x - xp1.x, xp2.y - xp1.y, xp2.z - xp1.z);
-                    if (bend_forces(d1, d2, be.z, fi, fk, cs)) { F.x += fi.x; F.y += fi.y; F.z += fi.z; }
-                }
-            }
-        }
-
-        // ---- point sources (a8)
-        if (p.nps > 0 && (mask & TERM_POINT)) {
-            const unsigned pm = (meta >> 8) & 0xffu;
-            for (int s = 0; s < p.nps; s++) {
-                if (!((pm >> s) & 1u)) continue;
-                const float3 d = make_float3(xi.x - p.ps[s].p[0], xi.y - p.ps[s].p[1], xi.z - p.ps[s].p[2]);
-                const float r2 = d.x * d.x + d.y * d.y + d.z * d.z;
-                float e, fr;
-                bond_pot(p.ps[s].kind, p.ps[s].k, p.ps[s].b, 2, 1, r2, e, fr);
-                F.x += fr * d.x; F.y += fr * d.y; F.z += fr * d.z;
-                if (MODE == GD_MODE_ENERGY) E += e;
-            }
-        }
+        if (p.has_bend && (mask & TERM_BEND)) bending_forces<MODE, TILED>(p, s_tile, bead, F, E);
+        if (p.nps > 0 && (mask & TERM_POINT)) point_source_forces<MODE>(p, bead, F, E);
 
         GD_STAMP(4);  // bending + point sources
-        // ---- ellipsoid wall (a9): second-order nearest-surface construction
-        // (5-sim-genome/src/analyze_lamina/geometry.py:13-28), conjugate form u = C/(B+sqrt(B^2-AC)).
-#ifdef GD_REPLAY
-        if (!RP_MEM)
-#endif
-        if (p.wall.enabled && (mask & TERM_WALL)) {
-            const float ia = s_ctx.inv_semi2[0], ib = s_ctx.inv_semi2[1], ic = s_ctx.inv_semi2[2];
-            const float3 s1 = make_float3(xi.x * ia, xi.y * ib, xi.z * ic);
-            const float C1 = xi.x * s1.x + xi.y * s1.y + xi.z * s1.z;
-            // waves of interior beads (the slots are cell-sorted) skip the nearest-point construction altogether
-            if (__builtin_amdgcn_ballot_w64(C1 >= s_ctx.near2) != 0ull) {
-            // C = C1 - 1 is a difference of two numbers near 1 for every bead the wall acts on (|C| < 0.05): its numerator in fp64
-            // (full-rate on this chip) from the fp64 semiaxes; everything downstream is a product, fp32 is enough there
-            const double xd = (double)xi.x, yd = (double)xi.y, zd = (double)xi.z;
-            const float C = (float)fma(xd * xd, s_ctx.w_q[0], fma(yd * yd, s_ctx.w_q[1], fma(zd * zd, s_ctx.w_q[2], -s_ctx.w_q[3]))) * s_ctx.w_inv_q3;
-            const float B = s1.x * s1.x + s1.y * s1.y + s1.z * s1.z;
-            const float A = s1.x * s1.x * ia + s1.y * s1.y * ib + s1.z * s1.z * ic;
-            // (hardware sqrt / rcp, 1 ulp: the IEEE-exact sequences are ~10 instructions each)
-            const float den = B + __builtin_amdgcn_sqrtf(fmaxf(B * B - A * C, 0.f));
-            if (den > 0.f && C != 0.f) {
-                const float u = C * __builtin_amdgcn_rcpf(den);
-                const float3 dl = make_float3(u * s1.x, u * s1.y, u * s1.z);
-                const float r2 = dl.x * dl.x + dl.y * dl.y + dl.z * dl.z;
-                float e = 0.f, fr = 0.f;
-                if (C < 0.f) {
-                    const float wa = 0.5f * (abi.x + p.wall.wall_a), wb = 0.5f * (abi.y + p.wall.wall_b);
-                    if (p.wall.fast2383 && MODE != GD_MODE_ENERGY) {
-                        // the wall's soft cores are the pair family (<2,3> + <8,3>, half diameters): branch-free form
-                        fr = softcore_2383(r2, s_ctx.w_inv_sa2, s_ctx.w_inv_sb2, wa * s_ctx.w_ca, wb * s_ctx.w_cb);
-                    } else {
-                        float ea, fa, eb, fb;
-                        softcore(p.wall.eps_a, s_ctx.w_inv_sa2, p.wall.p_a, p.wall.q_a, r2, ea, fa);
-                        softcore(p.wall.eps_b, s_ctx.w_inv_sb2, p.wall.p_b, p.wall.q_b, r2, eb, fb);
-                        e = wa * ea + wb * eb; fr = wa * fa + wb * fb;
-                    }
-                } else {
-                    e = 0.5f * p.wall.packing_spring * r2; fr = -p.wall.packing_spring;
-                }
-                if (fr != 0.f) {
-                    const float3 fw = make_float3(fr * dl.x, fr * dl.y, fr * dl.z);
-                    F.x += fw.x; F.y += fw.y; F.z += fw.z;
-                    // axial_reaction_k = -F_k q_k / a_k, q = contact point on the surface
-                    react.x = -fw.x * (xi.x - dl.x) * s_ctx.inv_semi[0];
-                    react.y = -fw.y * (xi.y - dl.y) * s_ctx.inv_semi[1];
-                    react.z = -fw.z * (xi.z - dl.z) * s_ctx.inv_semi[2];
-                }
-                if (MODE == GD_MODE_ENERGY) E += e;
-            }
-            }
-        }
-
-        // ---- inner spherical wall (excluded core of the 4-sim-ab sphere model): soft repulsion outside, harmonic inside
-        if (p.wall.inner_enabled && (mask & TERM_WALL)) {
-            const float rr2 = xi.x * xi.x + xi.y * xi.y + xi.z * xi.z;
-            const float reach = p.wall.in_radius + 0.5f * fmaxf(p.wall.in_sigma_a, p.wall.in_sigma_b);
-            if (__builtin_amdgcn_ballot_w64(rr2 < reach * reach) != 0ull && rr2 > 0.f) {
-                const float inv_r = rsqrtf(rr2), rad = rr2 * inv_r, gap = rad - p.wall.in_radius;
-                const float r2 = gap * gap, gs = gap * inv_r;          // delta = gs * x
-                float e = 0.f, fr = 0.f;
-                if (gap > 0.f) {
-                    const float sa = 0.5f * p.wall.in_sigma_a, sb = 0.5f * p.wall.in_sigma_b;
-                    const float wa = 0.5f * (abi.x + p.wall.in_wall_a), wb = 0.5f * (abi.y + p.wall.in_wall_b);
-                    float ea, fa, eb, fb;
-                    softcore(p.wall.in_eps_a, sa > 0.f ? 1.0f / (sa * sa) : 0.f, p.wall.in_p_a, p.wall.in_q_a, r2, ea, fa);
-                    softcore(p.wall.in_eps_b, sb > 0.f ? 1.0f / (sb * sb) : 0.f, p.wall.in_p_b, p.wall.in_q_b, r2, eb, fb);
-                    e = wa * ea + wb * eb; fr = wa * fa + wb * fb;
-                } else if (gap < 0.f) {
-                    e = 0.5f * p.wall.in_spring * r2; fr = -p.wall.in_spring;
-                }
-                F.x += fr * gs * xi.x; F.y += fr * gs * xi.y; F.z += fr * gs * xi.z;
-                if (MODE == GD_MODE_ENERGY) E += e;
-            }
-        }
+        if (p.wall.enabled && (mask & TERM_WALL)) ellipsoid_wall_force<MODE>(p, s_ctx, bead, F, E, react);
+        if (p.wall.inner_enabled && (mask & TERM_WALL)) inner_wall_force<MODE>(p, bead, F, E);
 
         if (MODE == GD_MODE_STEP) {
             GD_STAMP(5);  // wall
-            // ---- overdamped Langevin / Euler-Maruyama (a1): x += mu F dt + sqrt(2 mu kT dt) xi
-            const float mu_dt = mu * p.dt;
-            const float sg = s_ctx.sg_uniform >= 0.f ? s_ctx.sg_uniform : sqrtf(2.0f * p.kT * mu_dt);
-            const float ex = mu_dt * F.x + sg * z.x, ey = mu_dt * F.y + sg * z.y, ez = mu_dt * F.z + sg * z.z;
-            float nx = xi.x + ex, ny = xi.y + ey, nz = xi.z + ez;
-            if (p.comp) {
-                // Compensated update (uniform branch; gd_run selects it when the increment of a step is within a few ulp of an
-                // fp32 coordinate: the reference's deterministic fine-sampling run, T = 0 and dt = 1e-7,
-                // simulation_fine_sampling/simulation_driver.cc:30-34, moves a bead by 1e-7 ... 2e-6 per step at |x| of 3 ... 8,
-                // i.e. by 0.1 ... 4 ulp).  The bead's true position is x + lo; the increment is added to the residual first and
-                // the pair is re-normalised by a two-sum (Knuth; exact in round-to-nearest whatever the magnitudes), so that no
-                // part of mu F dt is lost.  Forces are evaluated on x alone: |lo| <= ulp(x) / 2, the rounding every fp32
-                // position carries anyway.  The residual lives by BEAD index, outside the cell sort.
-                float4 *lp = p.lo + ((size_t)r * p.N + oid);
-                const float4 l = *lp;
-                const float tx = l.x + ex, ty = l.y + ey, tz = l.z + ez;
-                nx = xi.x + tx; ny = xi.y + ty; nz = xi.z + tz;
-                const float bx = nx - xi.x, by = ny - xi.y, bz = nz - xi.z;
-                *lp = make_float4((xi.x - (nx - bx)) + (tx - bx), (xi.y - (ny - by)) + (ty - by), (xi.z - (nz - bz)) + (tz - bz), 0.f);
-            }
-            if (TILED) *(float4 *)((char *)(p.pos_out + rbase + (size_t)blk * GD_BLOCK) + local * 16u) = make_float4(nx, ny, nz, xi4.w);
-            else p.pos_out[g] = make_float4(nx, ny, nz, xi4.w);
-            // displacement of the NEW position since the build, bounded by the triangle inequality (the build position
-            // need not stay in registers): |x + dx - x0| <= |x - x0| + |dx|
-            // ((d + e)^2 = d^2 + e^2 + 2 sqrt(d^2 e^2): one square root)
-            if (TILED) { const float e2 = ex * ex + ey * ey + ez * ez; dnew2 = (disp2 + e2 + 2.0f * __builtin_amdgcn_sqrtf(disp2 * e2)) * 1.000002f; }
+            dnew2 = integrate<TILED>(p, s_ctx, bead, r, blk, mu, z, F, disp2);
         } else if (MODE == GD_MODE_FORCE) {
             p.fout[(size_t)r * p.N + oid] = make_float4(F.x, F.y, F.z, 0.f);
         }
@@ -1059,6 +1105,29 @@ __global__ __launch_bounds__(64) void k_ctx(const StepParams p, int mode)
     if (lane == 0) p.ctx_out[r] = c;
 }
 
+// The k_step instantiation of a launch: the one map from (MODE, SPLIT, periodic, tiled, pk, s16) to a variant, used by the launches
+// below and by the LDS opt-in (gd_kernels_init_device, which takes the tiled variants only).  A step split by tile class is tiled; the
+// generic path has plain-index lists only.
+typedef void (*StepKernel)(StepParams);
+template <int MODE, bool SPLIT, bool PER, bool TIL, bool S16>
+static StepKernel step_kernel_pk(int pk)
+{
+    return pk == 1 ? k_step<MODE, PER, TIL, 1, S16, SPLIT> : pk == 2 ? k_step<MODE, PER, TIL, 2, S16, SPLIT> : k_step<MODE, PER, TIL, 0, S16, SPLIT>;
+}
+template <int MODE, bool SPLIT>
+static StepKernel tiled_step_kernel(bool periodic, int pk, bool s16)
+{
+    static_assert(!SPLIT || MODE == GD_MODE_STEP, "only stepping is split by tile class");
+    if (periodic) return s16 ? step_kernel_pk<MODE, SPLIT, true, true, true>(pk) : step_kernel_pk<MODE, SPLIT, true, true, false>(pk);
+    return s16 ? step_kernel_pk<MODE, SPLIT, false, true, true>(pk) : step_kernel_pk<MODE, SPLIT, false, true, false>(pk);
+}
+template <int MODE>
+static StepKernel step_kernel(bool periodic, bool tiled, int pk, bool s16)
+{
+    if (tiled) return tiled_step_kernel<MODE, false>(periodic, pk, s16);
+    return periodic ? step_kernel_pk<MODE, false, true, false, false>(pk) : step_kernel_pk<MODE, false, false, false, false>(pk);
+}
+
 template <int MODE>
 static void launch_step_mode(const StepParams &p, hipStream_t st)
 {
@@ -1076,30 +1145,16 @@ static void launch_step_mode(const StepParams &p, hipStream_t st)
     // 80 registers, so the blocks with small tiles run three to a CU next to the few large ones.)
     const unsigned split_at = !p.tiled ? 0u : (s16 && p.tile_cap > 3312u) ? 3312u : (!s16 && p.tile_cap > 5072u) ? 5072u : (!s16 && p.tile_cap > 3312u) ? 3312u : 0u;
     if (MODE == GD_MODE_STEP && split_at) {
+        const StepKernel k = tiled_step_kernel<GD_MODE_STEP, true>(p.periodic, p.pk, s16);
         StepParams q = p;
         for (int half = 0; half < 2; half++) {
             q.tile_cap = half ? p.tile_cap : split_at; q.tile_lo = half ? split_at : 0u; q.tile_hi = half ? 0xffffffffu : split_at;
-            const size_t lds_q = (size_t)q.tile_cap * sizeof(float4);
-#define LS(PER, PK, S) hipLaunchKernelGGL((k_step<GD_MODE_STEP, PER, true, PK, S, true>), grid, block, lds_q, st, q)
-            if (s16) {
-                if (p.periodic) { if (p.pk == 1) LS(true, 1, true); else if (p.pk == 2) LS(true, 2, true); else LS(true, 0, true); }
-                else { if (p.pk == 1) LS(false, 1, true); else if (p.pk == 2) LS(false, 2, true); else LS(false, 0, true); }
-            } else {
-                if (p.periodic) { if (p.pk == 1) LS(true, 1, false); else if (p.pk == 2) LS(true, 2, false); else LS(true, 0, false); }
-                else { if (p.pk == 1) LS(false, 1, false); else if (p.pk == 2) LS(false, 2, false); else LS(false, 0, false); }
-            }
-#undef LS
+            hipLaunchKernelGGL(k, grid, block, (size_t)q.tile_cap * sizeof(float4), st, q);
         }
         return;
     }
-#define L(PER, TIL, PK, S) hipLaunchKernelGGL((k_step<MODE, PER, TIL, PK, S>), grid, block, lds, st, p)
-    if (p.periodic && p.tiled && s16) { if (p.pk == 1) L(true, true, 1, true); else if (p.pk == 2) L(true, true, 2, true); else L(true, true, 0, true); }
-    else if (p.periodic && p.tiled) { if (p.pk == 1) L(true, true, 1, false); else if (p.pk == 2) L(true, true, 2, false); else L(true, true, 0, false); }
-    else if (p.periodic) { if (p.pk == 1) L(true, false, 1, false); else if (p.pk == 2) L(true, false, 2, false); else L(true, false, 0, false); }
-    else if (p.tiled && s16) { if (p.pk == 1) L(false, true, 1, true); else if (p.pk == 2) L(false, true, 2, true); else L(false, true, 0, true); }
-    else if (p.tiled) { if (p.pk == 1) L(false, true, 1, false); else if (p.pk == 2) L(false, true, 2, false); else L(false, true, 0, false); }
-    else { if (p.pk == 1) L(false, false, 1, false); else if (p.pk == 2) L(false, false, 2, false); else L(false, false, 0, false); }
-#undef L
+    const StepKernel k = step_kernel<MODE>(p.periodic, p.tiled, p.pk, s16);
+    hipLaunchKernelGGL(k, grid, block, lds, st, p);
 }
 
 void gd_launch_step(const StepParams &p, int mode, hipStream_t st)
@@ -2478,14 +2533,12 @@ hipError_t gd_kernels_init_device(void)
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess && first == hipSuccess) first = e;
     };
-#define GD_AS(MODE, PER, PK, S, SP) set(reinterpret_cast<const void *>(&k_step<MODE, PER, true, PK, S, SP>), 128 * 1024)
-#define GD_AS_PK(MODE, PER, S, SP) GD_AS(MODE, PER, 0, S, SP); GD_AS(MODE, PER, 1, S, SP); GD_AS(MODE, PER, 2, S, SP)
-#define GD_AS_ALL(MODE, SP) GD_AS_PK(MODE, false, false, SP); GD_AS_PK(MODE, false, true, SP); GD_AS_PK(MODE, true, false, SP); GD_AS_PK(MODE, true, true, SP)
-    GD_AS_ALL(GD_MODE_STEP, false); GD_AS_ALL(GD_MODE_STEP, true);
-    GD_AS_ALL(GD_MODE_FORCE, false); GD_AS_ALL(GD_MODE_ENERGY, false);
-#undef GD_AS_ALL
-#undef GD_AS_PK
-#undef GD_AS
+    // every tiled k_step variant a launch can pick (launch_step_mode)
+    for (auto pick : {tiled_step_kernel<GD_MODE_STEP, false>, tiled_step_kernel<GD_MODE_STEP, true>, tiled_step_kernel<GD_MODE_FORCE, false>,
+                      tiled_step_kernel<GD_MODE_ENERGY, false>})
+        for (int per = 0; per < 2; per++)
+            for (int pk = 0; pk < 3; pk++)
+                for (int s16 = 0; s16 < 2; s16++) set(reinterpret_cast<const void *>(pick(per != 0, pk, s16 != 0)), 128 * 1024);
     set(reinterpret_cast<const void *>(&k_fill<false, true, false>), 128 * 1024);
     set(reinterpret_cast<const void *>(&k_fill<false, true, true>), 128 * 1024);
     set(reinterpret_cast<const void *>(&k_fill<true, true, false>), 128 * 1024);
