@@ -9,6 +9,8 @@
 //   gd_h5tool put-positions-f64 <file> <phase> <step> <in.f64>   replaces the snapshot with a float64 positions dataset (refine/run.py:41-46)
 //   gd_h5tool put-positions <file> <phase> <step> <in.f64>   a float32 snapshot quantised to 2^-16 (trajectory_store::save_positions);
 //        creates the file if it does not exist
+//   gd_h5tool put-context <file> <phase> <step> <a> <b> <c>   the snapshot's context JSON with wall_semiaxes [a, b, c] (the other
+//        fields at their defaults), beside put-positions: what the lamina analysis reads
 //   gd_h5tool steps <file> <phase>                     numerically ordered step list
 //   gd_h5tool positions <file> <phase> <step> <out.f64>
 //   gd_h5tool context <file> <phase> <step>            prints the JSON context fields
@@ -157,6 +159,14 @@ int main(int argc, char **argv)
             store.save_positions(std::stol(argv[4]), reinterpret_cast<double const *>(raw.data()), raw.size() / (3 * sizeof(double)));
             return 0;
         }
+        if (cmd == "put-context" && argc == 8) {
+            gd::trajectory_store store(argv[2]);
+            store.set_phase(argv[3]);
+            gd::context c;
+            for (int k = 0; k < 3; k++) c.wall_semiaxes[k] = std::stod(argv[5 + k]);
+            store.save_context(std::stol(argv[4]), c);
+            return 0;
+        }
         if (cmd == "steps" && argc == 4) {
             gd::trajectory_store store(argv[2]);
             store.set_phase(argv[3]);
@@ -294,7 +304,7 @@ int main(int argc, char **argv)
             else for (auto const &s : gd::h5::read_string_list(loc, name)) std::cout << s << '\n';
             return 0;
         }
-        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|steps|positions|context|contacts|dataset|strings ...\n";
+        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|put-context|steps|positions|context|contacts|dataset|strings ...\n";
         return 1;
     } catch (std::exception const &e) {
         std::cerr << "error: " << e.what() << '\n';
