@@ -11,6 +11,8 @@
 //        creates the file if it does not exist
 //   gd_h5tool put-context <file> <phase> <step> <a> <b> <c>   the snapshot's context JSON with wall_semiaxes [a, b, c] (the other
 //        fields at their defaults), beside put-positions: what the lamina analysis reads
+//   gd_h5tool put-contacts <file> <phase> <step> <rows.u32>   the snapshot's contact_map from raw little-endian uint32 (M,3) rows
+//        (i, j, count), beside put-positions: what the contact-map analyses read; creates the file if it does not exist
 //   gd_h5tool steps <file> <phase>                     numerically ordered step list
 //   gd_h5tool positions <file> <phase> <step> <out.f64>
 //   gd_h5tool context <file> <phase> <step>            prints the JSON context fields
@@ -21,9 +23,11 @@
 //        submitting thread, the pool runs every index once and rethrows
 //   gd_h5tool packed-check <file> <rows>               the same (rows,3) uint32 and float arrays written by the library's filter pipeline and
 //        as hand-packed chunks on a thread pool (gd_h5util.hpp, gd_async_io.hpp); reads both back, compares values, chunking and filters
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -167,6 +171,17 @@ int main(int argc, char **argv)
             store.save_context(std::stol(argv[4]), c);
             return 0;
         }
+        if (cmd == "put-contacts" && argc == 6) {
+            auto const raw = slurp(argv[5]);
+            if (raw.size() % (3 * sizeof(std::uint32_t))) throw std::runtime_error("rows file is not (M,3) uint32");
+            std::vector<std::array<std::uint32_t, 3>> rows(raw.size() / (3 * sizeof(std::uint32_t)));
+            if (!rows.empty()) std::memcpy(rows[0].data(), raw.data(), raw.size());
+            bool const create = !std::ifstream(argv[2]).good();
+            gd::trajectory_store store(argv[2], create);
+            store.set_phase(argv[3]);
+            store.save_contacts(std::stol(argv[4]), rows);
+            return 0;
+        }
         if (cmd == "steps" && argc == 4) {
             gd::trajectory_store store(argv[2]);
             store.set_phase(argv[3]);
@@ -304,7 +319,7 @@ int main(int argc, char **argv)
             else for (auto const &s : gd::h5::read_string_list(loc, name)) std::cout << s << '\n';
             return 0;
         }
-        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|put-context|steps|positions|context|contacts|dataset|strings ...\n";
+        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|put-context|put-contacts|steps|positions|context|contacts|dataset|strings ...\n";
         return 1;
     } catch (std::exception const &e) {
         std::cerr << "error: " << e.what() << '\n';
