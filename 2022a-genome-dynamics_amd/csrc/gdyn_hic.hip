@@ -1,0 +1,575 @@
+// gdyn_hic.hip -- the Hi-C signal analyses (include/gdyn_hic.h): the pixel pass of the reference's compute_interactions,
+// compute_local_alpha and hic_power_law over a cooler's (bin1_id, bin2_id, count) columns, and their per-bin signals.
+//
+//   k_hic_accumulate   one pass over a batch of pixels for every target of the handle.  A lane takes four consecutive pixels:
+//                      the three columns lie on 16-byte aligned buffers padded to whole lanes, so its 80 bytes are five
+//                      16-byte loads; pixels past the batch's end are masked by their index.  Per target kind:
+//                        band     one 64-bit integer atomic add at [i, d] per cis pixel with d < W.  Pixels are sorted by
+//                                 (bin1, bin2), so the lanes of a wave add to consecutive cells of a few rows.
+//                        profile  a histogram in LDS per block (a 64-bit sum and a 32-bit count per bin, the handle's first
+//                                 GD_HIC_LDS_BINS profile bins, 48 KiB), flushed with one global atomic pair per non-zero
+//                                 bin; the bins beyond that budget use global atomics.  Sums are int64, or fp64 when the
+//                                 target has weights.
+//                      Integer adds commute: no integer result depends on the batch size, the grid or the arrival order.
+//   k_hic_decay, k_hic_insulation   D(i, k) and I(i, k) of a band target, one thread per (bin, k)
+//   k_hic_alpha                     alpha(i) of a band target, one thread per bin
+// The signals are chains of fp64 operations in numpy's order (the object is built without fast-math and without contraction).
+// Every index that addresses memory is checked against its array in the kernel: pixels are data.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/gdyn.h"
+#include "../../include/gdyn_hic.h"
+
+int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
+
+static int fail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return gd_report_error(code, buf);
+}
+#define HIPCHK(call)                                                                                    \
+    do {                                                                                                \
+        hipError_t e_ = (call);                                                                         \
+        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kPerLane = 4;                   // pixels per lane
+constexpr unsigned kMaxBlocks = 2048;         // grid of k_hic_accumulate: blocks stride over the batch
+
+enum kind : int { kBand = 0, kProfile = 1 };
+
+struct target_desc {
+    int kind;
+    int weighted;                     // profile: fp64 sums of c / (w[i] * w[j])
+    unsigned width;                   // W of a band, size of a profile
+    unsigned lds, lds_count;          // profile: its first LDS bin and how many of its first bins are privatised
+    unsigned long long *sum;          // band cells; profile sums (int64, or the bits of a double)
+    unsigned long long *cnt;          // profile counts
+    const unsigned char *mask;        // profile: excluded bins, or NULL
+    const double *w;                  // profile: weights, or NULL
+};
+
+struct launch_args {
+    int n_targets;
+    unsigned lds_bins;                // LDS bins in use
+    unsigned n_bins;
+    const int *chrom;
+    target_desc t[GD_HIC_MAX_TARGETS];
+};
+
+__global__ void __launch_bounds__(kBlock) k_hic_accumulate(const longlong2 *__restrict__ bin1, const longlong2 *__restrict__ bin2,
+                                                          const int4 *__restrict__ count, unsigned n, unsigned groups, launch_args a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long hsum[];      // [lds_bins] sums, then [lds_bins] 32-bit counts
+    unsigned *const hcnt = reinterpret_cast<unsigned *>(hsum + a.lds_bins);
+    for (unsigned b = threadIdx.x; b < a.lds_bins; b += kBlock) {
+        hsum[b] = 0;
+        hcnt[b] = 0;
+    }
+    __syncthreads();
+    unsigned const stride = gridDim.x * kBlock;
+    for (unsigned g = blockIdx.x * kBlock + threadIdx.x; g < groups; g += stride) {
+        longlong2 const p0 = bin1[2 * (size_t)g], p1 = bin1[2 * (size_t)g + 1], q0 = bin2[2 * (size_t)g], q1 = bin2[2 * (size_t)g + 1];
+        int4 const c4 = count[g];
+        long long const x[kPerLane] = {p0.x, p0.y, p1.x, p1.y}, y[kPerLane] = {q0.x, q0.y, q1.x, q1.y};
+        int const c[kPerLane] = {c4.x, c4.y, c4.z, c4.w};
+        unsigned lo[kPerLane], hi[kPerLane], d[kPerLane];
+        bool cis[kPerLane];
+#pragma unroll
+        for (int k = 0; k < kPerLane; k++) {
+            // a negative id is a huge unsigned one
+            bool const live = g * kPerLane + k < n && (unsigned long long)x[k] < a.n_bins && (unsigned long long)y[k] < a.n_bins;
+            unsigned const u = live ? (unsigned)x[k] : 0u, v = live ? (unsigned)y[k] : 0u;
+            lo[k] = min(u, v);
+            hi[k] = max(u, v);
+            d[k] = hi[k] - lo[k];
+            cis[k] = live && a.chrom[lo[k]] == a.chrom[hi[k]];
+        }
+        for (int ti = 0; ti < a.n_targets; ti++) {
+            target_desc const &t = a.t[ti];
+            if (t.kind == kBand) {
+#pragma unroll
+                for (int k = 0; k < kPerLane; k++)
+                    if (cis[k] && d[k] < t.width) atomicAdd(t.sum + (size_t)lo[k] * t.width + d[k], (unsigned long long)(long long)c[k]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kPerLane; k++) {
+                    if (!cis[k] || d[k] >= t.width) continue;      // d < size for every counted pair was checked when the target was added
+                    if (t.mask && (t.mask[lo[k]] | t.mask[hi[k]])) continue;
+                    bool const in_lds = d[k] < t.lds_count;
+                    if (t.weighted) {
+                        double const v = (double)c[k] / (t.w[lo[k]] * t.w[hi[k]]);
+                        if (v != v) continue;
+                        if (in_lds) {
+                            unsafeAtomicAdd(reinterpret_cast<double *>(&hsum[t.lds + d[k]]), v);
+                            atomicAdd(&hcnt[t.lds + d[k]], 1u);
+                        } else {
+                            unsafeAtomicAdd(reinterpret_cast<double *>(t.sum + d[k]), v);
+                            atomicAdd(t.cnt + d[k], 1ull);
+                        }
+                    } else if (in_lds) {
+                        atomicAdd(&hsum[t.lds + d[k]], (unsigned long long)(long long)c[k]);
+                        atomicAdd(&hcnt[t.lds + d[k]], 1u);
+                    } else {
+                        atomicAdd(t.sum + d[k], (unsigned long long)(long long)c[k]);
+                        atomicAdd(t.cnt + d[k], 1ull);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int ti = 0; ti < a.n_targets; ti++) {
+        target_desc const &t = a.t[ti];
+        if (t.kind != kProfile) continue;
+        for (unsigned b = threadIdx.x; b < t.lds_count; b += kBlock) {
+            unsigned const m = hcnt[t.lds + b];
+            if (!m) continue;
+            if (t.weighted) unsafeAtomicAdd(reinterpret_cast<double *>(t.sum + b), *reinterpret_cast<double *>(&hsum[t.lds + b]));
+            else atomicAdd(t.sum + b, hsum[t.lds + b]);
+            atomicAdd(t.cnt + b, (unsigned long long)m);
+        }
+    }
+}
+
+// a zero cell is unmappable
+__device__ inline double cell(const long long *__restrict__ band, unsigned W, unsigned bin, unsigned k)
+{
+    long long const v = band[(size_t)bin * W + k];
+    return v == 0 ? __builtin_nan("") : (double)v;
+}
+
+// np.nanmean of two values
+__device__ inline double nanmean2(double a, double b)
+{
+    if (a != a) return b;
+    if (b != b) return a;
+    return (a + b) / 2;
+}
+
+// the symmetrised local decay of bin `bin` at separation k >= 1: run_beg <= bin < run_end is its chromosome
+__device__ inline double local_decay(const long long *__restrict__ band, unsigned W, unsigned bin, unsigned k, unsigned beg, unsigned end)
+{
+    double forw = __builtin_nan(""), back = __builtin_nan("");
+    if (k < end - bin) forw = cell(band, W, bin, k) / sqrt(cell(band, W, bin, 0) * cell(band, W, bin + k, 0));
+    if (bin - beg >= k) back = cell(band, W, bin - k, k) / sqrt(cell(band, W, bin - k, 0) * cell(band, W, bin, 0));
+    return nanmean2(forw, back);
+}
+
+// full: (n_bins, W) with column 0; out: (n_bins, W - 1), D1 .. D(W-1)
+__global__ void __launch_bounds__(kBlock) k_hic_decay(const long long *__restrict__ band, unsigned W, unsigned n_bins, const unsigned *__restrict__ run_beg,
+                                                     const unsigned *__restrict__ run_end, double *__restrict__ full, double *__restrict__ out)
+{
+    size_t const idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= (size_t)n_bins * W) return;
+    unsigned const bin = (unsigned)(idx / W), k = (unsigned)(idx % W);
+    unsigned const beg = run_beg[bin], end = run_end[bin];
+    double r;
+    if (end - beg <= 1) r = __builtin_nan("");
+    else if (k == 0) r = 1.0;
+    else r = local_decay(band, W, bin, k, beg, end);
+    full[idx] = r;
+    if (k) out[(size_t)bin * (W - 1) + (k - 1)] = r;
+}
+
+// out: (n_bins, W - 2), I1 .. I(W-2)
+__global__ void __launch_bounds__(kBlock) k_hic_insulation(const double *__restrict__ full, unsigned W, unsigned n_bins, double *__restrict__ out)
+{
+    size_t const idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (W < 3 || idx >= (size_t)n_bins * (W - 2)) return;
+    unsigned const bin = (unsigned)(idx / (W - 2)), k = 1 + (unsigned)(idx % (W - 2));
+    out[idx] = full[(size_t)bin * W + k] / full[(size_t)bin * W + k + 1];
+}
+
+__global__ void __launch_bounds__(kBlock) k_hic_alpha(const long long *__restrict__ band, unsigned W, unsigned n_bins, const unsigned *__restrict__ run_beg,
+                                                     const unsigned *__restrict__ run_end, double *__restrict__ alpha)
+{
+    unsigned const bin = blockIdx.x * kBlock + threadIdx.x;
+    if (bin >= n_bins) return;
+    unsigned const beg = run_beg[bin], end = run_end[bin];
+    double sx = 0, sxx = 0, sy = 0, sxy = 0;
+    unsigned finite = 0;
+    for (unsigned s = 1; s < W; s++) {
+        double const x = log((double)s);
+        sx += x;
+        sxx += x * x;
+        double const y = log(local_decay(band, W, bin, s, beg, end));
+        if (y != y) continue;
+        sy += y;
+        sxy += x * y;
+        finite++;
+    }
+    double const width = (double)(W - 1);
+    double const mx = sx / width, mxx = sxx / width;
+    double const my = finite ? sy / (double)finite : __builtin_nan(""), mxy = finite ? sxy / (double)finite : __builtin_nan("");
+    alpha[bin] = -((mxy - mx * my) / (mxx - mx * mx));
+}
+
+constexpr size_t kAutoPixels = (size_t)1 << 22;          // pixels per launch when max_pixels_per_launch is 0 (80 MiB)
+constexpr size_t kMaxPixels = (size_t)1 << 28;           // pixel indices of a batch stay 32-bit
+
+struct target_state {
+    target_desc d{};
+    size_t cells = 0;          // 64-bit values of `sum`
+    void *mask = nullptr, *w = nullptr;
+};
+
+}  // namespace
+
+struct gd_hic {
+    int device = 0;
+    unsigned max_pixels = 0;
+    unsigned n_bins = 0;
+    hipStream_t stream = nullptr;
+    int *chrom = nullptr;                        // device copy of chrom_code
+    unsigned *run_beg = nullptr, *run_end = nullptr;      // per bin: its run of equal codes
+    std::vector<int32_t> host_chrom;
+    char *pixels = nullptr;                      // one batch: bin1, bin2, count, each padded
+    size_t pixel_capacity = 0;
+    double *signal = nullptr;                    // scratch of the post-passes
+    size_t signal_capacity = 0;
+    std::vector<target_state> targets;
+    unsigned lds_bins = 0;
+
+    void drop_targets()
+    {
+        for (auto &t : targets) {
+            if (t.d.sum) (void)hipFree(t.d.sum);
+            if (t.d.cnt) (void)hipFree(t.d.cnt);
+            if (t.mask) (void)hipFree(t.mask);
+            if (t.w) (void)hipFree(t.w);
+        }
+        targets.clear();
+        lds_bins = 0;
+    }
+};
+
+namespace {
+
+int upload(void **dst, const void *src, size_t bytes)
+{
+    HIPCHK(hipMalloc(dst, std::max<size_t>(bytes, 1)));
+    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return GD_OK;
+}
+
+// zeroed accumulators and device copies of the target's arrays; nothing is left behind on failure
+int new_target(gd_hic *h, const char *who, target_state t, size_t counts, const uint8_t *mask, const double *w, int32_t *out)
+{
+    if (h->targets.size() >= GD_HIC_MAX_TARGETS) return fail(GD_EINVAL, "%s: a handle holds at most %d targets", who, GD_HIC_MAX_TARGETS);
+    HIPCHK(hipSetDevice(h->device));
+    int rc = GD_OK;
+    hipError_t e = hipMalloc(&t.d.sum, t.cells * 8);
+    if (e == hipSuccess && counts) e = hipMalloc(&t.d.cnt, counts * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(GD_ENOMEM, "%s: no device memory for %zu accumulator cells", who, t.cells + counts);
+    }
+    if (rc == GD_OK && mask) rc = upload(&t.mask, mask, h->n_bins);
+    if (rc == GD_OK && w) rc = upload(&t.w, w, (size_t)h->n_bins * sizeof(double));
+    if (rc == GD_OK) {
+        e = hipMemsetAsync(t.d.sum, 0, t.cells * 8, h->stream);
+        if (e == hipSuccess && counts) e = hipMemsetAsync(t.d.cnt, 0, counts * 8, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(GD_EHIP, "%s: hipMemset failed: %s", who, hipGetErrorString(e));
+    }
+    if (rc != GD_OK) {
+        if (t.d.sum) (void)hipFree(t.d.sum);
+        if (t.d.cnt) (void)hipFree(t.d.cnt);
+        if (t.mask) (void)hipFree(t.mask);
+        if (t.w) (void)hipFree(t.w);
+        return rc;
+    }
+    t.d.mask = static_cast<const unsigned char *>(t.mask);
+    t.d.w = static_cast<const double *>(t.w);
+    t.d.lds = t.d.lds_count = 0;
+    if (t.d.kind == kProfile) {
+        t.d.lds = h->lds_bins;
+        t.d.lds_count = std::min<unsigned>(t.d.width, GD_HIC_LDS_BINS - h->lds_bins);
+        h->lds_bins += t.d.lds_count;
+    }
+    h->targets.push_back(t);
+    *out = (int32_t)h->targets.size() - 1;
+    return GD_OK;
+}
+
+int find(gd_hic *h, const char *who, int32_t target, int kind, target_state **out)
+{
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (target < 0 || (size_t)target >= h->targets.size()) return fail(GD_EINVAL, "%s: target %d of %zu", who, target, h->targets.size());
+    if (h->targets[(size_t)target].d.kind != kind) return fail(GD_EINVAL, "%s: target %d is not a %s", who, target, kind == kBand ? "band" : "distance profile");
+    *out = &h->targets[(size_t)target];
+    return GD_OK;
+}
+
+int need_signal(gd_hic *h, size_t doubles)
+{
+    if (doubles <= h->signal_capacity) return GD_OK;
+    if (h->signal) (void)hipFree(h->signal);
+    h->signal = nullptr;
+    h->signal_capacity = 0;
+    HIPCHK(hipMalloc(&h->signal, doubles * sizeof(double)));
+    h->signal_capacity = doubles;
+    return GD_OK;
+}
+
+unsigned blocks_for(size_t threads) { return (unsigned)((threads + kBlock - 1) / kBlock); }
+
+}  // namespace
+
+extern "C" {
+
+int gd_hic_abi_version(void) { return GD_HIC_ABI_VERSION; }
+
+int gd_hic_create(const gd_hic_desc *desc, const int32_t *chrom_code, uint32_t n_bins, gd_hic **out)
+{
+    if (!desc || !out || !chrom_code) return fail(GD_EINVAL, "gd_hic_create: NULL argument");
+    *out = nullptr;
+    if (n_bins == 0 || n_bins >= 0x80000000u) return fail(GD_EINVAL, "gd_hic_create: %u bins; 1 <= n_bins < 2^31", n_bins);
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "gd_hic_create: no HIP device");
+    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "gd_hic_create: device %d of %d", desc->device, count);
+    HIPCHK(hipSetDevice(desc->device));
+    gd_hic *h = new (std::nothrow) gd_hic;
+    if (!h) return fail(GD_ENOMEM, "gd_hic_create: out of host memory");
+    h->device = desc->device;
+    h->max_pixels = desc->max_pixels_per_launch;
+    h->n_bins = n_bins;
+    h->host_chrom.assign(chrom_code, chrom_code + n_bins);
+    std::vector<unsigned> beg(n_bins), end(n_bins);
+    for (uint32_t b = 0, start = 0; b < n_bins; b++) {
+        if (b && chrom_code[b] != chrom_code[b - 1]) start = b;
+        beg[b] = start;
+    }
+    for (uint32_t b = n_bins, stop = n_bins; b-- > 0;) {
+        if (b + 1 < n_bins && chrom_code[b] != chrom_code[b + 1]) stop = b + 1;
+        end[b] = stop;
+    }
+    size_t const bytes = (size_t)n_bins * 4;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&h->chrom, bytes);
+    if (e == hipSuccess) e = hipMalloc(&h->run_beg, bytes);
+    if (e == hipSuccess) e = hipMalloc(&h->run_end, bytes);
+    if (e == hipSuccess) e = hipMemcpy(h->chrom, chrom_code, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->run_beg, beg.data(), bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(h->run_end, end.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        gd_hic_destroy(h);
+        return fail(GD_EHIP, "gd_hic_create failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return GD_OK;
+}
+
+int gd_hic_destroy(gd_hic *h)
+{
+    if (!h) return GD_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->drop_targets();
+    if (h->pixels) (void)hipFree(h->pixels);
+    if (h->signal) (void)hipFree(h->signal);
+    if (h->chrom) (void)hipFree(h->chrom);
+    if (h->run_beg) (void)hipFree(h->run_beg);
+    if (h->run_end) (void)hipFree(h->run_end);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return GD_OK;
+}
+
+int gd_hic_add_band(gd_hic *h, uint32_t W, int32_t *target)
+{
+    if (!h || !target) return fail(GD_EINVAL, "gd_hic_add_band: NULL argument");
+    if (W < 1 || W > GD_HIC_MAX_BAND) return fail(GD_EINVAL, "gd_hic_add_band: a band of %u columns; 1 <= W <= %d", W, GD_HIC_MAX_BAND);
+    target_state t;
+    t.d.kind = kBand;
+    t.d.width = W;
+    t.cells = (size_t)h->n_bins * W;
+    return new_target(h, "gd_hic_add_band", t, 0, nullptr, nullptr, target);
+}
+
+int gd_hic_add_distance_profile(gd_hic *h, const uint8_t *excluded_bin_mask, const double *weights, uint32_t size, int32_t *target)
+{
+    if (!h || !target) return fail(GD_EINVAL, "gd_hic_add_distance_profile: NULL argument");
+    if (size == 0) return fail(GD_EINVAL, "gd_hic_add_distance_profile: a profile of 0 bins");
+    std::unordered_map<int32_t, std::pair<uint32_t, uint32_t>> extent;      // first and last counted bin of every code
+    for (uint32_t b = 0; b < h->n_bins; b++) {
+        if (excluded_bin_mask && excluded_bin_mask[b]) continue;
+        auto it = extent.find(h->host_chrom[b]);
+        if (it == extent.end()) extent.emplace(h->host_chrom[b], std::make_pair(b, b));
+        else it->second.second = b;
+    }
+    for (auto const &e : extent)
+        if (e.second.second - e.second.first >= size)
+            return fail(GD_EINVAL, "gd_hic_add_distance_profile: chromosome code %d spans bins %u to %u, a distance beyond the profile's %u bins", e.first,
+                        e.second.first, e.second.second, size);
+    target_state t;
+    t.d.kind = kProfile;
+    t.d.weighted = weights != nullptr;
+    t.d.width = size;
+    t.cells = size;
+    return new_target(h, "gd_hic_add_distance_profile", t, size, excluded_bin_mask, weights, target);
+}
+
+int gd_hic_accumulate(gd_hic *h, const int64_t *bin1, const int64_t *bin2, const int32_t *count, uint64_t n)
+{
+    if (!h) return fail(GD_EINVAL, "gd_hic_accumulate: NULL handle");
+    if (n == 0) return GD_OK;
+    if (!bin1 || !bin2 || !count) return fail(GD_EINVAL, "gd_hic_accumulate: NULL column");
+    if (h->targets.empty()) return fail(GD_ESTATE, "gd_hic_accumulate: the handle has no target");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    size_t const B = (size_t)std::min<uint64_t>(std::min<size_t>(h->max_pixels ? h->max_pixels : kAutoPixels, kMaxPixels), n);
+    size_t const capacity = (B + kPerLane - 1) / kPerLane * kPerLane;      // whole lanes: every column stays 16-byte aligned
+    if (capacity > h->pixel_capacity) {
+        if (h->pixels) (void)hipFree(h->pixels);
+        h->pixels = nullptr;
+        h->pixel_capacity = 0;
+        HIPCHK(hipMalloc(&h->pixels, capacity * 20));
+        h->pixel_capacity = capacity;
+    }
+    char *const d1 = h->pixels, *const d2 = d1 + h->pixel_capacity * 8, *const dc = d2 + h->pixel_capacity * 8;
+    launch_args a{};
+    a.n_targets = (int)h->targets.size();
+    a.lds_bins = h->lds_bins;
+    a.n_bins = h->n_bins;
+    a.chrom = h->chrom;
+    for (int k = 0; k < a.n_targets; k++) a.t[k] = h->targets[(size_t)k].d;
+    for (uint64_t p0 = 0; p0 < n; p0 += B) {
+        unsigned const b = (unsigned)std::min<uint64_t>(B, n - p0);
+        unsigned const groups = (b + kPerLane - 1) / kPerLane;
+        HIPCHK(hipMemcpyAsync(d1, bin1 + p0, (size_t)b * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d2, bin2 + p0, (size_t)b * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dc, count + p0, (size_t)b * 4, hipMemcpyHostToDevice, st));
+        unsigned const blocks = std::min(blocks_for(groups), kMaxBlocks);
+        hipLaunchKernelGGL(k_hic_accumulate, dim3(blocks), dim3(kBlock), (size_t)h->lds_bins * 12, st, (const longlong2 *)d1, (const longlong2 *)d2,
+                           (const int4 *)dc, b, groups, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return GD_OK;
+}
+
+int gd_hic_decay_insulation(gd_hic *h, int32_t band, double *D, double *I)
+{
+    target_state *t = nullptr;
+    if (int rc = find(h, "gd_hic_decay_insulation", band, kBand, &t)) return rc;
+    unsigned const W = t->d.width, n = h->n_bins;
+    if (W < 2) return fail(GD_EINVAL, "gd_hic_decay_insulation: a band of %u columns has no D1", W);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    size_t const full = (size_t)n * W, nd = (size_t)n * (W - 1), ni = (size_t)n * (W - 2);
+    if (int rc = need_signal(h, full + nd + ni)) return rc;
+    double *const dfull = h->signal, *const dd = dfull + full, *const di = dd + nd;
+    hipLaunchKernelGGL(k_hic_decay, dim3(blocks_for(full)), dim3(kBlock), 0, st, (const long long *)t->d.sum, W, n, h->run_beg, h->run_end, dfull, dd);
+    HIPCHK(hipGetLastError());
+    if (ni) {
+        hipLaunchKernelGGL(k_hic_insulation, dim3(blocks_for(ni)), dim3(kBlock), 0, st, dfull, W, n, di);
+        HIPCHK(hipGetLastError());
+    }
+    if (D) HIPCHK(hipMemcpyAsync(D, dd, nd * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (I && ni) HIPCHK(hipMemcpyAsync(I, di, ni * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GD_OK;
+}
+
+int gd_hic_local_alpha(gd_hic *h, int32_t band, double *alpha)
+{
+    target_state *t = nullptr;
+    if (int rc = find(h, "gd_hic_local_alpha", band, kBand, &t)) return rc;
+    if (!alpha) return fail(GD_EINVAL, "gd_hic_local_alpha: NULL argument");
+    if (t->d.width < 2) return fail(GD_EINVAL, "gd_hic_local_alpha: a band of %u columns has no separation to fit", t->d.width);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    if (int rc = need_signal(h, h->n_bins)) return rc;
+    hipLaunchKernelGGL(k_hic_alpha, dim3(blocks_for(h->n_bins)), dim3(kBlock), 0, st, (const long long *)t->d.sum, t->d.width, h->n_bins, h->run_beg, h->run_end,
+                       h->signal);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(alpha, h->signal, (size_t)h->n_bins * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GD_OK;
+}
+
+int gd_hic_fetch_band(gd_hic *h, int32_t band, int64_t *out)
+{
+    target_state *t = nullptr;
+    if (int rc = find(h, "gd_hic_fetch_band", band, kBand, &t)) return rc;
+    if (!out) return fail(GD_EINVAL, "gd_hic_fetch_band: NULL argument");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out, t->d.sum, t->cells * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GD_OK;
+}
+
+int gd_hic_fetch_profile(gd_hic *h, int32_t profile, double *sum, int64_t *n, double *mean)
+{
+    target_state *t = nullptr;
+    if (int rc = find(h, "gd_hic_fetch_profile", profile, kProfile, &t)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    size_t const size = t->cells;
+    std::vector<unsigned long long> s(size), c(size);
+    HIPCHK(hipMemcpyAsync(s.data(), t->d.sum, size * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(c.data(), t->d.cnt, size * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < size; k++) {
+        double v;
+        if (t->d.weighted) memcpy(&v, &s[k], sizeof v);
+        else v = (double)(long long)s[k];
+        if (sum) sum[k] = v;
+        if (n) n[k] = (int64_t)c[k];
+        if (mean) mean[k] = c[k] ? v / (double)c[k] : std::nan("");
+    }
+    return GD_OK;
+}
+
+int gd_hic_fetch_profile_raw(gd_hic *h, int32_t profile, int64_t *sum)
+{
+    target_state *t = nullptr;
+    if (int rc = find(h, "gd_hic_fetch_profile_raw", profile, kProfile, &t)) return rc;
+    if (!sum) return fail(GD_EINVAL, "gd_hic_fetch_profile_raw: NULL argument");
+    if (t->d.weighted) return fail(GD_EINVAL, "gd_hic_fetch_profile_raw: target %d has weights; its sums are fp64", profile);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(sum, t->d.sum, t->cells * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GD_OK;
+}
+
+int gd_hic_reset(gd_hic *h)
+{
+    if (!h) return fail(GD_EINVAL, "gd_hic_reset: NULL handle");
+    HIPCHK(hipSetDevice(h->device));
+    for (auto &t : h->targets) {
+        HIPCHK(hipMemsetAsync(t.d.sum, 0, t.cells * 8, h->stream));
+        if (t.d.cnt) HIPCHK(hipMemsetAsync(t.d.cnt, 0, t.cells * 8, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GD_OK;
+}
+
+int gd_hic_clear(gd_hic *h)
+{
+    if (!h) return fail(GD_EINVAL, "gd_hic_clear: NULL handle");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->drop_targets();
+    return GD_OK;
+}
+
+}  // extern "C"

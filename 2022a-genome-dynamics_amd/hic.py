@@ -1,0 +1,318 @@
+"""The Hi-C signal analyses on the device: ctypes binding of ``include/gdyn_hic.h`` (exported by ``csrc/libgdyn.so``), one
+pass over a cooler's pixel table for the reference's 2-signal/src/{compute_interactions, compute_local_alpha} and
+5-sim-genome/scripts/hic_power_law.
+
+    with HicSignals(chrom_code, device=0) as hs:
+        b = hs.add_band(4)                                   # compute_interactions: band[i, d], d < 4
+        a = hs.add_band(width + 1)                           # compute_local_alpha -w width
+        p = hs.add_distance_profile(excluded, weights, size) # hic_power_law; weights=None is RAW
+        for bin1, bin2, count in chunks:                     # int64, int64, int32 as stored
+            hs.accumulate(bin1, bin2, count)                 # one pass over the pixels for every target
+        D, I = hs.decay_insulation(b)                        # (n_bins, 3), (n_bins, 2)
+        alpha = hs.local_alpha(a)
+        total, n, mean = hs.fetch_profile(p)
+
+``band_matrix``, ``decay_insulation``, ``local_alpha``, ``distance_profile`` and ``downsample`` are the same rules in numpy for
+users without a GPU; the device path never calls them.  ``chromosome_runs``, ``std_chrom_order``, ``excluded_bins`` and
+``largest_chromosome`` are the bookkeeping of the three programs.  Band sums are int64; the signals are fp64.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import LIBGDYN_PATH, GdynError
+
+HIC_ABI_VERSION = 1      # GD_HIC_ABI_VERSION of the include/gdyn_hic.h this binding mirrors
+HIC_SYMBOLS = ["gd_hic_abi_version", "gd_hic_create", "gd_hic_destroy", "gd_hic_add_band", "gd_hic_add_distance_profile",
+               "gd_hic_accumulate", "gd_hic_decay_insulation", "gd_hic_local_alpha", "gd_hic_fetch_band", "gd_hic_fetch_profile",
+               "gd_hic_fetch_profile_raw", "gd_hic_reset", "gd_hic_clear"]
+INTERACTIONS_BLACKLIST = ("MT",)             # compute_interactions.py: BLACKLISTED_CHROMS
+PROFILE_BLACKLIST = ("X", "Y", "MT")         # hic_power_law: BLACKLISTED_CHROMS
+NAMED_CHROM_RANK = {"X": 1, "Y": 2, "MT": 3, "M": 3}
+
+
+class _HicDesc(C.Structure):
+    _fields_ = [("device", C.c_int32), ("max_pixels_per_launch", C.c_uint32)]
+
+
+def load_hic_library(path=None):
+    """Loads libgdyn and checks the gd_hic_* symbols and their ABI version."""
+    path = path or LIBGDYN_PATH
+    d = C.CDLL(path)
+    for name in HIC_SYMBOLS + ["gd_last_error"]:
+        if not hasattr(d, name):
+            raise OSError(f"{path}: missing symbol {name}")
+    d.gd_hic_abi_version.restype = C.c_int
+    if d.gd_hic_abi_version() != HIC_ABI_VERSION:
+        raise OSError(f"{path}: hic ABI version {d.gd_hic_abi_version()}, this binding mirrors {HIC_ABI_VERSION}")
+    d.gd_last_error.restype = C.c_char_p
+    P32 = C.POINTER(C.c_int32)
+    d.gd_hic_create.argtypes = [C.POINTER(_HicDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+    d.gd_hic_destroy.argtypes = [C.c_void_p]
+    d.gd_hic_add_band.argtypes = [C.c_void_p, C.c_uint32, P32]
+    d.gd_hic_add_distance_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, P32]
+    d.gd_hic_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    d.gd_hic_decay_insulation.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    d.gd_hic_local_alpha.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    d.gd_hic_fetch_band.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    d.gd_hic_fetch_profile.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    d.gd_hic_fetch_profile_raw.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    d.gd_hic_reset.argtypes = [C.c_void_p]
+    d.gd_hic_clear.argtypes = [C.c_void_p]
+    return d
+
+
+# ---- bookkeeping of the programs
+
+def chromosome_runs(chrom_code):
+    """enumerate_runs (compute_local_alpha/command.py): the (start, end) of every run of equal codes."""
+    c = np.asarray(chrom_code)
+    if len(c) == 0:
+        return []
+    cuts = np.flatnonzero(c[1:] != c[:-1]) + 1
+    return list(zip([0, *cuts.tolist()], [*cuts.tolist(), len(c)]))
+
+
+def std_chrom_order(name):
+    """by_std_chrom_order (compute_interactions.py): numbered chromosomes first, then X, Y, MT / M.  KeyError for other names."""
+    if name.startswith("chr"):
+        name = name[3:]
+    try:
+        return 0, int(name)
+    except ValueError:
+        return NAMED_CHROM_RANK[name], 0
+
+
+def excluded_bins(chrom_code, names, blacklist=PROFILE_BLACKLIST):
+    """uint8 mask of the bins of blacklisted chromosomes.  names: {name: code}; a name matches with or without a chr prefix and
+    blacklisted names that the file does not have are skipped."""
+    c = np.asarray(chrom_code)
+    codes = [code for name, code in names.items() if (name[3:] if name.startswith("chr") else name) in blacklist]
+    return np.isin(c, codes).astype(np.uint8)
+
+
+def largest_chromosome(chrom_code):
+    """The size of hic_power_law's profile: the largest number of bins of any chromosome code."""
+    return int(np.unique(np.asarray(chrom_code), return_counts=True)[1].max())
+
+
+# ---- numpy: the same rules on the host
+
+def _pixels(bin1, bin2, count, n_bins):
+    b1, b2, c = np.asarray(bin1).astype(np.int64), np.asarray(bin2).astype(np.int64), np.asarray(count).astype(np.int64)
+    ok = (b1 >= 0) & (b1 < n_bins) & (b2 >= 0) & (b2 < n_bins)
+    b1, b2, c = b1[ok], b2[ok], c[ok]
+    return np.minimum(b1, b2), np.maximum(b1, b2), c
+
+
+def band_matrix(bin1, bin2, count, chrom_code, W, out=None):
+    """Rule 1: exact int64 sums band[i, d] += c over cis pixels with d < W; pixels with a bin id outside the table are ignored."""
+    chrom = np.asarray(chrom_code)
+    i, j, c = _pixels(bin1, bin2, count, len(chrom))
+    band = np.zeros((len(chrom), W), np.int64) if out is None else out
+    s = (chrom[i] == chrom[j]) & (j - i < W)
+    np.add.at(band, (i[s], (j - i)[s]), c[s])
+    return band
+
+
+def _nanmean2(a, b):
+    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, (a + b) / 2))
+
+
+def _symmetric_decay(band, chrom_code):
+    """D(i, k) for k = 0 .. W-1 of every run of equal codes, fp64, NaN for zero cells."""
+    band = np.asarray(band)
+    n_bins, W = band.shape
+    x = np.where(band == 0, np.nan, band.astype(np.float64))
+    D = np.full((n_bins, W), np.nan)
+    for beg, end in chromosome_runs(chrom_code):
+        n = end - beg
+        if n <= 1:
+            continue
+        r = x[beg:end]
+        D[beg:end, 0] = 1.0
+        for k in range(1, W):
+            forw, back = np.full(n, np.nan), np.full(n, np.nan)
+            if k < n:
+                f = r[:n - k, k] / np.sqrt(r[:n - k, 0] * r[k:, 0])
+                forw[:n - k] = f
+                back[k:] = f
+            D[beg:end, k] = _nanmean2(forw, back)
+    return D
+
+
+def decay_insulation(band, chrom_code):
+    """Rule 2: (D1 .. D(W-1), I1 .. I(W-2)) of a band of W >= 2 columns."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        D = _symmetric_decay(band, chrom_code)
+        return D[:, 1:].copy(), D[:, 1:-1] / D[:, 2:]
+
+
+def local_alpha(band, chrom_code):
+    """Rule 3: alpha of a band of width + 1 columns."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        D = _symmetric_decay(band, chrom_code)
+        xs = np.log(np.arange(1, D.shape[1], dtype=np.float64))
+        ys = np.log(D[:, 1:])
+        finite = ~np.isnan(ys)
+        count = finite.sum(axis=1)
+        my = np.where(finite, ys, 0).sum(axis=1) / count
+        mxy = np.where(finite, xs * ys, 0).sum(axis=1) / count
+        mx, mxx = xs.mean(), (xs * xs).mean()
+        return -((mxy - mx * my) / (mxx - mx * mx))
+
+
+def distance_profile(bin1, bin2, count, chrom_code, excluded=None, weights=None, size=None):
+    """Rule 4: (sum, n, mean) per distance.  Without weights sum is int64 and exact."""
+    chrom = np.asarray(chrom_code)
+    size = largest_chromosome(chrom) if size is None else size
+    i, j, c = _pixels(bin1, bin2, count, len(chrom))
+    s = chrom[i] == chrom[j]
+    if excluded is not None:
+        ex = np.asarray(excluded).astype(bool)
+        s &= ~(ex[i] | ex[j])
+    i, j, c = i[s], j[s], c[s]
+    if len(i) and (j - i).max() >= size:
+        raise ValueError(f"a distance of {(j - i).max()} bins in a profile of {size} bins")
+    n = np.zeros(size, np.int64)
+    if weights is None:
+        total = np.zeros(size, np.int64)
+        np.add.at(total, j - i, c)
+        np.add.at(n, j - i, 1)
+    else:
+        w = np.asarray(weights, np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            v = c / (w[i] * w[j])
+        keep = ~np.isnan(v)
+        total = np.bincount((j - i)[keep], weights=v[keep], minlength=size)
+        n += np.bincount((j - i)[keep], minlength=size)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return total, n, total / n
+
+
+def downsample(values, rate=2, window=None):
+    """Rule 5 for one chromosome: values (n, columns) -> (ceil(n / rate), columns)."""
+    v = np.asarray(values, np.float64)
+    window = rate if window is None else window
+    n = len(v)
+    out = np.full(((n + rate - 1) // rate, v.shape[1]), np.nan)
+    for m in range(len(out)):
+        lo, hi = max(rate * (m + 1) - window + 1, 0), min(rate * (m + 1), n - 1)
+        part = v[lo:hi + 1]
+        finite = ~np.isnan(part)
+        count = finite.sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[m] = np.where(count > 0, np.where(finite, part, 0).sum(axis=0) / count, np.nan)
+    return out
+
+
+# ---- the device
+
+class HicSignals:
+    """One device-side handle for one bin table.  max_pixels_per_launch: 0 = automatic (no integer result depends on it)."""
+
+    def __init__(self, chrom_code, device=0, max_pixels_per_launch=0, path=None):
+        self.dll = load_hic_library(path)
+        self._h = C.c_void_p()
+        self._targets = []
+        chrom = np.ascontiguousarray(chrom_code, dtype=np.int32)
+        if chrom.ndim != 1:
+            raise ValueError(f"chrom_code must be one-dimensional, got {chrom.shape}")
+        self.n_bins = len(chrom)
+        self._check(self.dll.gd_hic_create(C.byref(_HicDesc(device, max_pixels_per_launch)), chrom.ctypes.data, self.n_bins, C.byref(self._h)))
+
+    def _check(self, rc):
+        if rc != 0:
+            raise GdynError(rc, self.dll.gd_last_error().decode())
+
+    def close(self):
+        if self._h:
+            self.dll.gd_hic_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _added(self, rc, target, what):
+        self._check(rc)
+        assert target.value == len(self._targets)
+        self._targets.append(what)
+        return target.value
+
+    def add_band(self, W):
+        t = C.c_int32(-1)
+        return self._added(self.dll.gd_hic_add_band(self._h, W, C.byref(t)), t, ("band", W))
+
+    def add_distance_profile(self, excluded=None, weights=None, size=None):
+        ex = None if excluded is None else np.ascontiguousarray(np.asarray(excluded).astype(bool), dtype=np.uint8)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        for name, arr in (("excluded", ex), ("weights", w)):
+            if arr is not None and arr.shape != (self.n_bins,):
+                raise ValueError(f"{name} must have one value per bin ({self.n_bins}), got {arr.shape}")
+        if size is None:
+            raise ValueError("size is required: the largest number of bins of any chromosome (largest_chromosome)")
+        t = C.c_int32(-1)
+        rc = self.dll.gd_hic_add_distance_profile(self._h, None if ex is None else ex.ctypes.data, None if w is None else w.ctypes.data, size, C.byref(t))
+        return self._added(rc, t, ("profile", size))
+
+    def accumulate(self, bin1, bin2, count):
+        """The three pixel columns; every target of the handle is updated in one pass."""
+        b1, b2 = np.ascontiguousarray(bin1, dtype=np.int64), np.ascontiguousarray(bin2, dtype=np.int64)
+        c = np.ascontiguousarray(count, dtype=np.int32)
+        if not (b1.ndim == 1 and b1.shape == b2.shape == c.shape):
+            raise ValueError(f"the pixel columns must be one-dimensional and of one length, got {b1.shape}, {b2.shape}, {c.shape}")
+        self._check(self.dll.gd_hic_accumulate(self._h, b1.ctypes.data, b2.ctypes.data, c.ctypes.data, len(c)))
+
+    def _width(self, target, kind):
+        if not 0 <= target < len(self._targets) or self._targets[target][0] != kind:
+            return 1      # the library reports the error
+        return self._targets[target][1]
+
+    def fetch_band(self, target):
+        out = np.empty((self.n_bins, self._width(target, "band")), np.int64)
+        self._check(self.dll.gd_hic_fetch_band(self._h, target, out.ctypes.data))
+        return out
+
+    def decay_insulation(self, target):
+        W = max(self._width(target, "band"), 2)
+        D, I = np.empty((self.n_bins, W - 1)), np.empty((self.n_bins, W - 2))
+        self._check(self.dll.gd_hic_decay_insulation(self._h, target, D.ctypes.data, I.ctypes.data))
+        return D, I
+
+    def local_alpha(self, target):
+        out = np.empty(self.n_bins)
+        self._check(self.dll.gd_hic_local_alpha(self._h, target, out.ctypes.data))
+        return out
+
+    def fetch_profile(self, target):
+        """(sum, n, mean): fp64, int64, fp64."""
+        size = self._width(target, "profile")
+        total, n, mean = np.empty(size), np.empty(size, np.int64), np.empty(size)
+        self._check(self.dll.gd_hic_fetch_profile(self._h, target, total.ctypes.data, n.ctypes.data, mean.ctypes.data))
+        return total, n, mean
+
+    def fetch_profile_raw(self, target):
+        """The exact int64 sums of a profile without weights."""
+        out = np.empty(self._width(target, "profile"), np.int64)
+        self._check(self.dll.gd_hic_fetch_profile_raw(self._h, target, out.ctypes.data))
+        return out
+
+    def reset(self):
+        """Zeroes every accumulator; the targets stay."""
+        self._check(self.dll.gd_hic_reset(self._h))
+
+    def clear(self):
+        """Removes every target."""
+        self._check(self.dll.gd_hic_clear(self._h))
+        self._targets = []

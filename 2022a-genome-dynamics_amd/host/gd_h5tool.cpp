@@ -13,6 +13,12 @@
 //        fields at their defaults), beside put-positions: what the lamina analysis reads
 //   gd_h5tool put-contacts <file> <phase> <step> <rows.u32>   the snapshot's contact_map from raw little-endian uint32 (M,3) rows
 //        (i, j, count), beside put-positions: what the contact-map analyses read; creates the file if it does not exist
+//   gd_h5tool put-cool <file> <binsize> <names.txt> <chrom.i32> <start.i64> <end.i64> <bin1.i64> <bin2.i64> <count.i32> [<name> <weights.f64>]
+//        a resolutions/<binsize> group of a multi-resolution cooler file from raw little-endian arrays: bins/chrom as an int32 enum
+//        of the names (one per line, code = line number), bins/{start,end} int32, pixels/{bin1_id,bin2_id} int64 and pixels/count
+//        int32 (chunked, shuffled, deflated), and an optional float64 bins/<name> column: what the Hi-C signal programs read;
+//        creates the file if it does not exist
+//   gd_h5tool cool-bins <file> <binsize>               prints "name start end" of every bin
 //   gd_h5tool steps <file> <phase>                     numerically ordered step list
 //   gd_h5tool positions <file> <phase> <step> <out.f64>
 //   gd_h5tool context <file> <phase> <step>            prints the JSON context fields
@@ -182,6 +188,77 @@ int main(int argc, char **argv)
             store.save_contacts(std::stol(argv[4]), rows);
             return 0;
         }
+        if (cmd == "put-cool" && (argc == 11 || argc == 13)) {
+            std::vector<std::string> names;
+            std::ifstream nf(argv[4]);
+            if (!nf) throw std::runtime_error(std::string("cannot read ") + argv[4]);
+            for (std::string line; std::getline(nf, line);) if (!line.empty()) names.push_back(line);
+            auto const chrom = slurp(argv[5]), start = slurp(argv[6]), end = slurp(argv[7]), bin1 = slurp(argv[8]), bin2 = slurp(argv[9]), count = slurp(argv[10]);
+            std::size_t const n_bins = chrom.size() / 4, n_pixels = count.size() / 4;
+            if (chrom.size() % 4 || start.size() != n_bins * 8 || end.size() != n_bins * 8) throw std::runtime_error("chrom (int32), start and end (int64) disagree on the number of bins");
+            if (count.size() % 4 || bin1.size() != n_pixels * 8 || bin2.size() != n_pixels * 8) throw std::runtime_error("bin1, bin2 (int64) and count (int32) disagree on the number of pixels");
+            std::vector<char> weights;
+            if (argc == 13) {
+                weights = slurp(argv[12]);
+                if (weights.size() != n_bins * 8) throw std::runtime_error("the weight column (float64) has another length than chrom");
+            }
+            for (std::size_t b = 0; b < n_bins; b++) {
+                std::int32_t code;
+                std::memcpy(&code, chrom.data() + 4 * b, 4);
+                if (code < 0 || (std::size_t)code >= names.size()) throw std::runtime_error("a chromosome code is outside the list of names");
+            }
+            using gd::h5::hid;
+            H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+            hid file(std::ifstream(argv[2]).good() ? H5Fopen(argv[2], H5F_ACC_RDWR, H5P_DEFAULT) : H5Fcreate(argv[2], H5F_ACC_EXCL, H5P_DEFAULT, H5P_DEFAULT));
+            if (file < 0) throw std::runtime_error(std::string("cannot open ") + argv[2]);
+            std::string const res = std::string("/resolutions/") + argv[3];
+            gd::h5::unlink_if_present(file, res);
+            hid names_type(H5Tenum_create(H5T_STD_I32LE));
+            for (std::size_t k = 0; k < names.size(); k++) {
+                std::int32_t const v = (std::int32_t)k;
+                if (H5Tenum_insert(names_type, names[k].c_str(), &v) < 0) throw std::runtime_error("cannot add the name " + names[k]);
+            }
+            auto put = [&](std::string const &path, void const *data, hsize_t n, hid_t mem, hid_t stored, bool packed) {
+                hid space(H5Screate_simple(1, &n, nullptr)), props(H5Pcreate(H5P_DATASET_CREATE)), lcpl(H5Pcreate(H5P_LINK_CREATE));
+                H5Pset_create_intermediate_group(lcpl, 1);
+                if (packed && n) {
+                    hsize_t const chunk = std::min<hsize_t>(n, 1 << 16);
+                    H5Pset_chunk(props, 1, &chunk);
+                    H5Pset_shuffle(props);
+                    H5Pset_deflate(props, 6);
+                }
+                hid ds(H5Dcreate2(file, (res + path).c_str(), stored, space, lcpl, props, H5P_DEFAULT));
+                if (ds < 0 || (n && H5Dwrite(ds, mem, H5S_ALL, H5S_ALL, H5P_DEFAULT, data) < 0)) throw std::runtime_error("cannot write " + res + path);
+            };
+            put("/bins/chrom", chrom.data(), n_bins, names_type, names_type, false);
+            put("/bins/start", start.data(), n_bins, H5T_STD_I64LE, H5T_STD_I32LE, false);
+            put("/bins/end", end.data(), n_bins, H5T_STD_I64LE, H5T_STD_I32LE, false);
+            if (argc == 13) put(std::string("/bins/") + argv[11], weights.data(), n_bins, H5T_IEEE_F64LE, H5T_IEEE_F64LE, false);
+            put("/pixels/bin1_id", bin1.data(), n_pixels, H5T_STD_I64LE, H5T_STD_I64LE, true);
+            put("/pixels/bin2_id", bin2.data(), n_pixels, H5T_STD_I64LE, H5T_STD_I64LE, true);
+            put("/pixels/count", count.data(), n_pixels, H5T_STD_I32LE, H5T_STD_I32LE, true);
+            return 0;
+        }
+        if (cmd == "cool-bins" && argc == 4) {
+            using gd::h5::hid;
+            hid file(H5Fopen(argv[2], H5F_ACC_RDONLY, H5P_DEFAULT));
+            std::string const bins = std::string("/resolutions/") + argv[3] + "/bins/";
+            hid ds(H5Dopen2(file, (bins + "chrom").c_str(), H5P_DEFAULT));
+            if (file < 0 || ds < 0) throw std::runtime_error("no dataset " + bins + "chrom");
+            hid type(H5Dget_type(ds)), space(H5Dget_space(ds));
+            if (H5Tget_class(type) != H5T_ENUM || H5Tget_size(type) != 4) throw std::runtime_error(bins + "chrom is not an int32 enum");
+            std::size_t const n = (std::size_t)H5Sget_simple_extent_npoints(space);
+            std::vector<std::int32_t> code(n);
+            if (n && H5Dread(ds, type, H5S_ALL, H5S_ALL, H5P_DEFAULT, code.data()) < 0) throw std::runtime_error("cannot read " + bins + "chrom");
+            std::size_t rows = 0;
+            auto const start = gd::h5::read_array<long long>(file, bins + "start", 1, H5T_NATIVE_LLONG, &rows), end = gd::h5::read_array<long long>(file, bins + "end", 1, H5T_NATIVE_LLONG, &rows);
+            for (std::size_t b = 0; b < n; b++) {
+                char name[256] = "";
+                if (H5Tenum_nameof(type, &code[b], name, sizeof name) < 0) throw std::runtime_error("a code without a name");
+                std::cout << name << ' ' << start.at(b) << ' ' << end.at(b) << '\n';
+            }
+            return 0;
+        }
         if (cmd == "steps" && argc == 4) {
             gd::trajectory_store store(argv[2]);
             store.set_phase(argv[3]);
@@ -319,7 +396,7 @@ int main(int argc, char **argv)
             else for (auto const &s : gd::h5::read_string_list(loc, name)) std::cout << s << '\n';
             return 0;
         }
-        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|put-context|put-contacts|steps|positions|context|contacts|dataset|strings ...\n";
+        std::cerr << "usage: gd_h5tool make-input|make-metadata|dump-metadata|put-positions|put-positions-f64|put-context|put-contacts|put-cool|cool-bins|steps|positions|context|contacts|dataset|strings ...\n";
         return 1;
     } catch (std::exception const &e) {
         std::cerr << "error: " << e.what() << '\n';
