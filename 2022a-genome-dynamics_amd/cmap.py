@@ -22,7 +22,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import LIBGDYN_PATH, GdynError
+from ._binding import GdynError, Handle, load_library
 
 CMAP_ABI_VERSION = 1     # GD_CMAP_ABI_VERSION of the include/gdyn_cmap.h this binding mirrors
 CMAP_SYMBOLS = ["gd_cmap_abi_version", "gd_cmap_create", "gd_cmap_destroy", "gd_cmap_add_region", "gd_cmap_add_binned",
@@ -37,15 +37,7 @@ class _CmapDesc(C.Structure):
 
 def load_cmap_library(path=None):
     """Loads libgdyn and checks the gd_cmap_* symbols and their ABI version."""
-    path = path or LIBGDYN_PATH
-    d = C.CDLL(path)
-    for name in CMAP_SYMBOLS + ["gd_last_error"]:
-        if not hasattr(d, name):
-            raise OSError(f"{path}: missing symbol {name}")
-    d.gd_cmap_abi_version.restype = C.c_int
-    if d.gd_cmap_abi_version() != CMAP_ABI_VERSION:
-        raise OSError(f"{path}: cmap ABI version {d.gd_cmap_abi_version()}, this binding mirrors {CMAP_ABI_VERSION}")
-    d.gd_last_error.restype = C.c_char_p
+    d = load_library("cmap", CMAP_SYMBOLS, CMAP_ABI_VERSION, path)
     P32 = C.POINTER(C.c_int32)
     d.gd_cmap_create.argtypes = [C.POINTER(_CmapDesc), C.POINTER(C.c_void_p)]
     d.gd_cmap_destroy.argtypes = [C.c_void_p]
@@ -183,35 +175,15 @@ def power_law_exponents(profile):
 
 # ---- the device
 
-class ContactMaps:
+class ContactMaps(Handle):
     """One device-side handle.  max_rows_per_launch: 0 = automatic (no result depends on it)."""
 
+    _destroy = "gd_cmap_destroy"
+
     def __init__(self, device=0, max_rows_per_launch=0, path=None):
-        self.dll = load_cmap_library(path)
-        self._h = C.c_void_p()
+        super().__init__(load_cmap_library(path))
         self._shapes = []
         self._check(self.dll.gd_cmap_create(C.byref(_CmapDesc(device, max_rows_per_launch)), C.byref(self._h)))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise GdynError(rc, self.dll.gd_last_error().decode())
-
-    def close(self):
-        if self._h:
-            self.dll.gd_cmap_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def _added(self, rc, target, shape):
         self._check(rc)

@@ -1,0 +1,125 @@
+// gdyn_analysis.hpp -- the host-side plumbing that the device analyses (gdyn_flow, gdyn_rdf, gdyn_lamina, gdyn_cmap,
+// gdyn_hic) share: error reporting, owned device buffers, the device and stream of a handle with its create prologue and
+// destroy epilogue, and the grid size of a one-lane-per-element launch.  Nothing here is extern "C" or device code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <new>
+
+#include "../../include/gdyn.h"
+
+int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
+
+namespace gd {
+
+static int fail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return gd_report_error(code, buf);
+}
+#define HIPCHK(call)                                                                                    \
+    do {                                                                                                \
+        hipError_t e_ = (call);                                                                         \
+        if (e_ != hipSuccess) return gd::fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+
+// blocks of `block` lanes for n elements; no caller comes near the cap, which keeps the count inside a grid dimension
+inline unsigned blocks_for(size_t n, unsigned block) { return (unsigned)std::min<size_t>((n + block - 1) / block, 1u << 30); }
+
+// device memory of the current device, freed with its owner (the owner's device must be current then: gd::close)
+template <typename T>
+struct dbuf {
+    T *p = nullptr;
+    size_t n = 0;
+
+    dbuf() = default;
+    dbuf(dbuf &&o) noexcept : p(o.p), n(o.n)
+    {
+        o.p = nullptr;
+        o.n = 0;
+    }
+    dbuf &operator=(dbuf &&o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~dbuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    // room for `count` elements; grows by reallocation (the content is lost), never shrinks; n is 0 after a failure
+    hipError_t ensure(size_t count)
+    {
+        if (count <= n) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    hipError_t upload(const T *src, size_t count)
+    {
+        hipError_t e = ensure(count);
+        if (e == hipSuccess && count) e = hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t zero(hipStream_t st) { return n ? hipMemsetAsync(p, 0, n * sizeof(T), st) : hipSuccess; }
+};
+
+// what every gd_<x> handle starts with.  The stream goes after the derived handle's members, so after its buffers.
+struct handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+
+    handle() = default;
+    handle(const handle &) = delete;
+    handle &operator=(const handle &) = delete;
+    ~handle()
+    {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// the front of gd_<x>_create (`who`): *out is a new H on desc->device, which is made current, with its stream
+template <typename H, typename Desc>
+int open(const char *who, const Desc *desc, H **out)
+{
+    if (!desc || !out) return fail(GD_EINVAL, "%s: NULL argument", who);
+    *out = nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "%s: no HIP device", who);
+    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "%s: device %d of %d", who, desc->device, count);
+    HIPCHK(hipSetDevice(desc->device));
+    H *h = new (std::nothrow) H;
+    if (!h) return fail(GD_ENOMEM, "%s: out of host memory", who);
+    h->device = desc->device;
+    hipError_t const e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete h;
+        return fail(GD_EHIP, "%s: hipStreamCreate failed: %s", who, hipGetErrorString(e));
+    }
+    *out = h;
+    return GD_OK;
+}
+
+// gd_<x>_destroy: waits for the handle's work and frees it on its device
+template <typename H>
+int close(H *h)
+{
+    if (!h) return GD_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    delete h;
+    return GD_OK;
+}
+
+}  // namespace gd

@@ -23,31 +23,15 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstdarg>
 #include <cstdio>
-#include <new>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_cmap.h"
+#include "gdyn_analysis.hpp"
 
-int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
-
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return gd_report_error(code, buf);
-}
-#define HIPCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+using namespace gd;
 
 namespace {
 
@@ -254,31 +238,24 @@ constexpr size_t kMaxRows = (size_t)1 << 28;           // row indices of a batch
 constexpr size_t kFetchElements = (size_t)1 << 26;     // staging of a binned fetch (256 MiB)
 
 struct target_state {
-    target_desc d{};
+    target_desc d{};           // what the kernels see: plain pointers into acc and aux
     size_t count = 0;          // accumulator elements
-    void *aux = nullptr;
+    dbuf<int> acc;
+    dbuf<char> aux;
 };
 
 }  // namespace
 
-struct gd_cmap {
-    int device = 0;
+struct gd_cmap : gd::handle {
     unsigned max_rows = 0;
-    hipStream_t stream = nullptr;
-    char *rows = nullptr;              // one batch, padded
-    size_t rows_capacity = 0;          // in rows
-    int *stage = nullptr;              // binned fetch
-    size_t stage_capacity = 0;
-    unsigned long long *counters = nullptr;      // [2], then one int for gd_cmap_finish's maximum
+    dbuf<char> rows;                   // one batch, padded
+    dbuf<int> stage;                   // binned fetch
+    dbuf<unsigned long long> counters; // [2], then one int for gd_cmap_finish's maximum
     std::vector<target_state> targets;
     unsigned lds_bins = 0;
 
     void drop_targets()
     {
-        for (auto &t : targets) {
-            if (t.d.acc) (void)hipFree(t.d.acc);
-            if (t.aux) (void)hipFree(t.aux);
-        }
         targets.clear();
         lds_bins = 0;
     }
@@ -286,45 +263,35 @@ struct gd_cmap {
 
 namespace {
 
-// a zeroed accumulator of `count` int32 and a device copy of the target's array
+// a zeroed accumulator of `count` int32 and a device copy of the target's array; nothing is left behind on failure
 int new_target(gd_cmap *h, const char *who, target_desc d, size_t count, const void *aux, size_t aux_bytes, int32_t *out)
 {
     if (h->targets.size() >= GD_CMAP_MAX_TARGETS) return fail(GD_EINVAL, "%s: a handle holds at most %d targets", who, GD_CMAP_MAX_TARGETS);
     HIPCHK(hipSetDevice(h->device));
     target_state t;
     t.count = count;
-    if (hipMalloc(&d.acc, std::max<size_t>(count, 1) * sizeof(int)) != hipSuccess) {
+    if (t.acc.ensure(std::max<size_t>(count, 1)) != hipSuccess) {      // an empty target keeps one cell, which zero() and reset clear
         (void)hipGetLastError();
         return fail(GD_ENOMEM, "%s: no device memory for %zu accumulator cells", who, count);
     }
-    if (aux_bytes) {
-        if (hipMalloc(&t.aux, aux_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(d.acc);
-            return fail(GD_ENOMEM, "%s: no device memory for %zu bytes", who, aux_bytes);
-        }
-        hipError_t const e = hipMemcpy(t.aux, aux, aux_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d.acc);
-            (void)hipFree(t.aux);
-            return fail(GD_EHIP, "%s: hipMemcpy failed: %s", who, hipGetErrorString(e));
-        }
+    if (t.aux.ensure(aux_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(GD_ENOMEM, "%s: no device memory for %zu bytes", who, aux_bytes);
     }
-    hipError_t e = hipMemsetAsync(d.acc, 0, std::max<size_t>(count, 1) * sizeof(int), h->stream);
+    hipError_t e = aux_bytes ? hipMemcpy(t.aux.p, aux, aux_bytes, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) return fail(GD_EHIP, "%s: hipMemcpy failed: %s", who, hipGetErrorString(e));
+    e = t.acc.zero(h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d.acc);
-        if (t.aux) (void)hipFree(t.aux);
-        return fail(GD_EHIP, "%s: hipMemset failed: %s", who, hipGetErrorString(e));
-    }
-    d.aux = t.aux;
+    if (e != hipSuccess) return fail(GD_EHIP, "%s: hipMemset failed: %s", who, hipGetErrorString(e));
+    d.acc = t.acc.p;
+    d.aux = t.aux.p;
     d.lds = kNoLds;
     if (d.kind >= kNucleolus && h->lds_bins + d.size <= GD_CMAP_LDS_BINS) {
         d.lds = h->lds_bins;
         h->lds_bins += d.size;
     }
     t.d = d;
-    h->targets.push_back(t);
+    h->targets.push_back(std::move(t));
     *out = (int32_t)h->targets.size() - 1;
     return GD_OK;
 }
@@ -345,42 +312,20 @@ int gd_cmap_abi_version(void) { return GD_CMAP_ABI_VERSION; }
 
 int gd_cmap_create(const gd_cmap_desc *desc, gd_cmap **out)
 {
-    if (!desc || !out) return fail(GD_EINVAL, "gd_cmap_create: NULL argument");
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "gd_cmap_create: no HIP device");
-    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "gd_cmap_create: device %d of %d", desc->device, count);
-    HIPCHK(hipSetDevice(desc->device));
-    gd_cmap *h = new (std::nothrow) gd_cmap;
-    if (!h) return fail(GD_ENOMEM, "gd_cmap_create: out of host memory");
-    h->device = desc->device;
+    if (int rc = gd::open("gd_cmap_create", desc, out)) return rc;
+    gd_cmap *h = *out;
     h->max_rows = desc->max_rows_per_launch;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&h->counters, 4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(h->counters, 0, 4 * sizeof(unsigned long long));
+    hipError_t e = h->counters.ensure(4);
+    if (e == hipSuccess) e = hipMemset(h->counters.p, 0, 4 * sizeof(unsigned long long));
     if (e != hipSuccess) {
-        if (h->counters) (void)hipFree(h->counters);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-        delete h;
+        gd::close(h);
+        *out = nullptr;
         return fail(GD_EHIP, "gd_cmap_create failed: %s", hipGetErrorString(e));
     }
-    *out = h;
     return GD_OK;
 }
 
-int gd_cmap_destroy(gd_cmap *h)
-{
-    if (!h) return GD_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    h->drop_targets();
-    if (h->rows) (void)hipFree(h->rows);
-    if (h->stage) (void)hipFree(h->stage);
-    (void)hipFree(h->counters);
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return GD_OK;
-}
+int gd_cmap_destroy(gd_cmap *h) { return gd::close(h); }
 
 int gd_cmap_add_region(gd_cmap *h, uint32_t beg, uint32_t end, int32_t *target)
 {
@@ -452,13 +397,7 @@ int gd_cmap_accumulate(gd_cmap *h, const uint32_t *rows, uint64_t n_rows)
     hipStream_t st = h->stream;
     size_t const B = (size_t)std::min<uint64_t>(std::min<size_t>(h->max_rows ? h->max_rows : kAutoRows, kMaxRows), n_rows);
     size_t const capacity = (B + kPerLane - 1) / kPerLane * kPerLane;
-    if (capacity > h->rows_capacity) {
-        if (h->rows) (void)hipFree(h->rows);
-        h->rows = nullptr;
-        h->rows_capacity = 0;
-        HIPCHK(hipMalloc(&h->rows, capacity * 12));
-        h->rows_capacity = capacity;
-    }
+    HIPCHK(h->rows.ensure(capacity * 12));
     launch_args a{};
     a.n_targets = (int)h->targets.size();
     a.lds_bins = h->lds_bins;
@@ -466,9 +405,9 @@ int gd_cmap_accumulate(gd_cmap *h, const uint32_t *rows, uint64_t n_rows)
     for (uint64_t r0 = 0; r0 < n_rows; r0 += B) {
         unsigned const b = (unsigned)std::min<uint64_t>(B, n_rows - r0);
         unsigned const groups = (b + kPerLane - 1) / kPerLane;
-        HIPCHK(hipMemcpyAsync(h->rows, rows + r0 * 3, (size_t)b * 12, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(h->rows.p, rows + r0 * 3, (size_t)b * 12, hipMemcpyHostToDevice, st));
         unsigned const blocks = std::min((groups + kBlock - 1) / kBlock, kMaxBlocks);
-        hipLaunchKernelGGL(k_cmap_accumulate, dim3(blocks), dim3(kBlock), h->lds_bins * sizeof(int), st, (const uint4 *)h->rows, b, groups, a, h->counters);
+        hipLaunchKernelGGL(k_cmap_accumulate, dim3(blocks), dim3(kBlock), h->lds_bins * sizeof(int), st, (const uint4 *)h->rows.p, b, groups, a, h->counters.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
     }
@@ -484,7 +423,7 @@ int gd_cmap_finish(gd_cmap *h, int32_t target)
     if (n == 0) return GD_OK;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    int *best = reinterpret_cast<int *>(h->counters + 2);
+    int *best = reinterpret_cast<int *>(h->counters.p + 2);
     int const lowest = INT_MIN;
     HIPCHK(hipMemcpyAsync(best, &lowest, sizeof lowest, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_cmap_symmetrize, dim3((n + kBlock - 1) / kBlock, n), dim3(kBlock), 0, st, t->d.acc, n);
@@ -519,18 +458,12 @@ int gd_cmap_fetch(gd_cmap *h, int32_t target, int32_t *out)
     }
     unsigned const n = t->d.size;
     unsigned const piece = (unsigned)std::min<size_t>(n, std::max<size_t>(32, kFetchElements / n / 32 * 32));      // rows at a time
-    if ((size_t)piece * n > h->stage_capacity) {
-        if (h->stage) (void)hipFree(h->stage);
-        h->stage = nullptr;
-        h->stage_capacity = 0;
-        HIPCHK(hipMalloc(&h->stage, (size_t)piece * n * sizeof(int)));
-        h->stage_capacity = (size_t)piece * n;
-    }
+    HIPCHK(h->stage.ensure((size_t)piece * n));
     for (unsigned r0 = 0; r0 < n; r0 += piece) {
         unsigned const rows = std::min(piece, n - r0);
-        hipLaunchKernelGGL(k_cmap_symmetric_rows, dim3((n + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, st, (const int *)t->d.acc, n, r0, rows, h->stage);
+        hipLaunchKernelGGL(k_cmap_symmetric_rows, dim3((n + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, st, (const int *)t->d.acc, n, r0, rows, h->stage.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out + (size_t)r0 * n, h->stage, (size_t)rows * n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out + (size_t)r0 * n, h->stage.p, (size_t)rows * n * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     return GD_OK;
@@ -540,8 +473,8 @@ int gd_cmap_reset(gd_cmap *h)
 {
     if (!h) return fail(GD_EINVAL, "gd_cmap_reset: NULL handle");
     HIPCHK(hipSetDevice(h->device));
-    for (auto &t : h->targets) HIPCHK(hipMemsetAsync(t.d.acc, 0, std::max<size_t>(t.count, 1) * sizeof(int), h->stream));
-    HIPCHK(hipMemsetAsync(h->counters, 0, 2 * sizeof(unsigned long long), h->stream));
+    for (auto &t : h->targets) HIPCHK(t.acc.zero(h->stream));
+    HIPCHK(hipMemsetAsync(h->counters.p, 0, 2 * sizeof(unsigned long long), h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return GD_OK;
 }
@@ -560,7 +493,7 @@ int gd_cmap_counters(gd_cmap *h, uint64_t out[2])
     if (!h || !out) return fail(GD_EINVAL, "gd_cmap_counters: NULL argument");
     HIPCHK(hipSetDevice(h->device));
     unsigned long long v[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(v, h->counters, sizeof v, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(v, h->counters.p, sizeof v, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     out[0] = v[0];
     out[1] = v[1];

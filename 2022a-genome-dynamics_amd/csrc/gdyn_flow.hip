@@ -18,32 +18,16 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_flow.h"
+#include "gdyn_analysis.hpp"
 #include "gdyn_types.h"
 
-int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
-
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return gd_report_error(code, buf);
-}
-#define HIPCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+using namespace gd;
 
 namespace {
 
@@ -281,37 +265,12 @@ __global__ void __launch_bounds__(kBlock) k_flow_grid(const double4 *__restrict_
     coverage[idx] = o.n;
 }
 
-unsigned blocks_for(size_t n) { return (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 1u << 30); }
 unsigned stream_blocks(size_t n) { return (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 256 * 64); }
-
-template <typename T>
-struct dbuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count)
-    {
-        if (count <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
 
 }  // namespace
 
-struct gd_flow {
-    int device = 0;
+struct gd_flow : gd::handle {
     unsigned max_frames = 0;
-    hipStream_t stream = nullptr;
     unsigned F = 0, N = 0;
     bool have_velocities = false;
     dbuf<double> x, smoothed, vel, weights, points;
@@ -354,15 +313,15 @@ int bin_frames(gd_flow *h, unsigned f0, unsigned B, double r)
     const double *pos = h->pos + (size_t)f0 * h->N * 3;
     const double *vel = h->vel.p + (size_t)f0 * h->N * 3;
     hipLaunchKernelGGL(k_flow_bounds, dim3(B), dim3(kBlock), 0, st, pos, h->N, r, cap, h->grids.p);
-    hipLaunchKernelGGL(k_flow_keys, dim3(blocks_for(nb)), dim3(kBlock), 0, st, pos, h->N, B, cap, h->grids.p, h->keys[0].p, h->vals[0].p);
+    hipLaunchKernelGGL(k_flow_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, pos, h->N, B, cap, h->grids.p, h->keys[0].p, h->vals[0].p);
     unsigned bits = 1;
     while (bits < 64 && ((unsigned long long)B * cap) >> bits) bits++;
     size_t tmp_bytes = 0;
     HIPCHK(gd_sort_contacts(nullptr, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
     HIPCHK(h->sort_tmp.ensure(tmp_bytes));
     HIPCHK(gd_sort_contacts(h->sort_tmp.p, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
-    hipLaunchKernelGGL(k_flow_sorted, dim3(blocks_for(nb)), dim3(kBlock), 0, st, pos, vel, h->N, B, h->vals[1].p, h->spos.p, h->svel.p);
-    hipLaunchKernelGGL(k_flow_cell_starts, dim3(blocks_for((size_t)B * (cap + 1))), dim3(kBlock), 0, st, h->keys[1].p, h->N, B, cap,
+    hipLaunchKernelGGL(k_flow_sorted, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, pos, vel, h->N, B, h->vals[1].p, h->spos.p, h->svel.p);
+    hipLaunchKernelGGL(k_flow_cell_starts, dim3(blocks_for((size_t)B * (cap + 1), kBlock)), dim3(kBlock), 0, st, h->keys[1].p, h->N, B, cap,
                        h->grids.p, h->starts.p);
     HIPCHK(hipGetLastError());
     return GD_OK;
@@ -382,46 +341,12 @@ int gd_flow_abi_version(void) { return GD_FLOW_ABI_VERSION; }
 
 int gd_flow_create(const gd_flow_desc *desc, gd_flow **out)
 {
-    if (!desc || !out) return fail(GD_EINVAL, "gd_flow_create: NULL argument");
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "gd_flow_create: no HIP device");
-    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "gd_flow_create: device %d of %d", desc->device, count);
-    HIPCHK(hipSetDevice(desc->device));
-    gd_flow *h = new (std::nothrow) gd_flow;
-    if (!h) return fail(GD_ENOMEM, "gd_flow_create: out of host memory");
-    h->device = desc->device;
-    h->max_frames = desc->max_frames_per_launch;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(GD_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    if (int rc = gd::open("gd_flow_create", desc, out)) return rc;
+    (*out)->max_frames = desc->max_frames_per_launch;
     return GD_OK;
 }
 
-int gd_flow_destroy(gd_flow *h)
-{
-    if (!h) return GD_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    for (auto *b : {&h->x, &h->smoothed, &h->vel, &h->weights, &h->points}) b->release();
-    for (int k = 0; k < 2; k++) {
-        h->keys[k].release();
-        h->vals[k].release();
-    }
-    h->starts.release();
-    h->spos.release();
-    h->svel.release();
-    h->grids.release();
-    h->sort_tmp.release();
-    h->out_f.release();
-    h->out_i.release();
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return GD_OK;
-}
+int gd_flow_destroy(gd_flow *h) { return gd::close(h); }
 
 int gd_flow_set_history(gd_flow *h, const void *xyz, uint32_t frames, uint32_t n_beads, int is_f64)
 {
@@ -493,7 +418,7 @@ int gd_flow_particle(gd_flow *h, double radius, float *flows_out)
         unsigned const b = std::min(B, h->F - f0);
         if (int rc = bin_frames(h, f0, b, radius)) return rc;
         size_t const nb = (size_t)b * h->N;
-        hipLaunchKernelGGL(k_flow_particle, dim3(blocks_for(nb)), dim3(kBlock), 0, h->stream, h->spos.p, h->svel.p, h->vals[1].p, h->starts.p,
+        hipLaunchKernelGGL(k_flow_particle, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, h->stream, h->spos.p, h->svel.p, h->vals[1].p, h->starts.p,
                            h->grids.p, h->N, b, cap, radius, radius * radius, h->out_f.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(flows_out + (size_t)f0 * h->N * 3, h->out_f.p, nb * 3 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -522,7 +447,7 @@ int gd_flow_grid(gd_flow *h, double radius, const double *points, uint32_t n_poi
         unsigned const b = std::min(B, h->F - f0);
         if (int rc = bin_frames(h, f0, b, radius)) return rc;
         size_t const ng = (size_t)b * G;
-        hipLaunchKernelGGL(k_flow_grid, dim3(blocks_for(ng)), dim3(kBlock), 0, h->stream, h->spos.p, h->svel.p, h->starts.p, h->grids.p,
+        hipLaunchKernelGGL(k_flow_grid, dim3(blocks_for(ng, kBlock)), dim3(kBlock), 0, h->stream, h->spos.p, h->svel.p, h->starts.p, h->grids.p,
                            h->points.p, G, b, cap, radius, radius * radius, h->out_f.p, h->out_i.p);
         HIPCHK(hipGetLastError());
         if (flows_out)

@@ -19,32 +19,16 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_hic.h"
+#include "gdyn_analysis.hpp"
 
-int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
-
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return gd_report_error(code, buf);
-}
-#define HIPCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+using namespace gd;
 
 namespace {
 
@@ -223,38 +207,33 @@ __global__ void __launch_bounds__(kBlock) k_hic_alpha(const long long *__restric
 
 constexpr size_t kAutoPixels = (size_t)1 << 22;          // pixels per launch when max_pixels_per_launch is 0 (80 MiB)
 constexpr size_t kMaxPixels = (size_t)1 << 28;           // pixel indices of a batch stay 32-bit
+// blocks_for's cap of 2^30 blocks is never met here: a batch has at most kMaxPixels / kPerLane lanes, and the signals take one
+// lane per cell of a band that gd_hic_add_band has allocated at 8 bytes a cell: 2^38 cells (2^30 blocks) would be 2 TiB
+static_assert(kMaxPixels / kPerLane / kBlock < ((size_t)1 << 30), "a batch of pixels is one grid");
 
 struct target_state {
-    target_desc d{};
+    target_desc d{};           // what the kernels see: plain pointers into the buffers below
     size_t cells = 0;          // 64-bit values of `sum`
-    void *mask = nullptr, *w = nullptr;
+    dbuf<unsigned long long> sum, cnt;
+    dbuf<unsigned char> mask;
+    dbuf<double> w;
 };
 
 }  // namespace
 
-struct gd_hic {
-    int device = 0;
+struct gd_hic : gd::handle {
     unsigned max_pixels = 0;
     unsigned n_bins = 0;
-    hipStream_t stream = nullptr;
-    int *chrom = nullptr;                        // device copy of chrom_code
-    unsigned *run_beg = nullptr, *run_end = nullptr;      // per bin: its run of equal codes
+    dbuf<int> chrom;                             // device copy of chrom_code
+    dbuf<unsigned> run_beg, run_end;             // per bin: its run of equal codes
     std::vector<int32_t> host_chrom;
-    char *pixels = nullptr;                      // one batch: bin1, bin2, count, each padded
-    size_t pixel_capacity = 0;
-    double *signal = nullptr;                    // scratch of the post-passes
-    size_t signal_capacity = 0;
+    dbuf<char> pixels;                           // one batch: bin1, bin2, count, each padded
+    dbuf<double> signal;                         // scratch of the post-passes
     std::vector<target_state> targets;
     unsigned lds_bins = 0;
 
     void drop_targets()
     {
-        for (auto &t : targets) {
-            if (t.d.sum) (void)hipFree(t.d.sum);
-            if (t.d.cnt) (void)hipFree(t.d.cnt);
-            if (t.mask) (void)hipFree(t.mask);
-            if (t.w) (void)hipFree(t.w);
-        }
         targets.clear();
         lds_bins = 0;
     }
@@ -262,49 +241,35 @@ struct gd_hic {
 
 namespace {
 
-int upload(void **dst, const void *src, size_t bytes)
-{
-    HIPCHK(hipMalloc(dst, std::max<size_t>(bytes, 1)));
-    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return GD_OK;
-}
-
 // zeroed accumulators and device copies of the target's arrays; nothing is left behind on failure
-int new_target(gd_hic *h, const char *who, target_state t, size_t counts, const uint8_t *mask, const double *w, int32_t *out)
+int new_target(gd_hic *h, const char *who, target_desc d, size_t cells, size_t counts, const uint8_t *mask, const double *w, int32_t *out)
 {
     if (h->targets.size() >= GD_HIC_MAX_TARGETS) return fail(GD_EINVAL, "%s: a handle holds at most %d targets", who, GD_HIC_MAX_TARGETS);
     HIPCHK(hipSetDevice(h->device));
-    int rc = GD_OK;
-    hipError_t e = hipMalloc(&t.d.sum, t.cells * 8);
-    if (e == hipSuccess && counts) e = hipMalloc(&t.d.cnt, counts * 8);
-    if (e != hipSuccess) {
+    target_state t;
+    t.cells = cells;
+    if (t.sum.ensure(cells) != hipSuccess || t.cnt.ensure(counts) != hipSuccess) {
         (void)hipGetLastError();
-        rc = fail(GD_ENOMEM, "%s: no device memory for %zu accumulator cells", who, t.cells + counts);
+        return fail(GD_ENOMEM, "%s: no device memory for %zu accumulator cells", who, cells + counts);
     }
-    if (rc == GD_OK && mask) rc = upload(&t.mask, mask, h->n_bins);
-    if (rc == GD_OK && w) rc = upload(&t.w, w, (size_t)h->n_bins * sizeof(double));
-    if (rc == GD_OK) {
-        e = hipMemsetAsync(t.d.sum, 0, t.cells * 8, h->stream);
-        if (e == hipSuccess && counts) e = hipMemsetAsync(t.d.cnt, 0, counts * 8, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(GD_EHIP, "%s: hipMemset failed: %s", who, hipGetErrorString(e));
+    if (mask) HIPCHK(t.mask.upload(mask, h->n_bins));
+    if (w) HIPCHK(t.w.upload(w, h->n_bins));
+    hipError_t e = t.sum.zero(h->stream);
+    if (e == hipSuccess) e = t.cnt.zero(h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(GD_EHIP, "%s: hipMemset failed: %s", who, hipGetErrorString(e));
+    d.sum = t.sum.p;
+    d.cnt = t.cnt.p;
+    d.mask = t.mask.p;
+    d.w = t.w.p;
+    d.lds = d.lds_count = 0;
+    if (d.kind == kProfile) {
+        d.lds = h->lds_bins;
+        d.lds_count = std::min<unsigned>(d.width, GD_HIC_LDS_BINS - h->lds_bins);
+        h->lds_bins += d.lds_count;
     }
-    if (rc != GD_OK) {
-        if (t.d.sum) (void)hipFree(t.d.sum);
-        if (t.d.cnt) (void)hipFree(t.d.cnt);
-        if (t.mask) (void)hipFree(t.mask);
-        if (t.w) (void)hipFree(t.w);
-        return rc;
-    }
-    t.d.mask = static_cast<const unsigned char *>(t.mask);
-    t.d.w = static_cast<const double *>(t.w);
-    t.d.lds = t.d.lds_count = 0;
-    if (t.d.kind == kProfile) {
-        t.d.lds = h->lds_bins;
-        t.d.lds_count = std::min<unsigned>(t.d.width, GD_HIC_LDS_BINS - h->lds_bins);
-        h->lds_bins += t.d.lds_count;
-    }
-    h->targets.push_back(t);
+    t.d = d;
+    h->targets.push_back(std::move(t));
     *out = (int32_t)h->targets.size() - 1;
     return GD_OK;
 }
@@ -318,19 +283,6 @@ int find(gd_hic *h, const char *who, int32_t target, int kind, target_state **ou
     return GD_OK;
 }
 
-int need_signal(gd_hic *h, size_t doubles)
-{
-    if (doubles <= h->signal_capacity) return GD_OK;
-    if (h->signal) (void)hipFree(h->signal);
-    h->signal = nullptr;
-    h->signal_capacity = 0;
-    HIPCHK(hipMalloc(&h->signal, doubles * sizeof(double)));
-    h->signal_capacity = doubles;
-    return GD_OK;
-}
-
-unsigned blocks_for(size_t threads) { return (unsigned)((threads + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 extern "C" {
@@ -342,13 +294,8 @@ int gd_hic_create(const gd_hic_desc *desc, const int32_t *chrom_code, uint32_t n
     if (!desc || !out || !chrom_code) return fail(GD_EINVAL, "gd_hic_create: NULL argument");
     *out = nullptr;
     if (n_bins == 0 || n_bins >= 0x80000000u) return fail(GD_EINVAL, "gd_hic_create: %u bins; 1 <= n_bins < 2^31", n_bins);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "gd_hic_create: no HIP device");
-    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "gd_hic_create: device %d of %d", desc->device, count);
-    HIPCHK(hipSetDevice(desc->device));
-    gd_hic *h = new (std::nothrow) gd_hic;
-    if (!h) return fail(GD_ENOMEM, "gd_hic_create: out of host memory");
-    h->device = desc->device;
+    if (int rc = gd::open("gd_hic_create", desc, out)) return rc;
+    gd_hic *h = *out;
     h->max_pixels = desc->max_pixels_per_launch;
     h->n_bins = n_bins;
     h->host_chrom.assign(chrom_code, chrom_code + n_bins);
@@ -361,48 +308,28 @@ int gd_hic_create(const gd_hic_desc *desc, const int32_t *chrom_code, uint32_t n
         if (b + 1 < n_bins && chrom_code[b] != chrom_code[b + 1]) stop = b + 1;
         end[b] = stop;
     }
-    size_t const bytes = (size_t)n_bins * 4;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&h->chrom, bytes);
-    if (e == hipSuccess) e = hipMalloc(&h->run_beg, bytes);
-    if (e == hipSuccess) e = hipMalloc(&h->run_end, bytes);
-    if (e == hipSuccess) e = hipMemcpy(h->chrom, chrom_code, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->run_beg, beg.data(), bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->run_end, end.data(), bytes, hipMemcpyHostToDevice);
+    hipError_t e = h->chrom.upload(chrom_code, n_bins);
+    if (e == hipSuccess) e = h->run_beg.upload(beg.data(), n_bins);
+    if (e == hipSuccess) e = h->run_end.upload(end.data(), n_bins);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        gd_hic_destroy(h);
+        gd::close(h);
+        *out = nullptr;
         return fail(GD_EHIP, "gd_hic_create failed: %s", hipGetErrorString(e));
     }
-    *out = h;
     return GD_OK;
 }
 
-int gd_hic_destroy(gd_hic *h)
-{
-    if (!h) return GD_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->drop_targets();
-    if (h->pixels) (void)hipFree(h->pixels);
-    if (h->signal) (void)hipFree(h->signal);
-    if (h->chrom) (void)hipFree(h->chrom);
-    if (h->run_beg) (void)hipFree(h->run_beg);
-    if (h->run_end) (void)hipFree(h->run_end);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return GD_OK;
-}
+int gd_hic_destroy(gd_hic *h) { return gd::close(h); }
 
 int gd_hic_add_band(gd_hic *h, uint32_t W, int32_t *target)
 {
     if (!h || !target) return fail(GD_EINVAL, "gd_hic_add_band: NULL argument");
     if (W < 1 || W > GD_HIC_MAX_BAND) return fail(GD_EINVAL, "gd_hic_add_band: a band of %u columns; 1 <= W <= %d", W, GD_HIC_MAX_BAND);
-    target_state t;
-    t.d.kind = kBand;
-    t.d.width = W;
-    t.cells = (size_t)h->n_bins * W;
-    return new_target(h, "gd_hic_add_band", t, 0, nullptr, nullptr, target);
+    target_desc d{};
+    d.kind = kBand;
+    d.width = W;
+    return new_target(h, "gd_hic_add_band", d, (size_t)h->n_bins * W, 0, nullptr, nullptr, target);
 }
 
 int gd_hic_add_distance_profile(gd_hic *h, const uint8_t *excluded_bin_mask, const double *weights, uint32_t size, int32_t *target)
@@ -420,12 +347,11 @@ int gd_hic_add_distance_profile(gd_hic *h, const uint8_t *excluded_bin_mask, con
         if (e.second.second - e.second.first >= size)
             return fail(GD_EINVAL, "gd_hic_add_distance_profile: chromosome code %d spans bins %u to %u, a distance beyond the profile's %u bins", e.first,
                         e.second.first, e.second.second, size);
-    target_state t;
-    t.d.kind = kProfile;
-    t.d.weighted = weights != nullptr;
-    t.d.width = size;
-    t.cells = size;
-    return new_target(h, "gd_hic_add_distance_profile", t, size, excluded_bin_mask, weights, target);
+    target_desc d{};
+    d.kind = kProfile;
+    d.weighted = weights != nullptr;
+    d.width = size;
+    return new_target(h, "gd_hic_add_distance_profile", d, size, size, excluded_bin_mask, weights, target);
 }
 
 int gd_hic_accumulate(gd_hic *h, const int64_t *bin1, const int64_t *bin2, const int32_t *count, uint64_t n)
@@ -438,19 +364,13 @@ int gd_hic_accumulate(gd_hic *h, const int64_t *bin1, const int64_t *bin2, const
     hipStream_t st = h->stream;
     size_t const B = (size_t)std::min<uint64_t>(std::min<size_t>(h->max_pixels ? h->max_pixels : kAutoPixels, kMaxPixels), n);
     size_t const capacity = (B + kPerLane - 1) / kPerLane * kPerLane;      // whole lanes: every column stays 16-byte aligned
-    if (capacity > h->pixel_capacity) {
-        if (h->pixels) (void)hipFree(h->pixels);
-        h->pixels = nullptr;
-        h->pixel_capacity = 0;
-        HIPCHK(hipMalloc(&h->pixels, capacity * 20));
-        h->pixel_capacity = capacity;
-    }
-    char *const d1 = h->pixels, *const d2 = d1 + h->pixel_capacity * 8, *const dc = d2 + h->pixel_capacity * 8;
+    HIPCHK(h->pixels.ensure(capacity * 20));
+    char *const d1 = h->pixels.p, *const d2 = d1 + capacity * 8, *const dc = d2 + capacity * 8;
     launch_args a{};
     a.n_targets = (int)h->targets.size();
     a.lds_bins = h->lds_bins;
     a.n_bins = h->n_bins;
-    a.chrom = h->chrom;
+    a.chrom = h->chrom.p;
     for (int k = 0; k < a.n_targets; k++) a.t[k] = h->targets[(size_t)k].d;
     for (uint64_t p0 = 0; p0 < n; p0 += B) {
         unsigned const b = (unsigned)std::min<uint64_t>(B, n - p0);
@@ -458,7 +378,7 @@ int gd_hic_accumulate(gd_hic *h, const int64_t *bin1, const int64_t *bin2, const
         HIPCHK(hipMemcpyAsync(d1, bin1 + p0, (size_t)b * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d2, bin2 + p0, (size_t)b * 8, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(dc, count + p0, (size_t)b * 4, hipMemcpyHostToDevice, st));
-        unsigned const blocks = std::min(blocks_for(groups), kMaxBlocks);
+        unsigned const blocks = std::min(blocks_for(groups, kBlock), kMaxBlocks);
         hipLaunchKernelGGL(k_hic_accumulate, dim3(blocks), dim3(kBlock), (size_t)h->lds_bins * 12, st, (const longlong2 *)d1, (const longlong2 *)d2,
                            (const int4 *)dc, b, groups, a);
         HIPCHK(hipGetLastError());
@@ -476,12 +396,13 @@ int gd_hic_decay_insulation(gd_hic *h, int32_t band, double *D, double *I)
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     size_t const full = (size_t)n * W, nd = (size_t)n * (W - 1), ni = (size_t)n * (W - 2);
-    if (int rc = need_signal(h, full + nd + ni)) return rc;
-    double *const dfull = h->signal, *const dd = dfull + full, *const di = dd + nd;
-    hipLaunchKernelGGL(k_hic_decay, dim3(blocks_for(full)), dim3(kBlock), 0, st, (const long long *)t->d.sum, W, n, h->run_beg, h->run_end, dfull, dd);
+    HIPCHK(h->signal.ensure(full + nd + ni));
+    double *const dfull = h->signal.p, *const dd = dfull + full, *const di = dd + nd;
+    hipLaunchKernelGGL(k_hic_decay, dim3(blocks_for(full, kBlock)), dim3(kBlock), 0, st, (const long long *)t->d.sum, W, n, h->run_beg.p,
+                       h->run_end.p, dfull, dd);
     HIPCHK(hipGetLastError());
     if (ni) {
-        hipLaunchKernelGGL(k_hic_insulation, dim3(blocks_for(ni)), dim3(kBlock), 0, st, dfull, W, n, di);
+        hipLaunchKernelGGL(k_hic_insulation, dim3(blocks_for(ni, kBlock)), dim3(kBlock), 0, st, dfull, W, n, di);
         HIPCHK(hipGetLastError());
     }
     if (D) HIPCHK(hipMemcpyAsync(D, dd, nd * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -498,11 +419,11 @@ int gd_hic_local_alpha(gd_hic *h, int32_t band, double *alpha)
     if (t->d.width < 2) return fail(GD_EINVAL, "gd_hic_local_alpha: a band of %u columns has no separation to fit", t->d.width);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    if (int rc = need_signal(h, h->n_bins)) return rc;
-    hipLaunchKernelGGL(k_hic_alpha, dim3(blocks_for(h->n_bins)), dim3(kBlock), 0, st, (const long long *)t->d.sum, t->d.width, h->n_bins, h->run_beg, h->run_end,
-                       h->signal);
+    HIPCHK(h->signal.ensure(h->n_bins));
+    hipLaunchKernelGGL(k_hic_alpha, dim3(blocks_for(h->n_bins, kBlock)), dim3(kBlock), 0, st, (const long long *)t->d.sum, t->d.width, h->n_bins, h->run_beg.p,
+                       h->run_end.p, h->signal.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(alpha, h->signal, (size_t)h->n_bins * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(alpha, h->signal.p, (size_t)h->n_bins * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return GD_OK;
 }
@@ -556,8 +477,8 @@ int gd_hic_reset(gd_hic *h)
     if (!h) return fail(GD_EINVAL, "gd_hic_reset: NULL handle");
     HIPCHK(hipSetDevice(h->device));
     for (auto &t : h->targets) {
-        HIPCHK(hipMemsetAsync(t.d.sum, 0, t.cells * 8, h->stream));
-        if (t.d.cnt) HIPCHK(hipMemsetAsync(t.d.cnt, 0, t.cells * 8, h->stream));
+        HIPCHK(t.sum.zero(h->stream));
+        HIPCHK(t.cnt.zero(h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return GD_OK;

@@ -16,30 +16,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <new>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_lamina.h"
+#include "gdyn_analysis.hpp"
 
-int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
-
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return gd_report_error(code, buf);
-}
-#define HIPCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+using namespace gd;
 
 namespace {
 
@@ -151,41 +135,16 @@ __global__ void __launch_bounds__(kBlock) k_lamina_average(const float4 *__restr
     out[g] = make_float4(s.x / calls, s.y / calls, s.z / calls, s.w / calls);
 }
 
-unsigned blocks_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-template <typename T>
-struct dbuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count)
-    {
-        if (count <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
 constexpr size_t kAutoElements = (size_t)1 << 22;      // bead-frames per launch when max_frames_per_launch is 0
 constexpr size_t kMaxElements = (size_t)1 << 30;       // flat indices of a batch stay 32-bit
+static_assert(kMaxElements / kPerLane / kBlock < ((size_t)1 << 30), "the lanes of a batch are one grid, far below blocks_for's cap");
 
 size_t padded(size_t count) { return (count + kPerLane - 1) / kPerLane * kPerLane; }
 
 }  // namespace
 
-struct gd_lamina {
-    int device = 0;
+struct gd_lamina : gd::handle {
     unsigned max_frames = 0;
-    hipStream_t stream = nullptr;
     dbuf<char> in, out;                  // one batch
     dbuf<double> inv;
     dbuf<float> sum;                     // (frames, n_points) of the contacts calls, padded
@@ -206,38 +165,12 @@ int gd_lamina_abi_version(void) { return GD_LAMINA_ABI_VERSION; }
 
 int gd_lamina_create(const gd_lamina_desc *desc, gd_lamina **out)
 {
-    if (!desc || !out) return fail(GD_EINVAL, "gd_lamina_create: NULL argument");
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "gd_lamina_create: no HIP device");
-    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "gd_lamina_create: device %d of %d", desc->device, count);
-    HIPCHK(hipSetDevice(desc->device));
-    gd_lamina *h = new (std::nothrow) gd_lamina;
-    if (!h) return fail(GD_ENOMEM, "gd_lamina_create: out of host memory");
-    h->device = desc->device;
-    h->max_frames = desc->max_frames_per_launch;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(GD_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    if (int rc = gd::open("gd_lamina_create", desc, out)) return rc;
+    (*out)->max_frames = desc->max_frames_per_launch;
     return GD_OK;
 }
 
-int gd_lamina_destroy(gd_lamina *h)
-{
-    if (!h) return GD_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    h->in.release();
-    h->out.release();
-    h->inv.release();
-    h->sum.release();
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return GD_OK;
-}
+int gd_lamina_destroy(gd_lamina *h) { return gd::close(h); }
 
 int gd_lamina_distances(gd_lamina *h, const void *xyz, int is_f64, uint32_t frames, uint32_t n_points, const double *semiaxes, void *out,
                         int out_is_f64)
@@ -267,7 +200,7 @@ int gd_lamina_distances(gd_lamina *h, const void *xyz, int is_f64, uint32_t fram
         HIPCHK(hipMemcpyAsync(h->in.p, static_cast<const char *>(xyz) + (size_t)f0 * n_points * 3 * in_elem, count * 3 * in_elem,
                               hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(h->inv.p, inv.data() + (size_t)f0 * 3, (size_t)b * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        dim3 const grid(blocks_for(groups)), block(kBlock);
+        dim3 const grid(blocks_for(groups, kBlock)), block(kBlock);
         if (is_f64 && out_is_f64)
             hipLaunchKernelGGL((k_lamina_distance<double, double>), grid, block, 0, st, (const double *)h->in.p, n_points, b, groups, h->inv.p,
                                (double *)h->out.p);
@@ -318,7 +251,7 @@ int gd_lamina_contacts(gd_lamina *h, const float *distances, uint32_t frames, ui
             size_t const count = (size_t)b * n_points, offset = (size_t)f0 * n_points;
             unsigned const groups = (unsigned)(padded(count) / kPerLane);
             HIPCHK(hipMemcpyAsync(h->in.p, distances + offset, count * sizeof(float), hipMemcpyHostToDevice, st));
-            dim3 const grid(blocks_for(groups)), block(kBlock);
+            dim3 const grid(blocks_for(groups, kBlock)), block(kBlock);
             // the vector form may touch the sum's pad behind the last batch only: an earlier batch that is not a whole number
             // of lanes would add its pad lanes into the next batch's elements
             if (offset % kPerLane == 0 && (count % kPerLane == 0 || f0 + b == frames))
@@ -350,7 +283,7 @@ int gd_lamina_average(gd_lamina *h, float *out)
     for (size_t e0 = 0; e0 < total; e0 += step) {
         size_t const count = std::min(step, total - e0);
         unsigned const groups = (unsigned)(padded(count) / kPerLane);
-        hipLaunchKernelGGL(k_lamina_average, dim3(blocks_for(groups)), dim3(kBlock), 0, st, (const float4 *)(h->sum.p + e0), groups, (float)h->calls,
+        hipLaunchKernelGGL(k_lamina_average, dim3(blocks_for(groups, kBlock)), dim3(kBlock), 0, st, (const float4 *)(h->sum.p + e0), groups, (float)h->calls,
                            (float4 *)h->out.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out + e0, h->out.p, count * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -21,32 +21,16 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_rdf.h"
+#include "gdyn_analysis.hpp"
 #include "gdyn_types.h"
 
-int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
-
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return gd_report_error(code, buf);
-}
-#define HIPCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+using namespace gd;
 
 namespace {
 
@@ -199,36 +183,10 @@ __global__ void __launch_bounds__(kBlock) k_rdf_count(const double4 *__restrict_
     }
 }
 
-unsigned blocks_for(size_t n) { return (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 1u << 30); }
-
-template <typename T>
-struct dbuf {
-    T *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count)
-    {
-        if (count <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
 }  // namespace
 
-struct gd_rdf {
-    int device = 0;
+struct gd_rdf : gd::handle {
     unsigned max_frames = 0;
-    hipStream_t stream = nullptr;
     bool have_selection = false, self = true;
     unsigned n_points = 0, n_center = 0, n_target = 0;
     dbuf<unsigned> sel;                  // centres, then targets
@@ -281,7 +239,7 @@ int count_batch(gd_rdf *h, const void *xyz, int is_f64, unsigned B, const RdfGri
     HIPCHK(h->starts.ensure(n_starts));
     HIPCHK(h->counts.ensure((size_t)B * n_bins));
     HIPCHK(hipMemcpyAsync(h->in.p, xyz, n_in, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_rdf_keys, dim3(blocks_for(nb)), dim3(kBlock), 0, st, h->in.p, is_f64, h->n_points, h->sel.p, n_sel, h->n_center, B, g,
+    hipLaunchKernelGGL(k_rdf_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->in.p, is_f64, h->n_points, h->sel.p, n_sel, h->n_center, B, g,
                        h->keys[0].p, h->vals[0].p, h->gpos.p);
     unsigned long long const key_end = (unsigned long long)(h->self ? 1 : 2) * B * g.cells;
     unsigned bits = 1;
@@ -290,9 +248,9 @@ int count_batch(gd_rdf *h, const void *xyz, int is_f64, unsigned B, const RdfGri
     HIPCHK(gd_sort_contacts(nullptr, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
     HIPCHK(h->sort_tmp.ensure(tmp_bytes));
     HIPCHK(gd_sort_contacts(h->sort_tmp.p, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
-    hipLaunchKernelGGL(k_rdf_sorted, dim3(blocks_for(nb)), dim3(kBlock), 0, st, h->gpos.p, h->vals[1].p, nb, h->spos.p);
+    hipLaunchKernelGGL(k_rdf_sorted, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->gpos.p, h->vals[1].p, nb, h->spos.p);
     unsigned long long const base = h->self ? 0ull : (unsigned long long)B * g.cells;
-    hipLaunchKernelGGL(k_rdf_starts, dim3(blocks_for(n_starts)), dim3(kBlock), 0, st, h->keys[1].p, nb, base, n_starts, h->starts.p);
+    hipLaunchKernelGGL(k_rdf_starts, dim3(blocks_for(n_starts, kBlock)), dim3(kBlock), 0, st, h->keys[1].p, nb, base, n_starts, h->starts.p);
     HIPCHK(hipMemsetAsync(h->counts.p, 0, (size_t)B * n_bins * sizeof(unsigned long long), st));
     // a block adds at most kBlock * n_part to one uint32 counter
     bool const lds = n_bins <= GD_RDF_LDS_BINS && n_part < (1u << 24);
@@ -334,45 +292,12 @@ uint32_t gd_rdf_bins(double bin_width, double max_distance)
 
 int gd_rdf_create(const gd_rdf_desc *desc, gd_rdf **out)
 {
-    if (!desc || !out) return fail(GD_EINVAL, "gd_rdf_create: NULL argument");
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return fail(GD_ENODEVICE, "gd_rdf_create: no HIP device");
-    if (desc->device < 0 || desc->device >= count) return fail(GD_EINVAL, "gd_rdf_create: device %d of %d", desc->device, count);
-    HIPCHK(hipSetDevice(desc->device));
-    gd_rdf *h = new (std::nothrow) gd_rdf;
-    if (!h) return fail(GD_ENOMEM, "gd_rdf_create: out of host memory");
-    h->device = desc->device;
-    h->max_frames = desc->max_frames_per_launch;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(GD_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
-    *out = h;
+    if (int rc = gd::open("gd_rdf_create", desc, out)) return rc;
+    (*out)->max_frames = desc->max_frames_per_launch;
     return GD_OK;
 }
 
-int gd_rdf_destroy(gd_rdf *h)
-{
-    if (!h) return GD_OK;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    for (int k = 0; k < 2; k++) {
-        h->keys[k].release();
-        h->vals[k].release();
-    }
-    h->sel.release();
-    h->in.release();
-    h->gpos.release();
-    h->spos.release();
-    h->starts.release();
-    h->sort_tmp.release();
-    h->counts.release();
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return GD_OK;
-}
+int gd_rdf_destroy(gd_rdf *h) { return gd::close(h); }
 
 int gd_rdf_set_selection(gd_rdf *h, uint32_t n_points, const uint32_t *center_idx, uint32_t n_center, const uint32_t *target_idx,
                          uint32_t n_target)

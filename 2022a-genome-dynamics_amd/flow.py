@@ -15,7 +15,7 @@ import json
 
 import numpy as np
 
-from . import LIBGDYN_PATH, GdynError
+from ._binding import GdynError, Handle, as_frames, load_library
 
 FLOW_ABI_VERSION = 1       # GD_FLOW_ABI_VERSION of the include/gdyn_flow.h this binding mirrors
 FLOW_SYMBOLS = ["gd_flow_abi_version", "gd_flow_create", "gd_flow_destroy", "gd_flow_set_history", "gd_flow_velocities",
@@ -29,15 +29,7 @@ class _FlowDesc(C.Structure):
 
 def load_flow_library(path=None):
     """Loads libgdyn and checks the gd_flow_* symbols and their ABI version."""
-    path = path or LIBGDYN_PATH
-    d = C.CDLL(path)
-    for name in FLOW_SYMBOLS + ["gd_last_error"]:
-        if not hasattr(d, name):
-            raise OSError(f"{path}: missing symbol {name}")
-    d.gd_flow_abi_version.restype = C.c_int
-    if d.gd_flow_abi_version() != FLOW_ABI_VERSION:
-        raise OSError(f"{path}: flow ABI version {d.gd_flow_abi_version()}, this binding mirrors {FLOW_ABI_VERSION}")
-    d.gd_last_error.restype = C.c_char_p
+    d = load_library("flow", FLOW_SYMBOLS, FLOW_ABI_VERSION, path)
     d.gd_flow_create.argtypes = [C.POINTER(_FlowDesc), C.POINTER(C.c_void_p)]
     d.gd_flow_destroy.argtypes = [C.c_void_p]
     d.gd_flow_set_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
@@ -47,44 +39,23 @@ def load_flow_library(path=None):
     return d
 
 
-class Flow:
+class Flow(Handle):
     """One device-side history.  velocities() uploads it and computes the (smoothed) positions and velocities; particle()
     and grid() then reduce them around beads or points.  max_frames_per_launch: 0 = automatic (results do not depend on it)."""
 
+    _destroy = "gd_flow_destroy"
+
     def __init__(self, device=0, max_frames_per_launch=0, path=None):
-        self.dll = load_flow_library(path)
-        self._h = C.c_void_p()
+        super().__init__(load_flow_library(path))
         self._check(self.dll.gd_flow_create(C.byref(_FlowDesc(device, max_frames_per_launch)), C.byref(self._h)))
         self.shape = None
 
-    def _check(self, rc):
-        if rc != 0:
-            raise GdynError(rc, self.dll.gd_last_error().decode())
-
-    def close(self):
-        if self._h:
-            self.dll.gd_flow_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def velocities(self, history, smoothing=0, delay=1):
         """history (F, N, 3): returns the (smoothed, float64) positions and the float64 velocities, both (F, N, 3)."""
-        h = np.asarray(history)
+        h = np.asarray(history)      # a single (N, 3) frame, which as_frames would take, is no history
         if h.ndim != 3 or h.shape[2] != 3:
             raise ValueError(f"history must be (F, N, 3), got {h.shape}")
-        is64 = h.dtype == np.float64
-        h = np.ascontiguousarray(h, dtype=np.float64 if is64 else np.float32)
+        h, is64 = as_frames(h)
         F, N, _ = h.shape
         self._check(self.dll.gd_flow_set_history(self._h, h.ctypes.data, F, N, int(is64)))
         pos = np.empty((F, N, 3), np.float64)

@@ -22,7 +22,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import LIBGDYN_PATH, GdynError
+from ._binding import GdynError, Handle, load_library
 
 HIC_ABI_VERSION = 1      # GD_HIC_ABI_VERSION of the include/gdyn_hic.h this binding mirrors
 HIC_SYMBOLS = ["gd_hic_abi_version", "gd_hic_create", "gd_hic_destroy", "gd_hic_add_band", "gd_hic_add_distance_profile",
@@ -39,15 +39,7 @@ class _HicDesc(C.Structure):
 
 def load_hic_library(path=None):
     """Loads libgdyn and checks the gd_hic_* symbols and their ABI version."""
-    path = path or LIBGDYN_PATH
-    d = C.CDLL(path)
-    for name in HIC_SYMBOLS + ["gd_last_error"]:
-        if not hasattr(d, name):
-            raise OSError(f"{path}: missing symbol {name}")
-    d.gd_hic_abi_version.restype = C.c_int
-    if d.gd_hic_abi_version() != HIC_ABI_VERSION:
-        raise OSError(f"{path}: hic ABI version {d.gd_hic_abi_version()}, this binding mirrors {HIC_ABI_VERSION}")
-    d.gd_last_error.restype = C.c_char_p
+    d = load_library("hic", HIC_SYMBOLS, HIC_ABI_VERSION, path)
     P32 = C.POINTER(C.c_int32)
     d.gd_hic_create.argtypes = [C.POINTER(_HicDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
     d.gd_hic_destroy.argtypes = [C.c_void_p]
@@ -210,39 +202,19 @@ def downsample(values, rate=2, window=None):
 
 # ---- the device
 
-class HicSignals:
+class HicSignals(Handle):
     """One device-side handle for one bin table.  max_pixels_per_launch: 0 = automatic (no integer result depends on it)."""
 
+    _destroy = "gd_hic_destroy"
+
     def __init__(self, chrom_code, device=0, max_pixels_per_launch=0, path=None):
-        self.dll = load_hic_library(path)
-        self._h = C.c_void_p()
+        super().__init__(load_hic_library(path))
         self._targets = []
         chrom = np.ascontiguousarray(chrom_code, dtype=np.int32)
         if chrom.ndim != 1:
             raise ValueError(f"chrom_code must be one-dimensional, got {chrom.shape}")
         self.n_bins = len(chrom)
         self._check(self.dll.gd_hic_create(C.byref(_HicDesc(device, max_pixels_per_launch)), chrom.ctypes.data, self.n_bins, C.byref(self._h)))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise GdynError(rc, self.dll.gd_last_error().decode())
-
-    def close(self):
-        if self._h:
-            self.dll.gd_hic_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def _added(self, rc, target, what):
         self._check(rc)

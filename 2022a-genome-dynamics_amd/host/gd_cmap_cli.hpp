@@ -1,7 +1,7 @@
 // gd_cmap_cli.hpp -- what gd_contact_map, gd_nad_profile, gd_gw_contact_matrix and gd_power_law share: the command lines of
 // the reference's 5-sim-genome/src/{contact_map, nad_profile, gw_contact_matrix, power_law} (__main__.py), their reads of a
 // trajectory file (the metadata, the frames they select and the stored contact maps) and their outputs.  The sums are
-// libgdyn's (include/gdyn_cmap.h); the HDF5 helpers are the flow programs' (gd_flow_cli.hpp).
+// libgdyn's (include/gdyn_cmap.h); the HDF5 helpers are the programs' shared ones (gd_cli_util.hpp).
 //
 // Deviations from the reference, all documented in DESIGN.md section 7d: --chroms and --output are required (the reference's
 // defaults die in None.split and h5py.File(None)); a --frame-range of more than two tokens is a usage error; the NAD profile
@@ -17,7 +17,7 @@
 #include <json.hpp>   // nlohmann/json single header
 
 #include "../../include/gdyn_cmap.h"
-#include "gd_flow_cli.hpp"
+#include "gd_cli_util.hpp"
 
 namespace gd {
 namespace cmap {
@@ -93,7 +93,7 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
         else { err = "argument " + key + ": expected one argument"; return 2; }
         if (key == "--after" || key == "--before" || key == "--rebin-rate") {
             long value = 0;
-            if (!flow::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
+            if (!cli::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
             if (key == "--after") { o.has_after = true; o.after = value; }
             else if (key == "--before") { o.has_before = true; o.before = value; }
             else o.rebin_rate = value;
@@ -105,7 +105,7 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
             // the reference leaves three tokens or more as a string, which fails in slice(*frame_range)
             if (tokens.size() > 2) { err = "argument --frame-range: expected START[:END], got '" + v + "'"; return 2; }
             o.range_tokens = (int)tokens.size();
-            if (!flow::parse_int(tokens[0], o.range_a) || (tokens.size() == 2 && !flow::parse_int(tokens[1], o.range_b))) {
+            if (!cli::parse_int(tokens[0], o.range_a) || (tokens.size() == 2 && !cli::parse_int(tokens[1], o.range_b))) {
                 err = "argument --frame-range: invalid int value in '" + v + "'";
                 return 2;
             }
@@ -154,11 +154,6 @@ inline void print_plan(program p, options const &o)
     }
 }
 
-inline void check(int rc)
-{
-    if (rc != GD_OK) throw std::runtime_error(std::string("gdyn: ") + gd_last_error());
-}
-
 struct device {      // created when the first file has been read: a missing input is reported as such
     gd_cmap *h = nullptr;
     double startup = 0;      // seconds gd_cmap_create took (the HIP runtime starts there), inside whichever lap the caller opens it in
@@ -167,7 +162,7 @@ struct device {      // created when the first file has been read: a missing inp
         if (h) return;
         auto const t = std::chrono::steady_clock::now();
         gd_cmap_desc const d{0, 0};
-        check(gd_cmap_create(&d, &h));
+        cli::check(gd_cmap_create(&d, &h));
         startup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
     }
     ~device() { gd_cmap_destroy(h); }
@@ -175,9 +170,9 @@ struct device {      // created when the first file has been read: a missing inp
     std::vector<int32_t> fetch(int32_t target)
     {
         uint64_t count = 0;
-        check(gd_cmap_target_size(h, target, &count));
+        cli::check(gd_cmap_target_size(h, target, &count));
         std::vector<int32_t> out(count);
-        check(gd_cmap_fetch(h, target, out.data()));
+        cli::check(gd_cmap_fetch(h, target, out.data()));
         return out;
     }
 };
@@ -267,7 +262,7 @@ inline trajectory load(std::string const &path, request const &rq)
     if (rq.how == frames::by_step) {
         for (auto const &s : steps) {
             long v = 0;
-            h5::check(flow::parse_int(s, v), path + ": step '" + s + "' is not an integer");
+            h5::check(cli::parse_int(s, v), path + ": step '" + s + "' is not an integer");
             if ((!rq.o->has_before || v < rq.o->before) && (!rq.o->has_after || v >= rq.o->after)) chosen.push_back(std::to_string(v));
         }
     } else if (rq.how == frames::by_slice) {
@@ -325,7 +320,7 @@ inline void run_by_step(program p, options const &o)
 {
     bool const nad = p == program::nad_profile;
     auto const files = job_files(o.inputs[0]);
-    flow::stopwatch sw;
+    cli::stopwatch sw;
     request rq;
     rq.o = &o;
     rq.types = nad;
@@ -339,20 +334,20 @@ inline void run_by_step(program p, options const &o)
         sw.read += sw.lap();
         if (nad && !t.nucleolus_member) throw std::runtime_error(files[k] + ": particle_types has no enum member 'nucleolus'");      // KeyError
         dev.open();
-        check(gd_cmap_clear(dev.h));
+        cli::check(gd_cmap_clear(dev.h));
         std::vector<int32_t> targets;
         for (auto const &c : o.chroms) {
             auto const it = t.keys.find(c);
             if (it == t.keys.end() || it->second * 2 + 1 >= t.ranges.size()) throw std::runtime_error(files[k] + ": no chromosome '" + c + "'");      // KeyError
             uint32_t const beg = (uint32_t)t.ranges[2 * it->second], end = (uint32_t)t.ranges[2 * it->second + 1];
             int32_t id = -1;
-            if (nad) check(gd_cmap_add_nucleolus_profile(dev.h, beg, end, t.is_nucleolus.data(), (uint32_t)t.n_particles, &id));
-            else check(gd_cmap_add_region(dev.h, beg, end, &id));
+            if (nad) cli::check(gd_cmap_add_nucleolus_profile(dev.h, beg, end, t.is_nucleolus.data(), (uint32_t)t.n_particles, &id));
+            else cli::check(gd_cmap_add_region(dev.h, beg, end, &id));
             targets.push_back(id);
         }
-        check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
+        cli::check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
         for (auto id : targets) {
-            if (!nad) check(gd_cmap_finish(dev.h, id));
+            if (!nad) cli::check(gd_cmap_finish(dev.h, id));
             auto const part = dev.fetch(id);
             if (first) {
                 sum.assign(part.begin(), part.end());
@@ -419,7 +414,7 @@ inline rebinning rebin(trajectory const &t, long rate)
 
 inline void run_gw(options const &o)
 {
-    flow::stopwatch sw;
+    cli::stopwatch sw;
     request meta_only;
     meta_only.how = frames::none;
     trajectory const head = load(o.inputs[0], meta_only);
@@ -432,12 +427,12 @@ inline void run_gw(options const &o)
     device dev;
     dev.open();
     int32_t id = -1;
-    check(gd_cmap_add_binned(dev.h, rb.map.data(), (uint32_t)rb.map.size(), rb.n_bins, &id));
+    cli::check(gd_cmap_add_binned(dev.h, rb.map.data(), (uint32_t)rb.map.size(), rb.n_bins, &id));
     std::fputs("Loading: ", stderr);
     for (std::size_t k = 0; k < o.inputs.size(); k++) {
         trajectory const t = pf.take();
         sw.read += sw.lap();
-        check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
+        cli::check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
         sw.compute += sw.lap();
         if (k % 10 == 0) std::fprintf(stderr, "%zu", k);
         std::fputc('.', stderr);
@@ -454,12 +449,12 @@ inline void run_gw(options const &o)
         int32_t const v = (int32_t)kv.second;
         H5Tenum_insert(names, kv.first.c_str(), &v);
     }
-    flow::put_dataset(file, "/metadata/chromosome_ranges", rb.binned.data(), {rb.binned.size() / 2, 2}, 4, names, names, nullptr);
-    flow::put_dataset(file, "/metadata/rebin_map", rb.map.data(), {rb.map.size()}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, nullptr);
-    flow::filters f;
+    cli::put_dataset(file, "/metadata/chromosome_ranges", rb.binned.data(), {rb.binned.size() / 2, 2}, 4, names, names, nullptr);
+    cli::put_dataset(file, "/metadata/rebin_map", rb.map.data(), {rb.map.size()}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, nullptr);
+    cli::filters f;
     f.scaleoffset_kind = H5Z_SO_INT;
     f.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;      // scaleoffset=0: integer scale-offset is lossless
-    flow::put_dataset(file, "/contact_matrix", matrix.data(), {rb.n_bins, rb.n_bins}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &f);
+    cli::put_dataset(file, "/contact_matrix", matrix.data(), {rb.n_bins, rb.n_bins}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &f);
     H5Fflush(file, H5F_SCOPE_GLOBAL);
     sw.write += sw.lap();
     sw.report("gd_gw_contact_matrix");
@@ -497,7 +492,7 @@ inline double fit_exponent(std::vector<int32_t> const &profile, std::size_t beg,
 
 inline void run_power_law(options const &o)
 {
-    flow::stopwatch sw;
+    cli::stopwatch sw;
     request rq;
     rq.how = frames::last_with_map;
     rq.o = &o;
@@ -517,10 +512,10 @@ inline void run_power_law(options const &o)
             longest = std::max(longest, (uint32_t)(t.ranges[c + 1] - t.ranges[c]));
         }
         dev.open();
-        check(gd_cmap_clear(dev.h));
+        cli::check(gd_cmap_clear(dev.h));
         int32_t id = -1;
-        check(gd_cmap_add_separation_profile(dev.h, chain.data(), (uint32_t)chain.size(), longest, &id));
-        check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
+        cli::check(gd_cmap_add_separation_profile(dev.h, chain.data(), (uint32_t)chain.size(), longest, &id));
+        cli::check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
         auto const profile = dev.fetch(id);
         double const near = fit_exponent(profile, 3, 20), mid = fit_exponent(profile, 20, 100), far = fit_exponent(profile, 100, 1500);
         sw.compute += sw.lap();

@@ -23,6 +23,7 @@
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_flow.h"
+#include "gd_cli_util.hpp"
 #include "gd_h5util.hpp"
 
 namespace gd {
@@ -44,21 +45,6 @@ struct options {
     std::vector<std::string> trajfiles;
 };
 
-inline bool parse_int(std::string const &s, long &out)
-{
-    char *end = nullptr;
-    errno = 0;
-    out = std::strtol(s.c_str(), &end, 10);
-    return !s.empty() && errno == 0 && end && *end == '\0';
-}
-
-inline bool parse_float(std::string const &s, double &out)
-{
-    char *end = nullptr;
-    out = std::strtod(s.c_str(), &end);
-    return !s.empty() && end && *end == '\0';
-}
-
 // argparse's conventions: "--opt value" or "--opt=value"; exit status 2 with a usage line on any error
 inline int parse(int argc, char **argv, bool grid, options &o, std::string &err)
 {
@@ -75,16 +61,16 @@ inline int parse(int argc, char **argv, bool grid, options &o, std::string &err)
             else { err = "argument " + key + ": expected one argument"; return 2; }
             bool ok = true;
             if (key == "--name") o.name = v;
-            else if (key == "--smoothing") ok = o.has_smoothing = parse_int(v, o.smoothing);
-            else if (key == "--velocity-delay") ok = parse_int(v, o.delay);
-            else if (key == "--scan-radius") ok = o.has_radius = parse_float(v, o.radius);
-            else if (key == "--jobs") { long j; ok = parse_int(v, j); }      // accepted; one device does the work
-            else if (grid && key == "--grid-interval") ok = o.has_interval = parse_float(v, o.interval);
+            else if (key == "--smoothing") ok = o.has_smoothing = cli::parse_int(v, o.smoothing);
+            else if (key == "--velocity-delay") ok = cli::parse_int(v, o.delay);
+            else if (key == "--scan-radius") ok = o.has_radius = cli::parse_float(v, o.radius);
+            else if (key == "--jobs") { long j; ok = cli::parse_int(v, j); }      // accepted; one device does the work
+            else if (grid && key == "--grid-interval") ok = o.has_interval = cli::parse_float(v, o.interval);
             else if (grid && (key == "--x-range" || key == "--y-range" || key == "--z-range")) {
                 int const axis = key[2] - 'x';
                 auto comma = v.find(',');
                 ok = comma != std::string::npos && v.find(',', comma + 1) == std::string::npos &&
-                     parse_float(v.substr(0, comma), o.range[axis][0]) && parse_float(v.substr(comma + 1), o.range[axis][1]);
+                     cli::parse_float(v.substr(0, comma), o.range[axis][0]) && cli::parse_float(v.substr(comma + 1), o.range[axis][1]);
                 o.has_range[axis] = ok;
             } else { err = "unrecognized arguments: " + a; return 2; }
             if (!ok) { err = "argument " + key + ": invalid value: '" + v + "'"; return 2; }
@@ -104,43 +90,15 @@ inline int parse(int argc, char **argv, bool grid, options &o, std::string &err)
     return 0;
 }
 
-// repr(float) of Python: the shortest round-trip digits, fixed notation for exponents in [-4, 16), else d.ddde+XX
-inline std::string py_float(double v)
-{
-    if (std::isnan(v)) return "NaN";                       // json.dumps spellings
-    if (std::isinf(v)) return v > 0 ? "Infinity" : "-Infinity";
-    char buf[64];
-    auto res = std::to_chars(buf, buf + sizeof buf, v, std::chars_format::scientific);
-    std::string s(buf, res.ptr);
-    std::string sign;
-    if (s[0] == '-') { sign = "-"; s = s.substr(1); }
-    auto const e = s.find('e');
-    int const exp10 = std::atoi(s.c_str() + e + 1);
-    std::string digits;
-    for (std::size_t k = 0; k < e; k++) if (s[k] != '.') digits += s[k];
-    if (exp10 >= -4 && exp10 < 16) {
-        std::string out;
-        if (exp10 < 0) out = "0." + std::string((std::size_t)(-exp10 - 1), '0') + digits;
-        else if ((int)digits.size() <= exp10 + 1) out = digits + std::string((std::size_t)(exp10 + 1 - (int)digits.size()), '0') + ".0";
-        else out = digits.substr(0, (std::size_t)exp10 + 1) + "." + digits.substr((std::size_t)exp10 + 1);
-        return sign + out;
-    }
-    std::string mant = digits.substr(0, 1);
-    if (digits.size() > 1) mant += "." + digits.substr(1);
-    char ex[16];
-    std::snprintf(ex, sizeof ex, "e%c%02d", exp10 < 0 ? '-' : '+', std::abs(exp10));
-    return sign + mant + ex;
-}
-
 inline std::string config_json(options const &o, bool grid)
 {
     std::ostringstream s;
     s << "{\"smoothing\": " << (o.has_smoothing ? std::to_string(o.smoothing) : "null") << ", \"velocity_delay\": " << o.delay
-      << ", \"scan_radius\": " << py_float(o.radius);
+      << ", \"scan_radius\": " << cli::py_float(o.radius);
     if (grid) {
-        s << ", \"grid_interval\": " << py_float(o.interval);
+        s << ", \"grid_interval\": " << cli::py_float(o.interval);
         char const *names[3] = {"x_range", "y_range", "z_range"};
-        for (int a = 0; a < 3; a++) s << ", \"" << names[a] << "\": [" << py_float(o.range[a][0]) << ", " << py_float(o.range[a][1]) << "]";
+        for (int a = 0; a < 3; a++) s << ", \"" << names[a] << "\": [" << cli::py_float(o.range[a][0]) << ", " << cli::py_float(o.range[a][1]) << "]";
     }
     s << "}";
     return s.str();
@@ -187,14 +145,6 @@ inline std::string sha256_hex(std::string const &msg)
 
 inline std::string analysis_name(options const &o, std::string const &config) { return o.name.empty() ? sha256_hex(config).substr(0, 7) : o.name; }
 
-inline std::string sample_name(std::string const &path)      // os.path.splitext(os.path.basename(path))[0]
-{
-    std::string b = path.substr(path.rfind('/') == std::string::npos ? 0 : path.rfind('/') + 1);
-    auto dot = b.rfind('.');
-    if (dot != std::string::npos && dot != 0 && b.find_first_not_of('.') < dot) b = b.substr(0, dot);
-    return b;
-}
-
 // load_positions: /snapshots/interphase/<step>/positions for the steps of .steps in stored order, as float32 (F, N, 3)
 inline std::vector<float> load_history(std::string const &path, uint32_t &frames, uint32_t &beads)
 {
@@ -220,86 +170,14 @@ inline std::vector<float> load_history(std::string const &path, uint32_t &frames
     return out;
 }
 
-struct filters {
-    bool shuffle = true;
-    int deflate = 1;
-    int scaleoffset_kind = -1;          // H5Z_SO_FLOAT_DSCALE / H5Z_SO_INT, or -1: none
-    int scaleoffset_factor = 0;
-};
-
-// put_dataset: an n-d array, replaced if present; chunks of at most 1 MiB along the leading axes (h5py chunks any filtered dataset)
-inline void put_dataset(hid_t loc, std::string const &path, void const *data, std::vector<hsize_t> const &dims, std::size_t elem,
-                        hid_t mem_type, hid_t file_type, filters const *f)
-{
-    h5::unlink_if_present(loc, path);
-    h5::hid space(H5Screate_simple((int)dims.size(), dims.data(), nullptr)), props(H5Pcreate(H5P_DATASET_CREATE)),
-        lcpl(H5Pcreate(H5P_LINK_CREATE));
-    H5Pset_create_intermediate_group(lcpl, 1);
-    hsize_t count = 1;
-    for (auto d : dims) count *= d;
-    if (f && count > 0) {
-        std::vector<hsize_t> chunk(dims);
-        for (std::size_t a = 0; a < chunk.size(); a++) {
-            hsize_t bytes = elem;
-            for (std::size_t b = 0; b < chunk.size(); b++) bytes *= chunk[b];
-            if (bytes <= (1u << 20)) break;
-            hsize_t rest = bytes / chunk[a];
-            chunk[a] = std::max<hsize_t>(1, (1u << 20) / rest);
-        }
-        H5Pset_chunk(props, (int)chunk.size(), chunk.data());
-        if (f->scaleoffset_kind >= 0) H5Pset_scaleoffset(props, (H5Z_SO_scale_type_t)f->scaleoffset_kind, f->scaleoffset_factor);
-        if (f->shuffle) H5Pset_shuffle(props);
-        if (f->deflate >= 0) H5Pset_deflate(props, (unsigned)f->deflate);
-    }
-    h5::hid ds(H5Dcreate2(loc, path.c_str(), file_type, space, lcpl, props, H5P_DEFAULT));
-    h5::check(ds >= 0, "cannot create " + path);
-    if (count) h5::check(H5Dwrite(ds, mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, data) >= 0, "cannot write " + path);
-}
-
-inline hid_t open_output(std::string const &path)      // h5py.File(path, "a")
-{
-    H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
-    hid_t f = std::ifstream(path).good() ? H5Fopen(path.c_str(), H5F_ACC_RDWR, H5P_DEFAULT)
-                                                            : H5Fcreate(path.c_str(), H5F_ACC_EXCL, H5P_DEFAULT, H5P_DEFAULT);
-    h5::check(f >= 0, "cannot open " + path);
-    return f;
-}
-
-inline hid_t require_group(hid_t file, std::string const &path)      // put_group
-{
-    if (H5Lexists(file, path.c_str(), H5P_DEFAULT) > 0) return H5Gopen2(file, path.c_str(), H5P_DEFAULT);
-    h5::hid lcpl(H5Pcreate(H5P_LINK_CREATE));
-    H5Pset_create_intermediate_group(lcpl, 1);
-    hid_t g = H5Gcreate2(file, path.c_str(), lcpl, H5P_DEFAULT, H5P_DEFAULT);
-    h5::check(g >= 0, "cannot create group " + path);
-    return g;
-}
-
 struct device {      // one gd_flow handle; every failure of the library ends the program with its message
     gd_flow *h = nullptr;
     device()
     {
         gd_flow_desc d{0, 0};
-        check(gd_flow_create(&d, &h));
+        cli::check(gd_flow_create(&d, &h));
     }
     ~device() { gd_flow_destroy(h); }
-    static void check(int rc)
-    {
-        if (rc != GD_OK) throw std::runtime_error(std::string("gdyn: ") + gd_last_error());
-    }
-};
-
-struct stopwatch {
-    double read = 0, compute = 0, write = 0;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    double lap()
-    {
-        auto const now = std::chrono::steady_clock::now();
-        double const s = std::chrono::duration<double>(now - t).count();
-        t = now;
-        return s;
-    }
-    void report(char const *prog) const { std::fprintf(stderr, "%s: read %.3f s, compute %.3f s, write %.3f s\n", prog, read, compute, write); }
 };
 
 // common front: parse, print the config for --dry-run; returns -1 to go on, else the exit status

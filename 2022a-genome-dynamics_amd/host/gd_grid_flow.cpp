@@ -68,36 +68,36 @@ int main(int argc, char **argv)
         int64_t const shape[3] = {(int64_t)nx, (int64_t)ny, (int64_t)nz};
 
         device dev;
-        gd::h5::hid file(open_output(o.outfile));
-        gd::h5::hid group(require_group(file, "/grid_flow/" + name));
+        gd::h5::hid file(gd::cli::open_output(o.outfile));
+        gd::h5::hid group(gd::cli::require_group(file, "/grid_flow/" + name));
         gd::h5::write_string(group, ".config", config);
         auto samples = gd::h5::read_string_list(group, ".samples");      // incremental analysis: earlier samples stay listed
-        put_dataset(group, ".grid/shape", shape, {3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
-        put_dataset(group, ".grid/points", points.data(), {G, 3}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
-        put_dataset(group, ".grid/indices", indices.data(), {G, 3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
+        gd::cli::put_dataset(group, ".grid/shape", shape, {3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
+        gd::cli::put_dataset(group, ".grid/points", points.data(), {G, 3}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
+        gd::cli::put_dataset(group, ".grid/indices", indices.data(), {G, 3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
         bool const smooth = o.has_smoothing && o.smoothing > 0;
-        stopwatch sw;
+        gd::cli::stopwatch sw;
         for (auto const &path : o.trajfiles) {
-            std::string const sample = sample_name(path);
+            std::string const sample = gd::cli::sample_name(path);
             samples.push_back(sample);
             uint32_t F = 0, N = 0;
             auto const hist = load_history(path, F, N);
             sw.read += sw.lap();
             std::vector<float> flows((std::size_t)F * G * 3);
             std::vector<int32_t> cov((std::size_t)F * G);
-            device::check(gd_flow_set_history(dev.h, hist.data(), F, N, 0));
-            device::check(gd_flow_velocities(dev.h, smooth ? (uint32_t)o.smoothing : 0, (uint32_t)o.delay, nullptr, nullptr));
-            device::check(gd_flow_grid(dev.h, o.radius, points.data(), (uint32_t)G, flows.data(), cov.data()));
+            gd::cli::check(gd_flow_set_history(dev.h, hist.data(), F, N, 0));
+            gd::cli::check(gd_flow_velocities(dev.h, smooth ? (uint32_t)o.smoothing : 0, (uint32_t)o.delay, nullptr, nullptr));
+            gd::cli::check(gd_flow_grid(dev.h, o.radius, points.data(), (uint32_t)G, flows.data(), cov.data()));
             int const factor = scaleoffset_factor(flows);
             sw.compute += sw.lap();
-            filters ff;
+            gd::cli::filters ff;
             ff.scaleoffset_kind = H5Z_SO_FLOAT_DSCALE;
             ff.scaleoffset_factor = factor;
-            put_dataset(group, sample + "/flows", flows.data(), {F, G, 3}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &ff);
-            filters fc;
+            gd::cli::put_dataset(group, sample + "/flows", flows.data(), {F, G, 3}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &ff);
+            gd::cli::filters fc;
             fc.scaleoffset_kind = H5Z_SO_INT;
             fc.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;
-            put_dataset(group, sample + "/coverages", cov.data(), {F, G}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &fc);
+            gd::cli::put_dataset(group, sample + "/coverages", cov.data(), {F, G}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &fc);
             H5Fflush(file, H5F_SCOPE_GLOBAL);
             sw.write += sw.lap();
         }

@@ -13,7 +13,7 @@
 #include <map>
 
 #include "../../include/gdyn_hic.h"
-#include "gd_flow_cli.hpp"
+#include "gd_cli_util.hpp"
 
 namespace gd {
 namespace hic {
@@ -85,7 +85,7 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
         else if (key == "--normalize") o.normalize = v;
         else {
             long value = 0;
-            if (!flow::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
+            if (!cli::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
             if (key == "-b" || key == "--binsize") { o.binsize = value; o.has_binsize = true; }
             else if (key == "-w") o.width = value;
             else if (key == "--rate") o.rate = value;
@@ -131,11 +131,6 @@ inline void print_plan(program p, options const &o)
     std::printf("read\t%s\t%s/pixels/{bin1_id,bin2_id,count}\n", o.input.c_str(), res.c_str());
     std::printf("write\t%s\t%s\n", out.c_str(),
                 p == program::interactions ? signal_header(o.width).c_str() : p == program::alpha ? "chrom\tstart\tend\talpha" : "distance\tcontacts");
-}
-
-inline void check(int rc)
-{
-    if (rc != GD_OK) throw std::runtime_error(std::string("gdyn: ") + gd_last_error());
 }
 
 // Python's format(value, "g"); a NaN of either sign prints "nan"
@@ -287,7 +282,7 @@ struct device {
     {
         auto const t = std::chrono::steady_clock::now();
         gd_hic_desc const d{0, 0};
-        check(gd_hic_create(&d, bins.chrom.data(), (uint32_t)bins.chrom.size(), &h));
+        cli::check(gd_hic_create(&d, bins.chrom.data(), (uint32_t)bins.chrom.size(), &h));
         startup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
     }
     ~device() { gd_hic_destroy(h); }
@@ -295,7 +290,7 @@ struct device {
 };
 
 // one pass: chunk k + 1 is read on a second thread while the device accumulates chunk k
-inline void stream_pixels(cooler const &c, device &dev, flow::stopwatch &sw)
+inline void stream_pixels(cooler const &c, device &dev, cli::stopwatch &sw)
 {
     auto fetch = [&c](hsize_t first) { return c.read_pixels(first, std::min<hsize_t>(kChunkPixels, c.n_pixels - first)); };
     std::future<pixel_chunk> next;
@@ -304,7 +299,7 @@ inline void stream_pixels(cooler const &c, device &dev, flow::stopwatch &sw)
         pixel_chunk const chunk = next.get();
         if (first + kChunkPixels < c.n_pixels) next = std::async(std::launch::async, fetch, first + kChunkPixels);
         sw.read += sw.lap();
-        check(gd_hic_accumulate(dev.h, chunk.bin1.data(), chunk.bin2.data(), chunk.count.data(), chunk.count.size()));
+        cli::check(gd_hic_accumulate(dev.h, chunk.bin1.data(), chunk.bin2.data(), chunk.count.data(), chunk.count.size()));
         sw.compute += sw.lap();
     }
 }
@@ -329,7 +324,7 @@ inline bool std_chrom_order(std::string const &name, std::pair<long, long> &key)
 {
     std::string const s = strip_chr(name);
     long n = 0;
-    if (flow::parse_int(s, n)) { key = {0, n}; return true; }
+    if (cli::parse_int(s, n)) { key = {0, n}; return true; }
     static std::map<std::string, long> const rank = {{"X", 1}, {"Y", 2}, {"MT", 3}, {"M", 3}};
     auto const it = rank.find(s);
     if (it == rank.end()) return false;
@@ -341,7 +336,7 @@ inline bool std_chrom_order(std::string const &name, std::pair<long, long> &key)
 
 inline void run_interactions(options const &o)
 {
-    flow::stopwatch sw;
+    cli::stopwatch sw;
     cooler c(o.input, o.binsize);
     bin_table const bins = c.read_bins(true);
     auto const runs = runs_by_code(bins, o.input);
@@ -360,12 +355,12 @@ inline void run_interactions(options const &o)
     dev.open(bins);
     int32_t band = -1;
     uint32_t const W = (uint32_t)o.width;
-    check(gd_hic_add_band(dev.h, W, &band));
+    cli::check(gd_hic_add_band(dev.h, W, &band));
     sw.compute += sw.lap();
     stream_pixels(c, dev, sw);
     std::size_t const n = bins.chrom.size();
     std::vector<double> D(n * (W - 1)), I(n * (W - 2));
-    check(gd_hic_decay_insulation(dev.h, band, D.data(), I.data()));
+    cli::check(gd_hic_decay_insulation(dev.h, band, D.data(), I.data()));
     sw.compute += sw.lap();
     std::fprintf(out.f, "%s\n", signal_header(o.width).c_str());
     std::string line;
@@ -390,7 +385,7 @@ inline void run_interactions(options const &o)
 
 inline void run_alpha(options const &o)
 {
-    flow::stopwatch sw;
+    cli::stopwatch sw;
     cooler c(o.input, o.binsize);
     bin_table const bins = c.read_bins(true);
     // enumerate_runs; the reference looks the run of a chromosome up by its code: chrom_ranges[key]
@@ -410,11 +405,11 @@ inline void run_alpha(options const &o)
     device dev;
     dev.open(bins);
     int32_t band = -1;
-    check(gd_hic_add_band(dev.h, (uint32_t)o.width + 1, &band));
+    cli::check(gd_hic_add_band(dev.h, (uint32_t)o.width + 1, &band));
     sw.compute += sw.lap();
     stream_pixels(c, dev, sw);
     std::vector<double> alpha(bins.chrom.size());
-    check(gd_hic_local_alpha(dev.h, band, alpha.data()));
+    cli::check(gd_hic_local_alpha(dev.h, band, alpha.data()));
     sw.compute += sw.lap();
     std::fputs("chrom\tstart\tend\talpha\n", out.f);
     for (std::size_t m = 0; m < bins.names.size(); m++) {
@@ -431,7 +426,7 @@ inline void run_alpha(options const &o)
 
 inline void run_power_law(options const &o)
 {
-    flow::stopwatch sw;
+    cli::stopwatch sw;
     cooler c(o.input, o.binsize);
     bin_table const bins = c.read_bins(false);
     std::size_t const n = bins.chrom.size();
@@ -455,11 +450,11 @@ inline void run_power_law(options const &o)
     device dev;
     dev.open(bins);
     int32_t profile = -1;
-    check(gd_hic_add_distance_profile(dev.h, excluded.data(), weighted ? weights.data() : nullptr, size, &profile));
+    cli::check(gd_hic_add_distance_profile(dev.h, excluded.data(), weighted ? weights.data() : nullptr, size, &profile));
     sw.compute += sw.lap();
     stream_pixels(c, dev, sw);
     std::vector<double> mean(size);
-    check(gd_hic_fetch_profile(dev.h, profile, nullptr, nullptr, mean.data()));
+    cli::check(gd_hic_fetch_profile(dev.h, profile, nullptr, nullptr, mean.data()));
     sw.compute += sw.lap();
     std::puts("distance\tcontacts");
     for (uint32_t d = 0; d < size; d++) std::printf("%lld\t%s\n", (long long)d * o.binsize, fmt_g(mean[d]).c_str());
@@ -490,7 +485,7 @@ inline double parse_value(std::string const &s, std::string const &where)
     for (auto m : missing)
         if (s == m) return std::nan("");
     double v = 0;
-    if (!flow::parse_float(s, v)) throw std::runtime_error(where + ": '" + s + "' is not a number");
+    if (!cli::parse_float(s, v)) throw std::runtime_error(where + ": '" + s + "' is not a number");
     return v;
 }
 

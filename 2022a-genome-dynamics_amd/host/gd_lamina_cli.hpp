@@ -1,7 +1,7 @@
 // gd_lamina_cli.hpp -- gd_analyze_lamina: the command line of the reference's analyze_lamina (scripts/analyze_lamina,
 // 5-sim-genome/src/analyze_lamina/__main__.py), the inputs of command.py (interphase positions and the wall_semiaxes of
 // each snapshot's context, the metadata of the first trajectory) and the datasets of its output file.  The arithmetic is
-// libgdyn's (include/gdyn_lamina.h); the HDF5 helpers are the flow programs' (gd_flow_cli.hpp).
+// libgdyn's (include/gdyn_lamina.h); the HDF5 helpers are the programs' shared ones (gd_cli_util.hpp).
 #pragma once
 #include <future>
 #include <memory>
@@ -9,7 +9,7 @@
 #include <json.hpp>   // nlohmann/json single header
 
 #include "../../include/gdyn_lamina.h"
-#include "gd_flow_cli.hpp"
+#include "gd_cli_util.hpp"
 
 namespace gd {
 namespace lamina {
@@ -47,7 +47,7 @@ inline int parse(int argc, char **argv, options &o, std::string &err)
             else if (k + 1 < argc) v = argv[++k];
             else { err = "argument " + key + ": expected one argument"; return 2; }
             if (key == "--name") o.name = v;
-            else if (!(o.has_contact_distance = flow::parse_float(v, o.contact_distance))) {
+            else if (!(o.has_contact_distance = cli::parse_float(v, o.contact_distance))) {
                 err = "argument --contact-distance: invalid float value: '" + v + "'";
                 return 2;
             }
@@ -81,18 +81,13 @@ inline void print_plan(options const &o)
         std::printf("read\t%s\t/metadata/{config,particle_types,chromosome_ranges}\n", o.trajfiles[0].c_str());
         for (auto const &t : o.trajfiles) std::printf("read\t%s\t/snapshots/interphase/<step>/{positions,context}\n", t.c_str());
         std::printf("write\t%s\t/metadata/{simulation_config,particle_types,chromosome_ranges,chromosome_names}\n", o.outfile.c_str());
-        for (auto const &t : o.trajfiles) std::printf("write\t%s\t/distance/%s\n", o.outfile.c_str(), flow::sample_name(t).c_str());
+        for (auto const &t : o.trajfiles) std::printf("write\t%s\t/distance/%s\n", o.outfile.c_str(), cli::sample_name(t).c_str());
     } else {
-        std::printf("contact_distance\t%s\n", flow::py_float(o.contact_distance).c_str());
+        std::printf("contact_distance\t%s\n", cli::py_float(o.contact_distance).c_str());
         std::printf("read\t%s\t/distance/<key>\n", o.outfile.c_str());
         std::printf("write\t%s\t/contact/%s/<key>\n", o.outfile.c_str(), o.name.c_str());
         std::printf("write\t%s\t/average_contact/%s\n", o.outfile.c_str(), o.name.c_str());
     }
-}
-
-inline void check(int rc)
-{
-    if (rc != GD_OK) throw std::runtime_error(std::string("gdyn: ") + gd_last_error());
 }
 
 struct device {
@@ -100,7 +95,7 @@ struct device {
     device()
     {
         gd_lamina_desc const d{0, 0};
-        check(gd_lamina_create(&d, &h));
+        cli::check(gd_lamina_create(&d, &h));
     }
     ~device() { gd_lamina_destroy(h); }
 };
@@ -161,25 +156,25 @@ inline void copy_metadata(std::string const &path, hid_t output)
     std::vector<std::string> names(rows);
     for (auto it = keys.begin(); it != keys.end(); ++it) names.at(it.value().get<std::size_t>()) = it.key();
 
-    h5::hid out(flow::require_group(output, "/metadata"));
+    h5::hid out(cli::require_group(output, "/metadata"));
     h5::write_string(out, "simulation_config", config);
     h5::unlink_if_present(out, "particle_types");
     h5::hid ds(H5Dcreate2(out, "particle_types", ttype, tspace, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT));
     h5::check(ds >= 0, "cannot create metadata/particle_types");
     if (nt > 0) h5::check(H5Dwrite(ds, ttype, H5S_ALL, H5S_ALL, H5P_DEFAULT, tdata.data()) >= 0, "cannot write metadata/particle_types");
-    flow::put_dataset(out, "chromosome_ranges", ranges.data(), {rows, 2}, 4, H5T_NATIVE_INT, H5T_STD_I32LE, nullptr);
+    cli::put_dataset(out, "chromosome_ranges", ranges.data(), {rows, 2}, 4, H5T_NATIVE_INT, H5T_STD_I32LE, nullptr);
     h5::write_fixed_string_list(out, "chromosome_names", names);
 }
 
 inline void run_distance(options const &o)
 {
     device dev;
-    h5::hid file(flow::open_output(o.outfile));
-    flow::stopwatch sw;
+    h5::hid file(cli::open_output(o.outfile));
+    cli::stopwatch sw;
     copy_metadata(o.trajfiles[0], file);
     history cur = load_history(o.trajfiles[0]);
     sw.read += sw.lap();
-    flow::filters f;
+    cli::filters f;
     f.scaleoffset_kind = H5Z_SO_FLOAT_DSCALE;
     f.scaleoffset_factor = 3;
     for (std::size_t k = 0; k < o.trajfiles.size(); k++) {
@@ -187,11 +182,11 @@ inline void run_distance(options const &o)
         std::future<history> next;
         if (k + 1 < o.trajfiles.size()) next = std::async(std::launch::async, load_history, o.trajfiles[k + 1]);
         std::vector<float> dist((std::size_t)cur.frames * cur.beads);
-        check(gd_lamina_distances(dev.h, cur.xyz.data(), 0, cur.frames, cur.beads, cur.semiaxes.data(), dist.data(), 0));
+        cli::check(gd_lamina_distances(dev.h, cur.xyz.data(), 0, cur.frames, cur.beads, cur.semiaxes.data(), dist.data(), 0));
         sw.compute += sw.lap();
         history following = next.valid() ? next.get() : history{};      // (a std::async future joins its thread when it is dropped)
         sw.read += sw.lap();
-        flow::put_dataset(file, "/distance/" + flow::sample_name(o.trajfiles[k]), dist.data(), {cur.frames, cur.beads}, 4, H5T_NATIVE_FLOAT,
+        cli::put_dataset(file, "/distance/" + cli::sample_name(o.trajfiles[k]), dist.data(), {cur.frames, cur.beads}, 4, H5T_NATIVE_FLOAT,
                           H5T_IEEE_F32LE, &f);
         sw.write += sw.lap();
         cur = std::move(following);
@@ -208,8 +203,8 @@ inline herr_t collect_name(hid_t, const char *name, const H5L_info_t *, void *da
 inline void run_contact(options const &o)
 {
     device dev;
-    h5::hid file(flow::open_output(o.outfile));
-    flow::stopwatch sw;
+    h5::hid file(cli::open_output(o.outfile));
+    cli::stopwatch sw;
     h5::hid group(H5Gopen2(file, "/distance", H5P_DEFAULT));
     h5::check(group >= 0, o.outfile + ": no /distance");
     std::vector<std::string> keys;      // in name order, as h5py iterates a group
@@ -219,7 +214,7 @@ inline void run_contact(options const &o)
     std::int8_t const no = 0, yes = 1;
     H5Tenum_insert(boolean, "FALSE", &no);
     H5Tenum_insert(boolean, "TRUE", &yes);
-    flow::filters const f;
+    cli::filters const f;
     hsize_t dims[2] = {0, 0};
     for (auto const &key : keys) {
         h5::hid ds(H5Dopen2(group, key.c_str(), H5P_DEFAULT));
@@ -232,15 +227,15 @@ inline void run_contact(options const &o)
         if (!dist.empty()) h5::check(H5Dread(ds, H5T_NATIVE_FLOAT, H5S_ALL, H5S_ALL, H5P_DEFAULT, dist.data()) >= 0, "cannot read /distance/" + key);
         sw.read += sw.lap();
         std::vector<uint8_t> contacts(dist.size());
-        check(gd_lamina_contacts(dev.h, dist.data(), (uint32_t)dims[0], (uint32_t)dims[1], o.contact_distance, contacts.data()));
+        cli::check(gd_lamina_contacts(dev.h, dist.data(), (uint32_t)dims[0], (uint32_t)dims[1], o.contact_distance, contacts.data()));
         sw.compute += sw.lap();
-        flow::put_dataset(file, "/contact/" + o.name + "/" + key, contacts.data(), {dims[0], dims[1]}, 1, boolean, boolean, &f);
+        cli::put_dataset(file, "/contact/" + o.name + "/" + key, contacts.data(), {dims[0], dims[1]}, 1, boolean, boolean, &f);
         sw.write += sw.lap();
     }
     std::vector<float> average(dims[0] * dims[1]);
-    check(gd_lamina_average(dev.h, average.data()));
+    cli::check(gd_lamina_average(dev.h, average.data()));
     sw.compute += sw.lap();
-    flow::put_dataset(file, "/average_contact/" + o.name, average.data(), {dims[0], dims[1]}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+    cli::put_dataset(file, "/average_contact/" + o.name, average.data(), {dims[0], dims[1]}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
     sw.write += sw.lap();
     sw.report("gd_analyze_lamina contact");
 }

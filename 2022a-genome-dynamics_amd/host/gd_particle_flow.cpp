@@ -12,29 +12,29 @@ int main(int argc, char **argv)
     if (int rc = front(argc, argv, false, o, config, name); rc >= 0) return rc;
     try {
         device dev;
-        gd::h5::hid file(open_output(o.outfile));
-        gd::h5::hid group(require_group(file, "/particle_flow/" + name));
+        gd::h5::hid file(gd::cli::open_output(o.outfile));
+        gd::h5::hid group(gd::cli::require_group(file, "/particle_flow/" + name));
         gd::h5::write_string(group, ".config", config);
         bool const smooth = o.has_smoothing && o.smoothing > 0;
         std::vector<std::string> samples;
-        stopwatch sw;
+        gd::cli::stopwatch sw;
         for (auto const &path : o.trajfiles) {
-            std::string const sample = sample_name(path);
+            std::string const sample = gd::cli::sample_name(path);
             samples.push_back(sample);
             uint32_t F = 0, N = 0;
             auto const hist = load_history(path, F, N);
             sw.read += sw.lap();
             std::vector<double> pos(smooth ? (std::size_t)F * N * 3 : 0);
             std::vector<float> flows((std::size_t)F * N * 3);
-            device::check(gd_flow_set_history(dev.h, hist.data(), F, N, 0));
-            device::check(gd_flow_velocities(dev.h, smooth ? (uint32_t)o.smoothing : 0, (uint32_t)o.delay, smooth ? pos.data() : nullptr, nullptr));
-            device::check(gd_flow_particle(dev.h, o.radius, flows.data()));
+            gd::cli::check(gd_flow_set_history(dev.h, hist.data(), F, N, 0));
+            gd::cli::check(gd_flow_velocities(dev.h, smooth ? (uint32_t)o.smoothing : 0, (uint32_t)o.delay, smooth ? pos.data() : nullptr, nullptr));
+            gd::cli::check(gd_flow_particle(dev.h, o.radius, flows.data()));
             sw.compute += sw.lap();
-            filters const f;
+            gd::cli::filters const f;
             std::vector<hsize_t> const dims = {F, N, 3};
-            if (smooth) put_dataset(group, sample + "/position", pos.data(), dims, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            else put_dataset(group, sample + "/position", hist.data(), dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
-            put_dataset(group, sample + "/velocity", flows.data(), dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+            if (smooth) gd::cli::put_dataset(group, sample + "/position", pos.data(), dims, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
+            else gd::cli::put_dataset(group, sample + "/position", hist.data(), dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+            gd::cli::put_dataset(group, sample + "/velocity", flows.data(), dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
             sw.write += sw.lap();
         }
         gd::h5::write_fixed_string_list(group, ".samples", samples);      // this run's samples only, as the reference does

@@ -22,6 +22,7 @@
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_rdf.h"
+#include "gd_cli_util.hpp"
 #include "gd_h5util.hpp"
 
 namespace gd {
@@ -232,11 +233,6 @@ inline std::vector<float> read_frames(hid_t file, setup const &s, std::size_t k0
     return out;
 }
 
-inline void check(int rc)
-{
-    if (rc != GD_OK) throw std::runtime_error(std::string("gdyn: ") + gd_last_error());
-}
-
 // the frame loop of analysis.cc: counts on the device in batches (the next batch is read while the device counts), one line
 // per frame of n_bins values count * unit_weight / bin_volume / expected_density, printed as std::ostream prints a double
 inline void run(options const &o, hid_t file, setup const &s)
@@ -245,9 +241,9 @@ inline void run(options const &o, hid_t file, setup const &s)
     std::size_t const batch = std::max<std::size_t>(1, std::min<std::size_t>(4096, ((std::size_t)1 << 22) / std::max<std::size_t>(s.n_points, 1)));
     gd_rdf *h = nullptr;
     gd_rdf_desc const desc{0, (uint32_t)batch};
-    check(gd_rdf_create(&desc, &h));
+    cli::check(gd_rdf_create(&desc, &h));
     std::unique_ptr<gd_rdf, int (*)(gd_rdf *)> guard(h, gd_rdf_destroy);
-    check(gd_rdf_set_selection(h, (uint32_t)s.n_points, s.centers.data(), (uint32_t)s.centers.size(), o.hetero ? s.targets.data() : nullptr,
+    cli::check(gd_rdf_set_selection(h, (uint32_t)s.n_points, s.centers.data(), (uint32_t)s.centers.size(), o.hetero ? s.targets.data() : nullptr,
                                (uint32_t)s.targets.size()));
     double const box[3] = {s.box_size, s.box_size, s.box_size};
     std::vector<uint64_t> counts;
@@ -258,7 +254,7 @@ inline void run(options const &o, hid_t file, setup const &s)
         std::vector<float> const xyz = next.get();      // HDF5 is called from one thread at a time: the reader, then nobody
         if (k1 < F) next = std::async(std::launch::async, read_frames, file, std::cref(s), k1, std::min(F, k1 + batch));
         counts.resize((k1 - k0) * s.n_bins);
-        check(gd_rdf_counts(h, xyz.data(), 0, (uint32_t)(k1 - k0), box, o.bin_width, o.max_distance, counts.data()));
+        cli::check(gd_rdf_counts(h, xyz.data(), 0, (uint32_t)(k1 - k0), box, o.bin_width, o.max_distance, counts.data()));
         for (std::size_t f = 0; f < k1 - k0; f++) {
             for (uint32_t i = 0; i < s.n_bins; i++) {
                 double const freq = double(counts[f * s.n_bins + i]) * s.unit_weight;

@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import LIBGDYN_PATH, GdynError
+from ._binding import GdynError, Handle, as_frames, load_library
 
 LAMINA_ABI_VERSION = 1     # GD_LAMINA_ABI_VERSION of the include/gdyn_lamina.h this binding mirrors
 LAMINA_SYMBOLS = ["gd_lamina_abi_version", "gd_lamina_create", "gd_lamina_destroy", "gd_lamina_distances", "gd_lamina_contacts",
@@ -28,15 +28,7 @@ class _LaminaDesc(C.Structure):
 
 def load_lamina_library(path=None):
     """Loads libgdyn and checks the gd_lamina_* symbols and their ABI version."""
-    path = path or LIBGDYN_PATH
-    d = C.CDLL(path)
-    for name in LAMINA_SYMBOLS + ["gd_last_error"]:
-        if not hasattr(d, name):
-            raise OSError(f"{path}: missing symbol {name}")
-    d.gd_lamina_abi_version.restype = C.c_int
-    if d.gd_lamina_abi_version() != LAMINA_ABI_VERSION:
-        raise OSError(f"{path}: lamina ABI version {d.gd_lamina_abi_version()}, this binding mirrors {LAMINA_ABI_VERSION}")
-    d.gd_last_error.restype = C.c_char_p
+    d = load_library("lamina", LAMINA_SYMBOLS, LAMINA_ABI_VERSION, path)
     d.gd_lamina_create.argtypes = [C.POINTER(_LaminaDesc), C.POINTER(C.c_void_p)]
     d.gd_lamina_destroy.argtypes = [C.c_void_p]
     d.gd_lamina_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
@@ -68,46 +60,20 @@ def distance_from_surface(points, semiaxes):
         return np.abs(u * v)
 
 
-class Lamina:
+class Lamina(Handle):
     """One device-side handle.  max_frames_per_launch: 0 = automatic (no result depends on it)."""
 
+    _destroy = "gd_lamina_destroy"
+
     def __init__(self, device=0, max_frames_per_launch=0, path=None):
-        self.dll = load_lamina_library(path)
-        self._h = C.c_void_p()
+        super().__init__(load_lamina_library(path))
         self._shape = None
         self._check(self.dll.gd_lamina_create(C.byref(_LaminaDesc(device, max_frames_per_launch)), C.byref(self._h)))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise GdynError(rc, self.dll.gd_last_error().decode())
-
-    def close(self):
-        if self._h:
-            self.dll.gd_lamina_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def distances(self, frames, semiaxes, dtype=np.float64):
         """frames (F, N, 3) float32 or float64 (or one (N, 3) frame); semiaxes: three values for every frame or (F, 3).
         Returns (F, N) float64, or its float32 rounding for dtype=np.float32."""
-        x = np.asarray(frames)
-        if x.ndim == 2:
-            x = x[None]
-        if x.ndim != 3 or x.shape[2] != 3:
-            raise ValueError(f"frames must be (F, N, 3), got {x.shape}")
-        is64 = x.dtype == np.float64
-        x = np.ascontiguousarray(x, dtype=np.float64 if is64 else np.float32)
+        x, is64 = as_frames(frames)
         F, N, _ = x.shape
         s = np.ascontiguousarray(np.broadcast_to(np.asarray(semiaxes, dtype=np.float64), (F, 3)))
         dtype = np.dtype(dtype)

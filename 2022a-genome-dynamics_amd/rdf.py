@@ -13,7 +13,7 @@ import math
 
 import numpy as np
 
-from . import LIBGDYN_PATH, GdynError
+from ._binding import GdynError, Handle, as_frames, load_library
 
 RDF_ABI_VERSION = 1        # GD_RDF_ABI_VERSION of the include/gdyn_rdf.h this binding mirrors
 RDF_SYMBOLS = ["gd_rdf_abi_version", "gd_rdf_create", "gd_rdf_destroy", "gd_rdf_set_selection", "gd_rdf_bins", "gd_rdf_counts"]
@@ -27,15 +27,7 @@ class _RdfDesc(C.Structure):
 
 def load_rdf_library(path=None):
     """Loads libgdyn and checks the gd_rdf_* symbols and their ABI version."""
-    path = path or LIBGDYN_PATH
-    d = C.CDLL(path)
-    for name in RDF_SYMBOLS + ["gd_last_error"]:
-        if not hasattr(d, name):
-            raise OSError(f"{path}: missing symbol {name}")
-    d.gd_rdf_abi_version.restype = C.c_int
-    if d.gd_rdf_abi_version() != RDF_ABI_VERSION:
-        raise OSError(f"{path}: rdf ABI version {d.gd_rdf_abi_version()}, this binding mirrors {RDF_ABI_VERSION}")
-    d.gd_last_error.restype = C.c_char_p
+    d = load_library("rdf", RDF_SYMBOLS, RDF_ABI_VERSION, path)
     d.gd_rdf_create.argtypes = [C.POINTER(_RdfDesc), C.POINTER(C.c_void_p)]
     d.gd_rdf_destroy.argtypes = [C.c_void_p]
     d.gd_rdf_set_selection.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
@@ -76,46 +68,20 @@ def posterior(counts, bin_width, max_distance, box_size, n_center, n_target=None
         return c.astype(np.float64) * weight / bin_volumes(bin_width, max_distance) / expected
 
 
-class Rdf:
+class Rdf(Handle):
     """One device-side selection; counts() uploads frames and returns their pair counts per bin.
     max_frames_per_launch: 0 = automatic (the counts do not depend on it)."""
 
+    _destroy = "gd_rdf_destroy"
+
     def __init__(self, device=0, max_frames_per_launch=0, path=None):
-        self.dll = load_rdf_library(path)
-        self._h = C.c_void_p()
+        super().__init__(load_rdf_library(path))
         self._check(self.dll.gd_rdf_create(C.byref(_RdfDesc(device, max_frames_per_launch)), C.byref(self._h)))
-
-    def _check(self, rc):
-        if rc != 0:
-            raise GdynError(rc, self.dll.gd_last_error().decode())
-
-    def close(self):
-        if self._h:
-            self.dll.gd_rdf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def counts(self, frames, box, bin_width, max_distance, centers, targets=None):
         """frames (F, N, 3) float32 or float64 (or one (N, 3) frame); box: a period or three; centers / targets: bead indices.
         Returns uint64 (F, n_bins)."""
-        x = np.asarray(frames)
-        if x.ndim == 2:
-            x = x[None]
-        if x.ndim != 3 or x.shape[2] != 3:
-            raise ValueError(f"frames must be (F, N, 3), got {x.shape}")
-        is64 = x.dtype == np.float64
-        x = np.ascontiguousarray(x, dtype=np.float64 if is64 else np.float32)
+        x, is64 = as_frames(frames)
         F, N, _ = x.shape
         c = np.ascontiguousarray(centers, dtype=np.uint32).ravel()
         t = None if targets is None else np.ascontiguousarray(targets, dtype=np.uint32).ravel()
