@@ -1294,7 +1294,7 @@ static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, 
         q.pos = s->pos[s->pcur].p; q.x0 = s->list_tiled ? s->rec_x0.p : s->xb.p; q.rec_mo = s->rec_mo.p; q.meta = s->meta.p;
         q.orig = s->orig[s->ocur].p; q.nbr = s->nbr.p; q.nbr16 = s->nbr16.p; q.tiles = s->tiles.p; q.wtab = s->wtab.p;
         q.N = s->N; q.Np = s->Np; q.nblk = s->nblk; q.r = r0; q.nrep = nrep; q.W = s->list_W;
-        q.tiled = s->list_tiled ? 1 : 0; q.s16 = (s->list_tiled && s->list_tile_cap < 4096u) ? 1 : 0;
+        q.tiled = s->list_tiled ? 1 : 0; q.s16 = (s->list_tiled && gd_tile_s16(s->list_tile_cap)) ? 1 : 0;
         q.periodic = s->box_kind == GD_BOX_PERIODIC;
         for (int k = 0; k < 3; k++) { q.box[k] = (float)s->box[k]; q.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
         q.dcut2 = (float)(dcut * dcut); q.lim2 = (float)(lim * lim);

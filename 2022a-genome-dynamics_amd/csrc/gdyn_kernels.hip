@@ -1134,7 +1134,7 @@ static void launch_step_mode(const StepParams &p, hipStream_t st)
     const dim3 grid(p.cpb ? GD_XCDS * p.cpb * p.R : p.R * p.nblk), block(GD_BLOCK);
     const size_t lds = p.tiled ? (size_t)p.tile_cap * sizeof(float4) : 0;
     // (more than 64 KB of dynamic LDS: opted in per device at gd_create, gd_kernels_init_device below)
-    const bool s16 = p.tiled && p.tile_cap < 4096u;      // must match k_fill's choice (gd_launch_build)
+    const bool s16 = p.tiled && gd_tile_s16(p.tile_cap);
     // The LDS class of a launch is set by the LARGEST tile of any replica, and one tile a few beads over the three-block class
     // (3 312) costs every block a third of its occupancy (S-genome-62k x 64: a handful of tiles in the nucleus' centre).  While the
     // list entries stay 16-bit byte offsets (tile_cap < 4 096: the same kernel variant), the step is launched twice instead:
@@ -1651,574 +1651,513 @@ __global__ __launch_bounds__(GD_BLOCK) void k_scatter(const BuildParams p)
     if (p.has_bend) p.bendE[gn] = p.bendE_o[o];
 }
 
-// Per new slot: re-map the bonded topology to slots and fill the Verlet list (27-cell sweep).
-// TILED: candidates are read from the block's LDS tile and list entries are tile indices.
-// (register budget of the tiled variants: 6 waves per SIMD = three blocks per CU = at most 80 VGPRs for open boxes, as the LDS admits
-// with the 3 312-entry tile class; the periodic sweep holds 18 window bounds: 4 waves per SIMD = two blocks = 128)
-// REPAIR (tiled lists; launched behind the build's k_fill with blocks of ONE wave): the rows of a k_step wave in which some list outgrew
-// the predicted width are written again at the width they turned out to need -- the block's tile staged again, the 64 beads of
-// that wave listed by the 64 lanes, fresh rows from the pool; the queue of such waves is filled by the last wave of every k_fill
-// block (below) and is empty in almost every build.
-template <bool PERIODIC, bool TILED, bool S16, bool REPAIR = false>
-__global__ __launch_bounds__(REPAIR ? 64 : GD_BLOCK, REPAIR ? 1 : (TILED ? (PERIODIC ? 4 : 6) : 1)) void k_fill(const BuildParams p)
+// ------------------------------------------------------------- k_fill sections
+// Per new slot: re-map the bonded topology to slots and fill the Verlet list (27-cell sweep).  The sections of k_fill, one function
+// each, in the order the kernel calls them.  They are inlined: the kernel is one body as before.
+// The thread's bead as the sections hand it on, set up by the prologue of k_fill
+struct FillBead {
+    unsigned r, blk, slot;         // replica, block of GD_BLOCK slots, the bead's slot in the replica
+    size_t rbase, gt;              // first slot of the replica; where the bead's chunks and records go: the k_step thread that will own it
+    unsigned wk, row_off, row_nc;  // tiled: the k_step wave gt lies in, first KiB of that wave's rows in the pool, chunks per lane
+    unsigned o, deg;               // bead id, bond degree (through the sweep the degree rides in ListWriter::pk)
+    bool on;                       // the thread has a bead
+    // the bead's list as finish_rows leaves it: entries found, near entries in the fours k_step walks | generic: entries in the row; tiled:
+    // near entries in fours and far chunks of the record
+    unsigned cnt, near4, listlen, nAq, nB;
+};
+
+// slot -> tile index (nr: merged ranges in use, three typically)
+__device__ __forceinline__ bool tile_index(const TileDesc &td, unsigned nr, unsigned ps, unsigned &idx)
 {
-    static_assert(TILED || !REPAIR, "only the ragged rows of the tiled lists are repaired");
-    constexpr unsigned NTHR = REPAIR ? 64u : (unsigned)GD_BLOCK;
-    GD_FSTAMP_BEGIN();
-    extern __shared__ __attribute__((aligned(16))) float4 s_tile[];
-    // block totals (list entries, longest list): accumulated by LDS atomics as the waves finish; the last one to finish hands them on --
-    // no barrier at the end of the kernel, a wave that is done leaves.  (Static LDS is budgeted: with the tile class of 3 312 entries
-    // three blocks fit a CU only up to 704 bytes of it -- LDS is granted in 1 280-byte granules; tools/kregs.py shows the figure.)
-    __shared__ unsigned long long s_acc_cnt;
-    __shared__ unsigned s_acc_max, s_acc_done;
-    // ragged rows: chunks per lane and first KiB of the rows of each of the block's eight k_step waves
-    __shared__ unsigned s_wn[GD_BLOCK / 64], s_woff[GD_BLOCK / 64], s_wneed[GD_BLOCK / 64];      // (s_wneed: what the lists turned out to need)
-    unsigned r, blk, rep_w = 0, rep_need = 0;
-    if (REPAIR) {
-        if (blockIdx.x >= min(p.pool[3], p.rq_cap)) return;      // (queue items; one block = one wave each; the launch has rq_grid blocks)
-        const uint2 item = p.rqueue[blockIdx.x];
-        r = (item.x >> 3) / p.nblk; blk = (item.x >> 3) % p.nblk; rep_w = item.x & 7u; rep_need = item.y;
-    } else if (!block_map(blockIdx.x, p.nblk, p.cpb, r, blk)) return;
+    for (unsigned k = 0; k < nr; k++) {
+        const unsigned d = ps - td.start[k];
+        if (d < td.len[k]) { idx = td.base[k] + d; return true; }
+    }
+    return false;
+}
+
+// List writer: entries go straight into the wave-interleaved 16-byte chunk layout k_step reads (8 x u16 tiled, 4 x u32 generic); a bead's
+// 8 (4) consecutive entries share one chunk.  (tiled: the rows of the thread's k_step wave -- chunks() per lane from KiB row_off of the
+// pool; generic: uniform rows)
+template <bool TILED>
+struct ListWriter {
+    static constexpr unsigned PER = TILED ? 8u : 4u;
+    uint4 *lst;
+    // (tiled: the width is a per-lane value now, and the sweep sits exactly at its register budget -- 80 VGPRs for three blocks per CU:
+    // the width, the k_step wave and the bond degree share one register through the sweep and are unpacked where they are needed, a few
+    // times per bead; the empty asm keeps the unpacking from being hoisted back out)
+    unsigned pk, W;         // deg | wk << 8 | row_nc << 11; generic: entries per row
+    // the 16-byte chunk under construction lives in four registers (an LDS staging slot per thread would cost the 8 KB that separate
+    // two from three resident blocks per CU); every PER-th entry the finished chunk goes out as one 16-byte global store (2-byte
+    // scattered global stores were 25% of the build)
+    unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0, cnt = 0;
+    // A finished chunk is parked in p0..p3 and stored at the next flush point (the end of a row window), where the lanes of the wave
+    // store together: one store instruction per row instead of one per append iteration.
+    unsigned p0 = 0, p1 = 0, p2 = 0, p3 = 0, pend = 0;      // pend: chunk index + 1 of the parked chunk, 0 = none
+    unsigned b0 = 0, b1 = 0, b2 = 0, b3 = 0, cntB = 0;      // far class (tiled): its own shift register, chunks stored from the back
+
+    __device__ __forceinline__ ListWriter(const BuildParams &p, const FillBead &b)
+        : lst(TILED ? (uint4 *)p.nbr16 + ((size_t)b.row_off * 64 + (b.gt & 63)) : (uint4 *)p.nbr + (size_t)(b.gt >> 6) * (p.W / PER) * 64 + (b.gt & 63)),
+          pk(b.deg | (b.wk << 8) | (b.row_nc << 11)), W(p.W) {}
+    __device__ __forceinline__ unsigned chunks() const { if (!TILED) return W / PER; unsigned t = pk; asm volatile("" : "+v"(t)); return t >> 11; }
+    __device__ __forceinline__ void flush() {
+        if (pend) { lst[(size_t)(pend - 1) * 64] = make_uint4(p0, p1, p2, p3); pend = 0; }      // (non-temporal stores here cost 15%: the partial lines no longer merge in L2)
+    }
+    __device__ __forceinline__ void push(unsigned j) {
+        if (TILED) {        // 128-bit shift register: eight 16-bit entries, the first one ends up lowest
+            w0 = __builtin_amdgcn_alignbit(w1, w0, 16); w1 = __builtin_amdgcn_alignbit(w2, w1, 16);
+            w2 = __builtin_amdgcn_alignbit(w3, w2, 16); w3 = __builtin_amdgcn_alignbit(j, w3, 16);
+        } else { w0 = w1; w1 = w2; w2 = w3; w3 = j; }
+        cnt++;
+        if (cnt % PER == 0 && cnt / PER <= chunks()) {      // (inside the row; a list that outgrows its row is flagged by finish_rows, its chunk rolled back)
+            flush();                               // (only if a second chunk fills before the next flush point)
+            p0 = w0; p1 = w1; p2 = w2; p3 = w3; pend = cnt / PER;
+        }
+    }
+    __device__ __forceinline__ void push_far(unsigned j) {                // (tiled only; far chunks are few: stored as they fill)
+        b0 = __builtin_amdgcn_alignbit(b1, b0, 16); b1 = __builtin_amdgcn_alignbit(b2, b1, 16);
+        b2 = __builtin_amdgcn_alignbit(b3, b2, 16); b3 = __builtin_amdgcn_alignbit(j, b3, 16);
+        cntB++;
+        if (cntB % 8u == 0) { const unsigned nc = chunks(); if (cntB / 8u <= nc) lst[(size_t)(nc - cntB / 8u) * 64] = make_uint4(b0, b1, b2, b3); }
+    }
+    // pad a chunk under construction with the bead itself (sh entries, < PER, of `self` in from the top): the shift register moves down
+    // by the missing entries in three branch-free stages (four, two, one entry -- a loop of single pushes ran seven times in nearly
+    // every wave, 16 instructions each)
+    static __device__ __forceinline__ void pad(unsigned &a0, unsigned &a1, unsigned &a2, unsigned &a3, unsigned sh, unsigned self) {
+        const unsigned S = TILED ? self | (self << 16) : self;
+        if (TILED) {
+            const bool s4 = (sh & 4u) != 0u, s2 = (sh & 2u) != 0u, s1 = (sh & 1u) != 0u;
+            a0 = s4 ? a2 : a0; a1 = s4 ? a3 : a1; a2 = s4 ? S : a2; a3 = s4 ? S : a3;
+            a0 = s2 ? a1 : a0; a1 = s2 ? a2 : a1; a2 = s2 ? a3 : a2; a3 = s2 ? S : a3;
+            const unsigned c0 = __builtin_amdgcn_alignbit(a1, a0, 16), c1 = __builtin_amdgcn_alignbit(a2, a1, 16),
+                           c2 = __builtin_amdgcn_alignbit(a3, a2, 16), c3 = __builtin_amdgcn_alignbit(S, a3, 16);
+            a0 = s1 ? c0 : a0; a1 = s1 ? c1 : a1; a2 = s1 ? c2 : a2; a3 = s1 ? c3 : a3;
+        } else {
+            const bool s2 = (sh & 2u) != 0u, s1 = (sh & 1u) != 0u;
+            a0 = s2 ? a2 : a0; a1 = s2 ? a3 : a1; a2 = s2 ? S : a2; a3 = s2 ? S : a3;
+            a0 = s1 ? a1 : a0; a1 = s1 ? a2 : a1; a2 = s1 ? a3 : a2; a3 = s1 ? S : a3;
+        }
+    }
+};
+
+// ---- LDS-DMA staging as in k_step: descriptor by scalar loads first, then all pieces back to back; the descriptor itself is copied
+// to LDS by the threads from `first` on.  Complete at the next barrier.
+// (The descriptor is read many times, also after this thread has stored list chunks: from global memory those reads become per-lane
+// vector loads behind a full vmcnt(0) wait (the compiler cannot keep them scalar after a store), so it is copied once into LDS (188
+// bytes) and read from there.)
+template <unsigned NTHR>
+__device__ __forceinline__ void stage_tile(const TileDesc *__restrict__ tdp, const float4 *__restrict__ rpos, float4 *s_tile, TileDesc &s_td, unsigned first)
+{
     const unsigned lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { s_acc_cnt = 0ull; s_acc_max = 0u; s_acc_done = 0u; }
-    if (threadIdx.x < GD_BLOCK / 64) { s_wn[threadIdx.x] = 0u; s_woff[threadIdx.x] = 0xffffffffu; s_wneed[threadIdx.x] = 0u; }
-    if (!TILED) __syncthreads();      // (the tiled path has its barriers below)
-    const size_t rbase = (size_t)r * p.Np;
-    unsigned slot = blk * GD_BLOCK + threadIdx.x;      // (REPAIR: set below, from the record of the k_step thread this lane stands for)
-    size_t gt = rbase + slot;
-    const size_t g = rbase + slot;
-    const float4 *__restrict__ rpos = p.pos_out + rbase;
-    // block-uniform descriptor, read through a uniform pointer (scalar loads; a local copy indexed in
-    // loops would be demoted to scratch memory)
-    const TileDesc *__restrict__ tdp = p.tiles + (size_t)r * p.nblk + blk;
-    // The descriptor is read many times, also after this thread has stored list chunks: from global memory those
-    // reads become per-lane vector loads behind a full vmcnt(0) wait (the compiler cannot keep them scalar after a
-    // store), so it is copied once into LDS (188 bytes) and read from there.
-    __shared__ TileDesc s_tdesc;
-#define s_td s_tdesc
-    const unsigned o_pre = (TILED && !REPAIR && slot < p.N) ? p.orig_out[g] : 0u;      // (issued ahead of the DMAs: the balancing key below depends on it)
-    if (TILED) {
-        // LDS-DMA staging as in k_step: descriptor by scalar loads first, then all pieces back to back
-        unsigned tlen[GD_TILE_RANGES], tst[GD_TILE_RANGES], tbase[GD_TILE_RANGES];
-        const unsigned wq = (unsigned)__builtin_amdgcn_readfirstlane((int)(wid * 64u));
+    unsigned tlen[GD_TILE_RANGES], tst[GD_TILE_RANGES], tbase[GD_TILE_RANGES];
+    const unsigned wq = (unsigned)__builtin_amdgcn_readfirstlane((int)(wid * 64u));
 #pragma unroll
-        for (int k = 0; k < GD_TILE_RANGES; k++) { tlen[k] = tdp->len[k]; tst[k] = tdp->start[k]; tbase[k] = tdp->base[k]; }
+    for (int k = 0; k < GD_TILE_RANGES; k++) { tlen[k] = tdp->len[k]; tst[k] = tdp->start[k]; tbase[k] = tdp->base[k]; }
 #pragma unroll
-        for (int k = 0; k < GD_TILE_RANGES; k++) {
-            const unsigned len = tlen[k], st = tst[k], base = tbase[k];
-            for (unsigned q0 = wq; q0 < len; q0 += NTHR) {
-                if (q0 + lane < len)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(rpos + st + q0 + lane),
-                                                     (__attribute__((address_space(3))) void *)(s_tile + base + q0), 16, 0, 0);
-            }
-        }
+    for (int k = 0; k < GD_TILE_RANGES; k++) {
+        const unsigned len = tlen[k], st = tst[k], base = tbase[k];
+        for (unsigned q0 = wq; q0 < len; q0 += NTHR)
+            if (q0 + lane < len)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(rpos + st + q0 + lane),
+                                                 (__attribute__((address_space(3))) void *)(s_tile + base + q0), 16, 0, 0);
     }
-    // Tiled path: k_step's THREADS are ordered by the list length their bead had at the previous build (a very good
-    // predictor of the new one), longest first, so that the 64 lanes of a k_step wave run the same number of list
-    // batches.  This kernel still works slot by slot (neighbouring slots share their row windows: broadcast LDS reads, equal
-    // trip counts), but writes each bead's list, adjacency chunks and record at the position gt of the k_step thread
-    // that will own it.
-    if (TILED && REPAIR) {
-        if (threadIdx.x < sizeof(TileDesc) / 4) ((unsigned *)&s_tdesc)[threadIdx.x] = ((const unsigned *)tdp)[threadIdx.x];
-        __syncthreads();      // (also waits for the tile DMAs)
-        if (PERIODIC) {       // the wrapped tile, as below
-            const unsigned total = s_tdesc.total;
-            for (unsigned t = threadIdx.x; t < total; t += NTHR) {
-                float4 x = s_tile[t];
-                x.x -= p.box[0] * floorf(x.x * p.inv_box[0]); x.y -= p.box[1] * floorf(x.y * p.inv_box[1]); x.z -= p.box[2] * floorf(x.z * p.inv_box[2]);
-                s_tile[t] = x;
-            }
-            __syncthreads();
-        }
-        gt = rbase + (size_t)blk * GD_BLOCK + rep_w * 64u + lane;
+    if (threadIdx.x >= first && threadIdx.x - first < sizeof(TileDesc) / 4) ((unsigned *)&s_td)[threadIdx.x - first] = ((const unsigned *)tdp)[threadIdx.x - first];
+}
+
+// ---- Periodic boxes: wrap the staged tile into [0, L) in place (coordinates are kept unwrapped in memory: a chain that has diffused
+// around the box brings every periodic image into one cell).  With every candidate of a (row, x-interval) in the same image relative
+// to the bead, the minimum image of the sweep is ONE shift of the bead per interval instead of three round-to-nearest per candidate
+// (15 -> 9 instructions per test; the wrap costs ~6 entries per thread).
+template <unsigned NTHR>
+__device__ __forceinline__ void wrap_tile(const BuildParams &p, float4 *s_tile, unsigned total)
+{
+    for (unsigned t = threadIdx.x; t < total; t += NTHR) {
+        float4 x = s_tile[t];
+        x.x -= p.box[0] * floorf(x.x * p.inv_box[0]); x.y -= p.box[1] * floorf(x.y * p.inv_box[1]); x.z -= p.box[2] * floorf(x.z * p.inv_box[2]);
+        s_tile[t] = x;
     }
-    if (TILED && !REPAIR) {
-        // (two barriers: histogram cleared + descriptor copied | histogram complete; every wave then scans the 64 bins itself.
-        // The first barrier also waits for the tile DMAs issued above.)
-        // (the order is STABLE -- by bin, then by slot: ranks handed out by an LDS atomic would be arrival orders, and the thread a bead
-        // lands on decides the order in which the wall-reaction partials of a block are summed)
-        // (one byte per (bin, wave) -- a wave holds at most 64 threads of a bin; lane b reads the eight counts of bin b as one 64-bit
-        // word.  GD_KBINS bins: the lists beyond 4 x (GD_KBINS - 2) near entries share the first one.)
-        constexpr unsigned GD_KBINS = 48u;
-        static_assert(GD_BLOCK / 64 == 8, "one byte per wave in a 64-bit word");
-        __shared__ unsigned long long s_hist8[GD_KBINS];
-        if (threadIdx.x < GD_KBINS) s_hist8[threadIdx.x] = 0ull;
-        if (threadIdx.x >= 64 && threadIdx.x - 64 < sizeof(TileDesc) / 4) ((unsigned *)&s_tdesc)[threadIdx.x - 64] = ((const unsigned *)tdp)[threadIdx.x - 64];
-        unsigned bin = GD_KBINS - 1u;                              // slots past N: last
-        if (slot < p.N) bin = (GD_KBINS - 2u) - min((unsigned)p.len_prev[(size_t)r * p.N + o_pre], GD_KBINS - 2u);
-        // lanes of the wave in the same bin (six ballots), the thread's rank among them, their number
-        unsigned long long same = ~0ull;
+}
+
+// ---- Stable thread order: threads by the list length their bead had at the previous build, longest first; gives the position gt of the
+// k_step thread that will own the bead.  Holds the two barriers of the build: histogram cleared + descriptor copied (+ the tile DMAs
+// landed) | histogram complete (+ the tile wrapped, between them); every wave then scans the 64 bins itself.
+// (the order is STABLE -- by bin, then by slot: ranks handed out by an LDS atomic would be arrival orders, and the thread a bead
+// lands on decides the order in which the wall-reaction partials of a block are summed)
+// (one byte per (bin, wave) -- a wave holds at most 64 threads of a bin; lane b reads the eight counts of bin b as one 64-bit
+// word.  GD_KBINS bins: the lists beyond 4 x (GD_KBINS - 2) near entries share the first one.)
+constexpr unsigned GD_KBINS = 48u;
+template <bool PERIODIC>
+__device__ __forceinline__ size_t place_thread(const BuildParams &p, const FillBead &b, unsigned o_pre, unsigned long long *s_hist8, float4 *s_tile, const TileDesc &s_td)
+{
+    static_assert(GD_BLOCK / 64 == 8, "one byte per wave in a 64-bit word");
+    const unsigned lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (threadIdx.x < GD_KBINS) s_hist8[threadIdx.x] = 0ull;
+    unsigned bin = GD_KBINS - 1u;                              // slots past N: last
+    if (b.slot < p.N) bin = (GD_KBINS - 2u) - min((unsigned)p.len_prev[(size_t)b.r * p.N + o_pre], GD_KBINS - 2u);
+    // lanes of the wave in the same bin (six ballots), the thread's rank among them, their number
+    unsigned long long same = ~0ull;
 #pragma unroll
-        for (int bit = 0; bit < 6; bit++) {
-            const bool on = (bin >> bit) & 1u;
-            const unsigned long long b = __builtin_amdgcn_ballot_w64(on);
-            same &= on ? b : ~b;
-        }
-        const unsigned rank_w = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
-        __syncthreads();
-        if (PERIODIC) {
-            // Periodic boxes: wrap the staged tile into [0, L) in place (coordinates are kept unwrapped in memory: a chain that has
-            // diffused around the box brings every periodic image into one cell).  With every candidate of a (row, x-interval) in
-            // the same image relative to the bead, the minimum image of the sweep below is ONE shift of the bead per interval
-            // instead of three round-to-nearest per candidate (15 -> 9 instructions per test; the wrap costs ~6 entries per thread).
-            const unsigned total = s_tdesc.total;
-            for (unsigned t = threadIdx.x; t < total; t += GD_BLOCK) {
-                float4 x = s_tile[t];
-                x.x -= p.box[0] * floorf(x.x * p.inv_box[0]); x.y -= p.box[1] * floorf(x.y * p.inv_box[1]); x.z -= p.box[2] * floorf(x.z * p.inv_box[2]);
-                s_tile[t] = x;
-            }
-        }
-        if (rank_w == 0u) ((unsigned char *)s_hist8)[bin * 8u + wid] = (unsigned char)__popcll(same);
-        __syncthreads();
-        // lane b stands for bin b: threads of the block in that bin, and those of them in the waves in front of this one
-        unsigned incl = 0, before = 0;
-        {
-            const unsigned long long v = lane < GD_KBINS ? s_hist8[lane] : 0ull;
-            const unsigned long long vb = v & ((1ull << (8u * wid)) - 1ull);      // the waves in front (wid < 8)
-            incl = __builtin_amdgcn_sad_u8((unsigned)v, 0u, __builtin_amdgcn_sad_u8((unsigned)(v >> 32), 0u, 0u));
-            before = __builtin_amdgcn_sad_u8((unsigned)vb, 0u, __builtin_amdgcn_sad_u8((unsigned)(vb >> 32), 0u, 0u));
-        }
-        const unsigned own = incl;
-        for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += v; }
-        gt = rbase + blk * GD_BLOCK + (unsigned)__shfl((int)(incl - own + before), (int)bin, 64) + rank_w;
+    for (int bit = 0; bit < 6; bit++) {
+        const bool on = (bin >> bit) & 1u;
+        const unsigned long long bal = __builtin_amdgcn_ballot_w64(on);
+        same &= on ? bal : ~bal;
     }
-    // Ragged rows: the k_step wave a bead goes to (wk) gets rows as wide as the longest PREDICTED list among its 64 beads -- what the
-    // bead needed at the build before plus an eighth and a chunk per class (no history: the caller's guess, p.W entries); at least one
-    // chunk, so that k_step's unconditional first chunk load stays inside the pool.  A list that outgrows its row is REPAIRED at the
-    // end of the kernel (no rollback): see the repair pass below.
-    const unsigned wk = TILED ? ((unsigned)(gt - rbase) - blk * GD_BLOCK) >> 6 : 0u;
-    unsigned row_nc = 0u, row_off = 0u;
-    if (TILED && REPAIR) {      // fresh rows of the width the wave's lists need
-        unsigned off = 0u;
-        if (lane == 0) {
-            off = atomicAdd(&p.pool[0], rep_need);
-            if (!(off <= p.pool_cap && rep_need <= p.pool_cap - off)) {
-                if (!p.flags[r * GD_NFLAGS + GD_FLAG_TAINT]) atomicOr(&p.flags[r * GD_NFLAGS + GD_FLAG_OVERFLOW], 4u);
-                off = 0xffffffffu;
-            } else p.wtab[(rbase + (size_t)blk * GD_BLOCK) / 64 + rep_w] = make_uint2(off, rep_need);
-        }
-        off = (unsigned)__builtin_amdgcn_readfirstlane((int)off);
-        if (off == 0xffffffffu) return;      // (the pool is full: the rows stay as they are, flagged)
-        row_off = off; row_nc = rep_need;
+    const unsigned rank_w = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (PERIODIC) wrap_tile<GD_BLOCK>(p, s_tile, s_td.total);
+    if (rank_w == 0u) ((unsigned char *)s_hist8)[bin * 8u + wid] = (unsigned char)__popcll(same);
+    __syncthreads();
+    // lane b stands for bin b: threads of the block in that bin, and those of them in the waves in front of this one
+    const unsigned long long v = lane < GD_KBINS ? s_hist8[lane] : 0ull;
+    const unsigned long long vb = v & ((1ull << (8u * wid)) - 1ull);      // the waves in front (wid < 8)
+    unsigned incl = __builtin_amdgcn_sad_u8((unsigned)v, 0u, __builtin_amdgcn_sad_u8((unsigned)(v >> 32), 0u, 0u));
+    const unsigned before = __builtin_amdgcn_sad_u8((unsigned)vb, 0u, __builtin_amdgcn_sad_u8((unsigned)(vb >> 32), 0u, 0u));
+    const unsigned own = incl;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += u; }
+    return b.rbase + b.blk * GD_BLOCK + (unsigned)__shfl((int)(incl - own + before), (int)bin, 64) + rank_w;
+}
+
+// ---- Ragged rows: the k_step wave a bead goes to (wk) gets rows as wide as the longest PREDICTED list among its 64 beads -- what the
+// bead needed at the build before plus an eighth and a chunk per class (no history: the caller's guess, p.W entries); at least one
+// chunk, so that k_step's unconditional first chunk load stays inside the pool.  A list that outgrows its row is REPAIRED behind
+// the kernel (no rollback): see block_totals.  The rows are published in s_woff / s_wn.
+__device__ __forceinline__ void alloc_rows(const BuildParams &p, const FillBead &b, unsigned o_pre, unsigned *s_wn, unsigned *s_woff, unsigned *s_acc_done)
+{
+    const unsigned lane = threadIdx.x & 63;
+    unsigned want = 1u;
+    if (b.slot < p.N) {
+        if (p.predict) {
+            const unsigned q = p.need_prev[(size_t)b.r * p.N + o_pre];
+            unsigned pn = q & 1023u, pf = q >> 10;
+            pn += max(1u, pn >> 3); pf += max(1u, pf >> 3);
+            want = max(min(pn, GD_TILED_MAX_NEAR / 8u) + min(pf, GD_TILED_MAX_FAR / 8u), 1u);
+        } else want = max(p.W / 8u, 1u);
     }
-    if (TILED && !REPAIR) {
-        unsigned want = 1u;
-        if (slot < p.N) {
-            if (p.predict) {
-                const unsigned q = p.need_prev[(size_t)r * p.N + o_pre];
-                unsigned pn = q & 1023u, pf = q >> 10;
-                pn += max(1u, pn >> 3); pf += max(1u, pf >> 3);
-                want = max(min(pn, GD_TILED_MAX_NEAR / 8u) + min(pf, GD_TILED_MAX_FAR / 8u), 1u);
-            } else want = max(p.W / 8u, 1u);
-        }
-        atomicMax(&s_wn[wk], want);
-        // No barrier for this: every wave counts itself in once its lanes' widths are in (the counter the end of the kernel uses for "last
-        // wave done": it simply starts from eight there), wave 0 alone waits for the eight, allocates, and publishes (s_wn, then s_woff);
-        // the other waves go on into the re-map and pick their rows up where they first need them -- a barrier behind the re-map made
-        // all eight waves start their sweeps in lock step and cost the block the latency of the cursor's atomic.
-        if (lane == 0) { __threadfence_block(); atomicAdd(&s_acc_done, 1u); }
-        if (threadIdx.x < GD_BLOCK / 64) {      // eight lanes of wave 0: prefix of the widths, ONE atomic on the pool's cursor per block
-            while (atomicAdd(&s_acc_done, 0u) < GD_BLOCK / 64) __builtin_amdgcn_s_sleep(1);
-            __threadfence_block();
-            const unsigned nc = atomicMax(&s_wn[threadIdx.x], 0u);
-            unsigned incl = nc;
-            for (int o = 1; o < GD_BLOCK / 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += v; }
-            const unsigned total = __shfl(incl, GD_BLOCK / 64 - 1, 64);
-            unsigned base = 0;
-            if (threadIdx.x == GD_BLOCK / 64 - 1) base = atomicAdd(&p.pool[0], total);
-            base = __shfl(base, GD_BLOCK / 64 - 1, 64);
-            // (a pool that is full: flagged like a row overflow, the rows of this block get no chunks -- every bead of it then counts
-            // as overflowed -- and k_step's first chunk load reads the pool's first KiB)
-            const bool fits = base <= p.pool_cap && total <= p.pool_cap - base;
-            if (!fits && threadIdx.x == 0 && !p.flags[r * GD_NFLAGS + GD_FLAG_TAINT]) atomicOr(&p.flags[r * GD_NFLAGS + GD_FLAG_OVERFLOW], 4u);
-            const unsigned off = fits ? base + incl - nc : 0u;
-            p.wtab[(rbase + (size_t)blk * GD_BLOCK) / 64 + threadIdx.x] = make_uint2(off, fits ? nc : 0u);
-            s_wn[threadIdx.x] = fits ? nc : 0u;
-            __threadfence_block();
-            *(volatile unsigned *)&s_woff[threadIdx.x] = off;      // (published: 0xffffffff until here)
-        }
+    atomicMax(&s_wn[b.wk], want);
+    // No barrier for this: every wave counts itself in once its lanes' widths are in (the counter the end of the kernel uses for "last
+    // wave done": it simply starts from eight there), wave 0 alone waits for the eight, allocates, and publishes (s_wn, then s_woff);
+    // the other waves go on into the re-map and pick their rows up where they first need them -- a barrier behind the re-map made
+    // all eight waves start their sweeps in lock step and cost the block the latency of the cursor's atomic.
+    if (lane == 0) { __threadfence_block(); atomicAdd(s_acc_done, 1u); }
+    if (threadIdx.x < GD_BLOCK / 64) {      // eight lanes of wave 0: prefix of the widths, ONE atomic on the pool's cursor per block
+        while (atomicAdd(s_acc_done, 0u) < GD_BLOCK / 64) __builtin_amdgcn_s_sleep(1);
+        __threadfence_block();
+        const unsigned nc = atomicMax(&s_wn[threadIdx.x], 0u);
+        unsigned incl = nc;
+        for (int o = 1; o < GD_BLOCK / 64; o <<= 1) { const unsigned v = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += v; }
+        const unsigned total = __shfl(incl, GD_BLOCK / 64 - 1, 64);
+        unsigned base = 0;
+        if (threadIdx.x == GD_BLOCK / 64 - 1) base = atomicAdd(&p.pool[0], total);
+        base = __shfl(base, GD_BLOCK / 64 - 1, 64);
+        // (a pool that is full: flagged like a row overflow, the rows of this block get no chunks -- every bead of it then counts
+        // as overflowed -- and k_step's first chunk load reads the pool's first KiB)
+        const bool fits = base <= p.pool_cap && total <= p.pool_cap - base;
+        if (!fits && threadIdx.x == 0 && !p.flags[b.r * GD_NFLAGS + GD_FLAG_TAINT]) atomicOr(&p.flags[b.r * GD_NFLAGS + GD_FLAG_OVERFLOW], 4u);
+        const unsigned off = fits ? base + incl - nc : 0u;
+        p.wtab[(b.rbase + (size_t)b.blk * GD_BLOCK) / 64 + threadIdx.x] = make_uint2(off, fits ? nc : 0u);
+        s_wn[threadIdx.x] = fits ? nc : 0u;
+        __threadfence_block();
+        *(volatile unsigned *)&s_woff[threadIdx.x] = off;      // (published: 0xffffffff until here)
     }
-    GD_FSTAMP(0);     // staging + barrier
-    unsigned cnt = 0, near4 = 0;
-    unsigned o = 0, deg = 0;
-    const unsigned nr_tile = TILED ? (unsigned)__builtin_amdgcn_readfirstlane((int)s_td.nranges) : 0u;      // (merged ranges in use: three, typically)
-    auto to_local = [&](unsigned ps, unsigned &idx) -> bool {   // slot -> tile index
-        for (unsigned k = 0; k < nr_tile; k++) {
-            const unsigned d = ps - s_td.start[k];
-            if (d < s_td.len[k]) { idx = s_td.base[k] + d; return true; }
-        }
-        return false;
-    };
-    const size_t gw = TILED ? gt : g;          // where this thread's chunks and records go
-    bool on = slot < p.N;
-    if (REPAIR) {
-        const uint2 mo = p.rec_mo[gt];
-        on = mo.y != GD_REC_NOBEAD;
-        slot = blk * GD_BLOCK + ((mo.x >> 12) & 0x1ffu); o = mo.y & GD_REC_ID_MASK; deg = mo.x & 0xffu;
-    } else if (on) {
-        o = p.orig_out[g];
-        deg = p.bdeg_o[o];
+}
+
+// ---- Repair: fresh rows of the width the wave's lists need (false: the pool is full -- the rows stay as they are, flagged)
+__device__ __forceinline__ bool alloc_repair_rows(const BuildParams &p, FillBead &b, unsigned rep_w, unsigned rep_need)
+{
+    unsigned off = 0u;
+    if ((threadIdx.x & 63) == 0) {
+        off = atomicAdd(&p.pool[0], rep_need);
+        if (!(off <= p.pool_cap && rep_need <= p.pool_cap - off)) {
+            if (!p.flags[b.r * GD_NFLAGS + GD_FLAG_TAINT]) atomicOr(&p.flags[b.r * GD_NFLAGS + GD_FLAG_OVERFLOW], 4u);
+            off = 0xffffffffu;
+        } else p.wtab[(b.rbase + (size_t)b.blk * GD_BLOCK) / 64 + rep_w] = make_uint2(off, rep_need);
     }
-    if (!REPAIR && on) {
-        const unsigned *so = p.slot_of + (size_t)r * p.N;
-        uint4 *__restrict__ adjw = (uint4 *)p.badj + (size_t)(gw >> 6) * (p.WB / 4) * 64 + (gw & 63);
-        // one 16-byte adjacency chunk per round: its four gathers (entry by bead, then slot by partner) are in flight
-        // together and the chunk is written with one store
-        for (unsigned k0 = 0; k0 < deg; k0 += 4) {
-            unsigned ent[4], ps[4], out[4];
+    off = (unsigned)__builtin_amdgcn_readfirstlane((int)off);
+    if (off == 0xffffffffu) return false;
+    b.row_off = off; b.row_nc = rep_need;
+    return true;
+}
+
+// ---- Bond and chain re-map: partners by bead id -> slots (tile indices where the partner is staged), written where k_step's thread reads them
+template <bool TILED>
+__device__ __forceinline__ void remap_topology(const BuildParams &p, const FillBead &b, const TileDesc &td, unsigned nr)
+{
+    const unsigned o = b.o, deg = b.deg, *so = p.slot_of + (size_t)b.r * p.N;
+    uint4 *__restrict__ adjw = (uint4 *)p.badj + (size_t)(b.gt >> 6) * (p.WB / 4) * 64 + (b.gt & 63);
+    // one 16-byte adjacency chunk per round: its four gathers (entry by bead, then slot by partner) are in flight together, one store
+    for (unsigned k0 = 0; k0 < deg; k0 += 4) {
+        unsigned ent[4], ps[4], out[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) ent[u] = k0 + u < deg ? p.badj_o[(size_t)(k0 + u) * p.N + o] : 0u;
+        for (int u = 0; u < 4; u++) ent[u] = k0 + u < deg ? p.badj_o[(size_t)(k0 + u) * p.N + o] : 0u;
 #pragma unroll
-            for (int u = 0; u < 4; u++) ps[u] = k0 + u < deg ? so[ent[u] & GD_ADJ_MASK] : 0u;
+        for (int u = 0; u < 4; u++) ps[u] = k0 + u < deg ? so[ent[u] & GD_ADJ_MASK] : 0u;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            unsigned idx;
+            out[u] = ps[u] | (ent[u] & ~GD_ADJ_MASK);
+            if (TILED && tile_index(td, nr, ps[u], idx)) out[u] = idx | (ent[u] & ~GD_ADJ_MASK) | GD_ADJ_LOCAL;
+            if (k0 + u >= deg) out[u] = 0u;
+        }
+        adjw[(size_t)(k0 >> 2) * 64] = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+    if (p.chain_o) {
+        const int4 c = p.chain_o[o];
+        auto conv = [&](int cb) -> int {
+            if (cb < 0) return -1;
+            const unsigned ps = so[cb];
+            unsigned idx;
+            if (TILED && tile_index(td, nr, ps, idx)) return (int)(idx | GD_CHAIN_LOCAL);
+            return (int)ps;
+        };
+        p.chain[b.rbase + b.slot] = make_int4(conv(c.x), conv(c.y), conv(c.z), conv(c.w));
+    }
+}
+
+// ---- The tiled sweeps' test-and-append: the tile entries [lb, le) against the point (x, y, z) -- the bead, or its periodic image --
+// with the bead's own entry self_l left out; near entries before far ones inside a group of 32.
+// Branch-free distance tests into a per-lane bit mask, then one append per set bit: the (divergent) append code runs max-popcount
+// times per segment, not once per candidate.
+template <bool S16>
+__device__ __forceinline__ void test_and_append(const float4 *s_tile, unsigned lb, unsigned le, unsigned self_l, float x, float y, float z, float rv2, float dnear, ListWriter<true> &lw, FillStamps &fst_)
+{
+    for (unsigned j0 = lb; j0 < le; j0 += 32) {
+        const unsigned n = min(32u, le - j0);
+        unsigned m = 0, mn = 0;
+        // nine instructions per candidate: r2 - rv2 by three subtractions and three fmas, its sign bit shifted into the mask by one
+        // v_alignbit (candidate i of the n4 tested ends up at bit n4-1-i), one add and one more v_alignbit for the near-class mask.  Reads
+        // may run up to 3 slots past the window (slack is allocated behind the tile); those bits are shifted out below, the bead itself
+        // is masked once.
+        for (unsigned u0 = 0; u0 < n; u0 += 4) {
+            GD_FCOUNT(8);         // wave-level test groups (lane 0 runs while any lane does)
+            const float4 *cj = s_tile + j0 + u0;
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                unsigned idx;
-                out[u] = ps[u] | (ent[u] & ~GD_ADJ_MASK);
-                if (TILED && to_local(ps[u], idx)) out[u] = idx | (ent[u] & ~GD_ADJ_MASK) | GD_ADJ_LOCAL;
-                if (k0 + u >= deg) out[u] = 0u;
+                const float4 xj = cj[u];
+                const float dx = x - xj.x, dy = y - xj.y, dz = z - xj.z;
+                const float t = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, -rv2)));      // < 0 inside the list radius
+                m = __builtin_amdgcn_alignbit(m, __float_as_uint(t), 31);              // m = m << 1 | sign(t)
+                mn = __builtin_amdgcn_alignbit(mn, __float_as_uint(t + dnear), 31);    // < 0 inside the near radius
             }
-            adjw[(size_t)(k0 >> 2) * 64] = make_uint4(out[0], out[1], out[2], out[3]);
         }
-        if (p.chain_o) {
-            const int4 c = p.chain_o[o];
-            auto conv = [&](int cb) -> int {
-                if (cb < 0) return -1;
-                const unsigned ps = so[cb];
-                unsigned idx;
-                if (TILED && to_local(ps, idx)) return (int)(idx | GD_CHAIN_LOCAL);
-                return (int)ps;
-            };
-            p.chain[g] = make_int4(conv(c.x), conv(c.y), conv(c.z), conv(c.w));
+        m >>= ((n + 3u) & ~3u) - n; mn >>= ((n + 3u) & ~3u) - n;          // candidate i now at bit n-1-i
+        const unsigned sd = self_l - j0;
+        if (sd < n) m &= ~(1u << (n - 1u - sd));
+        mn &= m; m ^= mn;                                // near class, far class
+        GD_FSTAMP(3);     // distance tests
+        // (lowest set bit first: find-first-bit, then clear it with m & (m - 1) -- three instructions less per entry than isolating the
+        // highest bit; the order of a bead's entries is immaterial)
+        while (mn) {
+            GD_FCOUNT(9);
+            const unsigned bit = (unsigned)__builtin_ctz(mn);
+            mn &= mn - 1u;
+            lw.push(S16 ? (j0 + (n - 1u - bit)) << 4 : j0 + (n - 1u - bit));
+        }
+        while (m) {
+            const unsigned bit = (unsigned)__builtin_ctz(m);
+            m &= m - 1u;
+            lw.push_far(S16 ? (j0 + (n - 1u - bit)) << 4 : j0 + (n - 1u - bit));
+        }
+        GD_FSTAMP(4);     // appends
+    }
+}
+
+// ---- Tiled sweep, periodic box.  Periodic tile = whole rows: for each of the 9 wrapped (dz,dy) rows the x-window cx-1..cx+1 is one
+// slot interval, or two when it wraps around the row end.  The tile holds wrapped coordinates (wrap_tile), so the candidates of one
+// (row, interval) are all in the same periodic image relative to the bead: the bead, wrapped the same way, is shifted by that image
+// once and the tests are the open-box ones.  (Exact while cells are at least the list radius wide and the grid has three cells per
+// axis: k_tiles sends smaller grids to the generic path.)
+template <bool S16>
+__device__ __forceinline__ void sweep_tiled_periodic(const BuildParams &p, const FillBead &b, const GridP &gp, const unsigned *__restrict__ cs, int cx, int cy, int cz,
+                                                     const float4 xi, const float4 *s_tile, const TileDesc &td, unsigned nr, float rv2, float dnear, ListWriter<true> &lw, FillStamps &fst_)
+{
+    const int nx = gp.nc[0], ny = gp.nc[1], nz = gp.nc[2];
+    const float3 xw = make_float3(xi.x - p.box[0] * floorf(xi.x * p.inv_box[0]), xi.y - p.box[1] * floorf(xi.y * p.inv_box[1]),
+                                  xi.z - p.box[2] * floorf(xi.z * p.inv_box[2]));
+    unsigned pb[2 * GD_TILE_RANGES], pe[2 * GD_TILE_RANGES];
+#pragma unroll
+    for (int k = 0; k < GD_TILE_RANGES; k++) {
+        const int zz = (cz + k / 3 - 1 + nz) % nz, yy = (cy + k % 3 - 1 + ny) % ny;
+        const unsigned row = (unsigned)((zz * ny + yy) * nx);
+        if (cx == 0) { pb[2 * k] = cs[row]; pe[2 * k] = cs[row + 2]; pb[2 * k + 1] = cs[row + nx - 1]; pe[2 * k + 1] = cs[row + nx]; }
+        else if (cx == nx - 1) { pb[2 * k] = cs[row]; pe[2 * k] = cs[row + 1]; pb[2 * k + 1] = cs[row + nx - 2]; pe[2 * k + 1] = cs[row + nx]; }
+        else { pb[2 * k] = cs[row + cx - 1]; pe[2 * k] = cs[row + cx + 2]; pb[2 * k + 1] = 0; pe[2 * k + 1] = 0; }
+    }
+    GD_FSTAMP(2);     // row bounds
+#pragma unroll
+    for (int k2 = 0; k2 < 2 * GD_TILE_RANGES; k2++) {
+        const unsigned bb = pb[k2], e = pe[k2];
+        if (e > bb) {
+            unsigned lb = 0;
+            if (!tile_index(td, nr, bb, lb)) { p.flags[b.r * GD_NFLAGS + GD_FLAG_TILE_OVERFLOW] = 1u; continue; }   // (cannot happen: the row is staged)
+            // image of this interval: rows below / above the box in y and z; in x the first interval of a bead in the last
+            // cell is cell 0 (one period up), the second interval of a bead in cell 0 is the last cell (one period down)
+            const int y0 = cy + (k2 >> 1) % 3 - 1, z0 = cz + (k2 >> 1) / 3 - 1;
+            const float ax = xw.x + ((k2 & 1) ? (cx == 0 ? p.box[0] : 0.f) : (cx == nx - 1 ? -p.box[0] : 0.f));
+            const float ay = xw.y + (y0 < 0 ? p.box[1] : y0 >= ny ? -p.box[1] : 0.f);
+            const float az = xw.z + (z0 < 0 ? p.box[2] : z0 >= nz ? -p.box[2] : 0.f);
+            test_and_append<S16>(s_tile, lb, lb + (e - bb), lb + (b.slot - bb), ax, ay, az, rv2, dnear, lw, fst_);
+        }
+        if (k2 & 1) lw.flush();
+    }
+}
+
+// ---- Tiled sweep, open box: the nine (dz,dy) rows of the bead's window, each one slot interval of the tile
+template <bool S16>
+__device__ __forceinline__ void sweep_tiled_open(const BuildParams &p, const FillBead &b, const GridP &gp, const unsigned *__restrict__ cs, int cx, int cy, int cz,
+                                                 const float4 xi, const float4 *s_tile, const TileDesc &td, float rv2, float dnear, ListWriter<true> &lw, FillStamps &fst_)
+{
+    const unsigned x_lo = (unsigned)max(cx - p.kx, 0), x_hi = (unsigned)min(cx + p.kx, gp.nc[0] - 1);
+    // all 18 row-bound loads are issued before the first sweep (memory-level parallelism)
+    unsigned rb[GD_TILE_RANGES], re[GD_TILE_RANGES];
+#pragma unroll
+    for (int k = 0; k < GD_TILE_RANGES; k++) {
+        const int zz = cz + k / 3 - 1, yy = cy + k % 3 - 1;
+        rb[k] = 0; re[k] = 0;
+        if (zz < 0 || zz >= gp.nc[2] || yy < 0 || yy >= gp.nc[1] || td.kstart[k] == 0xffffffffu) continue;
+        const unsigned row = (unsigned)((zz * gp.nc[1] + yy) * gp.nc[0]);
+        rb[k] = cs[row + x_lo]; re[k] = cs[row + x_hi + 1];
+    }
+    GD_FSTAMP(2);     // row bounds
+#pragma unroll
+    for (int k = 0; k < GD_TILE_RANGES; k++) {
+        const unsigned bb = rb[k], e = re[k];
+        if (e > bb) {
+            const unsigned lb = td.kbase[k] + (bb - td.kstart[k]);
+            // (self: lb + (slot - bb) == own tile index when the bead is in this row segment)
+            test_and_append<S16>(s_tile, lb, lb + (e - bb), lb + (b.slot - bb), xi.x, xi.y, xi.z, rv2, dnear, lw, fst_);
+        }
+        lw.flush();
+    }
+}
+
+// ---- Generic sweep: the cells around the bead straight from global memory, one list class, entries are slots
+template <bool PERIODIC>
+__device__ __forceinline__ void sweep_generic(const BuildParams &p, const FillBead &b, const GridP &gp, const unsigned *__restrict__ cs, int cx, int cy, int cz,
+                                              const float4 xi, const float4 *__restrict__ rpos, float rv2, ListWriter<false> &lw)
+{
+    // distinct neighbour cells per dimension (small periodic grids alias)
+    const int nz = PERIODIC ? min(3, gp.nc[2]) : 3, ny = PERIODIC ? min(3, gp.nc[1]) : 3, nx = PERIODIC ? min(3, gp.nc[0]) : 2 * p.kx + 1;
+    const int z0 = (PERIODIC && gp.nc[2] < 3) ? 0 : cz - 1, y0 = (PERIODIC && gp.nc[1] < 3) ? 0 : cy - 1,
+              x0 = PERIODIC ? (gp.nc[0] < 3 ? 0 : cx - 1) : cx - p.kx;
+    for (int iz = 0; iz < nz; iz++) {
+        int zz = z0 + iz;
+        if (PERIODIC) zz = (zz + gp.nc[2]) % gp.nc[2]; else if (zz < 0 || zz >= gp.nc[2]) continue;
+        for (int iy = 0; iy < ny; iy++) {
+            int yy = y0 + iy;
+            if (PERIODIC) yy = (yy + gp.nc[1]) % gp.nc[1]; else if (yy < 0 || yy >= gp.nc[1]) continue;
+            for (int ix = 0; ix < nx; ix++) {
+                int xx = x0 + ix;
+                if (PERIODIC) xx = (xx + gp.nc[0]) % gp.nc[0]; else if (xx < 0 || xx >= gp.nc[0]) continue;
+                const unsigned c = (unsigned)((zz * gp.nc[1] + yy) * gp.nc[0] + xx);
+                const unsigned bb = cs[c], e = cs[c + 1];
+                for (unsigned j = bb; j < e; j++) {
+                    if (j == b.slot) continue;
+                    const float4 xj = rpos[j];
+                    float3 d = make_float3(xi.x - xj.x, xi.y - xj.y, xi.z - xj.z);
+                    if (PERIODIC) d = min_image(d, p.box, p.inv_box);
+                    if (d.x * d.x + d.y * d.y + d.z * d.z < rv2) lw.push(j);
+                }
+            }
         }
     }
-    GD_FSTAMP(1);     // bond / chain re-map
-    if (TILED && !REPAIR) {      // the rows of the block's waves have their place once wave 0 has published it (long ago, as a rule)
-        while ((row_off = *(volatile unsigned *)&s_woff[wk]) == 0xffffffffu) __builtin_amdgcn_s_sleep(1);
-        __threadfence_block();
-        row_nc = *(volatile unsigned *)&s_wn[wk];
+}
+
+// ---- Behind the sweep: both classes padded to whole chunks with the bead itself (zero displacement, zero force) in closed form,
+// overflow and class flags, what the bead needed (need_prev, s_wneed), the counts of its record
+template <bool TILED, bool S16, bool REPAIR>
+__device__ __forceinline__ void finish_rows(const BuildParams &p, FillBead &b, ListWriter<TILED> &lw, const TileDesc &td, unsigned nr, unsigned *s_wneed)
+{
+    constexpr unsigned PER = ListWriter<TILED>::PER;
+    const unsigned r = b.r;
+    const unsigned found = lw.cnt + lw.cntB;
+    unsigned self = b.slot;
+    if (TILED) { unsigned idx = 0; if (tile_index(td, nr, b.slot, idx)) self = S16 ? idx << 4 : idx; }
+    const unsigned needA = (lw.cnt + GD_UNROLL - 1u) & ~(GD_UNROLL - 1u), needB = (lw.cntB + GD_UNROLL - 1u) & ~(GD_UNROLL - 1u);
+    const unsigned needw = needA + needB;
+    // the tiled record counts the near entries in fours (11 bits: 8 184 entries) and the far chunks in 6 bits (504 entries): a
+    // class beyond that does not fit it even when the row is wide enough for the sum -- flagged like a row overflow, bit 1 on
+    // top (the host then builds single-class lists, or generic ones beyond 8 184 entries, until the dense transient has passed)
+    const bool class_over = TILED && (needA > GD_TILED_MAX_NEAR || needB > GD_TILED_MAX_FAR);
+    // (tiled lists: a row that is too narrow is repaired behind the kernel, only a class beyond its field is flagged; generic lists:
+    // the host widens the uniform rows and builds again)
+    const unsigned nc_row = lw.chunks(), Wrow = nc_row * PER;
+    if (((!TILED && needw > Wrow) || class_over) && !p.flags[r * GD_NFLAGS + GD_FLAG_TAINT]) {
+        atomicOr(&p.flags[r * GD_NFLAGS + GD_FLAG_OVERFLOW], class_over ? 3u : 1u);
+        atomicMax(&p.flags[r * GD_NFLAGS + GD_FLAG_NEED_W], needw);
     }
-    if (on) {
-        unsigned listlen = 0, nAq = 0, nB = 0;
-        if (!(p.nbr || p.nbr16)) {      // (a sort without lists: the counter of the bead's cell still goes back to zero, see below)
-            const GridP gp = p.grid[r];
-            int cx, cy, cz;
-            cell_coords<PERIODIC>(gp, rpos[slot], p.inv_box, cx, cy, cz);
-            p.cell_cnt[(size_t)r * (p.ncell_cap + 1) + (unsigned)((cz * gp.nc[1] + cy) * gp.nc[0] + cx)] = 0u;
-        }
-        if (p.nbr || p.nbr16) {
-            const GridP gp = p.grid[r];
-            const float4 xi = rpos[slot];
-            const unsigned *__restrict__ cs = p.cell_start + (size_t)r * (p.ncell_cap + 1);
-            int cx, cy, cz;
-            cell_coords<PERIODIC>(gp, xi, p.inv_box, cx, cy, cz);
-            // the counters k_bin counted into go back to zero for the next build: every bead clears its own cell's (the lanes of a
-            // wave sit in a handful of neighbouring cells: a line or two per store instruction); nothing reads them after k_scan
-            p.cell_cnt[(size_t)r * (p.ncell_cap + 1) + (unsigned)((cz * gp.nc[1] + cy) * gp.nc[0] + cx)] = 0u;
-            const float rv2 = p.rv * p.rv;
-            // Tiled lists are kept in TWO classes by the distance at the build: "near" entries (closer than rn) in the chunks
-            // from the front of the bead's row, "far" entries (rn <= d < rv) in the chunks from its back.  A pair that is not
-            // in the near class was at least rn apart at the build, so while cutoff + 2 x (largest displacement since the
-            // build) <= rn it exerts no force and k_step leaves the far chunks alone -- most steps of an interval.
-            const float dnear = rv2 - p.rn * p.rn;           // (r2 - rv2) + dnear = r2 - rn2
-            // list writer: entries go straight into the wave-interleaved 16-byte chunk layout k_step
-            // reads (8 x u16 tiled, 4 x u32 generic); a bead's 8 (4) consecutive entries share one chunk.
-            constexpr unsigned PER = TILED ? 8u : 4u;
-            // (tiled: the rows of the thread's k_step wave -- NC chunks per lane from KiB s_woff[wk] of the pool; generic: uniform rows)
-            // (tiled: the width is a per-lane value now, and the sweep below sits exactly at its register budget -- 80 VGPRs for three
-            // blocks per CU: the width, the k_step wave and the bond degree share one register through the sweep and are unpacked
-            // where they are needed, a few times per bead; the empty asm keeps the unpacking from being hoisted back out)
-            unsigned pk = deg | (wk << 8) | (row_nc << 11);
-            auto NCf = [&]() -> unsigned { if (!TILED) return p.W / PER; unsigned t = pk; asm volatile("" : "+v"(t)); return t >> 11; };
-#define NC NCf()
-            uint4 *__restrict__ lst = TILED ? (uint4 *)p.nbr16 + ((size_t)row_off * 64 + (gw & 63)) : (uint4 *)p.nbr + (size_t)(gw >> 6) * (p.W / PER) * 64 + (gw & 63);
-            // the 16-byte chunk under construction lives in four registers (an LDS staging slot per thread would cost
-            // the 8 KB that separate two from three resident blocks per CU); every PER-th entry the finished chunk
-            // goes out as one 16-byte global store (2-byte scattered global stores were 25% of the build)
-            unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-            // A finished chunk is parked in p0..p3 and stored at the next flush point (the end of a row window), where
-            // the lanes of the wave store together: one store instruction per row instead of one per append iteration.
-            unsigned p0 = 0, p1 = 0, p2 = 0, p3 = 0, pend = 0;      // pend: chunk index + 1 of the parked chunk, 0 = none
-            auto flush = [&]() {
-                if (pend) { lst[(size_t)(pend - 1) * 64] = make_uint4(p0, p1, p2, p3); pend = 0; }      // (non-temporal stores here cost 15%: the partial lines no longer merge in L2)
-            };
-            unsigned cntB = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;      // far class (tiled): its own shift register, chunks stored from the back
-            auto push = [&](unsigned j) {
-                if (TILED) {        // 128-bit shift register: eight 16-bit entries, the first one ends up lowest
-                    w0 = __builtin_amdgcn_alignbit(w1, w0, 16); w1 = __builtin_amdgcn_alignbit(w2, w1, 16);
-                    w2 = __builtin_amdgcn_alignbit(w3, w2, 16); w3 = __builtin_amdgcn_alignbit(j, w3, 16);
-                } else {
-                    w0 = w1; w1 = w2; w2 = w3; w3 = j;
-                }
-                cnt++;
-                if (cnt % PER == 0) {
-                    if (cnt / PER <= NC) {      // (inside the row; a list that outgrows its row is flagged below, its chunk rolled back)
-                        flush();                               // (only if a second chunk fills before the next flush point)
-                        p0 = w0; p1 = w1; p2 = w2; p3 = w3; pend = cnt / PER;
-                    }
-                }
-            };
-            auto push_far = [&](unsigned j) {                  // (tiled only; far chunks are few: stored as they fill)
-                b0 = __builtin_amdgcn_alignbit(b1, b0, 16); b1 = __builtin_amdgcn_alignbit(b2, b1, 16);
-                b2 = __builtin_amdgcn_alignbit(b3, b2, 16); b3 = __builtin_amdgcn_alignbit(j, b3, 16);
-                cntB++;
-                if (cntB % 8u == 0) { const unsigned nc = NC; if (cntB / 8u <= nc) lst[(size_t)(nc - cntB / 8u) * 64] = make_uint4(b0, b1, b2, b3); }
-            };
-            if (TILED && PERIODIC) {
-                // periodic tile = whole rows: for each of the 9 wrapped (dz,dy) rows the x-window cx-1..cx+1 is one slot interval, or
-                // two when it wraps around the row end.  The tile holds wrapped coordinates (above), so the candidates of one
-                // (row, interval) are all in the same periodic image relative to the bead: the bead, wrapped the same way, is shifted
-                // by that image once and the tests are the open-box ones.  (Exact while cells are at least the list radius wide and
-                // the grid has three cells per axis: k_tiles sends smaller grids to the generic path.)
-                const int nx = gp.nc[0], ny = gp.nc[1], nz = gp.nc[2];
-                const float3 xw = make_float3(xi.x - p.box[0] * floorf(xi.x * p.inv_box[0]), xi.y - p.box[1] * floorf(xi.y * p.inv_box[1]),
-                                              xi.z - p.box[2] * floorf(xi.z * p.inv_box[2]));
-                unsigned pb[2 * GD_TILE_RANGES], pe[2 * GD_TILE_RANGES];
-#pragma unroll
-                for (int k = 0; k < GD_TILE_RANGES; k++) {
-                    const int zz = (cz + k / 3 - 1 + nz) % nz, yy = (cy + k % 3 - 1 + ny) % ny;
-                    const unsigned row = (unsigned)((zz * ny + yy) * nx);
-                    if (cx == 0) { pb[2 * k] = cs[row]; pe[2 * k] = cs[row + 2]; pb[2 * k + 1] = cs[row + nx - 1]; pe[2 * k + 1] = cs[row + nx]; }
-                    else if (cx == nx - 1) { pb[2 * k] = cs[row]; pe[2 * k] = cs[row + 1]; pb[2 * k + 1] = cs[row + nx - 2]; pe[2 * k + 1] = cs[row + nx]; }
-                    else { pb[2 * k] = cs[row + cx - 1]; pe[2 * k] = cs[row + cx + 2]; pb[2 * k + 1] = 0; pe[2 * k + 1] = 0; }
-                }
-#pragma unroll
-                for (int k2 = 0; k2 < 2 * GD_TILE_RANGES; k2++) {
-                    const unsigned b = pb[k2], e = pe[k2];
-                    if (e > b) {
-                        unsigned lb = 0;
-                        if (!to_local(b, lb)) { p.flags[r * GD_NFLAGS + GD_FLAG_TILE_OVERFLOW] = 1u; continue; }   // (cannot happen: the row is staged)
-                        const unsigned le = lb + (e - b);
-                        const unsigned self_l = lb + (slot - b);
-                        // image of this interval: rows below / above the box in y and z; in x the first interval of a bead in the last
-                        // cell is cell 0 (one period up), the second interval of a bead in cell 0 is the last cell (one period down)
-                        const int y0 = cy + (k2 >> 1) % 3 - 1, z0 = cz + (k2 >> 1) / 3 - 1;
-                        const float ax = xw.x + ((k2 & 1) ? (cx == 0 ? p.box[0] : 0.f) : (cx == nx - 1 ? -p.box[0] : 0.f));
-                        const float ay = xw.y + (y0 < 0 ? p.box[1] : y0 >= ny ? -p.box[1] : 0.f);
-                        const float az = xw.z + (z0 < 0 ? p.box[2] : z0 >= nz ? -p.box[2] : 0.f);
-                        for (unsigned j0 = lb; j0 < le; j0 += 32) {
-                            const unsigned n = min(32u, le - j0);
-                            unsigned m = 0, mn = 0;
-                            for (unsigned u0 = 0; u0 < n; u0 += 4) {
-                                const float4 *cj = s_tile + j0 + u0;
-#pragma unroll
-                                for (int u = 0; u < 4; u++) {
-                                    const float4 xj = cj[u];
-                                    const float dx = ax - xj.x, dy = ay - xj.y, dz = az - xj.z;
-                                    const float t = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, -rv2)));
-                                    m = __builtin_amdgcn_alignbit(m, __float_as_uint(t), 31);
-                                    mn = __builtin_amdgcn_alignbit(mn, __float_as_uint(t + dnear), 31);
-                                }
-                            }
-                            m >>= ((n + 3u) & ~3u) - n; mn >>= ((n + 3u) & ~3u) - n;
-                            const unsigned sd = self_l - j0;
-                            if (sd < n) m &= ~(1u << (n - 1u - sd));
-                            mn &= m; m ^= mn;                                 // near class, far class
-                            // (lowest set bit first: find-first-bit, then clear it with m & (m - 1) -- three instructions less per entry than
-                            // isolating the highest bit; the order of a bead's entries is immaterial)
-                            while (mn) {
-                                const unsigned bit = (unsigned)__builtin_ctz(mn);
-                                mn &= mn - 1u;
-                                push(S16 ? (j0 + (n - 1u - bit)) << 4 : j0 + (n - 1u - bit));
-                            }
-                            while (m) {
-                                const unsigned bit = (unsigned)__builtin_ctz(m);
-                                m &= m - 1u;
-                                push_far(S16 ? (j0 + (n - 1u - bit)) << 4 : j0 + (n - 1u - bit));
-                            }
-                        }
-                    }
-                    if (k2 & 1) flush();
-                }
-            } else if (TILED) {
-                const unsigned x_lo = (unsigned)max(cx - p.kx, 0), x_hi = (unsigned)min(cx + p.kx, gp.nc[0] - 1);
-                // all 18 row-bound loads are issued before the first sweep (memory-level parallelism)
-                unsigned rb[GD_TILE_RANGES], re[GD_TILE_RANGES];
-#pragma unroll
-                for (int k = 0; k < GD_TILE_RANGES; k++) {
-                    const int zz = cz + k / 3 - 1, yy = cy + k % 3 - 1;
-                    rb[k] = 0; re[k] = 0;
-                    if (zz < 0 || zz >= gp.nc[2] || yy < 0 || yy >= gp.nc[1] || s_td.kstart[k] == 0xffffffffu) continue;
-                    const unsigned row = (unsigned)((zz * gp.nc[1] + yy) * gp.nc[0]);
-                    rb[k] = cs[row + x_lo]; re[k] = cs[row + x_hi + 1];
-                }
-                GD_FSTAMP(2);     // row bounds
-#pragma unroll
-                for (int k = 0; k < GD_TILE_RANGES; k++) {
-                    const unsigned b = rb[k], e = re[k];
-                    if (e > b) {
-                        const unsigned lb = s_td.kbase[k] + (b - s_td.kstart[k]), le = lb + (e - b);
-                        const unsigned self_l = lb + (slot - b);       // == own tile index when the bead is in this row segment
-                        // branch-free distance tests into a per-lane bit mask, then one append per set bit:
-                        // the (divergent) append code runs max-popcount times per segment, not once per candidate
-                        for (unsigned j0 = lb; j0 < le; j0 += 32) {
-                            const unsigned n = min(32u, le - j0);
-                            unsigned m = 0, mn = 0;
-                            // nine instructions per candidate: r2 - rv2 by three subtractions and three fmas, its sign bit
-                            // shifted into the mask by one v_alignbit (candidate i of the n4 tested ends up at bit
-                            // n4-1-i), one add and one more v_alignbit for the near-class mask.  Reads may run up to 3
-                            // slots past the window (slack is allocated behind the tile); those bits are shifted out
-                            // below, the bead itself is masked once.
-                            for (unsigned u0 = 0; u0 < n; u0 += 4) {
-                                GD_FCOUNT(8);         // wave-level test groups (lane 0 runs while any lane does)
-                                const float4 *cj = s_tile + j0 + u0;
-#pragma unroll
-                                for (int u = 0; u < 4; u++) {
-                                    const float4 xj = cj[u];
-                                    const float dx = xi.x - xj.x, dy = xi.y - xj.y, dz = xi.z - xj.z;
-                                    const float t = fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, -rv2)));      // < 0 inside the list radius
-                                    m = __builtin_amdgcn_alignbit(m, __float_as_uint(t), 31);              // m = m << 1 | sign(t)
-                                    mn = __builtin_amdgcn_alignbit(mn, __float_as_uint(t + dnear), 31);    // < 0 inside the near radius
-                                }
-                            }
-                            m >>= ((n + 3u) & ~3u) - n; mn >>= ((n + 3u) & ~3u) - n;          // candidate i now at bit n-1-i
-                            const unsigned sd = self_l - j0;
-                            if (sd < n) m &= ~(1u << (n - 1u - sd));
-                            mn &= m; m ^= mn;                                // near class, far class
-                            GD_FSTAMP(3);     // distance tests
-                            // (lowest set bit first: find-first-bit, then clear it with m & (m - 1) -- three instructions less per entry than
-                            // isolating the highest bit; the order of a bead's entries is immaterial)
-                            while (mn) {
-                                GD_FCOUNT(9);
-                                const unsigned bit = (unsigned)__builtin_ctz(mn);
-                                mn &= mn - 1u;
-                                push(S16 ? (j0 + (n - 1u - bit)) << 4 : j0 + (n - 1u - bit));
-                            }
-                            while (m) {
-                                const unsigned bit = (unsigned)__builtin_ctz(m);
-                                m &= m - 1u;
-                                push_far(S16 ? (j0 + (n - 1u - bit)) << 4 : j0 + (n - 1u - bit));
-                            }
-                            GD_FSTAMP(4);     // appends
-                        }
-                    }
-                    flush();
-                }
-            } else {
-                // distinct neighbour cells per dimension (small periodic grids alias)
-                const int nz = PERIODIC ? min(3, gp.nc[2]) : 3, ny = PERIODIC ? min(3, gp.nc[1]) : 3, nx = PERIODIC ? min(3, gp.nc[0]) : 2 * p.kx + 1;
-                const int z0 = (PERIODIC && gp.nc[2] < 3) ? 0 : cz - 1, y0 = (PERIODIC && gp.nc[1] < 3) ? 0 : cy - 1,
-                          x0 = PERIODIC ? (gp.nc[0] < 3 ? 0 : cx - 1) : cx - p.kx;
-                for (int iz = 0; iz < nz; iz++) {
-                    int zz = z0 + iz;
-                    if (PERIODIC) zz = (zz + gp.nc[2]) % gp.nc[2]; else if (zz < 0 || zz >= gp.nc[2]) continue;
-                    for (int iy = 0; iy < ny; iy++) {
-                        int yy = y0 + iy;
-                        if (PERIODIC) yy = (yy + gp.nc[1]) % gp.nc[1]; else if (yy < 0 || yy >= gp.nc[1]) continue;
-                        for (int ix = 0; ix < nx; ix++) {
-                            int xx = x0 + ix;
-                            if (PERIODIC) xx = (xx + gp.nc[0]) % gp.nc[0]; else if (xx < 0 || xx >= gp.nc[0]) continue;
-                            const unsigned c = (unsigned)((zz * gp.nc[1] + yy) * gp.nc[0] + xx);
-                            const unsigned b = cs[c], e = cs[c + 1];
-                            for (unsigned j = b; j < e; j++) {
-                                if (j == slot) continue;
-                                const float4 xj = rpos[j];
-                                float3 d = make_float3(xi.x - xj.x, xi.y - xj.y, xi.z - xj.z);
-                                if (PERIODIC) d = min_image(d, p.box, p.inv_box);
-                                if (d.x * d.x + d.y * d.y + d.z * d.z < rv2) push(j);
-                            }
-                        }
-                    }
-                }
-            }
-            const unsigned found = cnt + cntB;
-            // pad both classes to whole chunks with the bead itself: zero displacement, zero force
-            unsigned self = slot;
-            if (TILED) { unsigned idx = 0; if (to_local(slot, idx)) self = S16 ? idx << 4 : idx; }
-            const unsigned needA = (cnt + GD_UNROLL - 1u) & ~(GD_UNROLL - 1u), needB = (cntB + GD_UNROLL - 1u) & ~(GD_UNROLL - 1u);
-            const unsigned needw = needA + needB;
-            // the tiled record counts the near entries in fours (11 bits: 8 184 entries) and the far chunks in 6 bits (504 entries): a
-            // class beyond that does not fit it even when the row is wide enough for the sum -- flagged like a row overflow, bit 1 on
-            // top (the host then builds single-class lists, or generic ones beyond 8 184 entries, until the dense transient has passed)
-            const bool class_over = TILED && (needA > GD_TILED_MAX_NEAR || needB > GD_TILED_MAX_FAR);
-            // (tiled lists: a row that is too narrow is repaired below, only a class beyond its field is flagged; generic lists: the
-            // host widens the uniform rows and builds again)
-            const unsigned nc_row = NC, Wrow = nc_row * PER;
-            if (((!TILED && needw > Wrow) || class_over) && !p.flags[r * GD_NFLAGS + GD_FLAG_TAINT]) {
-                atomicOr(&p.flags[r * GD_NFLAGS + GD_FLAG_OVERFLOW], class_over ? 3u : 1u);
-                atomicMax(&p.flags[r * GD_NFLAGS + GD_FLAG_NEED_W], needw);
-            }
-            if (TILED) {
-                // what this bead needed: for the rows of the next build, and for the repair pass -- the k_step wave it goes to needs
-                // the sum for its longest list
-                const unsigned na8 = min(needA / 8u, GD_TILED_MAX_NEAR / 8u), nb8 = min(needB / 8u, GD_TILED_MAX_FAR / 8u);
-                p.need_prev[(size_t)r * p.N + o] = (unsigned short)(na8 | (nb8 << 10));
-                if (!REPAIR) atomicMax(&s_wneed[(pk >> 8) & 7u], na8 + nb8);
-            }
-            listlen = min(found, Wrow);
-            nAq = min((cnt + 3u) / 4u, GD_TILED_MAX_NEAR / 4u);            // near entries in fours (the record's count; chunks are still written whole)
-            // pad the chunk under construction with the bead itself: the shift register moves down by the missing entries in three
-            // branch-free stages (four, two, one entry -- a loop of single pushes ran seven times in nearly every wave, 16 instructions
-            // each) and goes out with one store
-            flush();
-            auto pad = [&](unsigned &a0, unsigned &a1, unsigned &a2, unsigned &a3, unsigned sh) {      // sh entries (< PER) of `self` in from the top
-                const unsigned S = TILED ? self | (self << 16) : self;
-                if (TILED) {
-                    const bool s4 = (sh & 4u) != 0u, s2 = (sh & 2u) != 0u, s1 = (sh & 1u) != 0u;
-                    a0 = s4 ? a2 : a0; a1 = s4 ? a3 : a1; a2 = s4 ? S : a2; a3 = s4 ? S : a3;
-                    a0 = s2 ? a1 : a0; a1 = s2 ? a2 : a1; a2 = s2 ? a3 : a2; a3 = s2 ? S : a3;
-                    const unsigned c0 = __builtin_amdgcn_alignbit(a1, a0, 16), c1 = __builtin_amdgcn_alignbit(a2, a1, 16),
-                                   c2 = __builtin_amdgcn_alignbit(a3, a2, 16), c3 = __builtin_amdgcn_alignbit(S, a3, 16);
-                    a0 = s1 ? c0 : a0; a1 = s1 ? c1 : a1; a2 = s1 ? c2 : a2; a3 = s1 ? c3 : a3;
-                } else {
-                    const bool s2 = (sh & 2u) != 0u, s1 = (sh & 1u) != 0u;
-                    a0 = s2 ? a2 : a0; a1 = s2 ? a3 : a1; a2 = s2 ? S : a2; a3 = s2 ? S : a3;
-                    a0 = s1 ? a1 : a0; a1 = s1 ? a2 : a1; a2 = s1 ? a3 : a2; a3 = s1 ? S : a3;
-                }
-            };
-            if (cnt % PER) {
-                pad(w0, w1, w2, w3, PER - cnt % PER);
-                cnt = (cnt + PER - 1u) & ~(PER - 1u);
-                if (cnt / PER <= nc_row) lst[(size_t)(cnt / PER - 1u) * 64] = make_uint4(w0, w1, w2, w3);
-            }
-            if (!TILED && cnt % GD_UNROLL) {      // (generic lists are walked in batches of two chunks: a whole chunk of the bead itself behind an odd one)
-                cnt += PER;
-                if (cnt / PER <= nc_row) lst[(size_t)(cnt / PER - 1u) * 64] = make_uint4(self, self, self, self);
-            }
-            if (TILED && cntB % 8u) {
-                pad(b0, b1, b2, b3, 8u - cntB % 8u);
-                cntB = (cntB + 7u) & ~7u;
-                if (cntB / 8u <= nc_row) lst[(size_t)(nc_row - cntB / 8u) * 64] = make_uint4(b0, b1, b2, b3);
-            }
-            // (an overflowed list: the chunk counts have to stay inside the row until it is repaired)
-            nAq = min(nAq, 2u * nc_row); nB = min(min(cntB / GD_UNROLL, GD_TILED_MAX_FAR / GD_UNROLL), nc_row - (nAq + 1u) / 2u);
-            cnt = found; near4 = 4u * nAq;
-            deg = pk & 0xffu;
-#undef NC
-        }
-        const unsigned meta = deg | ((unsigned)p.psmask_o[o] << 8) | (listlen << 16);
-        if (TILED) {
-            const float4 xb = rpos[slot];
-            p.rec_x0[gt] = make_float4(xb.x, xb.y, xb.z, __uint_as_float(slot - blk * GD_BLOCK));
-            // tiled record: bond degree | point-source mask << 8 | block-local slot << 12 | near entries / 4 << 21, bead id | far chunks << 26
-            // (y all ones: no bead)
-            p.rec_mo[gt] = make_uint2(deg | (((unsigned)p.psmask_o[o] & 0xfu) << 8) | ((slot - blk * GD_BLOCK) << 12) | (nAq << 21), o | (nB << 26));
-            p.len_prev[(size_t)r * p.N + o] = (unsigned char)min(nAq, 255u);       // (the near class is what most steps run over)
-        } else p.meta[g] = meta;
+    if (TILED) {
+        // what this bead needed: for the rows of the next build, and for the repair pass -- the k_step wave it goes to needs
+        // the sum for its longest list
+        const unsigned na8 = min(needA / 8u, GD_TILED_MAX_NEAR / 8u), nb8 = min(needB / 8u, GD_TILED_MAX_FAR / 8u);
+        p.need_prev[(size_t)r * p.N + b.o] = (unsigned short)(na8 | (nb8 << 10));
+        if (!REPAIR) atomicMax(&s_wneed[(lw.pk >> 8) & 7u], na8 + nb8);
     }
-    if (REPAIR) return;
-    if (TILED && !on) { p.rec_x0[gt] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xffffu)); p.rec_mo[gt] = make_uint2(0u, GD_REC_NOBEAD); }
-    GD_FSTAMP(5);     // padding, meta
+    b.listlen = min(found, Wrow);
+    b.nAq = min((lw.cnt + 3u) / 4u, GD_TILED_MAX_NEAR / 4u);            // near entries in fours (the record's count; chunks are still written whole)
+    // the chunk under construction goes out padded, with one store
+    lw.flush();
+    if (lw.cnt % PER) {
+        lw.pad(lw.w0, lw.w1, lw.w2, lw.w3, PER - lw.cnt % PER, self);
+        lw.cnt = (lw.cnt + PER - 1u) & ~(PER - 1u);
+        if (lw.cnt / PER <= nc_row) lw.lst[(size_t)(lw.cnt / PER - 1u) * 64] = make_uint4(lw.w0, lw.w1, lw.w2, lw.w3);
+    }
+    if (!TILED && lw.cnt % GD_UNROLL) {      // (generic lists are walked in batches of two chunks: a whole chunk of the bead itself behind an odd one)
+        lw.cnt += PER;
+        if (lw.cnt / PER <= nc_row) lw.lst[(size_t)(lw.cnt / PER - 1u) * 64] = make_uint4(self, self, self, self);
+    }
+    if (TILED && lw.cntB % 8u) {
+        lw.pad(lw.b0, lw.b1, lw.b2, lw.b3, 8u - lw.cntB % 8u, self);
+        lw.cntB = (lw.cntB + 7u) & ~7u;
+        if (lw.cntB / 8u <= nc_row) lw.lst[(size_t)(nc_row - lw.cntB / 8u) * 64] = make_uint4(lw.b0, lw.b1, lw.b2, lw.b3);
+    }
+    // (an overflowed list: the chunk counts have to stay inside the row until it is repaired)
+    b.nAq = min(b.nAq, 2u * nc_row); b.nB = min(min(lw.cntB / GD_UNROLL, GD_TILED_MAX_FAR / GD_UNROLL), nc_row - (b.nAq + 1u) / 2u);
+    b.cnt = found; b.near4 = 4u * b.nAq;
+    b.deg = lw.pk & 0xffu;
+}
+
+// ---- The bead's record: where k_step's thread finds its bead, its counts and (tiled) its position at the build
+template <bool TILED>
+__device__ __forceinline__ void write_record(const BuildParams &p, const FillBead &b, const float4 *__restrict__ rpos)
+{
+    const unsigned meta = b.deg | ((unsigned)p.psmask_o[b.o] << 8) | (b.listlen << 16);
+    if (TILED) {
+        const float4 xb = rpos[b.slot];
+        p.rec_x0[b.gt] = make_float4(xb.x, xb.y, xb.z, __uint_as_float(b.slot - b.blk * GD_BLOCK));
+        // tiled record: bond degree | point-source mask << 8 | block-local slot << 12 | near entries / 4 << 21, bead id | far chunks << 26
+        // (y all ones: no bead)
+        p.rec_mo[b.gt] = make_uint2(b.deg | (((unsigned)p.psmask_o[b.o] & 0xfu) << 8) | ((b.slot - b.blk * GD_BLOCK) << 12) | (b.nAq << 21), b.o | (b.nB << 26));
+        p.len_prev[(size_t)b.r * p.N + b.o] = (unsigned char)min(b.nAq, 255u);       // (the near class is what most steps run over)
+    } else p.meta[b.rbase + b.slot] = meta;
+}
+
+// ---- Block totals (list entries, longest list): accumulated by LDS atomics as the waves finish; the last one to finish hands them
+// on -- no barrier at the end of the kernel, a wave that is done leaves -- and queues the block's waves that need a repair.
+template <bool TILED>
+__device__ __forceinline__ void block_totals(const BuildParams &p, const FillBead &b, unsigned long long *s_acc_cnt, unsigned *s_acc_max, unsigned *s_acc_done, unsigned *s_wneed, const unsigned *s_wn)
+{
+    const unsigned r = b.r;
     // (per block both counts fit 32 bits: the entries in the low word, the near entries -- in the fours k_step walks -- in the high one)
-    unsigned long long c64 = (unsigned long long)cnt | ((unsigned long long)near4 << 32);
-    unsigned cmax = cnt;
+    unsigned long long c64 = (unsigned long long)b.cnt | ((unsigned long long)b.near4 << 32);
+    unsigned cmax = b.cnt;
     for (int o2 = 32; o2 > 0; o2 >>= 1) { c64 += __shfl_xor(c64, o2, 64); cmax = max(cmax, (unsigned)__shfl_xor((int)cmax, o2, 64)); }
-    if (lane == 0) {
-        atomicAdd(&s_acc_cnt, c64); atomicMax(&s_acc_max, cmax);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(s_acc_cnt, c64); atomicMax(s_acc_max, cmax);
         __threadfence_block();       // (this wave's needs are in LDS before it counts as done)
-        if (atomicAdd(&s_acc_done, 1u) == (TILED ? 2u : 1u) * (GD_BLOCK / 64) - 1u) {      // the last wave of the block to finish (tiled: the counter starts from the eight arrivals above)
+        if (atomicAdd(s_acc_done, 1u) == (TILED ? 2u : 1u) * (GD_BLOCK / 64) - 1u) {      // the last wave of the block to finish (tiled: the counter starts from the eight arrivals of alloc_rows)
             __threadfence_block();
-            const unsigned long long t = atomicAdd(&s_acc_cnt, 0ull);
-            const unsigned m = atomicMax(&s_acc_max, 0u);
+            const unsigned long long t = atomicAdd(s_acc_cnt, 0ull);
+            const unsigned m = atomicMax(s_acc_max, 0u);
             if (t) { atomicAdd(&p.lcount[r], t & 0xffffffffull); if (TILED) atomicAdd(&p.lcount[p.R + r], t >> 32); }
             if (m && !p.flags[r * GD_NFLAGS + GD_FLAG_TAINT]) atomicMax(&p.flags[r * GD_NFLAGS + GD_FLAG_NEED_W], m);      // longest list, always
             // k_step waves of this block whose lists outgrew their rows: queued for the repair kernel (a block without rows -- the
-            // pool was full -- is not repaired: flagged above, the host enlarges the pool)
+            // pool was full -- is not repaired: flagged by alloc_rows, the host enlarges the pool)
             if (TILED) {
                 for (unsigned w = 0; w < GD_BLOCK / 64; w++) {
                     const unsigned need = atomicMax(&s_wneed[w], 0u), have = s_wn[w];
                     if (have != 0u && need > have) {
                         const unsigned at = atomicAdd(&p.pool[3], 1u);
-                        if (at < p.rq_cap) p.rqueue[at] = make_uint2(((r * p.nblk + blk) << 3) | w, need);      // (the queue holds every wave of the handle)
+                        if (at < p.rq_cap) p.rqueue[at] = make_uint2(((r * p.nblk + b.blk) << 3) | w, need);      // (the queue holds every wave of the handle)
                         // more waves than the repair launch has blocks (a state that changes faster than a build predicts): flagged, the
                         // chunk is rolled back and the host launches the repair kernel with a block for every wave until that has passed
                         if (at >= p.rq_grid && !p.flags[r * GD_NFLAGS + GD_FLAG_TAINT]) atomicOr(&p.flags[r * GD_NFLAGS + GD_FLAG_OVERFLOW], 4u);
@@ -2228,11 +2167,126 @@ __global__ __launch_bounds__(REPAIR ? 64 : GD_BLOCK, REPAIR ? 1 : (TILED ? (PERI
             }
         }
     }
+}
+
+// TILED: candidates are read from the block's LDS tile and list entries are tile indices.
+// (register budget of the tiled variants: 6 waves per SIMD = three blocks per CU = at most 80 VGPRs for open boxes, as the LDS admits
+// with the 3 312-entry tile class; the periodic sweep holds 18 window bounds: 4 waves per SIMD = two blocks = 128)
+// Tiled path: k_step's THREADS are ordered by the list length their bead had at the previous build (a very good predictor of the new one),
+// longest first, so that the 64 lanes of a k_step wave run the same number of list batches.  This kernel still works slot by slot (neighbouring
+// slots share their row windows: broadcast LDS reads, equal trip counts), but writes each bead's list, adjacency chunks and record at gt.
+// REPAIR (tiled lists; launched behind the build's k_fill with blocks of ONE wave): the rows of a k_step wave in which some list outgrew
+// the predicted width are written again at the width they turned out to need -- the block's tile staged again, the 64 beads of
+// that wave listed by the 64 lanes, fresh rows from the pool; the queue of such waves is filled by the last wave of every k_fill
+// block (block_totals) and is empty in almost every build.
+template <bool PERIODIC, bool TILED, bool S16, bool REPAIR = false>
+__global__ __launch_bounds__(REPAIR ? 64 : GD_BLOCK, REPAIR ? 1 : (TILED ? (PERIODIC ? 4 : 6) : 1)) void k_fill(const BuildParams p)
+{
+    static_assert(TILED || !REPAIR, "only the ragged rows of the tiled lists are repaired");
+    constexpr unsigned NTHR = REPAIR ? 64u : (unsigned)GD_BLOCK;
+    GD_FSTAMP_BEGIN();
+    extern __shared__ __attribute__((aligned(16))) float4 s_tile[];
+    // (Static LDS is budgeted: with the tile class of 3 312 entries three blocks fit a CU only up to 704 bytes of it -- LDS is granted
+    // in 1 280-byte granules; tools/kregs.py shows the figure.)
+    __shared__ unsigned long long s_acc_cnt;              // block totals, see block_totals
+    __shared__ unsigned s_acc_max, s_acc_done;
+    // ragged rows: chunks per lane and first KiB of the rows of each of the block's eight k_step waves
+    __shared__ unsigned s_wn[GD_BLOCK / 64], s_woff[GD_BLOCK / 64], s_wneed[GD_BLOCK / 64];      // (s_wneed: what the lists turned out to need)
+    __shared__ TileDesc s_td;                             // the block's tile descriptor, see stage_tile
+    FillBead b;
+    unsigned rep_w = 0, rep_need = 0;
+    if (REPAIR) {
+        if (blockIdx.x >= min(p.pool[3], p.rq_cap)) return;      // (queue items; one block = one wave each; the launch has rq_grid blocks)
+        const uint2 item = p.rqueue[blockIdx.x];
+        b.r = (item.x >> 3) / p.nblk; b.blk = (item.x >> 3) % p.nblk; rep_w = item.x & 7u; rep_need = item.y;
+    } else if (!block_map(blockIdx.x, p.nblk, p.cpb, b.r, b.blk)) return;
+    const unsigned lane = threadIdx.x & 63;
+    if (threadIdx.x == 0) { s_acc_cnt = 0ull; s_acc_max = 0u; s_acc_done = 0u; }
+    if (threadIdx.x < GD_BLOCK / 64) { s_wn[threadIdx.x] = 0u; s_woff[threadIdx.x] = 0xffffffffu; s_wneed[threadIdx.x] = 0u; }
+    if (!TILED) __syncthreads();      // (the tiled path has its barriers below)
+    b.rbase = (size_t)b.r * p.Np;
+    b.slot = b.blk * GD_BLOCK + threadIdx.x;      // (REPAIR: set below, from the record of the k_step thread this lane stands for)
+    b.gt = b.rbase + b.slot;
+    b.row_nc = b.row_off = b.o = b.deg = 0u; b.cnt = b.near4 = b.listlen = b.nAq = b.nB = 0u;
+    const float4 *__restrict__ rpos = p.pos_out + b.rbase;
+    // block-uniform descriptor, read through a uniform pointer (scalar loads; a local copy indexed in loops would be demoted to scratch memory)
+    const TileDesc *__restrict__ tdp = p.tiles + (size_t)b.r * p.nblk + b.blk;
+    const unsigned o_pre = (TILED && !REPAIR && b.slot < p.N) ? p.orig_out[b.gt] : 0u;      // (issued ahead of the DMAs: the balancing key below depends on it)
+    if (TILED) stage_tile<NTHR>(tdp, rpos, s_tile, s_td, REPAIR ? 0u : 64u);
+    if (TILED && REPAIR) {
+        __syncthreads();      // (also waits for the tile DMAs)
+        if (PERIODIC) { wrap_tile<NTHR>(p, s_tile, s_td.total); __syncthreads(); }
+        b.gt = b.rbase + (size_t)b.blk * GD_BLOCK + rep_w * 64u + lane;
+    }
+    if (TILED && !REPAIR) {
+        __shared__ unsigned long long s_hist8[GD_KBINS];
+        b.gt = place_thread<PERIODIC>(p, b, o_pre, s_hist8, s_tile, s_td);      // (the build's two barriers, the tile wrapped between them)
+    }
+    b.wk = TILED ? ((unsigned)(b.gt - b.rbase) - b.blk * GD_BLOCK) >> 6 : 0u;
+    if (TILED && REPAIR) { if (!alloc_repair_rows(p, b, rep_w, rep_need)) return; }
+    if (TILED && !REPAIR) alloc_rows(p, b, o_pre, s_wn, s_woff, &s_acc_done);
+    GD_FSTAMP(0);     // staging + barrier
+    const unsigned nr_tile = TILED ? (unsigned)__builtin_amdgcn_readfirstlane((int)s_td.nranges) : 0u;      // (merged ranges in use: three, typically)
+    b.on = b.slot < p.N;
+    if (REPAIR) {
+        const uint2 mo = p.rec_mo[b.gt];
+        b.on = mo.y != GD_REC_NOBEAD;
+        b.slot = b.blk * GD_BLOCK + ((mo.x >> 12) & 0x1ffu); b.o = mo.y & GD_REC_ID_MASK; b.deg = mo.x & 0xffu;
+    } else if (b.on) {
+        b.o = p.orig_out[b.rbase + b.slot];
+        b.deg = p.bdeg_o[b.o];
+        remap_topology<TILED>(p, b, s_td, nr_tile);
+    }
+    GD_FSTAMP(1);     // bond / chain re-map
+    if (TILED && !REPAIR) {      // the rows of the block's waves have their place once wave 0 has published it (long ago, as a rule)
+        while ((b.row_off = *(volatile unsigned *)&s_woff[b.wk]) == 0xffffffffu) __builtin_amdgcn_s_sleep(1);
+        __threadfence_block();
+        b.row_nc = *(volatile unsigned *)&s_wn[b.wk];
+    }
+    if (b.on) {
+        // the counters k_bin counted into go back to zero for the next build (also by a sort without lists): every bead clears its own
+        // cell's (the lanes of a wave sit in a handful of neighbouring cells: a line or two per store instruction); nothing reads them
+        // after k_scan
+        const GridP gp = p.grid[b.r];
+        const float4 xi = rpos[b.slot];
+        int cx, cy, cz;
+        cell_coords<PERIODIC>(gp, xi, p.inv_box, cx, cy, cz);
+        p.cell_cnt[(size_t)b.r * (p.ncell_cap + 1) + (unsigned)((cz * gp.nc[1] + cy) * gp.nc[0] + cx)] = 0u;
+        if (p.nbr || p.nbr16) {
+            const unsigned *__restrict__ cs = p.cell_start + (size_t)b.r * (p.ncell_cap + 1);
+            const float rv2 = p.rv * p.rv;
+            // Tiled lists are kept in TWO classes by the distance at the build: "near" entries (closer than rn) in the chunks from the front
+            // of the bead's row, "far" entries (rn <= d < rv) in the chunks from its back.  A pair that is not in the near class was at least
+            // rn apart at the build, so while cutoff + 2 x (largest displacement since the build) <= rn it exerts no force and k_step leaves
+            // the far chunks alone -- most steps of an interval.
+            const float dnear = rv2 - p.rn * p.rn;           // (r2 - rv2) + dnear = r2 - rn2
+            ListWriter<TILED> lw(p, b);
+            if constexpr (TILED && PERIODIC) sweep_tiled_periodic<S16>(p, b, gp, cs, cx, cy, cz, xi, s_tile, s_td, nr_tile, rv2, dnear, lw, fst_);
+            else if constexpr (TILED) sweep_tiled_open<S16>(p, b, gp, cs, cx, cy, cz, xi, s_tile, s_td, rv2, dnear, lw, fst_);
+            else sweep_generic<PERIODIC>(p, b, gp, cs, cx, cy, cz, xi, rpos, rv2, lw);
+            finish_rows<TILED, S16, REPAIR>(p, b, lw, s_td, nr_tile, s_wneed);
+        }
+        write_record<TILED>(p, b, rpos);
+    }
+    if (REPAIR) return;
+    if (TILED && !b.on) { p.rec_x0[b.gt] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0xffffu)); p.rec_mo[b.gt] = make_uint2(0u, GD_REC_NOBEAD); }
+    GD_FSTAMP(5);     // padding, meta
+    block_totals<TILED>(p, b, &s_acc_cnt, &s_acc_max, &s_acc_done, s_wneed, s_wn);
     GD_FSTAMP(6);     // count
     GD_FSTAMP_END(p.dbg);
 }
 
-#undef s_td
+// The k_fill instantiation of a launch: the one map from (periodic, tiled, s16, repair) to a variant, used by gd_launch_build and by
+// the LDS opt-in (gd_kernels_init_device).  Generic lists have plain indices and no repair.
+typedef void (*FillKernel)(BuildParams);
+template <bool PERIODIC>
+static FillKernel fill_kernel_of(bool tiled, bool s16, bool repair)
+{
+    if (!tiled) return k_fill<PERIODIC, false, false>;
+    if (repair) return s16 ? k_fill<PERIODIC, true, true, true> : k_fill<PERIODIC, true, false, true>;
+    return s16 ? k_fill<PERIODIC, true, true> : k_fill<PERIODIC, true, false>;
+}
+static FillKernel fill_kernel(bool periodic, bool tiled, bool s16, bool repair) { return periodic ? fill_kernel_of<true>(tiled, s16, repair) : fill_kernel_of<false>(tiled, s16, repair); }
 
 void gd_launch_build(const BuildParams &p, hipStream_t st)
 {
@@ -2256,14 +2310,10 @@ void gd_launch_build(const BuildParams &p, hipStream_t st)
         const size_t lds = (size_t)(p.tile_cap + 4) * sizeof(float4);   // +4: read slack
         // (behind it the repair kernel: one wave per queued k_step wave; its blocks leave at once while the queue is empty)
         const dim3 gridr(p.rq_grid), blockr(64);
-        if (p.periodic) {
-            if (p.tile_cap < 4096u) { hipLaunchKernelGGL((k_fill<true, true, true>), gridx, block, lds, st, p); hipLaunchKernelGGL((k_fill<true, true, true, true>), gridr, blockr, lds, st, p); }
-            else { hipLaunchKernelGGL((k_fill<true, true, false>), gridx, block, lds, st, p); hipLaunchKernelGGL((k_fill<true, true, false, true>), gridr, blockr, lds, st, p); }
-        } else if (p.tile_cap < 4096u) {      // byte-offset entries, as k_step expects
-            hipLaunchKernelGGL((k_fill<false, true, true>), gridx, block, lds, st, p); hipLaunchKernelGGL((k_fill<false, true, true, true>), gridr, blockr, lds, st, p);
-        } else { hipLaunchKernelGGL((k_fill<false, true, false>), gridx, block, lds, st, p); hipLaunchKernelGGL((k_fill<false, true, false, true>), gridr, blockr, lds, st, p); }
-    } else if (p.periodic) hipLaunchKernelGGL((k_fill<true, false, false>), gridx, block, 0, st, p);
-    else hipLaunchKernelGGL((k_fill<false, false, false>), gridx, block, 0, st, p);
+        const bool s16 = gd_tile_s16(p.tile_cap);      // byte-offset entries, as k_step expects
+        hipLaunchKernelGGL(fill_kernel(p.periodic, true, s16, false), gridx, block, lds, st, p);
+        hipLaunchKernelGGL(fill_kernel(p.periodic, true, s16, true), gridr, blockr, lds, st, p);
+    } else hipLaunchKernelGGL(fill_kernel(p.periodic, false, false, false), gridx, block, 0, st, p);
 }
 
 // ------------------------------------------------------------- droplet attraction
@@ -2539,14 +2589,9 @@ hipError_t gd_kernels_init_device(void)
         for (int per = 0; per < 2; per++)
             for (int pk = 0; pk < 3; pk++)
                 for (int s16 = 0; s16 < 2; s16++) set(reinterpret_cast<const void *>(pick(per != 0, pk, s16 != 0)), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<false, true, false>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<false, true, true>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<true, true, false>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<true, true, true>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<false, true, false, true>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<false, true, true, true>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<true, true, false, true>), 128 * 1024);
-    set(reinterpret_cast<const void *>(&k_fill<true, true, true, true>), 128 * 1024);
+    for (int per = 0; per < 2; per++)
+        for (int s16 = 0; s16 < 2; s16++)
+            for (int rep = 0; rep < 2; rep++) set(reinterpret_cast<const void *>(fill_kernel(per != 0, true, s16 != 0, rep != 0)), 128 * 1024);
     set(reinterpret_cast<const void *>(&k_softwell<0>), 64 * 1024);
     set(reinterpret_cast<const void *>(&k_softwell<1>), 64 * 1024);
     set(reinterpret_cast<const void *>(&k_softwell<2>), 64 * 1024);

@@ -22,16 +22,19 @@
 #define GD_STAMP_END(buf) do { } while (0)
 #endif
 
+// (k_fill hands the stamp state to its section functions: an empty struct in the product build)
 #if GD_ABL == 34
-#define GD_FSTAMP_BEGIN() unsigned long long ftprev_ = __builtin_amdgcn_s_memtime(), facc_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define GD_FSTAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); facc_[k] += now_ - ftprev_; ftprev_ = __builtin_amdgcn_s_memtime(); } while (0)
-#define GD_FCOUNT(k) do { facc_[k] += 1; } while (0)
+struct FillStamps { unsigned long long tprev, acc[12]; };
+#define GD_FSTAMP_BEGIN() FillStamps fst_ = {__builtin_amdgcn_s_memtime(), {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}}
+#define GD_FSTAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); fst_.acc[k] += now_ - fst_.tprev; fst_.tprev = __builtin_amdgcn_s_memtime(); } while (0)
+#define GD_FCOUNT(k) do { fst_.acc[k] += 1; } while (0)
 #define GD_FSTAMP_END(buf) do { if ((threadIdx.x & 63) == 0) {                                                             \
         unsigned long long *rec_ = (buf) + ((size_t)blockIdx.x * (GD_BLOCK / 64) + (threadIdx.x >> 6)) * 16;              \
-        for (int k_ = 0; k_ < 12; k_++) rec_[k_] = facc_[k_];                                                             \
+        for (int k_ = 0; k_ < 12; k_++) rec_[k_] = fst_.acc[k_];                                                          \
         rec_[15] = 1ull; } } while (0)
 #else
-#define GD_FSTAMP_BEGIN() do { } while (0)
+struct FillStamps {};
+#define GD_FSTAMP_BEGIN() FillStamps fst_
 #define GD_FSTAMP(k) do { } while (0)
 #define GD_FCOUNT(k) do { } while (0)
 #define GD_FSTAMP_END(buf) do { } while (0)

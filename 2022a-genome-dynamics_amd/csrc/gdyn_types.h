@@ -33,6 +33,9 @@
 #define GD_TILED_MAX_NEAR 8184u            // near entries (1 023 chunks of 8; 2 046 fours in the record's 11 bits)
 #define GD_TILED_MAX_FAR 504u              // far entries (63 chunks)
 #define GD_TILED_MAX_W (GD_TILED_MAX_NEAR + GD_TILED_MAX_FAR)
+// tiled list entries are 16-bit BYTE offsets into the tile (k_step: one decode less per entry) while every tile index << 4 fits 16 bits,
+// plain tile indices in larger tile classes: k_fill writes and k_step / k_pairs read the variant this picks
+inline bool gd_tile_s16(unsigned tile_cap) { return tile_cap < 4096u; }
 #define GD_REC_ID_MASK 0x03ffffffu         // bead id field of rec_mo.y; all ones = no bead
 #define GD_DMAX_STRIDE 32u                  // words between the replicas' displacement maxima: one 128-byte line each
 #define GD_REPAIR_GRID 1024u               // blocks of the repair launch behind every k_fill (one k_step wave each; they leave at once while the

@@ -1419,3 +1419,44 @@ def test_rows_recover_from_a_first_guess_that_is_far_too_small(hip, oracle):
         s.begin_phase()
         s.run(20, info["timestep"], info["temperature"], seed=SEED, flags=g.RUN_UPDATE_SCALES | g.RUN_WALL_DYNAMICS)
     assert np.abs(sh.positions() - so.positions()).max() <= POS_ATOL_20STEP
+
+
+def test_rows_recover_from_a_first_guess_that_is_far_too_small_periodic(hip, oracle):
+    """The same in a periodic box (the repair kernel's periodic variants: the tile staged again is wrapped again).  The 1 kb chain at its
+    default list radius holds 47 neighbours per bead on average and more than 8 for 99.6 % of the beads, so with a guess of 8 entries
+    every one of the 96 k_step waves outgrows its one-chunk row -- fewer waves than the repair launch has blocks: the ordinary queue.
+    At the FIRST build the pool, sized from the guess, is too small for the repaired rows as well: flagged, built again from what the
+    beads needed.  So the state is listed a second time from the same guess (positions set again: no history) into the pool that
+    has its size now: that build's 96 waves are repaired in place and reported (gd_context.row_repairs), and its lists are the ones
+    the forces, the pair set and the run below use -- without a rollback."""
+    n, R = 3000, 2
+    sh, info = wl.chromatin_1kb(hip, n_beads=n, n_replicas=R, n_loops=30, n_glues=60)
+    so, _ = wl.chromatin_1kb(oracle, n_beads=n, n_replicas=R, n_loops=30, n_glues=60)
+    x, L = sh.positions(), float(info["box"])
+    Fo = so.forces()
+    for relisted in (False, True):
+        sh.set_positions(x)
+        sh.set_tuning(kernel_path=2, list_width=8)
+        Fh = sh.forces()
+        c0 = sh.context()
+        print("periodic repair: relisted", relisted, "list_path", c0.list_path, "row_repairs", c0.row_repairs, "rebuilds", c0.rebuilds,
+              "|dF|/|F|", np.abs(Fh - Fo).max() / np.abs(Fo).max(), "entries per bead", c0.list_entries / n)
+        assert c0.list_path == 2
+        assert np.abs(Fh - Fo).max() <= FORCE_RTOL * np.abs(Fo).max()
+    assert c0.row_repairs > 0            # (the build of the last force evaluation is the last one read back)
+    for r in range(R):
+        ph = {tuple(p) for p in sh.search_pairs(1.2, replica=r)}
+        po = {tuple(p) for p in so.search_pairs(1.2, replica=r)}
+        assert len(po) > n
+        for i, j in ph ^ po:
+            d = x[r][i] - x[r][j]
+            d -= L * np.rint(d / L)
+            print("periodic repair: pair", r, i, j, abs(np.linalg.norm(d) - 1.2))
+            assert abs(np.linalg.norm(d) - 1.2) < 1e-6
+    assert c0.list_bytes > 0 and c0.list_entries / n > 15
+    for s in (sh, so):
+        s.begin_phase()
+        s.run(20, info["timestep"], info["temperature"], seed=SEED)
+    print("periodic repair: |dx| after 20 steps", np.abs(sh.positions() - so.positions()).max(), "rollbacks", sh.context().rollbacks)
+    assert sh.context().rollbacks == 0
+    assert np.abs(sh.positions() - so.positions()).max() <= POS_ATOL_20STEP

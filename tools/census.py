@@ -61,9 +61,12 @@ def main():
         labels = {m.group(1): i for i, ln in enumerate(sec) for m in [re.match(r"(\.LBB\d+_\d+):", ln)] if m}
         headers = [i for i, ln in enumerate(sec) if "Loop Header" in ln]
         loops = []
-        for h in headers:
+        for hc in headers:
+            h = hc                # (an inner loop's header comment sits on the lines behind its label: "Parent Loop ..." comes first)
+            while not re.match(r"(\.LBB\d+_\d+):", sec[h]):
+                h -= 1
             lab = re.match(r"(\.LBB\d+_\d+):", sec[h]).group(1)
-            depth = int(re.search(r"Depth=(\d+)", sec[h]).group(1))
+            depth = int(re.search(r"Depth=(\d+)", sec[hc]).group(1))
             last = h
             for i in range(h, len(sec)):
                 m = re.match(r"\s+s_c?branch\w*\s+(\.LBB\d+_\d+)", sec[i])
