@@ -12,6 +12,15 @@ pass over a cooler's pixel table for the reference's 2-signal/src/{compute_inter
         alpha = hs.local_alpha(a)
         total, n, mean = hs.fetch_profile(p)
 
+The compartment analysis of hic_analysis/cool.py (dense cis matrices, observed / expected, leading principal components):
+
+        d = hs.add_dense(weights)                            # before the pass: one float32 (n, n) matrix per chromosome
+        contacts, counts, mean = hs.dense_profile(d, excluded)
+        E = hs.fetch_dense(d, code, DENSE_ENRICHMENT)
+        pcs, variances, axes, iterations = hs.dense_pca(d, code, mask=hs.dense_valid(d)[chrom_code == code], k=3)
+        pcs, variances, axes, iterations = hs.pca_matrix(any_square_matrix, k=3)
+
+``dense_matrices``, ``mean_contact_profile``, ``enrichment``, ``dense_valid`` and ``contact_pca`` are their numpy counterparts.
 ``band_matrix``, ``decay_insulation``, ``local_alpha``, ``distance_profile`` and ``downsample`` are the same rules in numpy for
 users without a GPU; the device path never calls them.  ``chromosome_runs``, ``std_chrom_order``, ``excluded_bins`` and
 ``largest_chromosome`` are the bookkeeping of the three programs.  Band sums are int64; the signals are fp64.
@@ -24,10 +33,13 @@ import numpy as np
 
 from ._binding import GdynError, Handle, load_library
 
-HIC_ABI_VERSION = 1      # GD_HIC_ABI_VERSION of the include/gdyn_hic.h this binding mirrors
+HIC_ABI_VERSION = 2      # GD_HIC_ABI_VERSION of the include/gdyn_hic.h this binding mirrors
 HIC_SYMBOLS = ["gd_hic_abi_version", "gd_hic_create", "gd_hic_destroy", "gd_hic_add_band", "gd_hic_add_distance_profile",
                "gd_hic_accumulate", "gd_hic_decay_insulation", "gd_hic_local_alpha", "gd_hic_fetch_band", "gd_hic_fetch_profile",
-               "gd_hic_fetch_profile_raw", "gd_hic_reset", "gd_hic_clear"]
+               "gd_hic_fetch_profile_raw", "gd_hic_reset", "gd_hic_clear", "gd_hic_add_dense", "gd_hic_dense_profile", "gd_hic_fetch_dense",
+               "gd_hic_dense_valid", "gd_hic_dense_pca", "gd_hic_pca_matrix"]
+HIC_MAX_PCS = 8                              # GD_HIC_MAX_PCS
+DENSE_CONTACT, DENSE_ENRICHMENT = 0, 1       # GD_HIC_DENSE_*
 INTERACTIONS_BLACKLIST = ("MT",)             # compute_interactions.py: BLACKLISTED_CHROMS
 PROFILE_BLACKLIST = ("X", "Y", "MT")         # hic_power_law: BLACKLISTED_CHROMS
 NAMED_CHROM_RANK = {"X": 1, "Y": 2, "MT": 3, "M": 3}
@@ -53,6 +65,12 @@ def load_hic_library(path=None):
     d.gd_hic_fetch_profile_raw.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     d.gd_hic_reset.argtypes = [C.c_void_p]
     d.gd_hic_clear.argtypes = [C.c_void_p]
+    d.gd_hic_add_dense.argtypes = [C.c_void_p, C.c_void_p, P32]
+    d.gd_hic_dense_profile.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    d.gd_hic_fetch_dense.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    d.gd_hic_dense_valid.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    d.gd_hic_dense_pca.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P32]
+    d.gd_hic_pca_matrix.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P32]
     return d
 
 
@@ -200,6 +218,82 @@ def downsample(values, rate=2, window=None):
     return out
 
 
+# ---- the compartment analysis (hic_analysis/cool.py) in numpy
+
+def dense_matrices(bin1, bin2, count, chrom_code, weights=None):
+    """load_contact_matrices: {code: float32 (n, n)} for every run of equal codes.  v = c / (w[i] w[j]) in fp64, rounded to
+    float32 once and added at [li, lj] and [lj, li] (two adds: a diagonal pixel counts twice); a NaN or infinite v is stored."""
+    chrom = np.asarray(chrom_code)
+    i, j, c = _pixels(bin1, bin2, count, len(chrom))
+    runs = chromosome_runs(chrom)
+    beg = np.zeros(len(chrom), np.int64)
+    for b, e in runs:
+        beg[b:e] = b
+    s = (chrom[i] == chrom[j]) & (beg[i] == beg[j])
+    i, j, c = i[s], j[s], c[s]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = (c.astype(np.float64) if weights is None else c / (np.asarray(weights, np.float64)[i] * np.asarray(weights, np.float64)[j])).astype(np.float32)
+    out = {}
+    for b, e in runs:
+        m = np.zeros((e - b, e - b), np.float32)
+        k = (i >= b) & (i < e)
+        np.add.at(m, (i[k] - b, j[k] - b), v[k])
+        np.add.at(m, (j[k] - b, i[k] - b), v[k])
+        out[int(chrom[b])] = m
+    return out
+
+
+def mean_contact_profile(matrices, valid=None):
+    """_compute_mean_contact_profile: (contacts, counts, mean) over the upper diagonals of the matrices with a key in `valid`
+    (None: all); cells equal to 0 and NaN cells are skipped, the float32 cells are added in fp64."""
+    size = max(m.shape[0] for m in matrices.values())
+    contacts, counts = np.zeros(size), np.zeros(size, np.int64)
+    for key, m in matrices.items():
+        if valid is not None and key not in valid:
+            continue
+        n = m.shape[0]
+        i, j = np.triu_indices(n)
+        x = m[i, j]
+        keep = (x != 0) & ~np.isnan(x)
+        contacts[:n] += np.bincount((j - i)[keep], weights=x[keep].astype(np.float64), minlength=n)
+        counts[:n] += np.bincount((j - i)[keep], minlength=n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return contacts, counts, contacts / counts
+
+
+def enrichment(matrix, mean):
+    """_compute_enrichment_matrices for one chromosome: (double)C[i, j] / mean[|i - j|]."""
+    k = np.arange(matrix.shape[0])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return matrix.astype(np.float64) / np.asarray(mean)[np.abs(k[:, None] - k[None, :])]
+
+
+def dense_valid(matrix):
+    """A bin is valid when its row has a finite non-zero cell and no non-finite cell."""
+    finite = np.isfinite(matrix)
+    return (finite & (matrix != 0)).any(axis=1) & finite.all(axis=1)
+
+
+def contact_pca(matrix, mask=None, k=3):
+    """compute_contact_pca for the leading k components with np.linalg.svd: (pcs (n, k), variances (k), axes (k, n)).  The
+    element of an axis of largest magnitude (lowest index on a tie) is positive."""
+    matrix = np.asarray(matrix, np.float64)
+    n = matrix.shape[0]
+    mask = np.any(matrix != 0, axis=1) if mask is None else np.asarray(mask).astype(bool)
+    m = int(mask.sum())
+    if m < 2 or not 1 <= k <= m:
+        raise ValueError(f"{k} components of {m} valid bins")
+    x = matrix[mask][:, mask]
+    xc = x - np.mean(x, axis=0)[None, :]
+    u, s, vh = np.linalg.svd(xc)
+    pcs, axes = np.full((n, k), np.nan), np.full((k, n), np.nan)
+    for j in range(k):
+        sign = 1.0 if vh[j, np.argmax(np.abs(vh[j]))] >= 0 else -1.0
+        axes[j, mask] = sign * vh[j]
+        pcs[mask, j] = sign * u[:, j] * np.sqrt(m - 1)
+    return pcs, s[:k] ** 2, axes
+
+
 # ---- the device
 
 class HicSignals(Handle):
@@ -214,6 +308,8 @@ class HicSignals(Handle):
         if chrom.ndim != 1:
             raise ValueError(f"chrom_code must be one-dimensional, got {chrom.shape}")
         self.n_bins = len(chrom)
+        self._chrom = chrom
+        self._run_of = np.concatenate([[0], np.cumsum(chrom[1:] != chrom[:-1])]) if len(chrom) else np.zeros(0, np.int64)
         self._check(self.dll.gd_hic_create(C.byref(_HicDesc(device, max_pixels_per_launch)), chrom.ctypes.data, self.n_bins, C.byref(self._h)))
 
     def _added(self, rc, target, what):
@@ -237,6 +333,72 @@ class HicSignals(Handle):
         t = C.c_int32(-1)
         rc = self.dll.gd_hic_add_distance_profile(self._h, None if ex is None else ex.ctypes.data, None if w is None else w.ctypes.data, size, C.byref(t))
         return self._added(rc, t, ("profile", size))
+
+    def add_dense(self, weights=None):
+        """One float32 (n, n) matrix per chromosome; weights=None is RAW."""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w is not None and w.shape != (self.n_bins,):
+            raise ValueError(f"weights must have one value per bin ({self.n_bins}), got {w.shape}")
+        t = C.c_int32(-1)
+        return self._added(self.dll.gd_hic_add_dense(self._h, None if w is None else w.ctypes.data, C.byref(t)), t, ("dense", 0))
+
+    def dense_profile(self, target, excluded=None):
+        """(contacts, counts, mean) per distance over the chromosomes whose first bin is not excluded; the mean stays in the
+        target for the enrichment."""
+        ex = None if excluded is None else np.ascontiguousarray(np.asarray(excluded).astype(bool), dtype=np.uint8)
+        if ex is not None and ex.shape != (self.n_bins,):
+            raise ValueError(f"excluded must have one value per bin ({self.n_bins}), got {ex.shape}")
+        size = int(np.bincount(self._run_of).max())
+        contacts, counts, mean = np.empty(size), np.empty(size, np.int64), np.empty(size)
+        self._check(self.dll.gd_hic_dense_profile(self._h, target, None if ex is None else ex.ctypes.data, contacts.ctypes.data, counts.ctypes.data, mean.ctypes.data))
+        return contacts, counts, mean
+
+    def _size_of(self, code):
+        return int((self._chrom == code).sum())
+
+    def fetch_dense(self, target, code, which=DENSE_CONTACT):
+        """The float32 contact matrix or the fp64 enrichment matrix of the chromosome with this code."""
+        n = self._size_of(code)
+        out = np.empty((n, n), np.float64 if which == DENSE_ENRICHMENT else np.float32)
+        self._check(self.dll.gd_hic_fetch_dense(self._h, target, code, which, out.ctypes.data))
+        return out
+
+    def dense_valid(self, target):
+        out = np.empty(self.n_bins, np.uint8)
+        self._check(self.dll.gd_hic_dense_valid(self._h, target, out.ctypes.data))
+        return out.astype(bool)
+
+    @staticmethod
+    def _mask(mask, n):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8)
+        if m.shape != (n,):
+            raise ValueError(f"the mask must have one value per bin of the matrix ({n}), got {m.shape}")
+        return m
+
+    def dense_pca(self, target, code, which=DENSE_ENRICHMENT, mask=None, k=3):
+        """(pcs (n, k), variances (k), axes (k, n), iterations) of a chromosome's matrix; mask=None is the reference's default."""
+        n = self._size_of(code)
+        m = self._mask(mask, n)
+        kk = min(max(k, 1), HIC_MAX_PCS)      # the library reports a k outside its range
+        pcs, var, axes, it = np.empty((n, kk)), np.empty(kk), np.empty((kk, n)), C.c_int32(0)
+        self._check(self.dll.gd_hic_dense_pca(self._h, target, code, which, None if m is None else m.ctypes.data, k, pcs.ctypes.data, var.ctypes.data,
+                                              axes.ctypes.data, C.byref(it)))
+        return pcs, var, axes, it.value
+
+    def pca_matrix(self, matrix, mask=None, k=3):
+        """The same for any square fp64 matrix of the host (it need not be symmetric)."""
+        a = np.ascontiguousarray(matrix, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError(f"a square matrix is required, got {a.shape}")
+        n = a.shape[0]
+        m = self._mask(mask, n)
+        kk = min(max(k, 1), HIC_MAX_PCS)
+        pcs, var, axes, it = np.empty((n, kk)), np.empty(kk), np.empty((kk, n)), C.c_int32(0)
+        self._check(self.dll.gd_hic_pca_matrix(self._h, a.ctypes.data, n, None if m is None else m.ctypes.data, k, pcs.ctypes.data, var.ctypes.data, axes.ctypes.data,
+                                               C.byref(it)))
+        return pcs, var, axes, it.value
 
     def accumulate(self, bin1, bin2, count):
         """The three pixel columns; every target of the handle is updated in one pass."""

@@ -1,8 +1,10 @@
-// gd_hic_cli.hpp -- what gd_compute_interactions, gd_compute_local_alpha, gd_hic_power_law and gd_downsample share: the command
+// gd_hic_cli.hpp -- what gd_compute_interactions, gd_compute_local_alpha, gd_hic_power_law, gd_downsample and gd_hic_compartments share: the command
 // lines of the reference's 2-signal/src/{compute_interactions, compute_local_alpha, downsample} and
 // 5-sim-genome/scripts/hic_power_law, the reads of a multi-resolution cooler file (resolutions/<binsize>/bins/{chrom, start,
 // end, <weights>} and pixels/{bin1_id, bin2_id, count}, the next chunk of pixels on a second thread while the device works) and
-// their text outputs.  The sums and signals are libgdyn's (include/gdyn_hic.h).
+// their text outputs.  The sums and signals are libgdyn's (include/gdyn_hic.h).  gd_hic_compartments has no command in the
+// reference: it is hic_analysis/cool.py (dense cis matrices, observed / expected, leading principal components) as a program with
+// the conventions of its siblings.
 //
 // Deviations from the reference, all documented in DESIGN.md section 7e: sums over repeated pixels are true sums; a chromosome
 // of 1 < n < 2 (W - 1) bins gets signals by the rule instead of an assertion; blacklisted names a file does not have are
@@ -18,7 +20,7 @@
 namespace gd {
 namespace hic {
 
-enum class program { interactions, alpha, power_law, downsample };
+enum class program { interactions, alpha, power_law, downsample, compartments };
 
 inline const char *name_of(program p)
 {
@@ -26,6 +28,7 @@ inline const char *name_of(program p)
     case program::interactions: return "gd_compute_interactions";
     case program::alpha: return "gd_compute_local_alpha";
     case program::power_law: return "gd_hic_power_law";
+    case program::compartments: return "gd_hic_compartments";
     default: return "gd_downsample";
     }
 }
@@ -36,6 +39,7 @@ inline const char *usage(program p)
     case program::interactions: return "usage: gd_compute_interactions -b BINSIZE [-w BANDWIDTH] [-o OUT] [--dry-run] mcoolfile\n";
     case program::alpha: return "usage: gd_compute_local_alpha [-w WIDTH] [-b BINSIZE] [-o OUT] [--dry-run] mcoolfile\n";
     case program::power_law: return "usage: gd_hic_power_law [--binsize BINSIZE] [--normalize NORMALIZE] [--dry-run] mcool\n";
+    case program::compartments: return "usage: gd_hic_compartments [-b BINSIZE] [-n NORM] [-k K] [--exclude X,Y,MT] [--chroms A,B] [--dry-run] coolfile\n";
     default: return "usage: gd_downsample [--rate RATE] [--window WINDOW] [-o OUT] [--dry-run] infile\n";
     }
 }
@@ -46,6 +50,9 @@ struct options {
     long width = 0;                   // -w: the band width of compute_interactions, the width of compute_local_alpha
     std::string normalize = "RAW";
     long rate = 2, window = 0;        // downsample; window 0: the rate
+    long components = 3;              // -k
+    std::string exclude = "X,Y,MT";   // compartments: chromosomes left out of the mean contact profile
+    std::string chroms;               // compartments: the chromosomes to print; empty: all
     std::string output;               // empty: stdout
     bool dry_run = false;
     std::string input;
@@ -75,6 +82,7 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
         }
         bool const known = (cooler_short && (key == "-b" || key == "-w" || key == "-o")) ||
                            (p == program::power_law && (key == "--binsize" || key == "--normalize")) ||
+                           (p == program::compartments && (key == "-b" || key == "-n" || key == "-k" || key == "--exclude" || key == "--chroms")) ||
                            (p == program::downsample && (key == "--rate" || key == "--window" || key == "-o"));
         if (!known) { err = "unrecognized arguments: " + a; return 2; }
         if (!has_value) {
@@ -82,17 +90,20 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
             v = argv[++k];
         }
         if (key == "-o") o.output = v;
-        else if (key == "--normalize") o.normalize = v;
+        else if (key == "--normalize" || key == "-n") o.normalize = v;
+        else if (key == "--exclude") o.exclude = v;
+        else if (key == "--chroms") o.chroms = v;
         else {
             long value = 0;
             if (!cli::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
             if (key == "-b" || key == "--binsize") { o.binsize = value; o.has_binsize = true; }
             else if (key == "-w") o.width = value;
+            else if (key == "-k") o.components = value;
             else if (key == "--rate") o.rate = value;
             else o.window = value;
         }
     }
-    char const *what = p == program::power_law ? "mcool" : p == program::downsample ? "infile" : "mcoolfile";
+    char const *what = p == program::power_law ? "mcool" : p == program::downsample ? "infile" : p == program::compartments ? "coolfile" : "mcoolfile";
     if (p == program::interactions && !o.has_binsize) { err = "the following arguments are required: -b"; return 2; }
     if (pos.empty()) { err = std::string("the following arguments are required: ") + what; return 2; }
     if (pos.size() > 1) { err = "unrecognized arguments: " + pos[1]; return 2; }
@@ -100,7 +111,8 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
     if (p == program::interactions && (o.width < 2 || o.width > GD_HIC_MAX_BAND)) { err = "argument -w: a band of 2 to " + std::to_string(GD_HIC_MAX_BAND) + " columns"; return 2; }
     if (p == program::alpha && (o.width < 1 || o.width >= GD_HIC_MAX_BAND)) { err = "argument -w: a width of 1 to " + std::to_string(GD_HIC_MAX_BAND - 1); return 2; }
     if (p == program::downsample && (o.rate < 1 || o.window < 0)) { err = "argument --rate: must be at least 1, and --window at least 1"; return 2; }
-    if (p != program::downsample && o.binsize < 1) { err = "argument " + std::string(cooler_short ? "-b" : "--binsize") + ": must be at least 1"; return 2; }
+    if (p == program::compartments && (o.components < 1 || o.components > GD_HIC_MAX_PCS)) { err = "argument -k: 1 to " + std::to_string(GD_HIC_MAX_PCS) + " components"; return 2; }
+    if (p != program::downsample && o.binsize < 1) { err = "argument " + std::string(cooler_short || p == program::compartments ? "-b" : "--binsize") + ": must be at least 1"; return 2; }
     return 0;
 }
 
@@ -122,6 +134,16 @@ inline void print_plan(program p, options const &o)
     }
     std::string const res = "/resolutions/" + std::to_string(o.binsize);
     std::printf("binsize\t%ld\n", o.binsize);
+    if (p == program::compartments) {
+        bool const w = o.normalize != "RAW";
+        std::string header = "chrom\tstart\tend";
+        for (long j = 1; j <= o.components; j++) header += "\tPC" + std::to_string(j);
+        std::printf("normalize\t%s\ncomponents\t%ld\nexclude\t%s\nchroms\t%s\n", o.normalize.c_str(), o.components, o.exclude.c_str(), o.chroms.empty() ? "all" : o.chroms.c_str());
+        std::printf("read\t%s\t%s/bins/%s\n", o.input.c_str(), res.c_str(), w ? ("{chrom,start,end," + o.normalize + "}").c_str() : "{chrom,start,end}");
+        std::printf("read\t%s\t%s/pixels/{bin1_id,bin2_id,count}\n", o.input.c_str(), res.c_str());
+        std::printf("write\tstdout\t%s\n", header.c_str());
+        return;
+    }
     if (p == program::interactions) std::printf("band_width\t%ld\n", o.width);
     if (p == program::alpha) std::printf("width\t%ld\n", o.width);
     if (p == program::power_law) std::printf("normalize\t%s\n", o.normalize.c_str());
@@ -464,6 +486,91 @@ inline void run_power_law(options const &o)
     dev.report("gd_hic_power_law");
 }
 
+// ---- compartments: dense cis matrices, observed / expected, the leading principal components of every requested chromosome
+
+inline std::vector<std::string> split_commas(std::string const &s)
+{
+    std::vector<std::string> out;
+    for (std::size_t at = 0; at <= s.size();) {
+        auto const next = std::min(s.find(',', at), s.size());
+        if (next > at) out.push_back(s.substr(at, next - at));
+        at = next + 1;
+    }
+    return out;
+}
+
+inline void run_compartments(options const &o)
+{
+    cli::stopwatch sw;
+    cooler c(o.input, o.binsize);
+    bin_table const bins = c.read_bins(true);
+    std::size_t const n = bins.chrom.size();
+    auto const runs = runs_by_code(bins, o.input);
+    bool const weighted = o.normalize != "RAW";
+    std::vector<double> weights;
+    if (weighted) {
+        weights = c.read_doubles("bins/" + o.normalize);
+        h5::check(weights.size() == n, o.input + ": bins/" + o.normalize + " differs from bins/chrom in length");
+    }
+    auto listed = [](std::vector<std::string> const &list, std::string const &name) {
+        for (auto const &l : list)
+            if (strip_chr(l) == strip_chr(name)) return true;
+        return false;
+    };
+    auto const exclude = split_commas(o.exclude), wanted = split_commas(o.chroms);
+    for (auto const &w : wanted)
+        if (!listed(bins.names, w)) throw std::runtime_error(o.input + ": no chromosome '" + w + "'");
+    std::vector<uint8_t> excluded(n, 0);
+    for (std::size_t m = 0; m < bins.names.size(); m++) {
+        auto const it = runs.find(bins.values[m]);
+        if (it == runs.end() || !listed(exclude, bins.names[m])) continue;
+        std::fill(excluded.begin() + (long)it->second.first, excluded.begin() + (long)it->second.second, 1);
+    }
+    sw.read += sw.lap();
+    device dev;
+    dev.open(bins);
+    int32_t dense = -1;
+    cli::check(gd_hic_add_dense(dev.h, weighted ? weights.data() : nullptr, &dense));
+    sw.compute += sw.lap();
+    stream_pixels(c, dev, sw);
+    cli::check(gd_hic_dense_profile(dev.h, dense, excluded.data(), nullptr, nullptr, nullptr));
+    std::vector<uint8_t> valid(n);
+    cli::check(gd_hic_dense_valid(dev.h, dense, valid.data()));
+    uint32_t const k = (uint32_t)o.components;
+    struct result { std::size_t member; std::vector<double> pcs; };
+    std::vector<result> results;
+    for (std::size_t m = 0; m < bins.names.size(); m++) {
+        auto const it = runs.find(bins.values[m]);
+        if (it == runs.end() || (!wanted.empty() && !listed(wanted, bins.names[m]))) continue;
+        std::size_t const beg = it->second.first, size = it->second.second - beg;
+        result r{m, std::vector<double>(size * k)};
+        std::vector<double> variances(k);
+        int32_t iterations = 0;
+        if (gd_hic_dense_pca(dev.h, dense, (int32_t)bins.values[m], GD_HIC_DENSE_ENRICHMENT, valid.data() + beg, k, r.pcs.data(), variances.data(), nullptr, &iterations))
+            throw std::runtime_error("chromosome " + bins.names[m] + ": " + gd_last_error());
+        std::string line = "# " + bins.names[m] + " variances";
+        for (double v : variances) line += " " + fmt_g(v);
+        std::printf("%s iterations %d\n", line.c_str(), iterations);
+        results.push_back(std::move(r));
+    }
+    sw.compute += sw.lap();
+    std::string header = "chrom\tstart\tend";
+    for (uint32_t j = 1; j <= k; j++) header += "\tPC" + std::to_string(j);
+    std::puts(header.c_str());
+    for (auto const &r : results) {
+        auto const &run = runs.find(bins.values[r.member])->second;
+        for (std::size_t b = run.first; b < run.second; b++) {
+            std::string line = bins.names[r.member] + "\t" + std::to_string(bins.start[b]) + "\t" + std::to_string(bins.end[b]);
+            for (uint32_t j = 0; j < k; j++) line += "\t" + fmt_g(r.pcs[(b - run.first) * k + j]);
+            std::puts(line.c_str());
+        }
+    }
+    std::fflush(stdout);
+    sw.write += sw.lap();
+    sw.report("gd_hic_compartments");
+    dev.report("gd_hic_compartments");
+}
+
 // ---- downsample: host only
 
 inline std::vector<std::string> split_tabs(std::string const &s)
@@ -558,6 +665,7 @@ inline int main(program p, int argc, char **argv)
         if (p == program::interactions) run_interactions(o);
         else if (p == program::alpha) run_alpha(o);
         else if (p == program::power_law) run_power_law(o);
+        else if (p == program::compartments) run_compartments(o);
         else run_downsample(o);
     } catch (std::exception const &e) {
         std::fprintf(stderr, "error: %s\n", e.what());
