@@ -21,6 +21,7 @@
 #include "gdyn_types.h"
 #include "gdyn_once.hpp"
 #include "gdyn_policy.hpp"
+#include "gdyn_live.hpp"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
 #endif
@@ -1433,6 +1434,38 @@ extern "C" int gd_contacts_clear(gd_system *s, uint32_t r)
     HIPCHK(hipMemsetAsync(s->ct_distinct.p + r0, 0, nr * sizeof(unsigned), s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     for (uint32_t k = r0; k < r0 + nr; k++) s->ct_distinct_h[k] = 0;
+    return GD_OK;
+}
+
+// ------------------------------------------------------------- live seams (gdyn_live.hpp)
+// What the live bridge reads of a handle.  Neither call needs prepare(): the tables and the positions are what gd_contacts_fetch
+// and gd_get_positions_f32 read, which do not prepare either.  Both end with the stream idle, so no chunk of a gd_run and no
+// update is in flight when an analysis stream reads the buffers.
+gd_live_shape gd_live_shape_of(const gd_system *s)
+{
+    gd_live_shape v{};
+    v.device = s->device; v.N = s->N; v.R = s->R;
+    v.periodic = s->box_kind == GD_BOX_PERIODIC; v.has_wall = s->has_wall;
+    memcpy(v.box, s->box, sizeof v.box);
+    return v;
+}
+
+int gd_live_contact_tab(gd_system *s, ContactTab *tab, const unsigned **occupancy)
+{
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *tab = contact_tab(s);
+    *occupancy = s->ct_cap ? s->ct_distinct_h.data() : nullptr;
+    return GD_OK;
+}
+
+int gd_live_positions(gd_system *s, int quantize, const float **xyz)
+{
+    HIPCHK(hipSetDevice(s->device));
+    gd_launch_gather_xyz(s->pos[s->pcur].p, s->slot_of.p, (float *)s->fout.p, s->N, s->Np, s->R, quantize, s->stream);      // as fetch_xyz
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s->stream));
+    *xyz = (const float *)s->fout.p;
     return GD_OK;
 }
 

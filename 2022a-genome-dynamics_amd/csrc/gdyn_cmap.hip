@@ -16,6 +16,8 @@
 //                                 flushed with one global atomic per non-zero bin; profiles beyond that budget use global
 //                                 atomics.
 //                      Integer adds commute: no result depends on the batch size, the grid or the arrival order.
+//   k_cmap_accumulate_tab  the same pass (accumulate_rows) with the slots of a stepper's contact tables as the rows, read in
+//                      place (gd_live_contacts, include/gdyn_live.h)
 //   k_cmap_symmetrize, k_cmap_max, k_cmap_diagonal   gd_cmap_finish of a region target
 //   k_cmap_symmetric_rows                            A + A^T of a binned target for a block of rows, through an LDS tile
 // Every index that addresses memory is checked against its array in the kernel: rows are data.
@@ -30,6 +32,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_cmap.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_live.hpp"
 
 using namespace gd;
 
@@ -85,14 +88,110 @@ __device__ inline int carry_between_lanes(unsigned long long head, unsigned long
     return link ? before : 0;
 }
 
+// four rows of one lane through every target.  Every lane of the wave calls it (carry_between_lanes); a row that is not
+// live is all zeros.  hist: the block's LDS histogram of the profile targets.
+__device__ __forceinline__ void accumulate_rows(launch_args const &a, int *hist, const unsigned (&ri)[kPerLane], const unsigned (&rj)[kPerLane],
+                                                const unsigned (&rv)[kPerLane], const bool (&live)[kPerLane], unsigned &requested, unsigned &issued)
+{
+    for (int ti = 0; ti < a.n_targets; ti++) {
+        target_desc const &t = a.t[ti];
+        if (t.kind == kRegion) {
+#pragma unroll
+            for (int k = 0; k < kPerLane; k++)
+                if (live[k] && ri[k] >= t.beg && ri[k] < t.end && rj[k] >= t.beg && rj[k] < t.end)
+                    atomicAdd(t.acc + (size_t)(ri[k] - t.beg) * t.size + (rj[k] - t.beg), (int)rv[k]);
+        } else if (t.kind == kBinned) {
+            const int *map = static_cast<const int *>(t.aux);
+            unsigned long long key[kPerLane];
+            int val[kPerLane];
+            bool dead[kPerLane];
+#pragma unroll
+            for (int k = 0; k < kPerLane; k++) {
+                bool const ok = live[k] && ri[k] < t.n && rj[k] < t.n;
+                unsigned const bi = ok ? (unsigned)map[ri[k]] : 0u, bj = ok ? (unsigned)map[rj[k]] : 0u;
+                bool const in = ok && bi < t.size && bj < t.size;
+                key[k] = in ? (unsigned long long)bi * t.size + bj : ~0ull;
+                val[k] = in ? (int)rv[k] : 0;
+                dead[k] = false;
+                requested += in;
+            }
+#pragma unroll
+            for (int k = 0; k + 1 < kPerLane; k++)      // a run's sum ends up in its last row
+                if (key[k] == key[k + 1]) {
+                    val[k + 1] += val[k];
+                    dead[k] = true;
+                }
+            int const first = dead[0] ? (dead[1] ? (dead[2] ? 3 : 2) : 1) : 0;      // where the lane's first run ends
+            bool forward;
+            int const carry = carry_between_lanes(key[0], key[kPerLane - 1], first == kPerLane - 1, val[kPerLane - 1], &forward);
+#pragma unroll
+            for (int k = 0; k < kPerLane; k++) {
+                if (dead[k] || key[k] == ~0ull || (k == kPerLane - 1 && forward)) continue;
+                atomicAdd(t.acc + key[k], val[k] + (k == first ? carry : 0));
+                issued++;
+            }
+        } else if (t.kind == kNucleolus) {
+            const unsigned char *nuc = static_cast<const unsigned char *>(t.aux);
+#pragma unroll
+            for (int k = 0; k < kPerLane; k++) {
+                if (!live[k]) continue;
+                bool const i_in = ri[k] >= t.beg && ri[k] < t.end, j_in = rj[k] >= t.beg && rj[k] < t.end;
+                bool const i_nuc = ri[k] < t.n && nuc[ri[k]], j_nuc = rj[k] < t.n && nuc[rj[k]];
+                if (i_in && j_nuc) {
+                    if (t.lds != kNoLds) atomicAdd(&hist[t.lds + (ri[k] - t.beg)], (int)rv[k]);
+                    else atomicAdd(t.acc + (ri[k] - t.beg), (int)rv[k]);
+                }
+                if (j_in && i_nuc) {
+                    if (t.lds != kNoLds) atomicAdd(&hist[t.lds + (rj[k] - t.beg)], (int)rv[k]);
+                    else atomicAdd(t.acc + (rj[k] - t.beg), (int)rv[k]);
+                }
+            }
+        } else {
+            const int *chain = static_cast<const int *>(t.aux);
+#pragma unroll
+            for (int k = 0; k < kPerLane; k++) {
+                if (!live[k] || ri[k] >= t.n || rj[k] >= t.n) continue;
+                int const ci = chain[ri[k]], cj = chain[rj[k]];
+                unsigned const d = ri[k] > rj[k] ? ri[k] - rj[k] : rj[k] - ri[k];
+                if (ci != cj || ci == -1 || d >= t.size) continue;      // d < size was checked when the target was added
+                if (t.lds != kNoLds) atomicAdd(&hist[t.lds + d], (int)rv[k]);
+                else atomicAdd(t.acc + d, (int)rv[k]);
+            }
+        }
+    }
+}
+
+// what a block does before and after its rows: zeroes the LDS histogram and the block's counters / flushes them
+__device__ __forceinline__ void block_begin(launch_args const &a, int *hist, unsigned *stat)
+{
+    for (unsigned b = threadIdx.x; b < a.lds_bins; b += kBlock) hist[b] = 0;
+    if (threadIdx.x < 2) stat[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void block_end(launch_args const &a, const int *hist, unsigned *stat, unsigned requested, unsigned issued,
+                                          unsigned long long *counters)
+{
+    if (requested) atomicAdd(&stat[0], requested);
+    if (issued) atomicAdd(&stat[1], issued);
+    __syncthreads();
+    for (int ti = 0; ti < a.n_targets; ti++) {
+        target_desc const &t = a.t[ti];
+        if (t.kind < kNucleolus || t.lds == kNoLds) continue;
+        for (unsigned b = threadIdx.x; b < t.size; b += kBlock) {
+            int const v = hist[t.lds + b];
+            if (v) atomicAdd(t.acc + b, v);
+        }
+    }
+    if (threadIdx.x < 2 && stat[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+}
+
 __global__ void __launch_bounds__(kBlock) k_cmap_accumulate(const uint4 *__restrict__ rows, unsigned n_rows, unsigned groups, launch_args a,
                                                            unsigned long long *__restrict__ counters)
 {
     extern __shared__ int hist[];
     __shared__ unsigned stat[2];
-    for (unsigned b = threadIdx.x; b < a.lds_bins; b += kBlock) hist[b] = 0;
-    if (threadIdx.x < 2) stat[threadIdx.x] = 0;
-    __syncthreads();
+    block_begin(a, hist, stat);
     unsigned const stride = gridDim.x * kBlock;
     unsigned const padded_groups = (groups + kBlock - 1) / kBlock * kBlock;
     unsigned requested = 0, issued = 0;
@@ -112,85 +211,46 @@ __global__ void __launch_bounds__(kBlock) k_cmap_accumulate(const uint4 *__restr
             live[k] = g < groups && g * kPerLane + k < n_rows;
             if (!live[k]) ri[k] = rj[k] = rv[k] = 0;
         }
-        for (int ti = 0; ti < a.n_targets; ti++) {
-            target_desc const &t = a.t[ti];
-            if (t.kind == kRegion) {
-#pragma unroll
-                for (int k = 0; k < kPerLane; k++)
-                    if (live[k] && ri[k] >= t.beg && ri[k] < t.end && rj[k] >= t.beg && rj[k] < t.end)
-                        atomicAdd(t.acc + (size_t)(ri[k] - t.beg) * t.size + (rj[k] - t.beg), (int)rv[k]);
-            } else if (t.kind == kBinned) {
-                const int *map = static_cast<const int *>(t.aux);
-                unsigned long long key[kPerLane];
-                int val[kPerLane];
-                bool dead[kPerLane];
-#pragma unroll
-                for (int k = 0; k < kPerLane; k++) {
-                    bool const ok = live[k] && ri[k] < t.n && rj[k] < t.n;
-                    unsigned const bi = ok ? (unsigned)map[ri[k]] : 0u, bj = ok ? (unsigned)map[rj[k]] : 0u;
-                    bool const in = ok && bi < t.size && bj < t.size;
-                    key[k] = in ? (unsigned long long)bi * t.size + bj : ~0ull;
-                    val[k] = in ? (int)rv[k] : 0;
-                    dead[k] = false;
-                    requested += in;
-                }
-#pragma unroll
-                for (int k = 0; k + 1 < kPerLane; k++)      // a run's sum ends up in its last row
-                    if (key[k] == key[k + 1]) {
-                        val[k + 1] += val[k];
-                        dead[k] = true;
-                    }
-                int const first = dead[0] ? (dead[1] ? (dead[2] ? 3 : 2) : 1) : 0;      // where the lane's first run ends
-                bool forward;
-                int const carry = carry_between_lanes(key[0], key[kPerLane - 1], first == kPerLane - 1, val[kPerLane - 1], &forward);
-#pragma unroll
-                for (int k = 0; k < kPerLane; k++) {
-                    if (dead[k] || key[k] == ~0ull || (k == kPerLane - 1 && forward)) continue;
-                    atomicAdd(t.acc + key[k], val[k] + (k == first ? carry : 0));
-                    issued++;
-                }
-            } else if (t.kind == kNucleolus) {
-                const unsigned char *nuc = static_cast<const unsigned char *>(t.aux);
-#pragma unroll
-                for (int k = 0; k < kPerLane; k++) {
-                    if (!live[k]) continue;
-                    bool const i_in = ri[k] >= t.beg && ri[k] < t.end, j_in = rj[k] >= t.beg && rj[k] < t.end;
-                    bool const i_nuc = ri[k] < t.n && nuc[ri[k]], j_nuc = rj[k] < t.n && nuc[rj[k]];
-                    if (i_in && j_nuc) {
-                        if (t.lds != kNoLds) atomicAdd(&hist[t.lds + (ri[k] - t.beg)], (int)rv[k]);
-                        else atomicAdd(t.acc + (ri[k] - t.beg), (int)rv[k]);
-                    }
-                    if (j_in && i_nuc) {
-                        if (t.lds != kNoLds) atomicAdd(&hist[t.lds + (rj[k] - t.beg)], (int)rv[k]);
-                        else atomicAdd(t.acc + (rj[k] - t.beg), (int)rv[k]);
-                    }
-                }
-            } else {
-                const int *chain = static_cast<const int *>(t.aux);
-#pragma unroll
-                for (int k = 0; k < kPerLane; k++) {
-                    if (!live[k] || ri[k] >= t.n || rj[k] >= t.n) continue;
-                    int const ci = chain[ri[k]], cj = chain[rj[k]];
-                    unsigned const d = ri[k] > rj[k] ? ri[k] - rj[k] : rj[k] - ri[k];
-                    if (ci != cj || ci == -1 || d >= t.size) continue;      // d < size was checked when the target was added
-                    if (t.lds != kNoLds) atomicAdd(&hist[t.lds + d], (int)rv[k]);
-                    else atomicAdd(t.acc + d, (int)rv[k]);
-                }
-            }
-        }
+        accumulate_rows(a, hist, ri, rj, rv, live, requested, issued);
     }
-    if (requested) atomicAdd(&stat[0], requested);
-    if (issued) atomicAdd(&stat[1], issued);
-    __syncthreads();
-    for (int ti = 0; ti < a.n_targets; ti++) {
-        target_desc const &t = a.t[ti];
-        if (t.kind < kNucleolus || t.lds == kNoLds) continue;
-        for (unsigned b = threadIdx.x; b < t.size; b += kBlock) {
-            int const v = hist[t.lds + b];
-            if (v) atomicAdd(t.acc + b, v);
+    block_end(a, hist, stat, requested, issued, counters);
+}
+
+// The same pass over the words of the stepper's contact tables (gdyn_types.h, ContactTab) in place: a lane takes four consecutive
+// slots of replica r0 + blockIdx.y (the capacity is a power of two >= 1024 and the tables are 16-byte aligned: two 16-byte
+// loads), an empty slot is a row that is not live.  Slots come in hash order: equal binned keys seldom meet, and where they do
+// carry_between_lanes combines them as it does for sorted rows (it compares neighbours only and never assumes an order).
+__global__ void __launch_bounds__(kBlock) k_cmap_accumulate_tab(const unsigned long long *__restrict__ words, unsigned long long cap, unsigned jbits,
+                                                               unsigned r0, launch_args a, unsigned long long *__restrict__ counters)
+{
+    extern __shared__ int hist[];
+    __shared__ unsigned stat[2];
+    block_begin(a, hist, stat);
+    const ulonglong2 *slots = reinterpret_cast<const ulonglong2 *>(words + (size_t)(r0 + blockIdx.y) * cap);
+    unsigned long long const groups = cap / kPerLane, stride = (unsigned long long)gridDim.x * kBlock;
+    unsigned const cbits = 64u - 2u * jbits;
+    unsigned long long const jmask = (1ull << jbits) - 1ull, cmask = (1ull << cbits) - 1ull;
+    unsigned requested = 0, issued = 0;
+    for (unsigned long long base = (unsigned long long)blockIdx.x * kBlock; base < groups; base += stride) {      // uniform over the block
+        unsigned long long const g = base + threadIdx.x;
+        unsigned long long w[kPerLane] = {GD_CT_EMPTY, GD_CT_EMPTY, GD_CT_EMPTY, GD_CT_EMPTY};
+        if (g < groups) {
+            ulonglong2 const p = slots[2 * g], q = slots[2 * g + 1];
+            w[0] = p.x; w[1] = p.y; w[2] = q.x; w[3] = q.y;
         }
+        unsigned ri[kPerLane], rj[kPerLane], rv[kPerLane];
+        bool live[kPerLane];
+#pragma unroll
+        for (int k = 0; k < kPerLane; k++) {
+            live[k] = w[k] != GD_CT_EMPTY;
+            unsigned long long const key = w[k] >> cbits;
+            ri[k] = live[k] ? (unsigned)(key >> jbits) : 0u;
+            rj[k] = live[k] ? (unsigned)(key & jmask) : 0u;
+            rv[k] = live[k] ? (unsigned)(w[k] & cmask) : 0u;
+        }
+        accumulate_rows(a, hist, ri, rj, rv, live, requested, issued);
     }
-    if (threadIdx.x < 2 && stat[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)stat[threadIdx.x]);
+    block_end(a, hist, stat, requested, issued, counters);
 }
 
 // M <- M + M^T: the thread of (r, c), c >= r, writes both cells
@@ -501,3 +561,28 @@ int gd_cmap_counters(gd_cmap *h, uint64_t out[2])
 }
 
 }  // extern "C"
+
+// ---- the live seam (gdyn_live.hpp)
+
+int gd_cmap_device(const gd_cmap *h) { return h->device; }
+
+int gd_cmap_accumulate_tab(gd_cmap *h, const char *who, const ContactTab &tab, uint32_t r0, uint32_t nr, uint64_t rows)
+{
+    if (rows == 0 || nr == 0) return GD_OK;                  // as gd_cmap_accumulate: no rows, nothing asked of the handle
+    if (h->targets.empty()) return fail(GD_ESTATE, "%s: the handle has no target", who);
+    HIPCHK(hipSetDevice(h->device));
+    launch_args a{};
+    a.n_targets = (int)h->targets.size();
+    a.lds_bins = h->lds_bins;
+    for (int k = 0; k < a.n_targets; k++) a.t[k] = h->targets[(size_t)k].d;
+    // the kernel's loop is uniform over a block only for whole blocks of lanes (the tables' capacity is a power of two >= 1024)
+    if (tab.cap == 0 || tab.cap % (kPerLane * kBlock)) return fail(GD_ESTATE, "%s: a table of %llu slots", who, tab.cap);
+    unsigned const blocks = (unsigned)std::min<unsigned long long>(tab.cap / kPerLane / kBlock, kMaxBlocks);
+    for (uint32_t y0 = 0; y0 < nr; y0 += 65535u) {           // the replica is the grid's y
+        hipLaunchKernelGGL(k_cmap_accumulate_tab, dim3(blocks, std::min(nr - y0, 65535u)), dim3(kBlock), h->lds_bins * sizeof(int), h->stream,
+                           tab.words, tab.cap, tab.jbits, r0 + y0, a, h->counters.p);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return GD_OK;
+}

@@ -22,6 +22,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_lamina.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_live.hpp"
 
 using namespace gd;
 
@@ -146,6 +147,7 @@ size_t padded(size_t count) { return (count + kPerLane - 1) / kPerLane * kPerLan
 struct gd_lamina : gd::handle {
     unsigned max_frames = 0;
     dbuf<char> in, out;                  // one batch
+    dbuf<char> flags;                    // the contacts of a batch whose distances were computed on the device (in h->out)
     dbuf<double> inv;
     dbuf<float> sum;                     // (frames, n_points) of the contacts calls, padded
     bool have_shape = false;
@@ -158,6 +160,148 @@ struct gd_lamina : gd::handle {
         return (unsigned)std::min<size_t>(std::min(want, std::max<size_t>(1, kMaxElements / n)), total_frames);
     }
 };
+
+namespace {
+
+// pow(s, -2) of every semiaxis (numpy's semiaxes ** -2), after the check of gd_lamina_distances
+int inverse_squares(const char *who, const double *semiaxes, uint32_t frames, std::vector<double> &inv)
+{
+    if (frames && !semiaxes) return fail(GD_EINVAL, "%s: NULL semiaxes", who);
+    inv.resize((size_t)frames * 3);
+    for (size_t k = 0; k < inv.size(); k++) {
+        if (!(semiaxes[k] > 0.0) || !std::isfinite(semiaxes[k]))
+            return fail(GD_EINVAL, "%s: semiaxis %zu of frame %zu = %g is not positive and finite", who, k % 3, k / 3, semiaxes[k]);
+        inv[k] = std::pow(semiaxes[k], -2.0);
+    }
+    return GD_OK;
+}
+
+// One batch of distances, enqueued: b frames at src (host memory, or the handle's device: kind) are copied into h->in, whose
+// pad and alignment the kernel relies on, their inverse squared semiaxes into h->inv, and the distances are left in h->out.
+int distance_batch(gd_lamina *h, const void *src, hipMemcpyKind kind, int is_f64, unsigned n_points, unsigned b, const double *inv, int out_is_f64)
+{
+    hipStream_t st = h->stream;
+    size_t const count = (size_t)b * n_points, in_elem = is_f64 ? 8 : 4;
+    unsigned const groups = (unsigned)(padded(count) / kPerLane);
+    HIPCHK(hipMemcpyAsync(h->in.p, src, count * 3 * in_elem, kind, st));
+    HIPCHK(hipMemcpyAsync(h->inv.p, inv, (size_t)b * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    dim3 const grid(blocks_for(groups, kBlock)), block(kBlock);
+    if (is_f64 && out_is_f64)
+        hipLaunchKernelGGL((k_lamina_distance<double, double>), grid, block, 0, st, (const double *)h->in.p, n_points, b, groups, h->inv.p,
+                           (double *)h->out.p);
+    else if (is_f64)
+        hipLaunchKernelGGL((k_lamina_distance<double, float>), grid, block, 0, st, (const double *)h->in.p, n_points, b, groups, h->inv.p,
+                           (float *)h->out.p);
+    else if (out_is_f64)
+        hipLaunchKernelGGL((k_lamina_distance<float, double>), grid, block, 0, st, (const float *)h->in.p, n_points, b, groups, h->inv.p,
+                           (double *)h->out.p);
+    else
+        hipLaunchKernelGGL((k_lamina_distance<float, float>), grid, block, 0, st, (const float *)h->in.p, n_points, b, groups, h->inv.p,
+                           (float *)h->out.p);
+    HIPCHK(hipGetLastError());
+    return GD_OK;
+}
+
+// gd_lamina_distances (`who`) of frames in host memory or on the handle's device (kind); out_optional: out may be NULL, and
+// then nothing is copied back
+int distances(gd_lamina *h, const char *who, const void *xyz, hipMemcpyKind kind, int is_f64, uint32_t frames, uint32_t n_points,
+              const double *semiaxes, void *out, int out_is_f64, bool out_optional)
+{
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (frames && !semiaxes) return fail(GD_EINVAL, "%s: NULL semiaxes", who);
+    if (n_points > (1u << 28)) return fail(GD_EINVAL, "%s: %u points exceed 2^28", who, n_points);
+    std::vector<double> inv;
+    if (int rc = inverse_squares(who, semiaxes, frames, inv)) return rc;
+    if (frames == 0 || n_points == 0) return GD_OK;
+    if (!xyz || (!out && !out_optional)) return fail(GD_EINVAL, "%s: NULL argument", who);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    unsigned const B = h->batch_frames(frames, n_points);
+    size_t const in_elem = is_f64 ? 8 : 4, out_elem = out_is_f64 ? 8 : 4;
+    HIPCHK(h->in.ensure(padded((size_t)B * n_points) * 3 * in_elem));
+    HIPCHK(h->out.ensure(padded((size_t)B * n_points) * out_elem));
+    HIPCHK(h->inv.ensure((size_t)B * 3));
+    for (unsigned f0 = 0; f0 < frames; f0 += B) {
+        unsigned const b = std::min(B, frames - f0);
+        size_t const count = (size_t)b * n_points;
+        if (int rc = distance_batch(h, static_cast<const char *>(xyz) + (size_t)f0 * n_points * 3 * in_elem, kind, is_f64, n_points, b,
+                                    inv.data() + (size_t)f0 * 3, out_is_f64))
+            return rc;
+        if (out) HIPCHK(hipMemcpyAsync(static_cast<char *>(out) + (size_t)f0 * n_points * out_elem, h->out.p, count * out_elem, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return GD_OK;
+}
+
+// gd_lamina_contacts (`who`).  The float32 distances of a batch come from host memory (distances), or are computed on the
+// device from float32 frames that lie there (xyz_dev, semiaxes) and never leave it.  out_optional: contacts_out may be NULL.
+int contacts(gd_lamina *h, const char *who, const float *distances, const float *xyz_dev, const double *semiaxes, uint32_t frames,
+             uint32_t n_points, double contact_distance, uint8_t *contacts_out, bool out_optional)
+{
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    std::vector<double> inv;
+    if (xyz_dev) {      // the checks of the distances call that the host-fed sequence makes first
+        if (n_points > (1u << 28)) return fail(GD_EINVAL, "%s: %u points exceed 2^28", who, n_points);
+        if (int rc = inverse_squares(who, semiaxes, frames, inv)) return rc;
+    }
+    if (std::isnan(contact_distance)) return fail(GD_EINVAL, "%s: the contact distance is NaN", who);
+    if (n_points > (1u << 28)) return fail(GD_EINVAL, "%s: %u points exceed 2^28", who, n_points);
+    if (h->have_shape && (frames != h->frames || n_points != h->n_points))
+        return fail(GD_EINVAL, "%s: a (%u, %u) history after (%u, %u) ones; call gd_lamina_reset between shapes", who, frames, n_points,
+                    h->frames, h->n_points);
+    size_t const total = (size_t)frames * n_points;
+    if (total && ((!distances && !xyz_dev) || (!contacts_out && !out_optional))) return fail(GD_EINVAL, "%s: NULL argument", who);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    if (!h->have_shape) {
+        HIPCHK(h->sum.ensure(padded(total) + kPerLane));
+        HIPCHK(hipMemsetAsync(h->sum.p, 0, (padded(total) + kPerLane) * sizeof(float), st));
+        HIPCHK(hipStreamSynchronize(st));
+        h->frames = frames;
+        h->n_points = n_points;
+        h->calls = 0;
+        h->have_shape = true;
+    }
+    if (total) {
+        unsigned const B = h->batch_frames(frames, n_points);
+        size_t const lanes = padded((size_t)B * n_points);
+        HIPCHK(h->in.ensure(lanes * (xyz_dev ? 3 : 1) * sizeof(float)));
+        HIPCHK(h->out.ensure(lanes * (xyz_dev ? sizeof(float) : 1)));
+        if (xyz_dev) {
+            HIPCHK(h->inv.ensure((size_t)B * 3));
+            HIPCHK(h->flags.ensure(lanes));
+        }
+        for (unsigned f0 = 0; f0 < frames; f0 += B) {
+            unsigned const b = std::min(B, frames - f0);
+            size_t const count = (size_t)b * n_points, offset = (size_t)f0 * n_points;
+            unsigned const groups = (unsigned)(padded(count) / kPerLane);
+            const float *dist = (const float *)h->in.p;
+            uchar4 *flags = (uchar4 *)h->out.p;
+            if (xyz_dev) {      // h->in: the frames, h->out: their distances, h->flags: the contacts
+                if (int rc = distance_batch(h, xyz_dev + offset * 3, hipMemcpyDeviceToDevice, 0, n_points, b, inv.data() + (size_t)f0 * 3, 0)) return rc;
+                dist = (const float *)h->out.p;
+                flags = (uchar4 *)h->flags.p;
+            } else
+                HIPCHK(hipMemcpyAsync(h->in.p, distances + offset, count * sizeof(float), hipMemcpyHostToDevice, st));
+            dim3 const grid(blocks_for(groups, kBlock)), block(kBlock);
+            // the vector form may touch the sum's pad behind the last batch only: an earlier batch that is not a whole number
+            // of lanes would add its pad lanes into the next batch's elements
+            if (offset % kPerLane == 0 && (count % kPerLane == 0 || f0 + b == frames))
+                hipLaunchKernelGGL((k_lamina_contact<true>), grid, block, 0, st, dist, groups, (unsigned)count, contact_distance, flags,
+                                   h->sum.p + offset);
+            else
+                hipLaunchKernelGGL((k_lamina_contact<false>), grid, block, 0, st, dist, groups, (unsigned)count, contact_distance, flags,
+                                   h->sum.p + offset);
+            HIPCHK(hipGetLastError());
+            if (contacts_out) HIPCHK(hipMemcpyAsync(contacts_out + offset, flags, count, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
+    h->calls++;
+    return GD_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -175,98 +319,13 @@ int gd_lamina_destroy(gd_lamina *h) { return gd::close(h); }
 int gd_lamina_distances(gd_lamina *h, const void *xyz, int is_f64, uint32_t frames, uint32_t n_points, const double *semiaxes, void *out,
                         int out_is_f64)
 {
-    if (!h) return fail(GD_EINVAL, "gd_lamina_distances: NULL handle");
-    if (frames && !semiaxes) return fail(GD_EINVAL, "gd_lamina_distances: NULL semiaxes");
-    if (n_points > (1u << 28)) return fail(GD_EINVAL, "gd_lamina_distances: %u points exceed 2^28", n_points);
-    std::vector<double> inv((size_t)frames * 3);
-    for (size_t k = 0; k < inv.size(); k++) {
-        if (!(semiaxes[k] > 0.0) || !std::isfinite(semiaxes[k]))
-            return fail(GD_EINVAL, "gd_lamina_distances: semiaxis %zu of frame %zu = %g is not positive and finite", k % 3, k / 3, semiaxes[k]);
-        inv[k] = std::pow(semiaxes[k], -2.0);      // numpy's semiaxes ** -2
-    }
-    if (frames == 0 || n_points == 0) return GD_OK;
-    if (!xyz || !out) return fail(GD_EINVAL, "gd_lamina_distances: NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    unsigned const B = h->batch_frames(frames, n_points);
-    size_t const in_elem = is_f64 ? 8 : 4, out_elem = out_is_f64 ? 8 : 4;
-    HIPCHK(h->in.ensure(padded((size_t)B * n_points) * 3 * in_elem));
-    HIPCHK(h->out.ensure(padded((size_t)B * n_points) * out_elem));
-    HIPCHK(h->inv.ensure((size_t)B * 3));
-    for (unsigned f0 = 0; f0 < frames; f0 += B) {
-        unsigned const b = std::min(B, frames - f0);
-        size_t const count = (size_t)b * n_points;
-        unsigned const groups = (unsigned)(padded(count) / kPerLane);
-        HIPCHK(hipMemcpyAsync(h->in.p, static_cast<const char *>(xyz) + (size_t)f0 * n_points * 3 * in_elem, count * 3 * in_elem,
-                              hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(h->inv.p, inv.data() + (size_t)f0 * 3, (size_t)b * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        dim3 const grid(blocks_for(groups, kBlock)), block(kBlock);
-        if (is_f64 && out_is_f64)
-            hipLaunchKernelGGL((k_lamina_distance<double, double>), grid, block, 0, st, (const double *)h->in.p, n_points, b, groups, h->inv.p,
-                               (double *)h->out.p);
-        else if (is_f64)
-            hipLaunchKernelGGL((k_lamina_distance<double, float>), grid, block, 0, st, (const double *)h->in.p, n_points, b, groups, h->inv.p,
-                               (float *)h->out.p);
-        else if (out_is_f64)
-            hipLaunchKernelGGL((k_lamina_distance<float, double>), grid, block, 0, st, (const float *)h->in.p, n_points, b, groups, h->inv.p,
-                               (double *)h->out.p);
-        else
-            hipLaunchKernelGGL((k_lamina_distance<float, float>), grid, block, 0, st, (const float *)h->in.p, n_points, b, groups, h->inv.p,
-                               (float *)h->out.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(static_cast<char *>(out) + (size_t)f0 * n_points * out_elem, h->out.p, count * out_elem, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return GD_OK;
+    return distances(h, "gd_lamina_distances", xyz, hipMemcpyHostToDevice, is_f64, frames, n_points, semiaxes, out, out_is_f64, false);
 }
 
 int gd_lamina_contacts(gd_lamina *h, const float *distances, uint32_t frames, uint32_t n_points, double contact_distance,
                        uint8_t *contacts_out)
 {
-    if (!h) return fail(GD_EINVAL, "gd_lamina_contacts: NULL handle");
-    if (std::isnan(contact_distance)) return fail(GD_EINVAL, "gd_lamina_contacts: the contact distance is NaN");
-    if (n_points > (1u << 28)) return fail(GD_EINVAL, "gd_lamina_contacts: %u points exceed 2^28", n_points);
-    if (h->have_shape && (frames != h->frames || n_points != h->n_points))
-        return fail(GD_EINVAL, "gd_lamina_contacts: a (%u, %u) history after (%u, %u) ones; call gd_lamina_reset between shapes", frames,
-                    n_points, h->frames, h->n_points);
-    size_t const total = (size_t)frames * n_points;
-    if (total && (!distances || !contacts_out)) return fail(GD_EINVAL, "gd_lamina_contacts: NULL argument");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    if (!h->have_shape) {
-        HIPCHK(h->sum.ensure(padded(total) + kPerLane));
-        HIPCHK(hipMemsetAsync(h->sum.p, 0, (padded(total) + kPerLane) * sizeof(float), st));
-        HIPCHK(hipStreamSynchronize(st));
-        h->frames = frames;
-        h->n_points = n_points;
-        h->calls = 0;
-        h->have_shape = true;
-    }
-    if (total) {
-        unsigned const B = h->batch_frames(frames, n_points);
-        HIPCHK(h->in.ensure(padded((size_t)B * n_points) * sizeof(float)));
-        HIPCHK(h->out.ensure(padded((size_t)B * n_points)));
-        for (unsigned f0 = 0; f0 < frames; f0 += B) {
-            unsigned const b = std::min(B, frames - f0);
-            size_t const count = (size_t)b * n_points, offset = (size_t)f0 * n_points;
-            unsigned const groups = (unsigned)(padded(count) / kPerLane);
-            HIPCHK(hipMemcpyAsync(h->in.p, distances + offset, count * sizeof(float), hipMemcpyHostToDevice, st));
-            dim3 const grid(blocks_for(groups, kBlock)), block(kBlock);
-            // the vector form may touch the sum's pad behind the last batch only: an earlier batch that is not a whole number
-            // of lanes would add its pad lanes into the next batch's elements
-            if (offset % kPerLane == 0 && (count % kPerLane == 0 || f0 + b == frames))
-                hipLaunchKernelGGL((k_lamina_contact<true>), grid, block, 0, st, (const float *)h->in.p, groups, (unsigned)count, contact_distance,
-                                   (uchar4 *)h->out.p, h->sum.p + offset);
-            else
-                hipLaunchKernelGGL((k_lamina_contact<false>), grid, block, 0, st, (const float *)h->in.p, groups, (unsigned)count, contact_distance,
-                                   (uchar4 *)h->out.p, h->sum.p + offset);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(contacts_out + offset, h->out.p, count, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-        }
-    }
-    h->calls++;
-    return GD_OK;
+    return contacts(h, "gd_lamina_contacts", distances, nullptr, nullptr, frames, n_points, contact_distance, contacts_out, false);
 }
 
 int gd_lamina_average(gd_lamina *h, float *out)
@@ -301,3 +360,19 @@ int gd_lamina_reset(gd_lamina *h)
 }
 
 }  // extern "C"
+
+// ---- the live seam (gdyn_live.hpp)
+
+int gd_lamina_device(const gd_lamina *h) { return h->device; }
+
+int gd_lamina_distances_dev(gd_lamina *h, const char *who, const float *xyz_dev, uint32_t frames, uint32_t n_points, const double *semiaxes,
+                            void *out, int out_is_f64)
+{
+    return distances(h, who, xyz_dev, hipMemcpyDeviceToDevice, 0, frames, n_points, semiaxes, out, out_is_f64, true);
+}
+
+int gd_lamina_contacts_dev(gd_lamina *h, const char *who, const float *xyz_dev, uint32_t frames, uint32_t n_points, const double *semiaxes,
+                           double contact_distance, uint8_t *contacts_out)
+{
+    return contacts(h, who, nullptr, xyz_dev, semiaxes, frames, n_points, contact_distance, contacts_out, true);
+}

@@ -28,6 +28,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_rdf.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_live.hpp"
 #include "gdyn_types.h"
 
 using namespace gd;
@@ -221,7 +222,9 @@ RdfGrid make_grid(const double box[3], double md, unsigned cap)
     return g;
 }
 
-int count_batch(gd_rdf *h, const void *xyz, int is_f64, unsigned B, const RdfGrid &g, double bin_width, double md, unsigned n_bins,
+// xyz: the B frames of the batch, in host memory (on_device false: they are uploaded into h->in first) or on the handle's device,
+// where k_rdf_keys reads them in place
+int count_batch(gd_rdf *h, const void *xyz, bool on_device, int is_f64, unsigned B, const RdfGrid &g, double bin_width, double md, unsigned n_bins,
                 uint64_t *counts_out)
 {
     hipStream_t st = h->stream;
@@ -229,7 +232,7 @@ int count_batch(gd_rdf *h, const void *xyz, int is_f64, unsigned B, const RdfGri
     unsigned const n_part = h->self ? h->n_center : h->n_target;
     size_t const nb = (size_t)B * n_sel, n_in = (size_t)B * h->n_points * 3 * (is_f64 ? 8 : 4);
     size_t const n_starts = (size_t)B * g.cells + 1;
-    HIPCHK(h->in.ensure(n_in));
+    if (!on_device) HIPCHK(h->in.ensure(n_in));
     HIPCHK(h->gpos.ensure(nb));
     HIPCHK(h->spos.ensure(nb));
     HIPCHK(h->keys[0].ensure(nb));
@@ -238,8 +241,9 @@ int count_batch(gd_rdf *h, const void *xyz, int is_f64, unsigned B, const RdfGri
     HIPCHK(h->vals[1].ensure(nb));
     HIPCHK(h->starts.ensure(n_starts));
     HIPCHK(h->counts.ensure((size_t)B * n_bins));
-    HIPCHK(hipMemcpyAsync(h->in.p, xyz, n_in, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_rdf_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->in.p, is_f64, h->n_points, h->sel.p, n_sel, h->n_center, B, g,
+    if (!on_device) HIPCHK(hipMemcpyAsync(h->in.p, xyz, n_in, hipMemcpyHostToDevice, st));
+    const void *frames = on_device ? xyz : h->in.p;
+    hipLaunchKernelGGL(k_rdf_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, frames, is_f64, h->n_points, h->sel.p, n_sel, h->n_center, B, g,
                        h->keys[0].p, h->vals[0].p, h->gpos.p);
     unsigned long long const key_end = (unsigned long long)(h->self ? 1 : 2) * B * g.cells;
     unsigned bits = 1;
@@ -274,6 +278,43 @@ int count_batch(gd_rdf *h, const void *xyz, int is_f64, unsigned B, const RdfGri
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(counts_out, h->counts.p, (size_t)B * n_bins * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return GD_OK;
+}
+
+// gd_rdf_counts (`who`) of frames in host memory or on the handle's device
+int counts(gd_rdf *h, const char *who, const void *xyz, bool on_device, int is_f64, uint32_t frames, const double box[3], double bin_width,
+           double max_distance, uint64_t *counts_out)
+{
+    if (!h || !box || (!counts_out && frames)) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (!h->have_selection) return fail(GD_ESTATE, "%s: call gd_rdf_set_selection first", who);
+    for (int a = 0; a < 3; a++)
+        if (!(box[a] > 0.0) || !std::isfinite(box[a])) return fail(GD_EINVAL, "%s: box[%d] = %g is not positive and finite", who, a, box[a]);
+    unsigned const n_bins = gd_rdf_bins(bin_width, max_distance);
+    if (!n_bins)
+        return fail(GD_EINVAL, "%s: bin width %g and max distance %g must be positive and finite, with at most %u bins", who, bin_width,
+                    max_distance, GD_RDF_MAX_BINS);
+    if (frames == 0) return GD_OK;
+    if (!xyz && h->n_points) return fail(GD_EINVAL, "%s: NULL coordinates", who);
+    unsigned const n_sel = h->n_center + (h->self ? 0u : h->n_target);
+    unsigned const n_part = h->self ? h->n_center : h->n_target;
+    if (h->n_center == 0 || n_part == 0) {      // nothing to pair
+        std::memset(counts_out, 0, (size_t)frames * n_bins * sizeof(uint64_t));
+        return GD_OK;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    RdfGrid const g = make_grid(box, max_distance, std::max(4096u, n_sel));
+    size_t const want = h->max_frames ? h->max_frames : ((size_t)1 << 20) / h->n_center + 1;      // ~1M centre lanes per launch
+    // sorted indices stay 32-bit, frames fit gridDim.y, the cell starts of a batch stay below 2^26 entries
+    size_t const limit = std::min<size_t>(std::min<size_t>(65535, ((size_t)1 << 26) / g.cells),
+                                          ((size_t)1 << 30) / std::max(n_sel, h->n_points));
+    unsigned const B = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(want, limit), frames));
+    size_t const frame_bytes = (size_t)h->n_points * 3 * (is_f64 ? 8 : 4);
+    for (unsigned f0 = 0; f0 < frames; f0 += B) {
+        unsigned const b = std::min(B, frames - f0);
+        if (int rc = count_batch(h, static_cast<const char *>(xyz) + f0 * frame_bytes, on_device, is_f64, b, g, bin_width, max_distance, n_bins,
+                                 counts_out + (size_t)f0 * n_bins))
+            return rc;
+    }
     return GD_OK;
 }
 
@@ -332,37 +373,19 @@ int gd_rdf_set_selection(gd_rdf *h, uint32_t n_points, const uint32_t *center_id
 int gd_rdf_counts(gd_rdf *h, const void *xyz, int is_f64, uint32_t frames, const double box[3], double bin_width, double max_distance,
                   uint64_t *counts_out)
 {
-    if (!h || !box || (!counts_out && frames)) return fail(GD_EINVAL, "gd_rdf_counts: NULL argument");
-    if (!h->have_selection) return fail(GD_ESTATE, "gd_rdf_counts: call gd_rdf_set_selection first");
-    for (int a = 0; a < 3; a++)
-        if (!(box[a] > 0.0) || !std::isfinite(box[a])) return fail(GD_EINVAL, "gd_rdf_counts: box[%d] = %g is not positive and finite", a, box[a]);
-    unsigned const n_bins = gd_rdf_bins(bin_width, max_distance);
-    if (!n_bins)
-        return fail(GD_EINVAL, "gd_rdf_counts: bin width %g and max distance %g must be positive and finite, with at most %u bins", bin_width,
-                    max_distance, GD_RDF_MAX_BINS);
-    if (frames == 0) return GD_OK;
-    if (!xyz && h->n_points) return fail(GD_EINVAL, "gd_rdf_counts: NULL coordinates");
-    unsigned const n_sel = h->n_center + (h->self ? 0u : h->n_target);
-    unsigned const n_part = h->self ? h->n_center : h->n_target;
-    if (h->n_center == 0 || n_part == 0) {      // nothing to pair
-        std::memset(counts_out, 0, (size_t)frames * n_bins * sizeof(uint64_t));
-        return GD_OK;
-    }
-    HIPCHK(hipSetDevice(h->device));
-    RdfGrid const g = make_grid(box, max_distance, std::max(4096u, n_sel));
-    size_t const want = h->max_frames ? h->max_frames : ((size_t)1 << 20) / h->n_center + 1;      // ~1M centre lanes per launch
-    // sorted indices stay 32-bit, frames fit gridDim.y, the cell starts of a batch stay below 2^26 entries
-    size_t const limit = std::min<size_t>(std::min<size_t>(65535, ((size_t)1 << 26) / g.cells),
-                                          ((size_t)1 << 30) / std::max(n_sel, h->n_points));
-    unsigned const B = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(want, limit), frames));
-    size_t const frame_bytes = (size_t)h->n_points * 3 * (is_f64 ? 8 : 4);
-    for (unsigned f0 = 0; f0 < frames; f0 += B) {
-        unsigned const b = std::min(B, frames - f0);
-        if (int rc = count_batch(h, static_cast<const char *>(xyz) + f0 * frame_bytes, is_f64, b, g, bin_width, max_distance, n_bins,
-                                 counts_out + (size_t)f0 * n_bins))
-            return rc;
-    }
-    return GD_OK;
+    return counts(h, "gd_rdf_counts", xyz, false, is_f64, frames, box, bin_width, max_distance, counts_out);
 }
 
 }  // extern "C"
+
+// ---- the live seam (gdyn_live.hpp)
+
+int gd_rdf_device(const gd_rdf *h) { return h->device; }
+
+int gd_rdf_counts_dev(gd_rdf *h, const char *who, const float *xyz_dev, uint32_t frames, uint32_t n_points, const double box[3], double bin_width,
+                      double max_distance, uint64_t *counts_out)
+{
+    if (h->have_selection && h->n_points != n_points)
+        return fail(GD_EINVAL, "%s: the selection is over %u points, the system has %u beads", who, h->n_points, n_points);
+    return counts(h, who, xyz_dev, true, 0, frames, box, bin_width, max_distance, counts_out);
+}

@@ -156,12 +156,13 @@ inline void print_plan(program p, options const &o)
 
 struct device {      // created when the first file has been read: a missing input is reported as such
     gd_cmap *h = nullptr;
+    int ordinal = 0;         // HIP device
     double startup = 0;      // seconds gd_cmap_create took (the HIP runtime starts there), inside whichever lap the caller opens it in
     void open()
     {
         if (h) return;
         auto const t = std::chrono::steady_clock::now();
-        gd_cmap_desc const d{0, 0};
+        gd_cmap_desc const d{ordinal, 0};
         cli::check(gd_cmap_create(&d, &h));
         startup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
     }
@@ -215,6 +216,24 @@ inline void read_ranges(hid_t file, std::string const &path, trajectory &t)
     }
     for (std::size_t k = 0; k < rows; k++)
         h5::check(t.ranges[2 * k] >= 0 && t.ranges[2 * k + 1] >= t.ranges[2 * k], path + ": chromosome_ranges holds a reversed or negative range");
+}
+
+// the chromosome table alone: of a prepared input as well, which has no /snapshots/interphase yet
+inline trajectory load_ranges(std::string const &path)
+{
+    trajectory t;
+    H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    hid_t const file = H5Fopen(path.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
+    h5::check(file >= 0, "cannot open " + path);
+    // closed here (h5::hid does not close files): gd_interphase opens the same file for writing next
+    try {
+        read_ranges(file, path, t);
+    } catch (...) {
+        H5Fclose(file);
+        throw;
+    }
+    H5Fclose(file);
+    return t;
 }
 
 // nad_profile.py:46-57: the phase's own metadata group if it has particle_types, else the file's
@@ -412,6 +431,27 @@ inline rebinning rebin(trajectory const &t, long rate)
     return r;
 }
 
+// save_contact_matrix (command.py): h5py.File(filename, "w") with /contact_matrix, /metadata/chromosome_ranges (the binned
+// ranges, typed by an enum of the chromosome names of `head`) and /metadata/rebin_map.  gd_gw_contact_matrix writes it from the
+// stored maps, gd_interphase --ensemble-matrix from the maps of its replicas as they are dumped.
+inline void write_gw_matrix(std::string const &output, trajectory const &head, rebinning const &rb, std::vector<int32_t> const &matrix)
+{
+    h5::hid file(H5Fcreate(output.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT));
+    h5::check(file >= 0, "cannot create " + output);
+    h5::hid names(H5Tenum_create(H5T_STD_I32LE));
+    for (auto const &kv : head.keys) {
+        int32_t const v = (int32_t)kv.second;
+        H5Tenum_insert(names, kv.first.c_str(), &v);
+    }
+    cli::put_dataset(file, "/metadata/chromosome_ranges", rb.binned.data(), {rb.binned.size() / 2, 2}, 4, names, names, nullptr);
+    cli::put_dataset(file, "/metadata/rebin_map", rb.map.data(), {rb.map.size()}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, nullptr);
+    cli::filters f;
+    f.scaleoffset_kind = H5Z_SO_INT;
+    f.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;      // scaleoffset=0: integer scale-offset is lossless
+    cli::put_dataset(file, "/contact_matrix", matrix.data(), {rb.n_bins, rb.n_bins}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &f);
+    H5Fflush(file, H5F_SCOPE_GLOBAL);
+}
+
 inline void run_gw(options const &o)
 {
     cli::stopwatch sw;
@@ -441,21 +481,7 @@ inline void run_gw(options const &o)
     std::fputs(" DONE\n", stderr);
     auto const matrix = dev.fetch(id);
     sw.compute += sw.lap();
-    // save_contact_matrix: h5py.File(filename, "w")
-    h5::hid file(H5Fcreate(o.output.c_str(), H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT));
-    h5::check(file >= 0, "cannot create " + o.output);
-    h5::hid names(H5Tenum_create(H5T_STD_I32LE));
-    for (auto const &kv : head.keys) {
-        int32_t const v = (int32_t)kv.second;
-        H5Tenum_insert(names, kv.first.c_str(), &v);
-    }
-    cli::put_dataset(file, "/metadata/chromosome_ranges", rb.binned.data(), {rb.binned.size() / 2, 2}, 4, names, names, nullptr);
-    cli::put_dataset(file, "/metadata/rebin_map", rb.map.data(), {rb.map.size()}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, nullptr);
-    cli::filters f;
-    f.scaleoffset_kind = H5Z_SO_INT;
-    f.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;      // scaleoffset=0: integer scale-offset is lossless
-    cli::put_dataset(file, "/contact_matrix", matrix.data(), {rb.n_bins, rb.n_bins}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &f);
-    H5Fflush(file, H5F_SCOPE_GLOBAL);
+    write_gw_matrix(o.output, head, rb, matrix);
     sw.write += sw.lap();
     sw.report("gd_gw_contact_matrix");
     dev.report("gd_gw_contact_matrix");

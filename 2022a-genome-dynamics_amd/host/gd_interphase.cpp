@@ -11,6 +11,10 @@
 // Differences from the reference, by construction: fp32 device arithmetic and a Philox noise stream (micromd's
 // generator is not reproducible); `spacestep` must be 0; the softwell droplet force
 // (nucleolus_droplet_energy != 0) uses a documented choice of micromd's potential form (include/gdyn.h).
+//
+// --ensemble-matrix RATE OUTPUT (not in the reference): the genome-wide contact matrix of the run's replicas, summed on the
+// device from the contact tables each time they are dumped (gd_live_contacts, include/gdyn_live.h) and written at the end
+// exactly as `gd_gw_contact_matrix --rebin-rate RATE -o OUTPUT <the same files>` writes it from the stored maps afterwards.
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -30,7 +34,17 @@
 #include <vector>
 
 #include "../../include/gdyn.h"
+#include "../../include/gdyn_live.h"
+// This program is also linked against libraries that implement gdyn.h alone (the fp64 oracle of the tests).  What
+// --ensemble-matrix calls is referenced weakly, and the option is refused where the symbols are absent.
+#pragma weak gd_cmap_create
+#pragma weak gd_cmap_destroy
+#pragma weak gd_cmap_add_binned
+#pragma weak gd_cmap_target_size
+#pragma weak gd_cmap_fetch
+#pragma weak gd_live_contacts
 #include "gd_async_io.hpp"
+#include "gd_cmap_cli.hpp"
 #include "gd_config.hpp"
 #include "gd_genome_model.hpp"
 #include "gd_store.hpp"
@@ -76,6 +90,27 @@ std::vector<std::array<std::uint32_t, 3>> fetch_contacts(gd_system *sys, uint32_
     return rows;
 }
 
+// --ensemble-matrix: one binned target over the chromosome ranges of the first file (gd_gw_contact_matrix's rebin rule), fed
+// from the device-resident contact tables of all replicas
+struct ensemble_matrix {
+    std::string output;
+    gd::cmap::trajectory head;
+    gd::cmap::rebinning rb;
+    gd::cmap::device dev;
+    int32_t target = -1;
+
+    static bool available() { return gd_cmap_create && gd_cmap_destroy && gd_cmap_add_binned && gd_cmap_target_size && gd_cmap_fetch && gd_live_contacts; }
+    ensemble_matrix(std::string const &first_file, long rate, std::string const &out, int device)
+        : output(out), head(gd::cmap::load_ranges(first_file)), rb(gd::cmap::rebin(head, rate))
+    {
+        dev.ordinal = device;
+        dev.open();
+        gd::cli::check(gd_cmap_add_binned(dev.h, rb.map.data(), (uint32_t)rb.map.size(), rb.n_bins, &target));
+    }
+    void add(gd_system *sys) { gd::cli::check(gd_live_contacts(sys, GD_ALL_REPLICAS, dev.h)); }
+    void write() { gd::cmap::write_gw_matrix(output, head, rb, dev.fetch(target)); }
+};
+
 // One driver = one libgdyn handle = R replicas = R trajectory files.  R = 1 is the reference program; R > 1 batches R runs
 // of the reference's ensemble (one process per seed, each with its own prepared file: 5-sim-genome/scripts/run_simulation:8-25,
 // read back as output-*.h5 by contact_map/contact_map.py:14-39) into one launch: replica r takes its initial structure, its
@@ -83,8 +118,9 @@ std::vector<std::array<std::uint32_t, 3>> fetch_contacts(gd_system *sys, uint32_
 // (gd_run_desc.replica_seeds), so a batched trajectory equals the solo one up to fp32 summation order.
 class simulation_driver {
 public:
-    simulation_driver(std::vector<std::unique_ptr<gd::trajectory_store>> &stores, int device, bool auto_skin = false)
-        : _stores(stores), _R(stores.size()), _config(gd::parse_simulation_config(stores[0]->load_config_text())), _auto_skin(auto_skin)
+    simulation_driver(std::vector<std::unique_ptr<gd::trajectory_store>> &stores, int device, bool auto_skin = false, ensemble_matrix *ensemble = nullptr)
+        : _stores(stores), _R(stores.size()), _config(gd::parse_simulation_config(stores[0]->load_config_text())), _auto_skin(auto_skin),
+          _ensemble(ensemble)
     {
         // compatibility defaults of older runs (simulation_driver.cc:20-29)
         auto set_default = [](double &var, double def) { if (var == 0) var = def; };
@@ -227,6 +263,10 @@ private:
     void save_contacts(long step)
     {
         auto rows = std::make_shared<std::vector<std::vector<std::array<std::uint32_t, 3>>>>(_R);
+        if (_ensemble) {      // the maps about to be dumped and cleared, summed where they lie
+            TIMED("ensemble_matrix");
+            _ensemble->add(_sys);
+        }
         {
             TIMED("contacts_fetch");
             for (std::size_t r = 0; r < _R; r++) (*rows)[r] = fetch_contacts(_sys, (uint32_t)r);
@@ -367,6 +407,7 @@ private:
     std::size_t _R;
     gd::simulation_config _config;
     bool _auto_skin = false;
+    ensemble_matrix *_ensemble = nullptr;
     std::vector<gd::context> _context;
     double _contact_distance = 0;
     std::vector<std::mt19937_64> _random;
@@ -387,8 +428,11 @@ int main(int argc, char **argv)
     // gd_interphase <trajectory> [device]                      the reference's command line
     // gd_interphase [--device d] <trajectory> <trajectory>...  R prepared files as R replicas of one handle
     // options: --timing (wall-time split on stderr at the end), --auto-skin (list width selected from measured chunk times: the
-    // trajectory of a seed then depends on timing; off by default.  --fixed-skin, the former spelling of the default, is accepted)
+    // trajectory of a seed then depends on timing; off by default.  --fixed-skin, the former spelling of the default, is accepted),
+    // --ensemble-matrix RATE OUTPUT (the genome-wide contact matrix of the replicas, as gd_gw_contact_matrix --rebin-rate RATE writes it)
     std::vector<std::string> files;
+    std::string matrix_output;
+    long matrix_rate = 0;
     int device = 0;
     bool timing = false, auto_skin = false;
     auto const t_start = std::chrono::steady_clock::now();
@@ -398,7 +442,21 @@ int main(int argc, char **argv)
         else if (arg == "--auto-skin") auto_skin = true;
         else if (arg == "--fixed-skin") auto_skin = false;
         else if (arg == "--device" && i + 1 < argc) device = std::stoi(argv[++i]);
+        else if (arg == "--ensemble-matrix") {
+            char *end = nullptr;
+            if (i + 2 < argc) matrix_rate = std::strtol(argv[i + 1], &end, 10);
+            if (i + 2 >= argc || *end || matrix_rate < 1) {
+                std::cerr << "error: --ensemble-matrix takes a rebin rate of at least 1 and an output file\n";
+                return 1;
+            }
+            matrix_output = argv[i + 2];
+            i += 2;
+        }
         else files.push_back(arg);
+    }
+    if (!matrix_output.empty() && !ensemble_matrix::available()) {
+        std::cerr << "error: --ensemble-matrix needs the device library\n";
+        return 1;
     }
     if (files.size() == 2 && !files[1].empty() && files[1].find_first_not_of("0123456789") == std::string::npos) {
         device = std::stoi(files[1]); files.pop_back();
@@ -408,6 +466,8 @@ int main(int argc, char **argv)
         return 1;
     }
     try {
+        std::unique_ptr<ensemble_matrix> ensemble;      // (reads the first file's chromosome table before the stores open the files)
+        if (!matrix_output.empty()) ensemble = std::make_unique<ensemble_matrix>(files[0], matrix_rate, matrix_output, device);
         std::vector<std::unique_ptr<gd::trajectory_store>> stores;
         {
             TIMED("open_files");
@@ -415,9 +475,10 @@ int main(int argc, char **argv)
         }
         double bead_steps = 0;
         {
-            simulation_driver driver{stores, device, auto_skin};
+            simulation_driver driver{stores, device, auto_skin, ensemble.get()};
             driver.run();
             bead_steps = driver.bead_steps();
+            if (ensemble) { TIMED("ensemble_matrix"); ensemble->write(); }
         }
         { TIMED("close_files"); stores.clear(); }
         double const total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();

@@ -91,8 +91,12 @@ class Lamina(Handle):
             raise ValueError(f"distances must be (F, N), got {d.shape}")
         out = np.empty(d.shape, np.uint8)
         self._check(self.dll.gd_lamina_contacts(self._h, d.ctypes.data, d.shape[0], d.shape[1], float(contact_distance), out.ctypes.data))
-        self._shape = d.shape
+        self._note_shape(d.shape)
         return out.view(np.bool_)
+
+    def _note_shape(self, shape):
+        """The (F, N) of the handle's sum, which average() returns: set by every call that adds contacts (live.lamina_contacts too)."""
+        self._shape = tuple(shape)
 
     def average(self):
         """float32 (F, N): the sum of the contacts since reset() over the number of contacts() calls."""

@@ -78,15 +78,20 @@ class Rdf(Handle):
         super().__init__(load_rdf_library(path))
         self._check(self.dll.gd_rdf_create(C.byref(_RdfDesc(device, max_frames_per_launch)), C.byref(self._h)))
 
+    def set_selection(self, n_points, centers, targets=None):
+        """The selection of the counts to come: centres alone (self mode) or centres against targets, as indices into
+        n_points beads.  counts() sets it itself; live.rdf_counts uses the one in force."""
+        c = np.ascontiguousarray(centers, dtype=np.uint32).ravel()
+        t = None if targets is None else np.ascontiguousarray(targets, dtype=np.uint32).ravel()
+        self._check(self.dll.gd_rdf_set_selection(self._h, n_points, c.ctypes.data, len(c), None if t is None else t.ctypes.data,
+                                                  0 if t is None else len(t)))
+
     def counts(self, frames, box, bin_width, max_distance, centers, targets=None):
         """frames (F, N, 3) float32 or float64 (or one (N, 3) frame); box: a period or three; centers / targets: bead indices.
         Returns uint64 (F, n_bins)."""
         x, is64 = as_frames(frames)
         F, N, _ = x.shape
-        c = np.ascontiguousarray(centers, dtype=np.uint32).ravel()
-        t = None if targets is None else np.ascontiguousarray(targets, dtype=np.uint32).ravel()
-        self._check(self.dll.gd_rdf_set_selection(self._h, N, c.ctypes.data, len(c), None if t is None else t.ctypes.data,
-                                                  0 if t is None else len(t)))
+        self.set_selection(N, centers, targets)
         b = np.broadcast_to(np.asarray(box, dtype=np.float64), (3,))
         nb = self.dll.gd_rdf_bins(float(bin_width), float(max_distance))
         out = np.zeros((F, max(nb, 1)), np.uint64)
