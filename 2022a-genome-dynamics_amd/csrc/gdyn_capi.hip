@@ -1114,11 +1114,18 @@ static int rollback_chunk(gd_system *s, const Chunk &c, bool over, bool comp, in
     s->hctx = c.snap_ctx; s->ctx_dirty = true; s->w_packed = c.snap_w_packed;
     GDCHK(upload_ctx(s));
     s->list_valid = false; s->bbox_valid = false;      // (the box the abandoned builds recorded may be that of positions stepped on incomplete lists)
-    if (retries > 24) return fail(GD_ESTATE, "gd_run: a chunk of %lld steps at step %lld was rolled back %d times (%s): giving up",
-                                  (long long)c.steps, (long long)s->hctx[0].step, retries, over ? "list / tile / pool overflow" : "skin violation");
+    s->pol.hold_for_retries();      // (the width and the interval before the chunk's first rollback: a chunk given up returns them)
+    if (retries > 24) {
+        s->pol.retries_over(true);
+        return fail(GD_ESTATE, "gd_run: a chunk of %lld steps at step %lld was rolled back %d times (%s): giving up",
+                    (long long)c.steps, (long long)s->hctx[0].step, retries, over ? "list / tile / pool overflow" : "skin violation");
+    }
     if (dev_env("GDYN_DEBUG")) fprintf(stderr, "[gdyn] rollback %llu: %s, K %u, skin %.3f, chunk of %lld steps at step %lld\n", (unsigned long long)s->rollbacks,
                                        over ? "overflow" : "skin violation", s->pol.K, s->pol.skin, (long long)c.steps, (long long)s->hctx[0].step);
-    if (c.rep.violated && !over && !s->pol.on_violation()) return fail(GD_ESTATE, "gd_run: Verlet skin cannot cover one step (timestep too large?)");
+    if (c.rep.violated && !over && !s->pol.on_violation()) {
+        s->pol.retries_over(true);
+        return fail(GD_ESTATE, "gd_run: Verlet skin cannot cover one step (timestep too large?)");
+    }
     s->timing.step_launches -= std::min<uint64_t>(s->timing.step_launches, (uint64_t)c.steps);
     s->pol.on_rollback(s->sw_n != 0);
     return GD_OK;
@@ -1194,6 +1201,7 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
 
     int64_t done = 0;
     int retries = 0;           // consecutive rollbacks of the chunk in progress
+    s->pol.retries_over(false);      // (a run that ended on a device error between two rollbacks holds nothing for this one)
     float last_dmax2 = 0;      // largest bound, over the replicas, of the squared displacement since the build of the positions the last accepted chunk WROTE
     while (done < run->steps) {
         Chunk c;
@@ -1201,6 +1209,7 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
         GDCHK(read_chunk(s, c));
         const bool over = s->pol.on_report(list_state(s), c.rep);
         if (c.rep.violated || over) { GDCHK(rollback_chunk(s, c, over, comp, ++retries)); continue; }
+        s->pol.retries_over(false);      // (accepted: what the retries arrived at stays)
         GDCHK(accept_chunk(s, run, c));
         done += c.steps; retries = 0; last_dmax2 = c.dmax2;
     }

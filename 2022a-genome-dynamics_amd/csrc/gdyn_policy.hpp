@@ -200,6 +200,20 @@ struct ListPolicy {
         else { K_bad = K; K_bad_ttl = 64; K = std::max(1u, K - std::max(1u, K / 4)); a2_ema = 0; }   // (a gentler cut, K/8 for 32 chunks, violates again sooner: measured 1% slower)
         return true;
     }
+    // What the rollbacks of one chunk change of the width and the interval (on_violation), as they stood before the first of them.  A
+    // chunk that is accepted in the end keeps what its retries arrived at; a chunk gd_run gives up (the skin cannot cover one step, too
+    // many rollbacks) returns them: the handle stands at the last accepted chunk, and so does what its next list build looks like --
+    // not a skin beyond 8 cutoffs and an interval of 1 that nothing would ever take back.
+    struct Retries { bool held = false; double skin = 0; uint32_t K = 0, K_bad = 0, K_bad_ttl = 0; } retries;
+    void hold_for_retries() { if (!retries.held) retries = Retries{true, skin, K, K_bad, K_bad_ttl}; }      // (every rollback: the first one of a chunk holds)
+    void retries_over(bool given_up)
+    {
+        if (given_up && retries.held) {
+            skin = std::min(skin, retries.skin);      // (a violation only widens; a width an overflow narrowed for a dense state meanwhile stays)
+            K = retries.K; K_bad = retries.K_bad; K_bad_ttl = retries.K_bad_ttl;
+        }
+        retries.held = false;
+    }
     // A chunk was rolled back: the candidate the sweep measures settles again
     void on_rollback(bool droplet)
     {

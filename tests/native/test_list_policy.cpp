@@ -322,6 +322,35 @@ static void test_interval()
     int widen = 0;
     while (w.on_violation() && widen < 50) widen++;
     CHECK(w.skin > 8 && w.skin == 0.75 * std::pow(1.5, widen) && widen == 6);
+    // a chunk gd_run gives up returns the width and the interval its rollbacks changed, as they stood before the first of them:
+    // the skin that no longer covers one step ...
+    ListPolicy g; g.K = 1;
+    do g.hold_for_retries(); while (g.on_violation());
+    CHECK(g.skin > 8 && g.K == 1u && g.retries.held);
+    g.retries_over(true);
+    CHECK(g.skin == 0.75 && g.K == 1u && !g.retries.held);
+    // ... and the interval of a chunk rolled back 25 times (1166: the smallest from which 24 cuts end above 1)
+    ListPolicy h; h.K = 1166; h.K_bad = 7; h.K_bad_ttl = 3;
+    for (int cuts = 0; cuts < 24; cuts++) { h.hold_for_retries(); CHECK(h.K >= 2u && h.on_violation()); }
+    CHECK(h.K == 2u && h.K_bad == 3u && h.K_bad_ttl == 64u && h.skin == 0.75);
+    ListPolicy h2; h2.K = 1165; for (int cuts = 0; cuts < 24; cuts++) h2.on_violation();
+    CHECK(h2.K == 1u);
+    h.hold_for_retries(); h.retries_over(true);
+    CHECK(h.K == 1166u && h.K_bad == 7u && h.K_bad_ttl == 3u && h.skin == 0.75 && !h.retries.held);
+    // an accepted chunk keeps what its retries arrived at, and the next chunk holds from there
+    ListPolicy k; k.K = 20;
+    k.hold_for_retries(); k.on_violation(); k.retries_over(false);
+    CHECK(k.K == 15u && k.K_bad == 20u && !k.retries.held);
+    k.retries_over(true);      // (nothing held: nothing returned)
+    CHECK(k.K == 15u && k.K_bad == 20u);
+    k.K_bad_ttl = 10; k.hold_for_retries(); k.on_violation(); CHECK(k.K == 12u && k.K_bad == 15u);
+    k.retries_over(true);
+    CHECK(k.K == 15u && k.K_bad == 20u && k.K_bad_ttl == 10u);
+    // a width that an overflow narrowed for a dense state between two violations stays narrowed
+    ListPolicy d; d.K = 1;
+    d.hold_for_retries(); d.on_violation(); CHECK(d.skin == 0.75 * 1.5);
+    d.skin = 0.3; d.retries_over(true);
+    CHECK(d.skin == 0.3 && d.K == 1u);
     // a pending skin: K by ratio^2 (x 0.9 on the way up), not beyond the measured rate
     ListPolicy s; s.K = 20; s.skin_next = 0.9;
     s.take_pending_skin(1.0);

@@ -309,6 +309,8 @@ def test_errors_match_oracle(hip):
         s.add_bond_range(g.System.bond_params(g.POT_HARMONIC, 1.0), 0, s.N + 1)
     with pytest.raises(g.GdynError):
         s.set_positions(np.full((1, s.N, 3), np.inf))
+    from test_run_failures_gpu import refused_calls      # every refusal made before the device is touched, each with its code
+    assert refused_calls(s, dt, kT) >= 12
 
 
 def test_rollback_is_transparent(hip):
