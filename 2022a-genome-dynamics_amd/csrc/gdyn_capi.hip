@@ -846,9 +846,9 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
         const size_t waves = (size_t)s->R * s->Np / 64;
         const bool predict = s->need_valid && s->need_all_near == pol.all_near && s->need_rv > 0 && std::fabs(rv / s->need_rv - 1.f) <= 0.02f;
         auto pool_kib = [&]() { return (size_t)(s->nbr16.n / 512); };
-        const size_t used = predict ? std::max<size_t>(s->pool_used, waves) : std::max<size_t>(s->pool_used, waves * (pol.W / 8));
-        const size_t want = used + used / 8 + 2 * waves;
-        if (pool_kib() < want || pool_kib() > 2 * want + 4 * waves) HIPCHK(s->nbr16.resize((want + want / 16) * 512, false));      // (not preserved: the list in it is about to be rebuilt)
+        const gd::PoolPlan plan = gd::plan_pool(s->pool_used, pool_kib(), waves, pol.W, predict);      // (the rule: gdyn_policy.hpp)
+        const size_t used = plan.used;
+        if (plan.resize) HIPCHK(s->nbr16.resize(plan.alloc_kib * 512, false));      // (not preserved: the list in it is about to be rebuilt)
         if (dev_env("GDYN_DEBUG") && dev_env("GDYN_DEBUG")[0] == '2')
             fprintf(stderr, "[gdyn] build %llu: %s, rows used %u KiB, pool %zu KiB, rv %.4f\n", (unsigned long long)s->rebuilds, predict ? "predicted" : "no history", s->pool_used, pool_kib(), rv);
         if (!predict) s->pool_used = (uint32_t)std::min<size_t>(used, 0xffffffffu);      // (the guess stands in until a chunk's readback brings the real use)

@@ -2094,6 +2094,9 @@ __device__ __forceinline__ void finish_rows(const BuildParams &p, FillBead &b, L
     }
     b.listlen = min(found, Wrow);
     b.nAq = min((lw.cnt + 3u) / 4u, GD_TILED_MAX_NEAR / 4u);            // near entries in fours (the record's count; chunks are still written whole)
+    // what near_entries counts: the fours k_step walks once the bead's row holds its list -- the row as it is, or the one a repair
+    // writes behind this kernel -- so not the count clamped to a row that is too narrow, below
+    b.near4 = 4u * b.nAq;
     // the chunk under construction goes out padded, with one store
     lw.flush();
     if (lw.cnt % PER) {
@@ -2112,7 +2115,7 @@ __device__ __forceinline__ void finish_rows(const BuildParams &p, FillBead &b, L
     }
     // (an overflowed list: the chunk counts have to stay inside the row until it is repaired)
     b.nAq = min(b.nAq, 2u * nc_row); b.nB = min(min(lw.cntB / GD_UNROLL, GD_TILED_MAX_FAR / GD_UNROLL), nc_row - (b.nAq + 1u) / 2u);
-    b.cnt = found; b.near4 = 4u * b.nAq;
+    b.cnt = found;
     b.deg = lw.pk & 0xffu;
 }
 

@@ -50,6 +50,28 @@ struct ListState {
 // cutoff now; whether it holds the last step of a complete K-step interval, whether it began on a (wider) contact-search list
 struct Accepted { double ms = 0; int64_t steps = 0; float maxd2 = 0; double scale_now = 1; bool full_interval = false, on_search_list = false; };
 
+// The row pool of tiled lists (KiB: one chunk of a k_step wave's rows, 64 lanes x 16 bytes) before a build.  With history
+// (predict: every bead's row is predicted from what it needed at the build before) the pool follows the use of the last build, at
+// least a chunk per wave; without (first build, positions from the caller, another list radius or class mode) every wave gets rows
+// of W entries, W / 8 chunks.  Margin: an eighth + 2 KiB per wave on top of that use (the builds between two readbacks grow with
+// the lists, repaired waves take fresh rows); the pool is reallocated -- with a sixteenth more, so that it is not reallocated at
+// every build of a growing state -- when it is smaller than that, and given back when it is larger than twice that + 4 KiB per wave.
+struct PoolPlan {
+    size_t used = 0;        // KiB the build is expected to take (what stands in for the use until a readback brings the real one)
+    size_t want = 0;        // KiB the pool has to hold: used + the margin
+    bool resize = false;    // the pool is outside [want, 2 want + 4 waves]
+    size_t alloc_kib = 0;   // ... and is reallocated at this size
+};
+inline PoolPlan plan_pool(size_t pool_used, size_t pool_kib, size_t waves, uint32_t W, bool predict)
+{
+    PoolPlan pl;
+    pl.used = std::max<size_t>(pool_used, predict ? waves : waves * std::max<size_t>(W / 8u, 1u));
+    pl.want = pl.used + pl.used / 8 + 2 * waves;
+    pl.resize = pool_kib < pl.want || pool_kib > 2 * pl.want + 4 * waves;
+    pl.alloc_kib = pl.want + pl.want / 16;
+    return pl;
+}
+
 struct ListPolicy {
     // developer hooks (gd_create)
     std::vector<unsigned> tile_caps = {3312u, 4080u, 5072u, 8192u};      // (4080: the largest tile with byte-offset list entries)
@@ -128,6 +150,8 @@ struct ListPolicy {
     }
     // A pending width (class_skin, a dense state easing) takes over at a list build: interval and radius change together
     void take_pending_skin(double cut) { if (skin_next > 0) { const double to = skin_next; skin_next = 0; move_skin(to, cut); } }
+    // Row width for a longest list of need_w entries: a quarter and 16 entries to spare, whole batches, at least 64
+    static unsigned want_width(unsigned need_w) { return std::max(64u, (need_w + need_w / 4 + 16 + GD_UNROLL - 1) & ~(GD_UNROLL - 1)); }
     // What a build reported: widen the list, enlarge the LDS tile or fall back to the generic path, narrow the width of a dense state.
     // True when the build has to be redone (its chunk rolled back).
     bool on_report(const ListState &ls, const BuildReport &r)
@@ -183,10 +207,12 @@ struct ListPolicy {
         else if (!r.tile_over && r.need_w > 0) {
             if (ls.tiled && (size_t)ls.pool_used * 1024u > ((size_t)4 << 30)) dense_guard(ls, r.need_w);      // (rows of several GB: within the budget?)
             if (all_near && r.need_w <= GD_TILED_MAX_FAR) all_near = false;      // (no far class can overflow its field any more; from the next build)
-            // the longest list is reported by every build: generic lists give the row width back when a dense transient has passed
-            const unsigned want_w = std::max(64u, (r.need_w + r.need_w / 4 + 16 + GD_UNROLL - 1) & ~(GD_UNROLL - 1));
-            if (!ls.tiled && 2 * want_w <= W) W = want_w;       // (takes effect at the next build; the list in use keeps its width)
-            else if (ls.tiled && W > GD_TILED_MAX_W && r.need_w <= GD_TILED_MAX_NEAR) W = 96;      // (a near class beyond the tiled record has passed)
+            // the longest list is reported by every build: the row width is given back when a dense transient has passed.  Generic
+            // lists: the uniform rows.  Tiled lists: the guess a build without history starts its ragged rows from, and sizes the row
+            // pool by (plan_pool) -- a width left behind by a generic excursion or a caller's list_width is honoured once, then
+            // replaced by what the lists were measured to need
+            const unsigned want_w = want_width(r.need_w);
+            if (2 * want_w <= W) W = want_w;       // (takes effect at the next build; the list in use keeps its width)
         }
         if ((r.over || r.tile_over) && trace)
             fprintf(trace, "[gdyn] overflow: list %d (bits %u, need %u -> W %u; rows %u KiB of a pool of %zu), tile %d (need %u -> cap %u, tiled_ok %d)\n", (int)r.over, r.bits,

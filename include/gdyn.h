@@ -234,10 +234,14 @@ typedef struct {
                                     tile class, and with it the list width the handle selects) */
     uint32_t row_repairs;        /* LDS-tiled lists: k_step waves whose rows the builds of the last chunk wrote twice (a list outgrew the
                                     width predicted for its wave: repaired on the device, no rollback) */
-    uint64_t near_entries;       /* LDS-tiled lists: entries of this replica's NEAR class, in the fours k_step walks them in (every step
-                                    walks these; the rest of list_entries only once displacements make it matter) */
+    uint64_t near_entries;       /* LDS-tiled lists: entries of this replica's NEAR class (closer than the near radius at the build), each
+                                    bead's count rounded up to the fours k_step walks them in (every step walks these; the rest of
+                                    list_entries only once displacements make it matter).  Single-class lists: all entries, in fours.
+                                    Counted from the lists, whether a bead's row held its list at once or was repaired.  Generic
+                                    lists: 0 */
     uint64_t list_bytes;         /* memory the lists of the whole handle occupy: tiled lists the rows taken from the pool by the last
-                                    build (ragged rows: every wave as wide as its longest list), generic lists uniform rows */
+                                    build (ragged rows: every wave as wide as its longest list, at least the guess of a build
+                                    without history; rows a repair abandoned count too), generic lists uniform rows */
 } gd_context;
 
 int gd_get_context(gd_system *sys, uint32_t replica, gd_context *out);

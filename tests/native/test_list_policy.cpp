@@ -1,6 +1,6 @@
 // CPU unit test of the list policy of libgdyn (csrc/gdyn_policy.hpp): synthetic build reports and accepted chunks in, the decisions
-// of the rules out -- tile class, dense states, generic row width, single-class lists, memory guard, width by tile class, interval
-// adaptation and the auto_skin sweep.  Built and run by tests/test_list_policy.py (plain g++, no HIP runtime).
+// of the rules out -- tile class, dense states, row width, the row pool of tiled lists, single-class lists, memory guard, width by
+// tile class, interval adaptation and the auto_skin sweep.  Built and run by tests/test_list_policy.py (plain g++, no HIP runtime).
 #include <cmath>
 #include <cstdio>
 #include <vector>
@@ -175,8 +175,9 @@ static void test_generic_rows()
     // a near class beyond the record: rows too wide for tiled lists
     p.on_report(tiled_list(p), overflow(2, GD_TILED_MAX_NEAR + 8));
     CHECK(!p.all_near && p.W == GD_TILED_MAX_W + 8u && !p.want_tiled(true));
-    p.on_report(tiled_list(p), fits(3000, 2000));
-    CHECK(p.W == 96u);
+    // ... generic lists then: they give the width back once the near class has passed (to what the longest list needs, as any width)
+    p.on_report(generic_list(p), fits(0, 2000));
+    CHECK(p.W == ListPolicy::want_width(2000) && p.W == 2520u && p.want_tiled(true));
     // the repair queue: pool bit with room in the pool -> 16 chunks of a repair block per wave
     gd::ListState l = tiled_list(p);
     p.on_report(l, overflow(4, 300));
@@ -186,6 +187,50 @@ static void test_generic_rows()
     ListPolicy q; l.pool_used = 3000;
     q.on_report(l, overflow(4, 300));
     CHECK(q.repair_wide == 0u);
+}
+
+// the width of tiled lists (the guess of a build without history) follows the lists, and the row pool is sized from it
+static void test_tiled_width_and_pool()
+{
+    const size_t waves = 128 * 30208 / 64;      // the benchmark shape: 128 replicas of 30 208 slots
+    // a generic excursion grows W to 4000 (within the tiled record: the tiled path is taken again) ...
+    ListPolicy p;
+    p.W = 96;
+    CHECK(p.on_report(generic_list(p), overflow(1, 3750)));
+    CHECK(p.W == 3750u + 3750u / 16 + 8 && p.W <= GD_TILED_MAX_W && p.want_tiled(true));
+    p.W = 4000;
+    // ... and tiled builds that report lists of 40 entries bring it back by the rule of the generic rows
+    CHECK(!p.on_report(tiled_list(p), fits(3000, 40)));
+    CHECK(p.W == ListPolicy::want_width(40) && p.W == 72u);
+    p.on_report(tiled_list(p), fits(3000, 40));
+    CHECK(p.W == 72u);
+    // a build without history then asks for what lists of 40 entries need, within the stated margins: 5 chunks (KiB) per wave,
+    // want_width's quarter + 16 entries (9 chunks), the pool's eighth + 2 KiB per wave -- not for rows of 4000 entries (500 KiB per wave)
+    gd::PoolPlan pl = gd::plan_pool(0, 0, waves, p.W, false);
+    CHECK(pl.used == 9 * waves && pl.want == 9 * waves + 9 * waves / 8 + 2 * waves && pl.resize && pl.alloc_kib == pl.want + pl.want / 16);
+    CHECK(pl.want >= 5 * waves && pl.alloc_kib <= 14 * waves && pl.alloc_kib * 1024 < ((size_t)1 << 30));
+    CHECK(gd::plan_pool(0, 0, waves, 4000, false).alloc_kib * 1024 > ((size_t)32 << 30));      // (what the width left behind would have asked for)
+    // a caller's list_width within the tiled record is honoured once, then replaced by the measured need
+    ListPolicy c;
+    CHECK(c.set_tuning(0, 0, 1, 1200, false) && c.W == 1200u && c.want_tiled(true));
+    CHECK(gd::plan_pool(0, 0, waves, c.W, false).used == 150 * waves);
+    c.on_report(tiled_list(c), fits(3000, 40));
+    CHECK(c.W == 72u);
+    // a width within twice the need stays (no flapping), the default 96 too; tiled lists do not widen W (their rows are repaired)
+    ListPolicy k; k.W = 96;
+    k.on_report(tiled_list(k), fits(3000, 40)); CHECK(k.W == 96u);
+    k.on_report(tiled_list(k), fits(3000, 400)); CHECK(k.W == 96u);
+    k.W = 1000; k.on_report(tiled_list(k), fits(3000, 400)); CHECK(k.W == 1000u);      // (want 520: more than half)
+    // the pool rule: with history the use of the last build, at least a KiB per wave; an eighth + 2 KiB per wave on top;
+    // kept while it is within [want, 2 want + 4 waves], reallocated with a sixteenth more otherwise
+    pl = gd::plan_pool(10000, 20000, 1000, 4000, true);
+    CHECK(pl.used == 10000 && pl.want == 10000 + 1250 + 2000 && !pl.resize);
+    CHECK(gd::plan_pool(10000, 13249, 1000, 96, true).resize && !gd::plan_pool(10000, 13250, 1000, 96, true).resize);
+    CHECK(!gd::plan_pool(10000, 2 * 13250 + 4000, 1000, 96, true).resize && gd::plan_pool(10000, 2 * 13250 + 4001, 1000, 96, true).resize);
+    CHECK(gd::plan_pool(10000, 0, 1000, 96, true).alloc_kib == 13250 + 13250 / 16);
+    CHECK(gd::plan_pool(10, 0, 1000, 96, true).used == 1000);          // (a KiB per wave)
+    CHECK(gd::plan_pool(10, 0, 1000, 96, false).used == 12000 && gd::plan_pool(50000, 0, 1000, 96, false).used == 50000);
+    CHECK(gd::plan_pool(0, 0, 1000, 0, false).used == 1000);           // (at least one chunk per wave, as alloc_rows)
 }
 
 static void test_memory_guard()
@@ -444,6 +489,7 @@ int main()
     test_tile_class();
     test_dense_tile();
     test_generic_rows();
+    test_tiled_width_and_pool();
     test_memory_guard();
     test_class_width();
     test_interval();
