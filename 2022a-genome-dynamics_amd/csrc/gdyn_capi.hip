@@ -5,6 +5,8 @@
 // Verlet skin is VERIFIED on the device (every step checks each bead's displacement since
 // the build) and a violated chunk is rolled back and re-run with a shorter interval, so
 // the fixed build cadence never changes results (only the summation order of pair terms).
+// What the host knows about the list in use is one gd::ResidentList (gdyn_list.hpp): this file calls its transitions -- a build, the
+// caller's positions, a new topology, a rollback, a dropped list -- and assigns none of its members ("Resident list").
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -21,6 +23,7 @@
 #include "gdyn_types.h"
 #include "gdyn_once.hpp"
 #include "gdyn_policy.hpp"
+#include "gdyn_list.hpp"
 #include "gdyn_live.hpp"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
@@ -104,14 +107,12 @@ struct gd_system {
     bool has_scaling = false; double bs_init = 1, bs_tau = 1, bo_init = 1, bo_tau = 1;
     std::vector<DevCtx> hctx;      // host mirror of the device context
 
-    bool topo_dirty = true, list_valid = false, ctx_dirty = true;
+    bool topo_dirty = true, ctx_dirty = true;
     bool has_bend = false, has_bonds = false;
     uint32_t WB = 0, ncell_cap = 0;
-    uint32_t list_W = 0;           // row width the list in use was built with (pol.W may change for the next build)
     int pcur = 0, ccur = 0;
     uint32_t kernel_path = 0;      // 0 auto, 1 generic, 2 tiled
-    bool packed_ab = false, list_tiled = false;
-    bool w_packed = false;         // pos.w of the current positions holds the packed (a,b) factors (set by a build, reset by gd_set_positions / a new topology)
+    bool packed_ab = false;
     bool has_inner = false; gd_inner_sphere inner{};
     bool has_softcore_bonds = false;
     bool bonds_premixed = false;   // every bond parameter record is unmixed (AB mixing resolved per bond by finalize_topology)
@@ -121,11 +122,9 @@ struct gd_system {
     float *h_stage = nullptr;      // pinned host staging for snapshot downloads (R*N*3 floats)
     char *h_chunk = nullptr;       // pinned host block for the per-chunk readback (flags, contexts, list counts): copies into pageable
                                    // memory are staged by the runtime and cost ~20 us each
-    uint32_t list_tile_cap = 0;    // tile capacity the current list was built with (fixes its entry encoding and LDS need)
     uint32_t cpb = 1;
     gd::ListPolicy pol;            // list width, rebuild interval, tile class, list path of the builds to come (gdyn_policy.hpp)
-    uint32_t steps_since_build = 0;
-    float rv = 0;
+    gd::ResidentList list;         // the list in use and what its build left for the next one (gdyn_list.hpp)
     uint64_t rebuilds = 0, rollbacks = 0;
     uint32_t n_bond_types = 0;
     std::vector<unsigned long long> lcount;
@@ -138,17 +137,11 @@ struct gd_system {
     DevBuf<float4> pos[2], xb, fout, snap;
     DevBuf<unsigned> orig[2], slot_of, rank, members, cell_cnt, cell_start, nbr, meta, badj, flags;
     DevBuf<float> bbox_enc, bbox_w;      // box of the last build's positions (two halves: read / written), k_scatter's per-wave partials
-    int bbox_cur = 0;              // half of bbox_enc the next build reads (the other one is accumulated by it)
-    bool bbox_valid = false;       // open boxes: bbox_enc[bbox_cur] holds the bounding box of the positions the last build sorted
     DevBuf<unsigned short> nbr16; DevBuf<TileDesc> tiles;
     DevBuf<float4> rec_x0; DevBuf<uint2> rec_mo; DevBuf<unsigned char> len_prev;
     // Ragged rows of the tiled lists (BuildParams): per-wave row table, what every bead needed at the last build, the pool's cursor.
     // nbr16 IS the pool: pool KiB = nbr16.n / 512 entries.
     DevBuf<uint2> wtab, rqueue; DevBuf<unsigned short> need_prev; DevBuf<unsigned> pool;
-    bool need_valid = false;       // need_prev describes the state about to be listed well enough to predict row widths from it
-    float need_rv = 0; bool need_all_near = false;      // list radius / class mode need_prev was counted at
-    uint32_t pool_used = 0;        // KiB the last build took (its cursor's final value: the need, when the pool was full)
-    uint32_t repairs = 0;          // k_step waves the last build read back had to repair (diagnostics)
     DevBuf<float> bbox;
     DevBuf<float2> ab; DevBuf<float> mobs; DevBuf<float4> bendE; DevBuf<int4> chain;
     float mob_uniform = -1.f;
@@ -156,10 +149,8 @@ struct gd_system {
     DevBuf<unsigned long long> lcount_d; DevBuf<float> noise;
     DevBuf<unsigned long long> seeds_d;     // gd_run_desc.replica_seeds of the run in progress
     DevBuf<unsigned> dmax;          // [R] largest squared displacement since the list build (k_step keeps it; zeroed by the build)
-    float rn = 0;                   // near-class radius of the tiled list in use
     double last_dt = 0, last_kT = -1;
     int last_flags = 0;             // flags of the last gd_run (the look-ahead of a list built between runs, gd_search_pairs)
-    bool search_list = false;       // the list in use was built by gd_search_pairs at a radius beyond the force list's
     double pend_dt = 0; int pend_flags = 0;      // timestep and flags of the run that left its last callback pending (GD_RUN_DEFER_CALLBACK)
     double near_frac = 0.65;        // near-class radius = cutoff + near_frac x (list radius - cutoff)
     // gd_search_pairs: device output, counters, and the cached result of the last call
@@ -170,8 +161,6 @@ struct gd_system {
     DevBuf<uint2> ct_pairs; DevBuf<unsigned long long> ct_count; std::vector<unsigned> ct_distinct_h;
     DevBuf<unsigned long long> ct_ck[2]; DevBuf<unsigned> ct_cv[2], ct_n; DevBuf<char> ct_tmp;
     uint64_t state_serial = 1;     // bumped by everything that changes positions or the model (invalidates the cache)
-    uint64_t verified_serial = 0;  // == state_serial: the last gd_run ended on an accepted chunk, i.e. the resident list was verified for the
-                                   // positions and the cutoff an observation now sees (no bead beyond the skin margin): energies need no build
     int ocur = 0;   // which orig[] buffer is current
     // Compensated positions (small-dt / T = 0 runs, k_step's p.comp): fp32 residuals by bead index, so that the position of a bead is
     // pos + lo.  gd_set_positions fills them from the fp64 input, a compensated run keeps them, any other run invalidates them.
@@ -309,8 +298,7 @@ extern "C" int gd_set_positions(gd_system *s, const double *xyz)
     s->lo_valid = true;
     gd_launch_identity(s->orig[s->ocur].p, s->slot_of.p, s->N, s->Np, s->R, s->stream);
     HIPCHK(hipStreamSynchronize(s->stream));
-    s->list_valid = false; s->state_serial++; s->w_packed = false; s->bbox_valid = false;
-    s->need_valid = false;      // (positions from the caller: what the beads needed before says nothing about their lists now)
+    s->list.positions_set(); s->state_serial++;
     return GD_OK;
 }
 
@@ -369,7 +357,7 @@ extern "C" int gd_set_pair_softcore(gd_system *s, const gd_pair_softcore *p)
     if (!s || !p) return fail(GD_EINVAL, "gd_set_pair_softcore: NULL argument");
     if (!valid_pq(p->p_a, p->q_a) || !valid_pq(p->p_b, p->q_b)) return fail(GD_EINVAL, "gd_set_pair_softcore: unsupported softcore powers");
     if (p->sigma_a < 0 || p->sigma_b < 0) return fail(GD_EINVAL, "gd_set_pair_softcore: negative diameter");
-    s->pair = *p; s->has_pair = true; s->list_valid = false;
+    s->pair = *p; s->has_pair = true; s->list.drop();
     return GD_OK;
 }
 
@@ -491,6 +479,14 @@ extern "C" int gd_set_pair_softwell(gd_system *s, double energy, double decay, d
     return GD_OK;
 }
 
+// the box of a kernel's parameter block: periodic flag, periods and their inverses
+template <class P>
+static void set_box(const gd_system *s, P &p)
+{
+    p.periodic = s->box_kind == GD_BOX_PERIODIC;
+    for (int k = 0; k < 3; k++) { p.box[k] = (float)s->box[k]; p.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
+}
+
 // the droplet term of the step / force / energy evaluation that `p` describes (same positions, same buffers)
 static void launch_softwell(gd_system *s, const StepParams &p, int mode)
 {
@@ -502,8 +498,7 @@ static void launch_softwell(gd_system *s, const StepParams &p, int mode)
     q.lo = p.lo; q.comp = p.comp;      // (a compensated step keeps the droplet's share of mu F dt in the residuals too)
     q.eps = (float)s->sw_eps; q.inv_d2 = (float)(1.0 / (s->sw_decay * s->sw_decay)); q.rc2 = (float)(s->sw_cut * s->sw_cut);
     q.N = s->N; q.Np = s->Np; q.R = s->R; q.M = s->sw_n;
-    q.periodic = s->box_kind == GD_BOX_PERIODIC;
-    for (int k = 0; k < 3; k++) { q.box[k] = (float)s->box[k]; q.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
+    set_box(s, q);
     gd_launch_softwell(q, mode, s->stream);
 }
 
@@ -522,7 +517,7 @@ extern "C" int gd_set_scaling(gd_system *s, double bi, double bt, double oi, dou
     if (!(bt > 0) || !(ot > 0) || !(bi > 0) || !(oi > 0)) return fail(GD_EINVAL, "gd_set_scaling: init and tau must be positive");
     s->has_scaling = true; s->bs_init = bi; s->bs_tau = bt; s->bo_init = oi; s->bo_tau = ot;
     for (auto &c : s->hctx) { c.bead_scale = bi; c.bond_scale = oi; }
-    s->ctx_dirty = true; s->list_valid = false;
+    s->ctx_dirty = true; s->list.drop();
     return GD_OK;
 }
 
@@ -535,15 +530,10 @@ extern "C" int gd_get_context(gd_system *s, uint32_t r, gd_context *o)
     o->step = c.step; o->time = c.time; o->bead_scale = c.bead_scale; o->bond_scale = c.bond_scale;
     memcpy(o->semiaxes, c.semi, sizeof c.semi); memcpy(o->axial_reaction, c.react, sizeof c.react);
     o->list_entries = s->lcount[r]; o->rebuilds = s->rebuilds; o->rollbacks = s->rollbacks;
-    o->rebuild_interval = s->pol.K; o->list_radius = s->rv;
-    o->list_path = !s->list_valid && s->rebuilds == 0 ? 0u : (s->list_tiled ? 2u : 1u);
+    o->rebuild_interval = s->pol.K;
     o->callback_pending = c.pending ? 1u : 0u;
-    o->tile_capacity = (s->list_valid && s->list_tiled) ? s->list_tile_cap : 0u;
     o->compensated = s->comp_last ? 1u : 0u;
-    o->largest_tile = (s->list_valid && s->list_tiled) ? s->pol.last_need_t : 0u;
-    o->row_repairs = s->list_tiled ? s->repairs : 0u;
-    o->near_entries = s->list_tiled ? s->lcount[(size_t)s->R + r] : 0ull;
-    o->list_bytes = !s->list_valid ? 0ull : s->list_tiled ? 1024ull * s->pool_used : (uint64_t)s->list_W * s->R * s->Np * 4ull;
+    s->list.fill_context(o, s->rebuilds, s->lcount[(size_t)s->R + r], s->pol.last_need_t, (uint64_t)s->R * s->Np);
     return GD_OK;
 }
 
@@ -556,7 +546,7 @@ extern "C" int gd_begin_phase(gd_system *s, const double *semi)
         if (s->has_scaling) { c.bead_scale = s->bs_init; c.bond_scale = s->bo_init; }
         if (semi) memcpy(c.semi, semi + 3 * r, sizeof c.semi);
     }
-    s->ctx_dirty = true; s->list_valid = false;
+    s->ctx_dirty = true; s->list.drop();
     return GD_OK;
 }
 
@@ -568,7 +558,7 @@ extern "C" int gd_set_context(gd_system *s, uint32_t r, int64_t step, double bea
     DevCtx &c = s->hctx[r];
     c.step = step; c.bead_scale = bead_scale; c.bond_scale = bond_scale; c.pending = 0;
     if (semi) memcpy(c.semi, semi, sizeof c.semi);
-    s->ctx_dirty = true; s->list_valid = false;
+    s->ctx_dirty = true; s->list.drop();
     return GD_OK;
 }
 
@@ -582,7 +572,7 @@ extern "C" int gd_set_tuning(gd_system *s, const gd_tuning *t)
         (void)s->nbr.resize(0);
     if (t->near_fraction > 0) s->near_frac = t->near_fraction;
     s->kernel_path = t->kernel_path;
-    s->list_valid = false;
+    s->list.drop();
     return GD_OK;
 }
 extern "C" int gd_get_timing(gd_system *s, gd_timing *o) { if (!s || !o) return fail(GD_EINVAL, "gd_get_timing: NULL"); *o = s->timing; return GD_OK; }
@@ -718,7 +708,7 @@ static int finalize_topology(gd_system *s)
     for (uint32_t i = 1; i < N; i++) if ((float)s->mob[i] != s->mob_uniform) { s->mob_uniform = -1.f; break; }
     s->mob_max = 0;
     for (uint32_t i = 0; i < N; i++) s->mob_max = std::max(s->mob_max, s->mob[i]);
-    s->topo_dirty = false; s->list_valid = false; s->w_packed = false;
+    s->topo_dirty = false; s->list.topology_changed();
     return GD_OK;
 }
 
@@ -743,14 +733,13 @@ static void fill_common(gd_system *s, StepParams &p)
 {
     memset(&p, 0, sizeof p);
     p.N = s->N; p.Np = s->Np; p.R = s->R; p.nblk = s->nblk; p.stride = (size_t)s->R * s->Np;
-    p.periodic = s->box_kind == GD_BOX_PERIODIC;
-    for (int k = 0; k < 3; k++) { p.box[k] = (float)s->box[k]; p.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
+    set_box(s, p);
     p.pos_in = s->pos[s->pcur].p; p.pos_out = s->pos[s->pcur ^ 1].p; p.xb = s->xb.p; p.orig = s->orig[s->ocur].p;
     p.ab = s->ab.p; p.mob = s->mobs.p; p.bendE = s->bendE.p; p.mob_uniform = s->mob_uniform; p.WB = s->WB;
-    p.nbr = s->nbr.p; p.nbr16 = s->nbr16.p; p.wtab = s->wtab.p; p.tiles = s->tiles.p; p.tiled = s->list_tiled ? 1 : 0; p.packed_ab = s->packed_ab ? 1 : 0;
-    p.cpb = s->cpb; p.tile_cap = s->list_tiled ? s->list_tile_cap : s->pol.tile_cap;   // as at the build of the list in use
+    p.nbr = s->nbr.p; p.nbr16 = s->nbr16.p; p.wtab = s->wtab.p; p.tiles = s->tiles.p; p.tiled = s->list.tiled ? 1 : 0; p.packed_ab = s->packed_ab ? 1 : 0;
+    p.cpb = s->cpb; p.tile_cap = s->list.tiled ? s->list.tile_cap : s->pol.tile_cap;   // as at the build of the list in use
     p.pk = (s->has_pair && s->pair.p_a == 2 && s->pair.q_a == 3 && s->pair.p_b == 8 && s->pair.q_b == 3) ? (s->pair.mix ? 1 : 2) : 0;
-    p.meta = s->meta.p; p.rec_x0 = s->rec_x0.p; p.rec_mo = s->rec_mo.p; p.W = s->list_W; p.badj = s->badj.p; p.chain = s->chain.p;
+    p.meta = s->meta.p; p.rec_x0 = s->rec_x0.p; p.rec_mo = s->rec_mo.p; p.W = s->list.W; p.badj = s->badj.p; p.chain = s->chain.p;
     p.ctx_in = s->ctx[s->ccur].p; p.ctx_out = s->ctx[s->ccur ^ 1].p; p.flags = s->flags.p;
     // wall-reaction partials ping-pong with the context: a launch reads the previous step's partials while its blocks
     // write this step's (one buffer would let late blocks read a mix of two steps)
@@ -786,7 +775,7 @@ static void fill_common(gd_system *s, StepParams &p)
         for (int k = 0; k < 3; k++) p.ps[q].p[k] = (float)s->psrc[q].p[k];
     }
     p.has_bend = s->has_bend; p.has_bonds = s->has_bonds;
-    p.rv = s->rv; p.rn = s->sw_n ? 0.f : s->rn; p.dmax = s->dmax.p; p.term_mask = GD_TERM_ALL;      // (the droplet kernel moves beads after k_step has bounded their displacement: both list classes then)
+    p.rv = s->list.rv; p.rn = s->sw_n ? 0.f : s->list.rn; p.dmax = s->dmax.p; p.term_mask = GD_TERM_ALL;      // (the droplet kernel moves beads after k_step has bounded their displacement: both list classes then)
     if (dev_env("GDYN_FORCE_FAR")) p.rn = 0.f;      // (timing experiments: the far class in every step)
     if (dev_env("GDYN_FORCE_NEAR")) p.rn = 1e3f;    // (timing experiments with gd_debug_bench only: never the far class -- wrong forces late in an interval)
     p.fout = s->fout.p; p.epart = s->epart.p;
@@ -797,7 +786,9 @@ static void fill_common(gd_system *s, StepParams &p)
 static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tiled = true)
 {
     gd::ListPolicy &pol = s->pol;
-    const bool tiled = with_list && allow_tiled && pol.want_tiled(s->kernel_path != 1 && s->packed_ab);
+    gd::ResidentList::Build built;
+    built.rv = rv; built.with_list = with_list; built.packed_ab = s->packed_ab;
+    const bool tiled = built.tiled = with_list && allow_tiled && pol.want_tiled(s->kernel_path != 1 && s->packed_ab);
     if (with_list) {
         if (pol.W == 0) pol.W = 96;
         pol.W = (pol.W + GD_UNROLL - 1) & ~(GD_UNROLL - 1);
@@ -806,27 +797,26 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
         const size_t need = (size_t)pol.W * s->R * s->Np;
         const size_t grow = pol.W >= 512 ? need + need / 8 : need;
         if (!tiled && (s->nbr.n < need || s->nbr.n > 4 * need)) HIPCHK(s->nbr.resize(grow, false));
-        s->list_W = pol.W;
     }
+    built.W = pol.W; built.tile_cap = pol.tile_cap; built.all_near = pol.all_near;
     BuildParams b;
     memset(&b, 0, sizeof b);
     b.N = s->N; b.Np = s->Np; b.R = s->R; b.nblk = s->nblk; b.stride = (size_t)s->R * s->Np;
-    b.periodic = s->box_kind == GD_BOX_PERIODIC;
-    for (int k = 0; k < 3; k++) { b.box[k] = (float)s->box[k]; b.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
+    set_box(s, b);
     b.rv = rv; b.ncell_cap = s->ncell_cap; b.dmax = s->dmax.p;
     b.kx = b.periodic ? 1 : 2;
     if (const char *e = dev_env("GDYN_KX")) b.kx = b.periodic ? 1 : std::max(1, atoi(e));      // (experiments: cells per list radius in x)
     b.scan_segments = std::min((pol.ncell_seen + pol.ncell_seen / 4 + 8191u) / 8192u, (s->ncell_cap + 8191u) / 8192u);      // (0 before the first build: one block per replica)
     {   // near-class radius: the (look-ahead) cutoff the list radius was derived from, plus a share of the skin
         const float cutb = rv - (float)(pair_cutoff(s) * pol.skin);
-        b.rn = (cutb > 0.f && cutb < rv && !pol.all_near) ? cutb + (float)s->near_frac * (rv - cutb) : rv;
+        built.rn = b.rn = (cutb > 0.f && cutb < rv && !pol.all_near) ? cutb + (float)s->near_frac * (rv - cutb) : rv;
     }
     b.pos_in = s->pos[s->pcur].p; b.pos_out = s->pos[s->pcur ^ 1].p; b.xb = s->xb.p;
     b.orig_in = s->orig[s->ocur].p; b.orig_out = s->orig[s->ocur ^ 1].p; b.slot_of = s->slot_of.p;
     b.rank = s->rank.p; b.members = s->members.p; b.cell_cnt = s->cell_cnt.p; b.cell_start = s->cell_start.p;
     b.bbox = s->bbox.p; b.grid = s->grid.p;
-    b.bbox_cur = s->bbox_enc.p + (size_t)s->bbox_cur * s->R * 6; b.bbox_next = s->bbox_enc.p + (size_t)(s->bbox_cur ^ 1) * s->R * 6;
-    b.warm = (b.periodic || s->bbox_valid) ? 1 : 0; b.bbox_w = s->bbox_w.p;
+    b.bbox_cur = s->bbox_enc.p + (size_t)s->list.bbox_cur * s->R * 6; b.bbox_next = s->bbox_enc.p + (size_t)(s->list.bbox_cur ^ 1) * s->R * 6;
+    b.warm = (b.periodic || s->list.bbox_valid) ? 1 : 0; b.bbox_w = s->bbox_w.p;
     b.ab_o = s->ab_o.p; b.mob_o = s->mob_o.p; b.bendE_o = s->bendE_o.p; b.psmask_o = s->psmask_o.p;
     b.badj_o = s->badj_o.p; b.bdeg_o = s->bdeg_o.p; b.chain_o = s->has_bend ? s->chain_o.p : nullptr; b.WB = s->WB;
     b.ab = s->ab.p; b.mob = s->mobs.p; b.bendE = s->bendE.p; b.badj = s->badj.p; b.has_bend = s->has_bend ? 1 : 0;
@@ -834,7 +824,7 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
     b.chain = s->chain.p; b.nbr = (with_list && !tiled) ? s->nbr.p : nullptr; b.nbr16 = tiled ? s->nbr16.p : nullptr;
     b.meta = s->meta.p; b.rec_x0 = s->rec_x0.p; b.rec_mo = s->rec_mo.p; b.len_prev = s->len_prev.p; b.W = pol.W; b.tiles = s->tiles.p; b.tiled = tiled ? 1 : 0;
     b.packed_ab = s->packed_ab ? 1 : 0; b.cpb = s->cpb; b.tile_cap = pol.tile_cap;
-    b.w_valid = (s->packed_ab && s->w_packed) ? 1 : 0;
+    b.w_valid = (s->packed_ab && s->list.w_packed) ? 1 : 0;
     b.flags = s->flags.p; b.lcount = s->lcount_d.p; b.dbg = (unsigned long long *)s->fout.p;
     b.wtab = s->wtab.p; b.need_prev = s->need_prev.p; b.pool = s->pool.p; b.rqueue = s->rqueue.p; b.rq_cap = (unsigned)s->rqueue.n; b.rq_grid = pol.repair_wide > 0 ? b.rq_cap : std::min(GD_REPAIR_GRID, b.rq_cap);
     if (tiled) {
@@ -844,23 +834,19 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
         // build with an eighth + a KiB per wave to spare (the use is read back with every chunk; the builds in between grow with the
         // lists); a pool that turns out too small is flagged, its cursor has counted the need, and the chunk is rolled back.
         const size_t waves = (size_t)s->R * s->Np / 64;
-        const bool predict = s->need_valid && s->need_all_near == pol.all_near && s->need_rv > 0 && std::fabs(rv / s->need_rv - 1.f) <= 0.02f;
+        const bool predict = built.predicted = s->list.predicts(rv, pol.all_near);
         auto pool_kib = [&]() { return (size_t)(s->nbr16.n / 512); };
-        const gd::PoolPlan plan = gd::plan_pool(s->pool_used, pool_kib(), waves, pol.W, predict);      // (the rule: gdyn_policy.hpp)
-        const size_t used = plan.used;
+        const gd::PoolPlan plan = gd::plan_pool(s->list.pool_used, pool_kib(), waves, pol.W, predict);      // (the rule: gdyn_policy.hpp)
         if (plan.resize) HIPCHK(s->nbr16.resize(plan.alloc_kib * 512, false));      // (not preserved: the list in it is about to be rebuilt)
         if (dev_env("GDYN_DEBUG") && dev_env("GDYN_DEBUG")[0] == '2')
-            fprintf(stderr, "[gdyn] build %llu: %s, rows used %u KiB, pool %zu KiB, rv %.4f\n", (unsigned long long)s->rebuilds, predict ? "predicted" : "no history", s->pool_used, pool_kib(), rv);
-        if (!predict) s->pool_used = (uint32_t)std::min<size_t>(used, 0xffffffffu);      // (the guess stands in until a chunk's readback brings the real use)
+            fprintf(stderr, "[gdyn] build %llu: %s, rows used %u KiB, pool %zu KiB, rv %.4f\n", (unsigned long long)s->rebuilds, predict ? "predicted" : "no history", s->list.pool_used, pool_kib(), rv);
+        built.pool_guess = (uint32_t)std::min<size_t>(plan.used, 0xffffffffu);
         b.predict = predict ? 1 : 0; b.nbr16 = s->nbr16.p; b.pool_cap = (unsigned)std::min<size_t>(pool_kib(), 0xffffffffu);
-        s->need_valid = true; s->need_rv = rv; s->need_all_near = pol.all_near;
     }
+    s->list.build_enqueued(built);
     gd_launch_build(b, s->stream);
-    s->bbox_cur ^= 1; s->bbox_valid = tiled;      // (the box of the positions this build sorted, reduced by k_tiles: the next build's grid)
-    s->list_tiled = tiled; s->list_tile_cap = pol.tile_cap;
-    s->w_packed = s->packed_ab;
     s->pcur ^= 1; s->ocur ^= 1;
-    s->rv = rv; s->rn = b.rn; s->steps_since_build = 0; s->rebuilds++;
+    s->rebuilds++;
     s->timing.rebuild_launches++;
     return GD_OK;
 }
@@ -875,8 +861,7 @@ static int clear_flags(gd_system *s)
 // The list in use and the handle, as the list policy sees them
 static gd::ListState list_state(const gd_system *s)
 {
-    return {pair_cutoff(s), s->rv, s->list_tiled, s->list_tile_cap, s->list_W, s->pool_used, s->nbr16.n / 512, (double)s->R * (double)s->Np,
-            s->sw_n != 0, s->kernel_path != 1 && s->packed_ab};
+    return s->list.state(pair_cutoff(s), s->nbr16.n / 512, (double)s->R * (double)s->Np, s->sw_n != 0, s->kernel_path != 1 && s->packed_ab);
 }
 
 // A build or a chunk of gd_run: what it ran and the state before it (gd_run), what the device reported (read_chunk)
@@ -907,7 +892,7 @@ static int read_chunk(gd_system *s, Chunk &c)
     c.ctx.resize(s->R); memcpy(c.ctx.data(), s->h_chunk + nf, nc); memcpy(s->lcount.data(), s->h_chunk + nf + nc, nl);
     c.dmax2 = 0; for (uint32_t r = 0; r < s->R; r++) { float d2; memcpy(&d2, s->h_chunk + nf + nc + nl + r * sizeof(float), 4); c.dmax2 = std::max(c.dmax2, d2); }
     unsigned used[4]; memcpy(used, s->h_chunk + nf + nc + nl + nd, 16);
-    if (s->list_tiled && used[0] > 0) { s->pool_used = std::max(used[0], used[1]); s->repairs = used[2]; }
+    s->list.chunk_read(used);
     if (c.rep.tile_over && dev_env("GDYN_DEBUG")) {      // (developer builds: the grids of a tile overflow)
         std::vector<GridP> gp(s->R);
         (void)hipMemcpy(gp.data(), s->grid.p, s->R * sizeof(GridP), hipMemcpyDeviceToHost);
@@ -956,10 +941,10 @@ static float list_radius(gd_system *s, const gd_run_desc *run, uint32_t ahead)
 
 static int ensure_fresh_list(gd_system *s)
 {
-    if (s->list_valid && (s->steps_since_build == 0 || s->verified_serial == s->state_serial)) return GD_OK;
+    if (s->list.fresh(s->state_serial)) return GD_OK;
     s->pol.take_pending_skin(pair_cutoff(s));
     GDCHK(build_now(s, list_radius(s, nullptr, 0), pair_cutoff(s) > 0));
-    s->list_valid = true; s->search_list = false;
+    s->list.enter_use(false);
     return GD_OK;
 }
 
@@ -1031,7 +1016,7 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
     // snapshot for rollback: positions in bead order + context
     gd_launch_gather_positions(s->pos[s->pcur].p, s->slot_of.p, s->snap.p, s->N, s->Np, s->R, 0, s->stream);
     if (comp) HIPCHK(hipMemcpyAsync(s->snap_lo.p, s->lo.p, RN * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-    c.snap_ctx = s->hctx; c.snap_w_packed = s->w_packed;
+    c.snap_ctx = s->hctx; c.snap_w_packed = s->list.w_packed;
     GDCHK(clear_flags(s));
     StepParams p;
     // The scales a callback sets are pure functions of the step index (simulation_driver_interphase.cc:42-43): when every
@@ -1053,18 +1038,17 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
     int64_t k = 0;
     // (an interval that runs on a contact-search list has a wider skin than the force lists: its displacement is no measure
     // for the interval of those)
-    c.on_search_list = s->list_valid && s->search_list;
+    c.on_search_list = s->list.valid && s->list.search_list;
     while (k < chunk) {
-        if (!s->list_valid || s->steps_since_build >= s->pol.K) {
+        if (!s->list.valid || s->list.steps_since_build >= s->pol.K) {
             s->pol.take_pending_skin(pair_cutoff(s));
             hipEvent_t e1 = get_event(s, nev++);
             GDCHK(enqueue_build(s, list_radius(s, run, (uint32_t)(k + s->pol.K)), with_list));
-            s->search_list = false;
+            s->list.enter_use(false);
             HIPCHK(hipEventRecord(e1, s->stream));
             c.spans.push_back({nev - 1, 1});
-            s->list_valid = true;
         }
-        const int64_t n = std::min<int64_t>((int64_t)s->pol.K - s->steps_since_build, chunk - k);
+        const int64_t n = std::min<int64_t>((int64_t)s->pol.K - s->list.steps_since_build, chunk - k);
         hipEvent_t e1 = get_event(s, nev++);
         for (int64_t q = 0; q < n; q++) {
             fill_common(s, p);
@@ -1075,7 +1059,7 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
             host_scales(p, k + q);
             // the interval adaptation needs the displacement at K steps since the build: recorded at the last force
             // evaluation of a COMPLETE interval only (a chunk that ends mid-interval records nothing and adapts nothing)
-            p.record_disp = (s->steps_since_build + (uint32_t)q + 1u == s->pol.K);
+            p.record_disp = (s->list.steps_since_build + (uint32_t)q + 1u == s->pol.K);
             c.full_interval |= p.record_disp != 0;
             gd_launch_step(p, GD_MODE_STEP, s->stream);
             if (s->sw_n) launch_softwell(s, p, 0);
@@ -1084,7 +1068,7 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
         HIPCHK(hipEventRecord(e1, s->stream));
         c.spans.push_back({nev - 1, 0});
         s->timing.step_launches += (uint64_t)n;
-        s->steps_since_build += (uint32_t)n;
+        s->list.stepped((uint32_t)n);
         k += n;
     }
     // apply the callback of the last step (unless the caller wants to observe the state its callback sees first)
@@ -1111,9 +1095,8 @@ static int rollback_chunk(gd_system *s, const Chunk &c, bool over, bool comp, in
                             (size_t)s->N * sizeof(float4), s->R, hipMemcpyDeviceToDevice, s->stream));
     gd_launch_identity(s->orig[s->ocur].p, s->slot_of.p, s->N, s->Np, s->R, s->stream);
     if (comp) HIPCHK(hipMemcpyAsync(s->lo.p, s->snap_lo.p, RN * sizeof(float4), hipMemcpyDeviceToDevice, s->stream));
-    s->hctx = c.snap_ctx; s->ctx_dirty = true; s->w_packed = c.snap_w_packed;
+    s->hctx = c.snap_ctx; s->ctx_dirty = true; s->list.rolled_back(c.snap_w_packed);
     GDCHK(upload_ctx(s));
-    s->list_valid = false; s->bbox_valid = false;      // (the box the abandoned builds recorded may be that of positions stepped on incomplete lists)
     s->pol.hold_for_retries();      // (the width and the interval before the chunk's first rollback: a chunk given up returns them)
     if (retries > 24) {
         s->pol.retries_over(true);
@@ -1145,7 +1128,7 @@ static int accept_chunk(gd_system *s, const gd_run_desc *run, const Chunk &c)
     unsigned long long L = 0; for (uint32_t r = 0; r < s->R; r++) L += s->lcount[r];
     s->timing.list_entries_visited += L * (uint64_t)c.steps;   // L of the last build, per step
     const gd::Accepted a{ms, c.steps, c.rep.maxd2, cut_scale(s, nullptr, 0), c.full_interval, c.on_search_list};
-    if (s->pol.on_accepted(list_state(s), a, [&](uint32_t ahead) { return cut_scale(s, run, ahead); })) s->list_valid = false;
+    if (s->pol.on_accepted(list_state(s), a, [&](uint32_t ahead) { return cut_scale(s, run, ahead); })) s->list.drop();
     return GD_OK;
 }
 
@@ -1218,11 +1201,8 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
     // the resident list then serves gd_compute_energy as it is (not with the droplet term: its kernel moves beads behind k_step's
     // check).  The positions the last step WROTE are covered by the running bound of the tiled path (dmax, read back with the chunk)
     // only: the list serves an observation if that bound is inside the margin too.  The generic path's observations build a list.
-    if (run->steps > 0 && with_list && s->list_valid && !s->sw_n && (!(run->flags & GD_RUN_UPDATE_SCALES) || (run->flags & GD_RUN_DEFER_CALLBACK))) {
-        const double cut_obs = pair_cutoff(s) * cut_scale(s, nullptr, 0);
-        const double lim = 0.5 * ((double)s->rv - cut_obs);
-        if (s->list_tiled && lim > 0 && (double)last_dmax2 <= lim * lim) s->verified_serial = s->state_serial;
-    }
+    const bool settled = run->steps > 0 && with_list && !s->sw_n && (!(run->flags & GD_RUN_UPDATE_SCALES) || (run->flags & GD_RUN_DEFER_CALLBACK));
+    s->list.run_ended(settled, pair_cutoff(s) * cut_scale(s, nullptr, 0), last_dmax2, s->state_serial);
     return GD_OK;
 }
 
@@ -1287,7 +1267,7 @@ static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, 
     HIPCHK(count.resize(2 * (size_t)nrep));
     cnt.assign(2 * (size_t)nrep, 0ull);
     for (int attempt = 0; attempt < 6; attempt++) {
-        if (!s->list_valid || !((float)dcut <= s->rv) || s->list_W == 0) {
+        if (!s->list.serves_search(dcut)) {
             // the list stays in use as the force list of the next run: built with that run's look-ahead (a growing bead
             // scale over the rest of an interval), like the builds inside gd_run
             gd_run_desc ahead{};
@@ -1296,17 +1276,16 @@ static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, 
             const float rv_force = with_list ? list_radius(s, s->last_dt > 0 ? &ahead : nullptr, s->pol.K) : 0.f;
             const float rv_search = (float)(dcut * (1.0 + 1e-6));
             GDCHK(build_now(s, std::max(rv_force, rv_search), true, true, rv_search));
-            s->list_valid = true; s->search_list = rv_search > rv_force;
+            s->list.enter_use(rv_search > rv_force);
         }
-        const double lim = 0.5 * ((double)s->rv - dcut);
+        const double lim = 0.5 * ((double)s->list.rv - dcut);
         PairsP q;
         memset(&q, 0, sizeof q);
-        q.pos = s->pos[s->pcur].p; q.x0 = s->list_tiled ? s->rec_x0.p : s->xb.p; q.rec_mo = s->rec_mo.p; q.meta = s->meta.p;
+        q.pos = s->pos[s->pcur].p; q.x0 = s->list.tiled ? s->rec_x0.p : s->xb.p; q.rec_mo = s->rec_mo.p; q.meta = s->meta.p;
         q.orig = s->orig[s->ocur].p; q.nbr = s->nbr.p; q.nbr16 = s->nbr16.p; q.tiles = s->tiles.p; q.wtab = s->wtab.p;
-        q.N = s->N; q.Np = s->Np; q.nblk = s->nblk; q.r = r0; q.nrep = nrep; q.W = s->list_W;
-        q.tiled = s->list_tiled ? 1 : 0; q.s16 = (s->list_tiled && gd_tile_s16(s->list_tile_cap)) ? 1 : 0;
-        q.periodic = s->box_kind == GD_BOX_PERIODIC;
-        for (int k = 0; k < 3; k++) { q.box[k] = (float)s->box[k]; q.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
+        q.N = s->N; q.Np = s->Np; q.nblk = s->nblk; q.r = r0; q.nrep = nrep; q.W = s->list.W;
+        q.tiled = s->list.tiled ? 1 : 0; q.s16 = (s->list.tiled && gd_tile_s16(s->list.tile_cap)) ? 1 : 0;
+        set_box(s, q);
         q.dcut2 = (float)(dcut * dcut); q.lim2 = (float)(lim * lim);
         q.out = out.p; q.cap = out.n / nrep; q.count = count.p;
         q.dmax = s->dmax.p;
@@ -1317,7 +1296,7 @@ static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, 
         HIPCHK(hipGetLastError());
         unsigned long long moved = 0, most = 0;
         for (uint32_t y = 0; y < nrep; y++) { most = std::max(most, cnt[2 * y]); moved |= cnt[2 * y + 1]; }
-        if (moved) { s->list_valid = false; continue; }                  // a bead moved beyond the margin: fresh list
+        if (moved) { s->list.drop(); continue; }                      // a bead moved beyond the margin: fresh list
         if (most > q.cap) { HIPCHK(out.resize((size_t)nrep * (size_t)(most + most / 8 + 64), false)); continue; }
         return GD_OK;
     }
