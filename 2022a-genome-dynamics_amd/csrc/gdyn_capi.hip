@@ -1079,7 +1079,17 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
         host_scales(p, chunk);
         gd_launch_finalize(p, 0, s->stream);
         s->ccur ^= 1;
-    } else { s->pend_dt = run->timestep; s->pend_flags = run->flags; }
+    } else {
+        s->pend_dt = run->timestep; s->pend_flags = run->flags;
+        // axial_reaction is that of the last step's force evaluation, as an observer of the deferred state reads it: folded into the
+        // context IN PLACE (one wave per replica reads and writes its own entry), so that context and partials do not swap sides and
+        // the pending callback still finds the last step's partials where it reads them
+        if (s->has_wall) {
+            fill_common(s, p);
+            p.ctx_out = s->ctx[s->ccur].p;
+            gd_launch_finalize(p, 1, s->stream);
+        }
+    }
     c.ev_end = nev;
     HIPCHK(hipEventRecord(get_event(s, nev++), s->stream));
     return GD_OK;
@@ -1247,13 +1257,15 @@ extern "C" int gd_compute_forces(gd_system *s, uint32_t mask, double *forces)
     HIPCHK(hipMemsetAsync(p.react_out, 0, s->react_part[0].n * sizeof(float4), s->stream));
     gd_launch_step(p, GD_MODE_FORCE, s->stream);
     if (s->sw_n && (mask & GD_TERM_PAIR)) launch_softwell(s, p, 1);
-    if (s->has_wall) { p.react_in = p.react_out; gd_launch_finalize(p, 1, s->stream); s->ccur ^= 1; }
+    // (a mask without the wall leaves axial_reaction as the last evaluation of the wall set it: no fold of the zeroed partials)
+    const bool fold = s->has_wall && (mask & GD_TERM_WALL);
+    if (fold) { p.react_in = p.react_out; gd_launch_finalize(p, 1, s->stream); s->ccur ^= 1; }
     const size_t RN = (size_t)s->R * s->N;
     std::vector<float4> h(RN);
     HIPCHK(hipMemcpyAsync(h.data(), s->fout.p, RN * sizeof(float4), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     for (size_t i = 0; i < RN; i++) { forces[3 * i] = h[i].x; forces[3 * i + 1] = h[i].y; forces[3 * i + 2] = h[i].z; }
-    if (s->has_wall) GDCHK(download_ctx(s));
+    if (fold) GDCHK(download_ctx(s));
     return GD_OK;
 }
 

@@ -219,7 +219,9 @@ typedef struct {
     double   time;           /* step * timestep of the last run */
     double   bead_scale, bond_scale;
     double   semiaxes[3];
-    double   axial_reaction[3];   /* stats.axial_reaction of the last force evaluation */
+    double   axial_reaction[3];   /* stats.axial_reaction of the last force evaluation that included the wall: the last step of
+                                     gd_run (also when its callback is left pending, GD_RUN_DEFER_CALLBACK) or a gd_compute_forces
+                                     whose mask has GD_TERM_WALL; a gd_compute_forces without it leaves the value as it was */
     /* diagnostics (not part of the reference's state) */
     uint64_t list_entries;   /* L: directed neighbour-list entries currently stored */
     uint64_t rebuilds;       /* neighbour-list builds since creation */
@@ -313,7 +315,7 @@ enum {
 /* md::system::compute_energy() (simulation_driver_interphase.cc:20-22): per replica. */
 int gd_compute_energy(gd_system *sys, uint32_t term_mask, double *energy /* (R) */);
 /* Forces on the current positions under the current context, (R,N,3) fp64;
- * also refreshes axial_reaction. Parity/diagnostic entry point. */
+ * also refreshes axial_reaction when term_mask has GD_TERM_WALL. Parity/diagnostic entry point. */
 int gd_compute_forces(gd_system *sys, uint32_t term_mask, double *forces);
 
 /* md::neighbor_searcher<Box>{box,dcut}.set_points().search(out)

@@ -6,6 +6,9 @@ builders here return configured :class:`System` handles for any library (hip or 
 the total and the branches kernels get wrong are reached:
 
   perturbed(lib, name)   a util.CASES workload, R = 2, every replica jittered differently (and its scales set per replica)
+  pressed_genome(lib, n_beads, n_replicas)
+                         the perturbed genome inside a tighter wall with three unequal semiaxes per replica: hundreds of beads on the
+                         wall, on both sides of the surface, and an axial reaction of the size of spring * semiaxes
   composite(lib)         an open-box model with all six terms (pair, bond, bend, point, wall, dynamic), R = 2
   chromatin_1kb_images(lib, shifted, shape)
                          the 1 kb force field with beads shifted by whole periods, so that pair neighbours and glue pairs straddle
@@ -47,10 +50,36 @@ def perturbed(lib, name, n_replicas=2, seed=7, **over):
     x = f32(x + JITTER * rng.normal(size=x.shape))
     s.set_positions(x)
     if name == "genome":
+        s.initial_semiaxes = [tuple(s.context(r).semiaxes) for r in range(n_replicas)]
         for r in range(n_replicas):
             bs, os_, w = SCALES[r % len(SCALES)]
-            s.set_context(r, 0, bs, os_, semiaxes=[w * a for a in s.context(r).semiaxes])
+            s.set_context(r, 0, bs, os_, semiaxes=[w * a for a in s.initial_semiaxes[r]])
     return s
+
+
+# the pressed genome: replica r's semiaxes as fractions of the workload's initial radius -- unequal, and tight enough that hundreds
+# of beads press on the wall from both sides and the axial reaction is a sizeable part of spring * semiaxes (the wall ODE's other term)
+PRESSED = (0.985, 0.975, 0.965)
+PRESSED_STEP = 0.003
+WALL_SPRING, WALL_MOBILITY = 1.0e4, 1.0e-4       # workloads.genome_interphase and composite(): semiaxes_spring (each axis), mobility
+
+
+def pressed_genome(lib, n_beads=1500, n_replicas=2, seed=7):
+    """perturbed(lib, "genome") at `n_beads`, the wall of replica r set to PRESSED * (1 - PRESSED_STEP r) times the initial radius
+    (the per-replica scales of SCALES kept): the state at which the wall's axial reaction and semiaxis ODE are compared."""
+    s = perturbed(lib, "genome", n_replicas=n_replicas, seed=seed, n_beads=n_beads)
+    for r in range(n_replicas):
+        bs, os_, _ = SCALES[r % len(SCALES)]
+        s.set_context(r, 0, bs, os_, semiaxes=[f * (1.0 - PRESSED_STEP * r) * a for f, a in zip(PRESSED, s.initial_semiaxes[r])])
+    return s
+
+
+def nudged(x, seed):
+    """x (fp32-exact) with every coordinate moved by one fp32 ulp, up or down at random: the smallest change of the input a device that
+    holds fp32 coordinates can see."""
+    x32 = np.asarray(x).astype(np.float32)
+    up = np.random.default_rng(seed).random(x32.shape) < 0.5
+    return np.where(up, np.nextafter(x32, np.float32(np.inf)), np.nextafter(x32, np.float32(-np.inf))).astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------------ the composite model

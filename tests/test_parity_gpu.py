@@ -455,7 +455,8 @@ def test_full_size_1kb_vs_oracle(hip, oracle):
 def test_wall_context_on_a_grid_larger_than_the_chip(hip, oracle):
     """30 000 beads x 16 replicas = 944 blocks, more than are resident at once (256 CUs x 3): the per-step callback
     state (semiaxes, axial reaction: reduced from per-block partials by every block's prologue) must not depend on
-    which blocks of the previous step have already been replaced -- the partials are double-buffered."""
+    which blocks of the previous step have already been replaced -- the partials are double-buffered.
+    (No bead is on the wall in this state: the reaction compared here is zero.  test_wall_context_gpu.py runs the pressed version.)"""
     R = 16
     sh, info = wl.genome_interphase(hip, n_beads=30000, n_replicas=R, bead_scale_init=0.9)
     so, _ = wl.genome_interphase(oracle, n_beads=30000, n_replicas=R, bead_scale_init=0.9)

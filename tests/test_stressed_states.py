@@ -5,11 +5,15 @@
    both sides of the wall, pair distances from 0 to the cutoff, images across the box faces) are populated.  These keep
    tests/test_term_parity_gpu.py from going vacuous the way the golden states are (test_golden_states_leave_terms_idle).
 2. Per-term finite differences of the fp64 oracle at those states: the reference the device is held to is -grad U term by term.
+   The wall's axial reaction: the production-size initial states leave it at zero (the record of why pressed_genome exists), the pressed
+   genome presses on the wall from both sides, and the oracle's reaction equals its numpy restatement (tests/wall_restatement.py) --
+   the reference tests/test_wall_context_gpu.py holds the device to.
 3. The softcore-bond rule (include/gdyn.h): mix / scale_by_bond_scale are rejected; the accepted form is k_a (1-(r/l_a)^p)^q."""
 import numpy as np
 import pytest
 
 import stressed_states as ss
+import wall_restatement as wr
 from util import CASES, build, g
 
 
@@ -126,6 +130,76 @@ def test_1kb_images_straddle_the_box_faces(oracle, shape):
     for term in (g.TERM_PAIR,):
         assert np.abs(s.forces(term) - base.forces(term)).max() <= 1e-9 * np.abs(base.forces(term)).max()
     assert np.abs(s.forces(g.TERM_BOND)).max() > 100 * np.abs(base.forces(g.TERM_BOND)).max()
+
+
+# ------------------------------------------------------------------------------------------------ the wall's axial reaction
+
+@pytest.mark.parametrize("n_beads,bead_scale_init", [(30000, 0.9), (62178, 0.8)])
+def test_production_size_initial_states_leave_the_wall_idle(oracle, n_beads, bead_scale_init):
+    """Why pressed_genome exists (as test_golden_states_leave_terms_idle for the terms): in the initial states the large device tests
+    run from (test_parity_gpu.py: the 944-block wall context test, the many-tiles trajectory, the full-size and split-step
+    comparisons) no bead is within the wall's reach, the axial reaction is exactly zero and stays zero over the 12 noisy steps with
+    wall dynamics those tests take -- their semiaxes are driven by the spring alone, and their reaction compares 0 with 0."""
+    s, info = ss.g_wl().genome_interphase(oracle, n_beads=n_beads, bead_scale_init=bead_scale_init)
+    assert np.linalg.norm(s.positions()[0], axis=-1).max() < info["wall_radius"]
+    acted, _ = wr.on_the_wall(s)[0]
+    assert acted.sum() == 0 and tuple(s.context().axial_reaction) == (0.0, 0.0, 0.0)
+    s.begin_phase()
+    s.run(12, info["timestep"], info["temperature"], seed=20220101, flags=g.RUN_UPDATE_SCALES | g.RUN_WALL_DYNAMICS)
+    assert tuple(s.context().axial_reaction) == (0.0, 0.0, 0.0)
+    decay = (1 - info["timestep"] * ss.WALL_MOBILITY * ss.WALL_SPRING) ** 12          # the spring alone
+    assert np.allclose(np.array(s.context().semiaxes), info["wall_radius"] * decay, rtol=1e-13, atol=0)
+
+
+# What the pressed genome must reach, per replica, at 33 280 beads; the beads on the wall are a surface layer, so at n beads their number
+# goes as (n / 33 280)^(2/3) and the reaction against spring * semiaxes (semiaxes ~ n^(1/3)) as (n / 33 280)^(1/3): the figures for
+# 1 500 beads are these, scaled and rounded up
+PRESSED_REACH = {33280: dict(on_wall=500, per_side=30, reaction=0.2), 1500: dict(on_wall=64, per_side=4, reaction=0.072)}
+
+
+@pytest.mark.parametrize("n_beads", list(PRESSED_REACH))
+def test_pressed_genome_presses_on_the_wall(oracle, n_beads):
+    reach = PRESSED_REACH[n_beads]
+    assert reach["on_wall"] >= 500 * (n_beads / 33280) ** (2 / 3) and reach["per_side"] >= 30 * (n_beads / 33280) ** (2 / 3)
+    assert reach["reaction"] >= 0.2 * (n_beads / 33280) ** (1 / 3)
+    s = ss.pressed_genome(oracle, n_beads, 2)
+    x = s.positions()
+    assert np.array_equal(x, ss.f32(x)) and np.abs(x[0] - x[1]).max() > 0.05
+    react, S, reported = wr.oracle_reaction(s)
+    semis = []
+    for r, (acted, C) in enumerate(wr.on_the_wall(s)):
+        semi = np.array(s.context(r).semiaxes)
+        semis.append(semi)
+        assert len(set(semi)) == 3                                                   # three unequal semiaxes
+        assert (s.context(r).bead_scale, s.context(r).bond_scale) == ss.SCALES[r][:2]
+        assert acted.sum() >= reach["on_wall"], (r, acted.sum())
+        assert (acted & (C > 0)).sum() >= reach["per_side"] and (acted & (C < 0)).sum() >= reach["per_side"], r
+        assert np.all(react[r] >= reach["reaction"] * ss.WALL_SPRING * semi), (r, react[r] / (ss.WALL_SPRING * semi))
+        # every bead pushes every semiaxis outwards: the contributions share one sign, |react_k| is its own rounding scale
+        assert np.all(np.abs(S[r] - react[r]) <= 1e-12 * react[r]), r
+    assert np.all(semis[1] < semis[0])                                               # and a tighter wall for replica 1
+    # the wall is a sizeable part of the total force (the coverage rule of every stressed state)
+    _assert_covered(s, ss.CONFIGURED["genome"])
+
+
+def _restated(oracle, state):
+    if state == "golden_genome":
+        s, *_ = build(oracle, "genome")
+        assert len(set(s.context().semiaxes)) == 1                                   # a sphere: the closed form
+        x, F = s.positions(), s.forces(g.TERM_WALL)
+        return np.array([wr.reaction_on_a_sphere(x[0], F[0])]), np.array([tuple(s.context().axial_reaction)])
+    s = ss.composite(oracle) if state == "composite" else ss.pressed_genome(oracle, int(state), 2)
+    react, _, reported = wr.oracle_reaction(s)
+    return react, reported
+
+
+@pytest.mark.parametrize("state", ["1500", "33280", "composite", "golden_genome"])
+def test_oracle_axial_reaction_equals_its_restatement(oracle, state):
+    """The reference the device's reaction is held to, against -sum_i F_wall,ik q_ik / a_k formed in numpy from the oracle's wall forces
+    and positions (tests/wall_restatement.py): 1e-12 of the reaction (a sum of up to 1 400 one-signed terms in another order)."""
+    react, reported = _restated(oracle, state)
+    assert np.all(np.abs(reported) > 0)
+    assert np.all(np.abs(react - reported) <= 1e-12 * np.abs(reported)), (react - reported) / reported
 
 
 # ------------------------------------------------------------------------------------------------ per-term finite differences
