@@ -25,6 +25,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_flow.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_live.hpp"
 #include "gdyn_types.h"
 
 using namespace gd;
@@ -334,6 +335,29 @@ int check_radius(double r, const char *who)
 }
 
 }  // namespace
+
+// ---- the seams of the live bridge (gdyn_live.hpp)
+int gd_flow_device(const gd_flow *h) { return h->device; }
+
+int gd_flow_history_begin(gd_flow *h, const char *who, uint32_t frames, uint32_t n_beads, double **x, hipStream_t *stream)
+{
+    if (frames == 0 || n_beads == 0) return fail(GD_EINVAL, "%s: empty history (%u frames of %u beads)", who, frames, n_beads);
+    if (n_beads > (1u << 28)) return fail(GD_EINVAL, "%s: %u beads exceed 2^28", who, n_beads);
+    HIPCHK(hipSetDevice(h->device));
+    h->have_velocities = false;
+    h->F = 0;      // x is about to be overwritten: no history until gd_flow_history_end
+    HIPCHK(h->x.ensure((size_t)frames * n_beads * 3));
+    *x = h->x.p;
+    *stream = h->stream;
+    return GD_OK;
+}
+
+void gd_flow_history_end(gd_flow *h, uint32_t frames, uint32_t n_beads, bool ok)
+{
+    h->F = ok ? frames : 0;
+    h->N = ok ? n_beads : 0;
+    h->pos = h->x.p;
+}
 
 extern "C" {
 

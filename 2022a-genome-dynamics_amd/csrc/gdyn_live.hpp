@@ -7,6 +7,7 @@
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_cmap.h"
+#include "../../include/gdyn_flow.h"
 #include "../../include/gdyn_lamina.h"
 #include "../../include/gdyn_rdf.h"
 #include "gdyn_types.h"
@@ -41,3 +42,9 @@ GD_SEAM int gd_lamina_contacts_dev(gd_lamina *h, const char *who, const float *x
 // gd_rdf_counts on float32 frames that lie on the handle's device; n_points must equal the selection's
 GD_SEAM int gd_rdf_counts_dev(gd_rdf *h, const char *who, const float *xyz_dev, uint32_t frames, uint32_t n_points, const double box[3],
                               double bin_width, double max_distance, uint64_t *counts_out);
+GD_SEAM int gd_flow_device(const gd_flow *h);
+// a device-side gd_flow_set_history in two halves.  begin: the argument checks of the host-fed call, earlier velocities forgotten,
+// and the handle's fp64 (frames, n_beads, 3) copy with the handle's stream, for the caller to fill there.  end, once that stream is
+// idle: the handle holds the history, or none when the caller found it unusable (ok == false).
+GD_SEAM int gd_flow_history_begin(gd_flow *h, const char *who, uint32_t frames, uint32_t n_beads, double **x, hipStream_t *stream);
+GD_SEAM void gd_flow_history_end(gd_flow *h, uint32_t frames, uint32_t n_beads, bool ok);

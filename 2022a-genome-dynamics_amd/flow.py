@@ -6,6 +6,7 @@ analyze_grid_flow): the grid mesh, the stored config JSON and its hashed name.
     pos, vel = fl.velocities(history, smoothing=0, delay=1)   # history: (F, N, 3) float32 or float64
     flows = fl.particle(0.6)                                  # (F, N, 3) float32
     flows, coverage = fl.grid(0.6, points)                    # (F, G, 3) float32, (F, G) int32
+    pos, vel = fl.velocities_from(recorder, replica)          # the same from frames a live.History recorded on the device
 """
 from __future__ import annotations
 
@@ -58,6 +59,17 @@ class Flow(Handle):
         h, is64 = as_frames(h)
         F, N, _ = h.shape
         self._check(self.dll.gd_flow_set_history(self._h, h.ctypes.data, F, N, int(is64)))
+        pos = np.empty((F, N, 3), np.float64)
+        vel = np.empty((F, N, 3), np.float64)
+        self._check(self.dll.gd_flow_velocities(self._h, int(smoothing or 0), int(delay), pos.ctypes.data, vel.ctypes.data))
+        self.shape = (F, N)
+        return pos, vel
+
+    def velocities_from(self, history, replica, smoothing=0, delay=1):
+        """velocities(the stacked frames that ``history`` (a live.History) recorded of ``replica``, smoothing, delay), with the
+        frames going from the recorder to this handle on the device."""
+        history.set_history(self, replica)
+        F, N = history.frames, history.N
         pos = np.empty((F, N, 3), np.float64)
         vel = np.empty((F, N, 3), np.float64)
         self._check(self.dll.gd_flow_velocities(self._h, int(smoothing or 0), int(delay), pos.ctypes.data, vel.ctypes.data))

@@ -1,7 +1,8 @@
 // gd_flow_cli.hpp -- what gd_particle_flow and gd_grid_flow share: the command line of the reference's
 // analyze_particle_flow / analyze_grid_flow (__main__.py), the stored config JSON as Python's json.dumps prints it and its
-// SHA-256 name (analysis.py: run), the input history (load_positions), and the HDF5 datasets of the output file
-// (put_dataset with h5py's filters).  The computation itself is libgdyn's (include/gdyn_flow.h).
+// SHA-256 name (analysis.py: run), the input history (load_positions), the grid mesh, and the writers of the two output layouts
+// (put_dataset with h5py's filters).  The computation itself is libgdyn's (include/gdyn_flow.h).  gd_interphase writes the same
+// outputs from frames recorded on the device (--particle-flow / --grid-flow) through the same writers.
 #pragma once
 #include <hdf5.h>
 
@@ -45,8 +46,9 @@ struct options {
     std::vector<std::string> trajfiles;
 };
 
-// argparse's conventions: "--opt value" or "--opt=value"; exit status 2 with a usage line on any error
-inline int parse(int argc, char **argv, bool grid, options &o, std::string &err)
+// argparse's conventions: "--opt value" or "--opt=value"; exit status 2 with a usage line on any error.  grid_options: the grid's
+// options are accepted (a particle analysis that shares its command line with a grid analysis ignores them)
+inline int parse(int argc, char **argv, bool grid, options &o, std::string &err, bool grid_options)
 {
     std::vector<std::string> pos;
     for (int k = 1; k < argc; k++) {
@@ -65,8 +67,8 @@ inline int parse(int argc, char **argv, bool grid, options &o, std::string &err)
             else if (key == "--velocity-delay") ok = cli::parse_int(v, o.delay);
             else if (key == "--scan-radius") ok = o.has_radius = cli::parse_float(v, o.radius);
             else if (key == "--jobs") { long j; ok = cli::parse_int(v, j); }      // accepted; one device does the work
-            else if (grid && key == "--grid-interval") ok = o.has_interval = cli::parse_float(v, o.interval);
-            else if (grid && (key == "--x-range" || key == "--y-range" || key == "--z-range")) {
+            else if (grid_options && key == "--grid-interval") ok = o.has_interval = cli::parse_float(v, o.interval);
+            else if (grid_options && (key == "--x-range" || key == "--y-range" || key == "--z-range")) {
                 int const axis = key[2] - 'x';
                 auto comma = v.find(',');
                 ok = comma != std::string::npos && v.find(',', comma + 1) == std::string::npos &&
@@ -89,6 +91,8 @@ inline int parse(int argc, char **argv, bool grid, options &o, std::string &err)
     o.trajfiles.assign(pos.begin() + 1, pos.end());
     return 0;
 }
+
+inline int parse(int argc, char **argv, bool grid, options &o, std::string &err) { return parse(argc, argv, grid, o, err, grid); }
 
 inline std::string config_json(options const &o, bool grid)
 {
@@ -172,9 +176,9 @@ inline std::vector<float> load_history(std::string const &path, uint32_t &frames
 
 struct device {      // one gd_flow handle; every failure of the library ends the program with its message
     gd_flow *h = nullptr;
-    device()
+    explicit device(int ordinal = 0)
     {
-        gd_flow_desc d{0, 0};
+        gd_flow_desc d{ordinal, 0};
         cli::check(gd_flow_create(&d, &h));
     }
     ~device() { gd_flow_destroy(h); }
@@ -203,6 +207,129 @@ inline int front(int argc, char **argv, bool grid, options &o, std::string &conf
     }
     return -1;
 }
+
+inline bool smoothed(options const &o) { return o.has_smoothing && o.smoothing > 0; }
+
+// ---- /particle_flow/<name> of the output file: .config, <sample>/{position,velocity}, and at the end .samples
+class particle_writer {
+public:
+    particle_writer(std::string const &outfile, std::string const &name, std::string const &config)
+        : _file(cli::open_output(outfile)), _group(cli::require_group(_file, "/particle_flow/" + name))
+    {
+        h5::write_string(_group, ".config", config);
+    }
+    // position: the smoothed fp64 history when given, else the float32 history itself
+    void put(std::string const &sample, uint32_t F, uint32_t N, float const *history, double const *smoothed_history, float const *flows)
+    {
+        _samples.push_back(sample);
+        cli::filters const f;
+        std::vector<hsize_t> const dims = {F, N, 3};
+        if (smoothed_history) cli::put_dataset(_group, sample + "/position", smoothed_history, dims, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
+        else cli::put_dataset(_group, sample + "/position", history, dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+        cli::put_dataset(_group, sample + "/velocity", flows, dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+    }
+    void finish() { h5::write_fixed_string_list(_group, ".samples", _samples); }      // this run's samples only, as the reference does
+
+private:
+    h5::hid _file, _group;
+    std::vector<std::string> _samples;
+};
+
+inline std::vector<double> arange(double start, double stop, double step)      // numpy.arange for floats, its fill rule included
+{
+    double const len = std::ceil((stop - start) / step);
+    std::vector<double> out(len > 0 ? (std::size_t)len : 0);
+    if (out.empty()) return out;
+    out[0] = start;
+    if (out.size() > 1) out[1] = start + step;
+    double const delta = (start + step) - start;
+    for (std::size_t i = 2; i < out.size(); i++) out[i] = start + (double)i * delta;
+    return out;
+}
+
+struct mesh {      // analyze_grid_flow's grid: inclusive aranges, points in np.meshgrid(x, y, z) ('xy') order
+    std::size_t G = 0;
+    std::vector<double> points;
+    std::vector<int64_t> indices;
+    int64_t shape[3] = {0, 0, 0};
+
+    explicit mesh(options const &o)
+    {
+        if (!(o.interval > 0)) throw std::runtime_error("--grid-interval must be positive");
+        std::vector<double> axes[3];
+        for (int a = 0; a < 3; a++) axes[a] = arange(o.range[a][0], o.range[a][1] + o.interval * 0.1, o.interval);
+        std::size_t const nx = axes[0].size(), ny = axes[1].size(), nz = axes[2].size();
+        G = nx * ny * nz;
+        if (G == 0 || G > (1u << 28)) throw std::runtime_error("the grid has " + std::to_string(G) + " points");
+        points.resize(3 * G);
+        indices.resize(3 * G);
+        for (std::size_t iy = 0, k = 0; iy < ny; iy++)      // y slowest, then x, then z
+            for (std::size_t ix = 0; ix < nx; ix++)
+                for (std::size_t iz = 0; iz < nz; iz++, k++) {
+                    points[3 * k] = axes[0][ix]; points[3 * k + 1] = axes[1][iy]; points[3 * k + 2] = axes[2][iz];
+                    indices[3 * k] = (int64_t)ix; indices[3 * k + 1] = (int64_t)iy; indices[3 * k + 2] = (int64_t)iz;
+                }
+        shape[0] = (int64_t)nx; shape[1] = (int64_t)ny; shape[2] = (int64_t)nz;
+    }
+};
+
+// estimate_scaleoffset_factor(values, q=1): -floor(log10(0.1 * percentile(values[values > 0], 1))) in float32, numpy's linear rule
+inline int scaleoffset_factor(std::vector<float> const &v)
+{
+    std::vector<float> pos;
+    for (float x : v) if (x > 0) pos.push_back(x);
+    if (pos.empty()) throw std::runtime_error("no positive flow component: the scale-offset factor is undefined");
+    std::sort(pos.begin(), pos.end());
+    double const idx = 0.01 * (double)(pos.size() - 1);
+    std::size_t const lo = (std::size_t)std::floor(idx);
+    std::size_t const hi = std::min(lo + 1, pos.size() - 1);
+    float const t = (float)(idx - (double)lo), a = pos[lo], b = pos[hi], diff = b - a;
+    float const p = t >= 0.5f ? b - diff * (1.0f - t) : a + diff * t;
+    float const resolution = 0.1f * p;
+    return -(int)std::floor(std::log10(resolution));
+}
+
+inline std::vector<std::string> remove_duplicates(std::vector<std::string> const &xs)      // keeps the last occurrence
+{
+    std::vector<std::string> out;
+    for (std::size_t i = 0; i < xs.size(); i++)
+        if (std::find(xs.begin() + (long)i + 1, xs.end(), xs[i]) == xs.end()) out.push_back(xs[i]);
+    return out;
+}
+
+// ---- /grid_flow/<name> of the output file: .config, .grid/{shape,points,indices}, <sample>/{flows,coverages}, and at the end
+// .samples merged with those of earlier runs
+class grid_writer {
+public:
+    grid_writer(std::string const &outfile, std::string const &name, std::string const &config, mesh const &m)
+        : _file(cli::open_output(outfile)), _group(cli::require_group(_file, "/grid_flow/" + name)), _G(m.G)
+    {
+        h5::write_string(_group, ".config", config);
+        _samples = h5::read_string_list(_group, ".samples");      // incremental analysis: earlier samples stay listed
+        cli::put_dataset(_group, ".grid/shape", m.shape, {3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
+        cli::put_dataset(_group, ".grid/points", m.points.data(), {m.G, 3}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
+        cli::put_dataset(_group, ".grid/indices", m.indices.data(), {m.G, 3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
+    }
+    void put(std::string const &sample, uint32_t F, std::vector<float> const &flows, std::vector<int32_t> const &coverages, int factor)
+    {
+        _samples.push_back(sample);
+        cli::filters ff;
+        ff.scaleoffset_kind = H5Z_SO_FLOAT_DSCALE;
+        ff.scaleoffset_factor = factor;
+        cli::put_dataset(_group, sample + "/flows", flows.data(), {F, _G, 3}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &ff);
+        cli::filters fc;
+        fc.scaleoffset_kind = H5Z_SO_INT;
+        fc.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;
+        cli::put_dataset(_group, sample + "/coverages", coverages.data(), {F, _G}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &fc);
+        H5Fflush(_file, H5F_SCOPE_GLOBAL);
+    }
+    void finish() { h5::write_fixed_string_list(_group, ".samples", remove_duplicates(_samples)); }
+
+private:
+    h5::hid _file, _group;
+    std::size_t _G;
+    std::vector<std::string> _samples;
+};
 
 }  // namespace flow
 }  // namespace gd

@@ -15,6 +15,11 @@
 // --ensemble-matrix RATE OUTPUT (not in the reference): the genome-wide contact matrix of the run's replicas, summed on the
 // device from the contact tables each time they are dumped (gd_live_contacts, include/gdyn_live.h) and written at the end
 // exactly as `gd_gw_contact_matrix --rebin-rate RATE -o OUTPUT <the same files>` writes it from the stored maps afterwards.
+//
+// --particle-flow OUTPUT, --grid-flow OUTPUT (not in the reference): the flow fields of the run's replicas.  Every frame stored under
+// snapshots/interphase is also recorded on the device (gd_live_history, include/gdyn_live.h), and at the end one gd_flow handle
+// works through the replicas in file order and writes exactly what `gd_particle_flow OUTPUT <flow options> <the same files>` and
+// `gd_grid_flow OUTPUT ...` write from the stored frames afterwards.  The flow options are theirs (gd_flow_cli.hpp) and shared.
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -36,15 +41,27 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_live.h"
 // This program is also linked against libraries that implement gdyn.h alone (the fp64 oracle of the tests).  What
-// --ensemble-matrix calls is referenced weakly, and the option is refused where the symbols are absent.
+// --ensemble-matrix and the flow options call is referenced weakly, and the options are refused where the symbols are absent.
 #pragma weak gd_cmap_create
 #pragma weak gd_cmap_destroy
 #pragma weak gd_cmap_add_binned
 #pragma weak gd_cmap_target_size
 #pragma weak gd_cmap_fetch
 #pragma weak gd_live_contacts
+#pragma weak gd_flow_create
+#pragma weak gd_flow_destroy
+#pragma weak gd_flow_velocities
+#pragma weak gd_flow_particle
+#pragma weak gd_flow_grid
+#pragma weak gd_live_history_create
+#pragma weak gd_live_history_destroy
+#pragma weak gd_live_history_record
+#pragma weak gd_live_history_frames
+#pragma weak gd_live_history_fetch
+#pragma weak gd_live_flow_set_history
 #include "gd_async_io.hpp"
 #include "gd_cmap_cli.hpp"
+#include "gd_flow_cli.hpp"
 #include "gd_config.hpp"
 #include "gd_genome_model.hpp"
 #include "gd_store.hpp"
@@ -111,6 +128,75 @@ struct ensemble_matrix {
     void write() { gd::cmap::write_gw_matrix(output, head, rb, dev.fetch(target)); }
 };
 
+// --particle-flow / --grid-flow: the interphase frames recorded on the device as they are stored, and the two analyses of them
+struct flow_outputs {
+    gd::flow::options particle, grid;      // outfile empty: not asked for.  Both hold the shared flow options
+    gd_live_history *history = nullptr;
+    uint32_t beads = 0;
+
+    static bool available()
+    {
+        return gd_flow_create && gd_flow_destroy && gd_flow_velocities && gd_flow_particle && gd_flow_grid && gd_live_history_create &&
+               gd_live_history_destroy && gd_live_history_record && gd_live_history_frames && gd_live_history_fetch && gd_live_flow_set_history;
+    }
+    ~flow_outputs() { if (history) gd_live_history_destroy(history); }
+    // all replicas, automatic blocks; `frames` is what the run will store
+    void open(gd_system *sys, std::size_t replicas, std::size_t frames, std::size_t n)
+    {
+        beads = (uint32_t)n;
+        std::clog << "[flow] recording " << frames << " frames of " << replicas << " replicas of " << n << " beads on the device: "
+                  << replicas * frames * n * 12 << " bytes\n";
+        gd::cli::check(gd_live_history_create(sys, nullptr, 0, 0, &history));
+    }
+    void record(gd_system *sys) { gd::cli::check(gd_live_history_record(history, sys, /*quantize=*/1)); }
+    uint32_t frames() const
+    {
+        uint32_t f = 0;
+        gd::cli::check(gd_live_history_frames(history, &f));
+        return f;
+    }
+    void write(std::vector<std::string> const &files, int ordinal)
+    {
+        using namespace gd::flow;
+        uint32_t const F = frames(), N = beads;
+        options const &o = particle.outfile.empty() ? grid : particle;      // (the velocity options are the same in both)
+        bool const smooth = smoothed(o);
+        gd::flow::device dev(ordinal);
+        std::unique_ptr<particle_writer> pw;
+        std::unique_ptr<grid_writer> gw;
+        std::unique_ptr<mesh> m;
+        if (!particle.outfile.empty()) {
+            std::string const config = config_json(particle, false);
+            pw = std::make_unique<particle_writer>(particle.outfile, analysis_name(particle, config), config);
+        }
+        if (!grid.outfile.empty()) {
+            std::string const config = config_json(grid, true);
+            m = std::make_unique<mesh>(grid);
+            gw = std::make_unique<grid_writer>(grid.outfile, analysis_name(grid, config), config, *m);
+        }
+        for (std::size_t r = 0; r < files.size(); r++) {
+            std::string const sample = gd::cli::sample_name(files[r]);
+            gd::cli::check(gd_live_flow_set_history(history, (uint32_t)r, dev.h));
+            std::vector<double> pos(pw && smooth ? (std::size_t)F * N * 3 : 0);
+            gd::cli::check(gd_flow_velocities(dev.h, smooth ? (uint32_t)o.smoothing : 0, (uint32_t)o.delay, pos.empty() ? nullptr : pos.data(), nullptr));
+            if (pw) {
+                std::vector<float> flows((std::size_t)F * N * 3), hist(smooth ? 0 : (std::size_t)F * N * 3);
+                gd::cli::check(gd_flow_particle(dev.h, o.radius, flows.data()));
+                if (!smooth) gd::cli::check(gd_live_history_fetch(history, (uint32_t)r, 0, F, hist.data()));
+                pw->put(sample, F, N, hist.data(), smooth ? pos.data() : nullptr, flows.data());
+            }
+            if (gw) {
+                std::vector<float> flows((std::size_t)F * m->G * 3);
+                std::vector<int32_t> cov((std::size_t)F * m->G);
+                gd::cli::check(gd_flow_grid(dev.h, o.radius, m->points.data(), (uint32_t)m->G, flows.data(), cov.data()));
+                gw->put(sample, F, flows, cov, scaleoffset_factor(flows));
+            }
+        }
+        if (pw) pw->finish();
+        if (gw) gw->finish();
+    }
+};
+
 // One driver = one libgdyn handle = R replicas = R trajectory files.  R = 1 is the reference program; R > 1 batches R runs
 // of the reference's ensemble (one process per seed, each with its own prepared file: 5-sim-genome/scripts/run_simulation:8-25,
 // read back as output-*.h5 by contact_map/contact_map.py:14-39) into one launch: replica r takes its initial structure, its
@@ -118,9 +204,10 @@ struct ensemble_matrix {
 // (gd_run_desc.replica_seeds), so a batched trajectory equals the solo one up to fp32 summation order.
 class simulation_driver {
 public:
-    simulation_driver(std::vector<std::unique_ptr<gd::trajectory_store>> &stores, int device, bool auto_skin = false, ensemble_matrix *ensemble = nullptr)
+    simulation_driver(std::vector<std::unique_ptr<gd::trajectory_store>> &stores, int device, bool auto_skin = false, ensemble_matrix *ensemble = nullptr,
+                      flow_outputs *flow = nullptr)
         : _stores(stores), _R(stores.size()), _config(gd::parse_simulation_config(stores[0]->load_config_text())), _auto_skin(auto_skin),
-          _ensemble(ensemble)
+          _ensemble(ensemble), _flow(flow)
     {
         // compatibility defaults of older runs (simulation_driver.cc:20-29)
         auto set_default = [](double &var, double def) { if (var == 0) var = def; };
@@ -198,6 +285,7 @@ private:
         }
         _buffer.resize(3 * _n * _R);
         _energy.resize(_R);
+        if (_flow) _flow->open(_sys, _R, (std::size_t)(_config.interphase_steps / _config.interphase_sampling_interval) + 1, _n);
     }
 
     std::vector<double> semiaxes() const
@@ -242,6 +330,10 @@ private:
             TIMED("snapshot_download");
             chk(gd_get_positions_f32(_sys, _buffer.data(), /*quantize=*/1));      // 16 fractional bits, rounded on the device
             xyz = std::make_shared<std::vector<float>>(_buffer);
+        }
+        if (_flow && _interphase) {      // the same frame, kept on the device
+            TIMED("flow_record");
+            _flow->record(_sys);
         }
         auto ctx = std::make_shared<std::vector<gd::context>>(_context);
         TIMED("writer_wait");
@@ -347,6 +439,7 @@ private:
     {
         { TIMED("writer_wait"); _writer.drain(); }          // (the relaxation's last snapshot goes to the relaxation phase)
         for (auto &st : _stores) st->set_phase("interphase");
+        _interphase = true;
         double const dt = _config.interphase_timestep;
         chk(gd_begin_phase(_sys, semiaxes().data()));       // step = 0, time = 0
         std::vector<std::array<double, 3>> reaction(_R);
@@ -408,6 +501,8 @@ private:
     gd::simulation_config _config;
     bool _auto_skin = false;
     ensemble_matrix *_ensemble = nullptr;
+    flow_outputs *_flow = nullptr;
+    bool _interphase = false;
     std::vector<gd::context> _context;
     double _contact_distance = 0;
     std::vector<std::mt19937_64> _random;
@@ -423,14 +518,26 @@ private:
 
 }  // namespace
 
+static bool is_flow_option(std::string const &arg)
+{
+    std::string const key = arg.substr(0, arg.find('='));
+    for (char const *k : {"--scan-radius", "--smoothing", "--velocity-delay", "--name", "--grid-interval", "--x-range", "--y-range", "--z-range"})
+        if (key == k) return true;
+    return false;
+}
+
 int main(int argc, char **argv)
 {
     // gd_interphase <trajectory> [device]                      the reference's command line
     // gd_interphase [--device d] <trajectory> <trajectory>...  R prepared files as R replicas of one handle
     // options: --timing (wall-time split on stderr at the end), --auto-skin (list width selected from measured chunk times: the
     // trajectory of a seed then depends on timing; off by default.  --fixed-skin, the former spelling of the default, is accepted),
-    // --ensemble-matrix RATE OUTPUT (the genome-wide contact matrix of the replicas, as gd_gw_contact_matrix --rebin-rate RATE writes it)
-    std::vector<std::string> files;
+    // --ensemble-matrix RATE OUTPUT (the genome-wide contact matrix of the replicas, as gd_gw_contact_matrix --rebin-rate RATE writes it),
+    // --particle-flow OUTPUT / --grid-flow OUTPUT with the options of gd_particle_flow / gd_grid_flow: --scan-radius, --smoothing,
+    // --velocity-delay, --name, and for the grid --grid-interval, --x-range, --y-range, --z-range
+    std::vector<std::string> files, flow_args;
+    std::string particle_output, grid_output;
+    bool particle_asked = false, grid_asked = false;
     std::string matrix_output;
     long matrix_rate = 0;
     int device = 0;
@@ -452,7 +559,28 @@ int main(int argc, char **argv)
             matrix_output = argv[i + 2];
             i += 2;
         }
+        else if (arg == "--particle-flow" || arg == "--grid-flow") {
+            bool const grid = arg == "--grid-flow";
+            (grid ? grid_asked : particle_asked) = true;
+            if (i + 1 < argc) (grid ? grid_output : particle_output) = argv[++i];
+        }
+        else if (is_flow_option(arg)) {
+            flow_args.push_back(arg);
+            if (arg.find('=') == std::string::npos && i + 1 < argc) flow_args.push_back(argv[++i]);
+        }
         else files.push_back(arg);
+    }
+    if ((particle_asked || grid_asked) && !flow_outputs::available()) {
+        std::cerr << "error: " << (particle_asked ? "--particle-flow" : "--grid-flow") << " needs the device library\n";
+        return 1;
+    }
+    if ((particle_asked && particle_output.empty()) || (grid_asked && grid_output.empty())) {
+        std::cerr << "error: --particle-flow and --grid-flow take an output file\n";
+        return 1;
+    }
+    if (!flow_args.empty() && !particle_asked && !grid_asked) {
+        std::cerr << "error: " << flow_args[0] << " needs --particle-flow or --grid-flow\n";
+        return 1;
     }
     if (!matrix_output.empty() && !ensemble_matrix::available()) {
         std::cerr << "error: --ensemble-matrix needs the device library\n";
@@ -465,6 +593,29 @@ int main(int argc, char **argv)
         std::cerr << "usage: gd_interphase <trajectory> [device]\n       gd_interphase [--device d] <trajectory> <trajectory>...\n";
         return 1;
     }
+    std::unique_ptr<flow_outputs> flow;
+    if (particle_asked || grid_asked) {      // the shared flow options, parsed once per analysis as its own program parses them
+        flow = std::make_unique<flow_outputs>();
+        std::vector<char *> av = {argv[0]};
+        for (auto &a : flow_args) av.push_back(a.data());
+        for (int grid = 0; grid < 2; grid++) {
+            if (!(grid ? grid_asked : particle_asked)) continue;
+            gd::flow::options &o = grid ? flow->grid : flow->particle;
+            std::string err;
+            std::string out = grid ? grid_output : particle_output, dummy = "trajfile";
+            std::vector<char *> full = av;
+            full.push_back(out.data());
+            full.push_back(dummy.data());
+            if (gd::flow::parse((int)full.size(), full.data(), grid != 0, o, err, grid_asked)) {
+                std::cerr << "error: " << err << '\n';
+                return 1;
+            }
+            if (o.delay < 0 || o.smoothing < 0) {
+                std::cerr << "error: --velocity-delay and --smoothing must be >= 0\n";
+                return 1;
+            }
+        }
+    }
     try {
         std::unique_ptr<ensemble_matrix> ensemble;      // (reads the first file's chromosome table before the stores open the files)
         if (!matrix_output.empty()) ensemble = std::make_unique<ensemble_matrix>(files[0], matrix_rate, matrix_output, device);
@@ -475,10 +626,20 @@ int main(int argc, char **argv)
         }
         double bead_steps = 0;
         {
-            simulation_driver driver{stores, device, auto_skin, ensemble.get()};
+            simulation_driver driver{stores, device, auto_skin, ensemble.get(), flow.get()};
             driver.run();
             bead_steps = driver.bead_steps();
             if (ensemble) { TIMED("ensemble_matrix"); ensemble->write(); }
+            if (flow) {
+                TIMED("flow_outputs");
+                // the stand-alone programs read every stored frame: a file that held interphase snapshots before this run has more
+                // of them than were recorded
+                for (std::size_t r = 0; r < stores.size(); r++)
+                    if (stores[r]->load_steps().size() != flow->frames())
+                        throw std::runtime_error(files[r] + " holds " + std::to_string(stores[r]->load_steps().size()) + " interphase snapshots, " +
+                                                 std::to_string(flow->frames()) + " were recorded in this run: the flow outputs are not written");
+                flow->write(files, device);
+            }
         }
         { TIMED("close_files"); stores.clear(); }
         double const total_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();

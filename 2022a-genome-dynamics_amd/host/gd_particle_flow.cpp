@@ -12,15 +12,10 @@ int main(int argc, char **argv)
     if (int rc = front(argc, argv, false, o, config, name); rc >= 0) return rc;
     try {
         device dev;
-        gd::h5::hid file(gd::cli::open_output(o.outfile));
-        gd::h5::hid group(gd::cli::require_group(file, "/particle_flow/" + name));
-        gd::h5::write_string(group, ".config", config);
-        bool const smooth = o.has_smoothing && o.smoothing > 0;
-        std::vector<std::string> samples;
+        particle_writer out(o.outfile, name, config);
+        bool const smooth = smoothed(o);
         gd::cli::stopwatch sw;
         for (auto const &path : o.trajfiles) {
-            std::string const sample = gd::cli::sample_name(path);
-            samples.push_back(sample);
             uint32_t F = 0, N = 0;
             auto const hist = load_history(path, F, N);
             sw.read += sw.lap();
@@ -30,14 +25,10 @@ int main(int argc, char **argv)
             gd::cli::check(gd_flow_velocities(dev.h, smooth ? (uint32_t)o.smoothing : 0, (uint32_t)o.delay, smooth ? pos.data() : nullptr, nullptr));
             gd::cli::check(gd_flow_particle(dev.h, o.radius, flows.data()));
             sw.compute += sw.lap();
-            gd::cli::filters const f;
-            std::vector<hsize_t> const dims = {F, N, 3};
-            if (smooth) gd::cli::put_dataset(group, sample + "/position", pos.data(), dims, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            else gd::cli::put_dataset(group, sample + "/position", hist.data(), dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
-            gd::cli::put_dataset(group, sample + "/velocity", flows.data(), dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+            out.put(gd::cli::sample_name(path), F, N, hist.data(), smooth ? pos.data() : nullptr, flows.data());
             sw.write += sw.lap();
         }
-        gd::h5::write_fixed_string_list(group, ".samples", samples);      // this run's samples only, as the reference does
+        out.finish();
         sw.write += sw.lap();
         sw.report("gd_particle_flow");
     } catch (std::exception const &e) {

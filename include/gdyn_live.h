@@ -18,6 +18,18 @@
  *                                    system's periods, bin_width, max_distance, counts_out) with the handle's selection.
  * Frames are the R replicas at the present step.
  *
+ * The flow analyses (gdyn_flow.h) need a history of frames, not the present one.  A gd_live_history records it on the device
+ * (DESIGN.md section 7h): float32 (F, N, 3) per selected replica, 12 bytes per bead and frame, in blocks of frames_per_block
+ * frames that are allocated as needed and never moved.
+ *   gd_live_history_record           appends, for every selected replica, what gd_get_positions_f32(sys, ., quantize) gives for
+ *                                    it at the present step.  The system is not modified.  GD_ENOMEM when a new block cannot be
+ *                                    allocated: the frames recorded so far stay valid and the count does not change.
+ *   gd_live_history_fetch            frames [first, first + count) of one recorded replica, float32 (count, N, 3)
+ *   gd_live_flow_set_history         gd_flow_set_history(flow, the F recorded frames of that replica, F, N, 0): earlier
+ *                                    velocities are forgotten, GD_ESTATE when no frame was recorded, GD_EINVAL for a non-finite
+ *                                    coordinate (the handle is then left without a history).  The frames are widened to the
+ *                                    handle's fp64 copy on the device.
+ *
  * Every call is synchronous: it waits for the stepper's stream before it reads, and its result is complete when it returns.
  * The two handles of a call must live on one device.  The lamina calls need a system with an ellipsoid wall, the rdf call a
  * periodic system and a selection over the system's N beads.  The argument checks of the host-fed calls apply unchanged.
@@ -31,6 +43,7 @@
 
 #include "gdyn.h"
 #include "gdyn_cmap.h"
+#include "gdyn_flow.h"
 #include "gdyn_lamina.h"
 #include "gdyn_rdf.h"
 
@@ -38,7 +51,7 @@
 extern "C" {
 #endif
 
-#define GD_LIVE_ABI_VERSION 1
+#define GD_LIVE_ABI_VERSION 2
 
 int gd_live_abi_version(void);
 /* the current contents of the contact table of one replica, or of all (GD_ALL_REPLICAS), streamed through every target of cm */
@@ -49,6 +62,19 @@ int gd_live_lamina_distances(gd_system *sys, gd_lamina *lam, int quantize, void 
 int gd_live_lamina_contacts(gd_system *sys, gd_lamina *lam, int quantize, double contact_distance, uint8_t *contacts_out);
 /* counts_out: R * gd_rdf_bins(bin_width, max_distance) values */
 int gd_live_rdf_counts(gd_system *sys, gd_rdf *rdf, int quantize, double bin_width, double max_distance, uint64_t *counts_out);
+
+typedef struct gd_live_history gd_live_history;
+/* a recorder on the system's device for systems of its N and R.  replicas: n_replicas distinct ids below R, in any order;
+ * n_replicas == 0: all R.  frames_per_block == 0: blocks of about 256 MiB, at least one frame */
+int gd_live_history_create(gd_system *sys, const uint32_t *replicas, uint32_t n_replicas, uint32_t frames_per_block, gd_live_history **out);
+int gd_live_history_destroy(gd_live_history *h);
+int gd_live_history_record(gd_live_history *h, gd_system *sys, int quantize);
+int gd_live_history_frames(const gd_live_history *h, uint32_t *frames);
+/* out: count * N * 3 floats */
+int gd_live_history_fetch(gd_live_history *h, uint32_t replica, uint32_t first, uint32_t count, float *out);
+/* keeps the blocks and sets the frame count to 0 */
+int gd_live_history_clear(gd_live_history *h);
+int gd_live_flow_set_history(gd_live_history *h, uint32_t replica, gd_flow *flow);
 
 #ifdef __cplusplus
 }
