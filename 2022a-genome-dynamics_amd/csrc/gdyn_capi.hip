@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/gdyn.h"
+#include "../../include/gdyn_replica.h"
 #include <hip/hip_fp16.h>
 
 #include "gdyn_types.h"
@@ -25,6 +26,7 @@
 #include "gdyn_policy.hpp"
 #include "gdyn_list.hpp"
 #include "gdyn_live.hpp"
+#include "gdyn_replica_pairs.hpp"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
 #endif
@@ -119,6 +121,11 @@ struct gd_system {
     bool bonds_all_scaled = false; // every bond parameter record has scale_by_bond_scale set
     uint32_t sw_n = 0; double sw_eps = 0, sw_decay = 1, sw_cut = 0;     // droplet attraction (gd_set_pair_softwell)
     DevBuf<unsigned> sw_targets; DevBuf<double> sw_esum;
+    // per-replica dynamic pairs (gdyn_replica.h): what the caller set, the block of the last upload (layout, pinned staging, device
+    // copy; both grown geometrically, never shrunk), the slots' parameters, the energy sums
+    gd::ReplicaPairs rp; gd::ReplicaLayout rp_layout; gd_bond_params rp_params[gd::RP_SLOTS] = {};
+    uint32_t *rp_stage = nullptr; size_t rp_stage_cap = 0; hipEvent_t rp_copied = nullptr;      // (rp_copied: the last upload has left the staging block)
+    DevBuf<uint32_t> rp_dev; DevBuf<double> rp_esum;
     float *h_stage = nullptr;      // pinned host staging for snapshot downloads (R*N*3 floats)
     char *h_chunk = nullptr;       // pinned host block for the per-chunk readback (flags, contexts, list counts): copies into pageable
                                    // memory are staged by the runtime and cost ~20 us each
@@ -172,6 +179,7 @@ struct gd_system {
     ~gd_system()
     {
         for (auto e : events) (void)hipEventDestroy(e);
+        if (rp_copied) (void)hipEventDestroy(rp_copied);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -212,6 +220,7 @@ extern "C" int gd_create_abi(int abi_version, const gd_desc *d, gd_system **out)
     s->a.assign(s->N, 0.0); s->b.assign(s->N, 0.0); s->mob.assign(s->N, 1.0); s->bend.assign(s->N, 0.0);
     s->hctx.assign(s->R, DevCtx{});
     for (auto &c : s->hctx) { c.bead_scale = 1; c.bond_scale = 1; }   // wall_semiaxes {0,0,0} until a wall is set (simulation_context.hpp:16)
+    s->rp.reset(s->N, s->R);
     s->lcount.assign(2 * (size_t)s->R, 0ull);      // per replica: directed entries, then the near entries (in fours) of tiled lists
     s->ncell_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(8ull * s->N, 4096ull), 262144ull);
     if (const char *e = dev_env("GDYN_NEAR_FRAC")) s->near_frac = atof(e);
@@ -256,6 +265,7 @@ extern "C" int gd_destroy(gd_system *s)
     (void)hipStreamSynchronize(s->stream);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->h_chunk) (void)hipHostFree(s->h_chunk);
+    if (s->rp_stage) (void)hipHostFree(s->rp_stage);
     delete s;
     return GD_OK;
 }
@@ -500,6 +510,102 @@ static void launch_softwell(gd_system *s, const StepParams &p, int mode)
     q.N = s->N; q.Np = s->Np; q.R = s->R; q.M = s->sw_n;
     set_box(s, q);
     gd_launch_softwell(q, mode, s->stream);
+}
+
+// ---- per-replica dynamic pairs (include/gdyn_replica.h)
+static_assert(gd::RP_SLOT_SHIFT == GD_RP_SLOT_SHIFT && gd::RP_PARTNER_MASK == GD_RP_PARTNER_MASK && GD_ADJ_MASK <= GD_RP_PARTNER_MASK, "entry format");
+static_assert(gd::RP_RECORD_WORDS * sizeof(uint32_t) == gd::RP_SLOTS * sizeof(BondType), "record words");
+
+// A kernel behind k_step moves beads after k_step has bounded their displacement (the droplet term, the per-replica pairs): the running
+// bound then covers no step's output, so both list classes are walked and the list serves no observation after the run.
+static bool post_step_active(const gd_system *s) { return s->sw_n != 0 || s->rp.any(); }
+
+static BondType bond_record(const gd_bond_params &p, int term)
+{
+    const bool harmonic = p.kind == GD_POT_HARMONIC;     // U = K r^2 / 2 is the spring with rest length 0
+    return BondType{(float)p.k_a, (float)p.k_b, harmonic ? 0.f : (float)p.l_a, harmonic ? 0.f : (float)p.l_b,
+                    (p.mix ? 1 : 0) | (p.scale_by_bond_scale ? 2 : 0) | (p.minimum_image ? 4 : 0) | (term << 8),
+                    p.kind == GD_POT_SEMISPRING ? 0.f : -3.0e38f, p.kind, p.p | (p.q << 8)};
+}
+
+// The lists the caller set since the last evaluation: flattened, packed into the pinned block and sent with one asynchronous copy.
+// (Every evaluation ends behind a stream synchronisation, so the copy before has left the block by now: the wait on its event returns
+// at once, except after an evaluation that ended early on an error.)
+static int sync_replica_pairs(gd_system *s)
+{
+    if (!s->rp.dirty()) return GD_OK;
+    const gd::ReplicaLayout l = s->rp.flatten();
+    if (l.words > 0xffffffffull) return fail(GD_ENOMEM, "per-replica pair lists: %zu words exceed the table's 32-bit offsets", l.words);
+    if (!s->rp_copied) HIPCHK(hipEventCreateWithFlags(&s->rp_copied, hipEventDisableTiming));
+    else HIPCHK(hipEventSynchronize(s->rp_copied));
+    if (l.words > s->rp_stage_cap) {
+        const size_t cap = gd::grown_capacity(s->rp_stage_cap, l.words);
+        uint32_t *h = nullptr;
+        HIPCHK(hipHostMalloc((void **)&h, cap * sizeof(uint32_t), hipHostMallocDefault));
+        if (s->rp_stage) (void)hipHostFree(s->rp_stage);
+        s->rp_stage = h; s->rp_stage_cap = cap;
+    }
+    if (l.words > s->rp_dev.n) HIPCHK(s->rp_dev.resize(gd::grown_capacity(s->rp_dev.n, l.words), false));
+    if (!s->rp_esum.p) HIPCHK(s->rp_esum.resize(s->R));
+    s->rp.pack(l, s->rp_stage);
+    BondType rec[gd::RP_SLOTS];
+    for (uint32_t k = 0; k < gd::RP_SLOTS; k++) rec[k] = s->rp.defined(k) ? bond_record(s->rp_params[k], GD_TERM_DYNAMIC) : BondType{};
+    memcpy(s->rp_stage + l.rec, rec, sizeof rec);
+    HIPCHK(hipMemcpyAsync(s->rp_dev.p, s->rp_stage, l.words * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipEventRecord(s->rp_copied, s->stream));
+    s->rp_layout = l;
+    return GD_OK;
+}
+
+// the per-replica pairs of the step / force / energy evaluation that `p` describes (same positions, same buffers)
+static void launch_replica_pairs(gd_system *s, const StepParams &p, int mode)
+{
+    const gd::ReplicaLayout &l = s->rp_layout;
+    ReplicaPairsP q;
+    memset(&q, 0, sizeof q);
+    q.pos_in = p.pos_in; q.pos_out = p.pos_out; q.fout = s->fout.p; q.esum = s->rp_esum.p; q.slot_of = s->slot_of.p;
+    q.base = (const uint4 *)(s->rp_dev.p + l.base); q.rec = (const BondType *)(s->rp_dev.p + l.rec);
+    q.row_bead = s->rp_dev.p + l.row_bead; q.row_off = s->rp_dev.p + l.row_off; q.ent = s->rp_dev.p + l.ent;
+    q.ctx = mode == 0 ? p.ctx_out : p.ctx_in;      // (a step's k_step has applied the pending callback and left the result there)
+    q.ab_o = s->ab_o.p;
+    q.mob_o = s->mob_uniform >= 0.f ? nullptr : s->mob_o.p; q.mob_uniform = s->mob_uniform; q.dt = p.dt;
+    q.lo = p.lo; q.comp = p.comp;
+    q.N = s->N; q.Np = s->Np; q.R = s->R; q.max_rows = l.max_rows;
+    set_box(s, q);
+    gd_launch_replica_pairs(q, mode, s->stream);
+}
+
+extern "C" int gd_replica_abi_version(void) { return GD_REPLICA_ABI_VERSION; }
+
+extern "C" int gd_replica_pairs_define(gd_system *s, uint32_t slot, const gd_bond_params *p)
+{
+    if (!s || !p) return fail(GD_EINVAL, "gd_replica_pairs_define: NULL argument");
+    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_define: slot %u out of range", slot);
+    GDCHK(check_bond_params(p));
+    s->rp_params[slot] = *p;
+    s->rp.define(slot);
+    return GD_OK;
+}
+
+extern "C" int gd_replica_pairs_set(gd_system *s, uint32_t slot, uint32_t replica, const uint32_t *pairs, uint32_t n)
+{
+    if (!s || (n && !pairs)) return fail(GD_EINVAL, "gd_replica_pairs_set: NULL argument");
+    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_set: slot %u out of range", slot);
+    if (replica >= s->R) return fail(GD_EINVAL, "gd_replica_pairs_set: replica %u out of range", replica);
+    if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_replica_pairs_set: slot %u was never defined (gd_replica_pairs_define)", slot);
+    if (const size_t bad = s->rp.set(slot, replica, pairs, n))
+        return fail(GD_EINVAL, "gd_replica_pairs_set: bad pair %zu (%u,%u)", bad - 1, pairs[2 * (bad - 1)], pairs[2 * (bad - 1) + 1]);
+    return GD_OK;
+}
+
+extern "C" int gd_replica_pairs_count(gd_system *s, uint32_t slot, uint32_t replica, uint32_t *n)
+{
+    if (!s || !n) return fail(GD_EINVAL, "gd_replica_pairs_count: NULL argument");
+    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_count: slot %u out of range", slot);
+    if (replica >= s->R) return fail(GD_EINVAL, "gd_replica_pairs_count: replica %u out of range", replica);
+    if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_replica_pairs_count: slot %u was never defined (gd_replica_pairs_define)", slot);
+    *n = s->rp.count(slot, replica);
+    return GD_OK;
 }
 
 extern "C" int gd_set_inner_sphere_wall(gd_system *s, const gd_inner_sphere *w)
@@ -775,7 +881,7 @@ static void fill_common(gd_system *s, StepParams &p)
         for (int k = 0; k < 3; k++) p.ps[q].p[k] = (float)s->psrc[q].p[k];
     }
     p.has_bend = s->has_bend; p.has_bonds = s->has_bonds;
-    p.rv = s->list.rv; p.rn = s->sw_n ? 0.f : s->list.rn; p.dmax = s->dmax.p; p.term_mask = GD_TERM_ALL;      // (the droplet kernel moves beads after k_step has bounded their displacement: both list classes then)
+    p.rv = s->list.rv; p.rn = post_step_active(s) ? 0.f : s->list.rn; p.dmax = s->dmax.p; p.term_mask = GD_TERM_ALL;      // (a kernel behind k_step moves beads after k_step has bounded their displacement: both list classes then)
     if (dev_env("GDYN_FORCE_FAR")) p.rn = 0.f;      // (timing experiments: the far class in every step)
     if (dev_env("GDYN_FORCE_NEAR")) p.rn = 1e3f;    // (timing experiments with gd_debug_bench only: never the far class -- wrong forces late in an interval)
     p.fout = s->fout.p; p.epart = s->epart.p;
@@ -861,7 +967,7 @@ static int clear_flags(gd_system *s)
 // The list in use and the handle, as the list policy sees them
 static gd::ListState list_state(const gd_system *s)
 {
-    return s->list.state(pair_cutoff(s), s->nbr16.n / 512, (double)s->R * (double)s->Np, s->sw_n != 0, s->kernel_path != 1 && s->packed_ab);
+    return s->list.state(pair_cutoff(s), s->nbr16.n / 512, (double)s->R * (double)s->Np, post_step_active(s), s->kernel_path != 1 && s->packed_ab);
 }
 
 // A build or a chunk of gd_run: what it ran and the state before it (gd_run), what the device reported (read_chunk)
@@ -925,6 +1031,7 @@ static int prepare(gd_system *s)
     HIPCHK(hipSetDevice(s->device));
     GDCHK(finalize_topology(s));
     GDCHK(upload_ctx(s));
+    GDCHK(sync_replica_pairs(s));
     return GD_OK;
 }
 
@@ -1063,6 +1170,7 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
             c.full_interval |= p.record_disp != 0;
             gd_launch_step(p, GD_MODE_STEP, s->stream);
             if (s->sw_n) launch_softwell(s, p, 0);
+            if (s->rp.any()) launch_replica_pairs(s, p, 0);      // (a step evaluates every term: GD_TERM_DYNAMIC is in its mask)
             s->pcur ^= 1; s->ccur ^= 1;
         }
         HIPCHK(hipEventRecord(e1, s->stream));
@@ -1120,7 +1228,7 @@ static int rollback_chunk(gd_system *s, const Chunk &c, bool over, bool comp, in
         return fail(GD_ESTATE, "gd_run: Verlet skin cannot cover one step (timestep too large?)");
     }
     s->timing.step_launches -= std::min<uint64_t>(s->timing.step_launches, (uint64_t)c.steps);
-    s->pol.on_rollback(s->sw_n != 0);
+    s->pol.on_rollback(post_step_active(s));
     return GD_OK;
 }
 
@@ -1208,10 +1316,10 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
     }
     // The last chunk was accepted: every bead is within the margin the list in use was built for, at the cutoff of the last step --
     // still the cutoff an observation sees when the scales did not move behind that step (callback deferred, or no scale updates):
-    // the resident list then serves gd_compute_energy as it is (not with the droplet term: its kernel moves beads behind k_step's
-    // check).  The positions the last step WROTE are covered by the running bound of the tiled path (dmax, read back with the chunk)
+    // the resident list then serves gd_compute_energy as it is (not with a kernel behind k_step -- the droplet term, the per-replica
+    // pairs: it moves beads behind k_step's check).  The positions the last step WROTE are covered by the running bound of the tiled path (dmax, read back with the chunk)
     // only: the list serves an observation if that bound is inside the margin too.  The generic path's observations build a list.
-    const bool settled = run->steps > 0 && with_list && !s->sw_n && (!(run->flags & GD_RUN_UPDATE_SCALES) || (run->flags & GD_RUN_DEFER_CALLBACK));
+    const bool settled = run->steps > 0 && with_list && !post_step_active(s) && (!(run->flags & GD_RUN_UPDATE_SCALES) || (run->flags & GD_RUN_DEFER_CALLBACK));
     s->list.run_ended(settled, pair_cutoff(s) * cut_scale(s, nullptr, 0), last_dmax2, s->state_serial);
     return GD_OK;
 }
@@ -1228,7 +1336,13 @@ extern "C" int gd_compute_energy(gd_system *s, uint32_t mask, double *energy)
     p.term_mask = mask;
     gd_launch_step(p, GD_MODE_ENERGY, s->stream);
     const bool droplet = s->sw_n && (mask & GD_TERM_PAIR);
-    std::vector<double> esw(s->R, 0.0);
+    const bool replica_pairs = s->rp.any() && (mask & GD_TERM_DYNAMIC);
+    std::vector<double> esw(s->R, 0.0), erp(s->R, 0.0);
+    if (replica_pairs) {
+        HIPCHK(hipMemsetAsync(s->rp_esum.p, 0, s->R * sizeof(double), s->stream));
+        launch_replica_pairs(s, p, 2);
+        HIPCHK(hipMemcpyAsync(erp.data(), s->rp_esum.p, s->R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    }
     if (droplet) {
         HIPCHK(hipMemsetAsync(s->sw_esum.p, 0, s->R * sizeof(double), s->stream));
         launch_softwell(s, p, 2);
@@ -1238,7 +1352,7 @@ extern "C" int gd_compute_energy(gd_system *s, uint32_t mask, double *energy)
     HIPCHK(hipMemcpyAsync(part.data(), s->epart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     for (uint32_t r = 0; r < s->R; r++) {
-        double e = esw[r];
+        double e = esw[r] + erp[r];
         for (uint32_t b = 0; b < s->nblk; b++) e += part[(size_t)r * s->nblk + b];
         energy[r] = e;
     }
@@ -1257,6 +1371,7 @@ extern "C" int gd_compute_forces(gd_system *s, uint32_t mask, double *forces)
     HIPCHK(hipMemsetAsync(p.react_out, 0, s->react_part[0].n * sizeof(float4), s->stream));
     gd_launch_step(p, GD_MODE_FORCE, s->stream);
     if (s->sw_n && (mask & GD_TERM_PAIR)) launch_softwell(s, p, 1);
+    if (s->rp.any() && (mask & GD_TERM_DYNAMIC)) launch_replica_pairs(s, p, 1);
     // (a mask without the wall leaves axial_reaction as the last evaluation of the wall set it: no fold of the zeroed partials)
     const bool fold = s->has_wall && (mask & GD_TERM_WALL);
     if (fold) { p.react_in = p.react_out; gd_launch_finalize(p, 1, s->stream); s->ccur ^= 1; }

@@ -12,6 +12,7 @@
 //   k_ctx                  one wave per replica: the pending callback at the end of a chunk, the reaction fold of a force
 //                          evaluation.
 //   k_softwell             droplet attraction among the few hundred target beads (after k_step; linear in the force).
+//   k_replica_pairs        the bonded pairs every replica has of its own (after k_step, like k_softwell; owner computes).
 //   k_bbox .. k_fill       neighbour search (micromd md::neighbor_searcher; call sites e.g.
 //                          simulation_interphase/contact_map.cc:64-66): bounding box, cell binning, counting sort into
 //                          slot order, tile descriptors, list fill (27-cell sweep from the LDS tile, or from global
@@ -2391,6 +2392,92 @@ void gd_launch_softwell(const SoftwellP &p, int mode, hipStream_t st)
     if (mode == 0) hipLaunchKernelGGL(k_softwell<0>, grid, block, lds, st, p);
     else if (mode == 1) hipLaunchKernelGGL(k_softwell<1>, grid, block, lds, st, p);
     else hipLaunchKernelGGL(k_softwell<2>, grid, block, lds, st, p);
+}
+
+// ------------------------------------------------------------- per-replica dynamic pairs
+// The bonded pairs every replica has of its own (include/gdyn_replica.h): the loops and glues of one trajectory of an ensemble.  Like
+// the droplet term a small kernel behind k_step, for the same reason: x_out += mu dt F on top of k_step's result is the same step.
+// Owner computes: one thread per ACTIVE bead of a replica (a bead with a pair) walks its row of the table (gdyn_replica_pairs.hpp) and
+// is the only writer of its bead's position, residual or force -- no floating-point atomics, a fixed summation order per bead.
+// The potential is k_step's bonded arithmetic: bond_pot on the slot's record, mixed with the a / b factors of the two beads and scaled
+// with the replica's bond_scale as the record's flags say.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_replica_pairs(const ReplicaPairsP p)
+{
+    __shared__ BondType s_rec[4];
+    if (threadIdx.x < 4 * sizeof(BondType) / sizeof(unsigned)) ((unsigned *)s_rec)[threadIdx.x] = ((const unsigned *)p.rec)[threadIdx.x];
+    __syncthreads();
+    const unsigned r = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    const uint4 base = p.base[r];
+    const unsigned *__restrict__ so = p.slot_of + (size_t)r * p.N;
+    const float4 *__restrict__ rpos = p.pos_in + (size_t)r * p.Np;
+    const bool active = t < base.x;
+    float3 F = make_float3(0.f, 0.f, 0.f);
+    float E = 0.f;
+    unsigned bead = 0;
+    if (active) {
+        bead = p.row_bead[base.y + t];
+        const unsigned k0 = p.row_off[base.z + t], k1 = p.row_off[base.z + t + 1];
+        const unsigned *__restrict__ ent = p.ent + base.w;
+        const float4 xi = rpos[so[bead]];
+        const float2 abi = p.ab_o[bead];
+        const float bs = (float)p.ctx[r].bond_scale, inv_bs2 = __builtin_amdgcn_rcpf(bs * bs);      // (as fill_ctxf has them)
+        for (unsigned k = k0; k < k1; k++) {
+            const unsigned e = ent[k], j = e & GD_RP_PARTNER_MASK;
+            const BondType bt = s_rec[e >> GD_RP_SLOT_SHIFT];
+            const float4 xj = rpos[so[j]];
+            float3 d = make_float3(xi.x - xj.x, xi.y - xj.y, xi.z - xj.z);
+            if (p.periodic && (bt.flags & 4)) d = min_image(d, p.box, p.inv_box);
+            const float r2 = d.x * d.x + d.y * d.y + d.z * d.z;
+            float K = bt.ka, l = bt.la;
+            if (bt.flags & 1) {
+                const float2 abj = p.ab_o[j];
+                const float a = 0.5f * (abi.x + abj.x), b = 0.5f * (abi.y + abj.y);
+                K = a * bt.ka + b * bt.kb; l = a * bt.la + b * bt.lb;
+            }
+            if (bt.flags & 2) { K = K * inv_bs2; l = l * bs; }
+            float en, fr;
+            bond_pot(bt.kind, K, l, bt.pq & 0xff, bt.pq >> 8, r2, en, fr);
+            F.x += fr * d.x; F.y += fr * d.y; F.z += fr * d.z;
+            E += 0.5f * en;      // every pair is visited from both ends
+        }
+    }
+    if (MODE == 0) {
+        if (active) {
+            const float mu_dt = (p.mob_o ? p.mob_o[bead] : p.mob_uniform) * p.dt;
+            float4 *o = p.pos_out + (size_t)r * p.Np + so[bead];
+            float4 x = *o;
+            const float ex = mu_dt * F.x, ey = mu_dt * F.y, ez = mu_dt * F.z;
+            if (p.comp) {      // the two-sum over (x, lo) of k_step's update, on the pair k_step has just written (as k_softwell)
+                float4 *lp = p.lo + ((size_t)r * p.N + bead);
+                const float4 l = *lp;
+                const float tx = l.x + ex, ty = l.y + ey, tz = l.z + ez;
+                const float nx = x.x + tx, ny = x.y + ty, nz = x.z + tz;
+                const float bx = nx - x.x, by = ny - x.y, bz = nz - x.z;
+                *lp = make_float4((x.x - (nx - bx)) + (tx - bx), (x.y - (ny - by)) + (ty - by), (x.z - (nz - bz)) + (tz - bz), 0.f);
+                x.x = nx; x.y = ny; x.z = nz;
+            } else { x.x += ex; x.y += ey; x.z += ez; }
+            *o = x;
+        }
+    } else if (MODE == 1) {
+        if (active) {
+            float4 *o = p.fout + (size_t)r * p.N + bead;
+            float4 f = *o;
+            f.x += F.x; f.y += F.y; f.z += F.z;
+            *o = f;
+        }
+    } else {
+        double e = wave_sum_d((double)E);
+        if ((threadIdx.x & 63) == 0 && e != 0.0) atomicAdd(&p.esum[r], e);
+    }
+}
+
+void gd_launch_replica_pairs(const ReplicaPairsP &p, int mode, hipStream_t st)
+{
+    const dim3 grid((p.max_rows + 255) / 256, p.R), block(256);
+    if (mode == 0) hipLaunchKernelGGL(k_replica_pairs<0>, grid, block, 0, st, p);
+    else if (mode == 1) hipLaunchKernelGGL(k_replica_pairs<1>, grid, block, 0, st, p);
+    else hipLaunchKernelGGL(k_replica_pairs<2>, grid, block, 0, st, p);
 }
 
 // ------------------------------------------------------------- pair search

@@ -324,6 +324,29 @@ struct SoftwellP {
     float box[3], inv_box[3];
 };
 void gd_launch_softwell(const SoftwellP &p, int mode, hipStream_t st);
+// Per-replica dynamic pairs (include/gdyn_replica.h): one thread per active bead of a replica walks its row of the table that
+// gdyn_replica_pairs.hpp lays out.  The modes and the position / force / energy buffers are those of SoftwellP.
+#define GD_RP_SLOT_SHIFT 30                // table entry = partner | slot << 30 (gd::RP_SLOT_SHIFT, gdyn_replica_pairs.hpp)
+#define GD_RP_PARTNER_MASK ((1u << GD_RP_SLOT_SHIFT) - 1u)
+struct ReplicaPairsP {
+    const float4 *pos_in;
+    float4 *pos_out, *fout;
+    double *esum;
+    const unsigned *slot_of;
+    const uint4 *base;          // [R]: M_r, first row, first offset, first entry
+    const BondType *rec;        // [4]: the slots' parameter records
+    const unsigned *row_bead, *row_off, *ent;
+    const DevCtx *ctx;          // the contexts the evaluation's k_step used (bond_scale)
+    const float2 *ab_o;         // (a, b) by bead id, for mixed sets
+    const float *mob_o;         // per-bead mobility, or NULL with mob_uniform
+    float mob_uniform, dt;
+    float4 *lo;
+    int comp;
+    unsigned N, Np, R, max_rows;
+    int periodic;
+    float box[3], inv_box[3];
+};
+void gd_launch_replica_pairs(const ReplicaPairsP &p, int mode, hipStream_t st);
 // Unique pairs (bead ids i < j) of one replica closer than dcut, filtered from the RESIDENT Verlet list (k_pairs)
 struct PairsP {
     const float4 *pos, *x0;             // current positions (slot order); build positions: rec_x0 (tiled, thread order) or xb (slot order)

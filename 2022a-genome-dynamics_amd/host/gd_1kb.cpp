@@ -15,11 +15,16 @@
 // selection changes cost only, but it reads a clock -- the cell decomposition, and with it the fp32 summation order of a
 // trajectory, would differ from run to run, where the reference gives one trajectory per seed.  (--fixed-skin, the former
 // spelling of the default, is still accepted.)
+// --seeds s0,s1,...: an ensemble of trajectories as the replicas of ONE handle (class ensemble below): replica r is the trajectory
+// `-s s_r` would start, with its own generator, kinetics, output file (the output name holds the placeholder {seed}) and trace
+// (<dir>/seed-<s_r>/).  Its loops and glues are the per-replica pair lists of include/gdyn_replica.h, which only libgdyn has: the
+// symbols are referenced weakly, and two or more seeds are refused where they are absent.  One seed runs exactly as -s.
 // The program reads no environment variable.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <filesystem>
 #include <fstream>
 #include <iostream>
 #include <memory>
@@ -30,6 +35,11 @@
 #include <vector>
 
 #include "../../include/gdyn.h"
+#include "../../include/gdyn_replica.h"
+// This program is also linked against libraries that implement gdyn.h alone (the fp64 oracle of the tests): what --seeds calls is
+// referenced weakly, and an ensemble is refused where the symbols are absent.
+#pragma weak gd_replica_pairs_define
+#pragma weak gd_replica_pairs_set
 #include "gd_1kb_config.hpp"
 #include "gd_1kb_kinetics.hpp"
 #include "gd_1kb_store.hpp"
@@ -306,6 +316,281 @@ private:
     bool _auto_skin = false;
 };
 
+// --seeds: K trajectories as the replicas of one handle.  Every member function is simulation's, per replica: the same draws from the
+// replica's own generator in the same order, the same log lines (prefixed "[seed s]"), the same datasets in the replica's own file.
+class ensemble {
+public:
+    ensemble(simulation_config const &config, std::vector<std::uint64_t> const &seeds, std::vector<std::string> const &outputs, int device,
+             std::string const &trace_dir, bool auto_skin)
+        : _config(config), _chains(make_chain_assignments(_config)), _auto_skin(auto_skin)
+    {
+        for (auto const &c : _chains) _n += c.config->length;
+        if (_n == 0) throw std::runtime_error("no monomers: the configuration defines no chains");
+        std::vector<int> ranges;
+        for (auto const &c : _chains) { ranges.push_back(int(c.start)); ranges.push_back(int(c.end)); }
+        for (std::size_t r = 0; r < seeds.size(); r++) {
+            simulation_config own = _config;      // what `-s s_r -o <its file>` would run with
+            own.sampling.random_seed = seeds[r]; own.sampling.output_filename = outputs[r];
+            _replicas.push_back(std::make_unique<replica>(own, _chains));
+            auto &t = *_replicas.back();
+            if (!trace_dir.empty()) {
+                t.trace_dir = trace_dir + "/seed-" + std::to_string(seeds[r]);
+                std::filesystem::create_directories(t.trace_dir);
+                t.trace.open(t.trace_dir + "/trace.txt");
+            }
+            t.store.save_metadata(format_simulation_config(own), own.config_text, ranges);
+        }
+        setup_system(device);
+    }
+    ~ensemble() { gd_destroy(_sys); }
+
+    void run()
+    {
+        _xyz.assign(3 * _n * _replicas.size(), 0.0);
+        for (std::size_t r = 0; r < _replicas.size(); r++) initialize_particles(r);
+        chk(gd_set_positions(_sys, _xyz.data()));
+        if (_config.sampling.loop_preloading) for (auto &t : _replicas) t->loops.preload(t->random);
+        run_simulation();
+    }
+
+private:
+    struct replica {
+        replica(simulation_config const &own, std::vector<chain_assignment> const &chains)
+            : seed(own.sampling.random_seed), random(make_random(seed)), store(own.sampling.output_filename),
+              loops(make_loop_extruder(own, chains)),
+              glues(own.glue.max_glues, own.glue.glue_distance, own.glue.glue_binding_rate, own.glue.glue_unbinding_rate, own.chain.box_size)
+        {
+        }
+        std::uint64_t seed;
+        std::mt19937_64 random;      // shared by this trajectory's initialiser, loop preloading, integrator seed and kinetics
+        history_store store;
+        gd::loop_extruder loops;
+        gd::glue_binder glues;
+        std::size_t zero_length_loops = 0;
+        std::string trace_dir;
+        std::ofstream trace;
+    };
+
+    // simulation::setup_system with K replicas; the loop and glue sets are per-replica slots 0 and 1
+    void setup_system(int device)
+    {
+        auto const &ch = _config.chain;
+        gd_desc desc{};
+        desc.n_beads = (uint32_t)_n; desc.n_replicas = (uint32_t)_replicas.size(); desc.device = device; desc.box_kind = GD_BOX_PERIODIC;
+        desc.box[0] = desc.box[1] = desc.box[2] = ch.box_size;
+        chk(gd_create(&desc, &_sys));
+        {
+            gd_tuning tune{};
+            tune.adapt_interval = 1; tune.auto_skin = _auto_skin ? 1 : 0;
+            chk(gd_set_tuning(_sys, &tune));
+        }
+        std::vector<double> mobility(_n, ch.monomer_mobility), bending(_n, ch.bending_energy);
+        for (auto const &c : _chains)
+            for (auto const &block : c.config->blocks)
+                for (std::size_t i = block.start; i < block.end; i++)
+                    if (block.bending_energy) bending.at(c.start + i) = *block.bending_energy;
+        chk(gd_set_bead_params(_sys, nullptr, nullptr, mobility.data(), bending.data()));
+        gd_pair_softcore pair{};
+        pair.eps_a = ch.repulsive_energy; pair.sigma_a = ch.repulsive_diameter; pair.p_a = 2; pair.q_a = 3;
+        pair.eps_b = ch.attractive_energy * -1; pair.sigma_b = ch.attractive_diameter; pair.p_b = 8; pair.q_b = 3;
+        chk(gd_set_pair_softcore(_sys, &pair));
+        gd_bond_params bond{};
+        bond.kind = GD_POT_SPRING; bond.k_a = ch.bond_spring; bond.l_a = ch.bond_length;
+        for (auto const &c : _chains) {
+            chk(gd_add_bond_range(_sys, &bond, (uint32_t)c.start, (uint32_t)c.end, 1));
+            chk(gd_add_bending_range(_sys, (uint32_t)c.start, (uint32_t)c.end, 0.0, /*per_bead=*/1));
+        }
+        _loop_bond.kind = GD_POT_SPRING; _loop_bond.k_a = _config.loop.bond_spring; _loop_bond.l_a = ch.repulsive_diameter;
+        _glue_bond.kind = GD_POT_SOFTCORE; _glue_bond.k_a = -_config.glue.glue_energy; _glue_bond.l_a = _config.glue.glue_distance;
+        _glue_bond.p = 8; _glue_bond.q = 3; _glue_bond.minimum_image = 1;
+        chk(gd_replica_pairs_define(_sys, 0, &_loop_bond));
+        chk(gd_replica_pairs_define(_sys, 1, &_glue_bond));
+    }
+
+    double *xyz(std::size_t r) { return _xyz.data() + 3 * _n * r; }
+
+    // simulation::initialize_particles on replica r's generator, into its part of the positions
+    void initialize_particles(std::size_t r)
+    {
+        auto const &ch = _config.chain;
+        auto &random = _replicas[r]->random;
+        double *x = xyz(r);
+        std::vector<double> centroids;
+        for (std::size_t c = 0; c < _chains.size(); c++) {
+            std::uniform_real_distribution<double> coord{0, ch.box_size};
+            for (int k = 0; k < 3; k++) centroids.push_back(coord(random));
+        }
+        double walk[3] = {0, 0, 0};
+        for (std::size_t i = 0; i < _n; i++) {
+            for (int k = 0; k < 3; k++) x[3 * i + k] = walk[k];
+            std::normal_distribution<double> normal;
+            double d[3] = {normal(random), normal(random), normal(random)};
+            double const inv = 1 / std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            for (int k = 0; k < 3; k++) walk[k] += ch.initial_bond_length * (d[k] * inv);
+        }
+        for (std::size_t c = 0; c < _chains.size(); c++) {
+            auto const &chain = _chains[c];
+            double offset[3] = {0, 0, 0};
+            for (std::size_t i = chain.start; i < chain.end; i++)
+                for (int k = 0; k < 3; k++) offset[k] += x[3 * i + k] - centroids[3 * c + k];
+            for (int k = 0; k < 3; k++) offset[k] /= double(chain.end - chain.start);
+            for (std::size_t i = chain.start; i < chain.end; i++)
+                for (int k = 0; k < 3; k++) x[3 * i + k] -= offset[k];
+        }
+        if (!_replicas[r]->trace_dir.empty()) {
+            std::ofstream out(_replicas[r]->trace_dir + "/init.f64", std::ios::binary);
+            out.write(reinterpret_cast<char const *>(x), (std::streamsize)(3 * _n * sizeof(double)));
+        }
+    }
+
+    void upload_loops(std::size_t r, long step)
+    {
+        auto &t = *_replicas[r];
+        std::vector<uint32_t> pairs;
+        t.zero_length_loops = 0;      // (a zero-length loop: no force, a constant energy added in show_progress)
+        for (auto const &l : t.loops.loops()) {
+            if (!l.id) continue;
+            if (l.start == l.end) { t.zero_length_loops++; continue; }
+            pairs.push_back((uint32_t)l.start); pairs.push_back((uint32_t)l.end);
+        }
+        chk(gd_replica_pairs_set(_sys, 0, (uint32_t)r, pairs.data(), (uint32_t)(pairs.size() / 2)));
+        trace(t, "loops", step, pairs);
+    }
+
+    void upload_glues(std::size_t r, long step)
+    {
+        auto &t = *_replicas[r];
+        std::vector<std::pair<uint32_t, uint32_t>> sorted;
+        for (auto const &g : t.glues.pairs()) sorted.push_back({g.i, g.j});
+        std::sort(sorted.begin(), sorted.end());
+        std::vector<uint32_t> pairs;
+        for (auto const &g : sorted) { pairs.push_back(g.first); pairs.push_back(g.second); }
+        chk(gd_replica_pairs_set(_sys, 1, (uint32_t)r, pairs.data(), (uint32_t)(pairs.size() / 2)));
+        trace(t, "glues", step, pairs);
+    }
+
+    static void trace(replica &t, char const *what, long step, std::vector<uint32_t> const &pairs)
+    {
+        if (!t.trace.is_open()) return;
+        t.trace << what << ' ' << step << ' ' << pairs.size() / 2;
+        for (auto v : pairs) t.trace << ' ' << v;
+        t.trace << '\n' << std::flush;
+    }
+
+    void step_loops(long step)
+    {
+        auto const &s = _config.sampling;
+        double const leap = s.timestep * double(s.loop_update_interval);
+        for (std::size_t r = 0; r < _replicas.size(); r++) {
+            auto &t = *_replicas[r];
+            if (!s.clear_loops_at || step < s.clear_loops_at) t.loops.step(leap, t.random);
+            if (step + 1 == s.clear_loops_at) t.loops.clear();
+            upload_loops(r, step);
+        }
+    }
+
+    void step_glues(long step)
+    {
+        if (!_replicas[0]->glues.enabled()) return;
+        auto const &s = _config.sampling;
+        double const leap = s.timestep * double(s.glue_update_interval);
+        chk(gd_get_positions(_sys, _xyz.data()));
+        for (std::size_t r = 0; r < _replicas.size(); r++) {
+            auto &t = *_replicas[r];
+            uint64_t n = 0;
+            chk(gd_search_pairs(_sys, (uint32_t)r, t.glues.reach(), nullptr, 0, &n));
+            std::vector<uint32_t> candidates(2 * n);
+            if (n) chk(gd_search_pairs(_sys, (uint32_t)r, t.glues.reach(), candidates.data(), n, &n));
+            t.glues.update(leap, xyz(r), candidates, t.random);
+            upload_glues(r, step);
+        }
+    }
+
+    // one line per replica: "[seed s] step \t E: .. \t L: .. \t G: .."
+    void show_progress(long step)
+    {
+        std::vector<double> e(_replicas.size(), 0.0);
+        chk(gd_compute_energy(_sys, GD_TERM_ALL, e.data()));
+        double const n = double(_n);
+        for (std::size_t r = 0; r < _replicas.size(); r++) {
+            auto const &t = *_replicas[r];
+            double const er = e[r] + double(t.zero_length_loops) * 0.5 * _loop_bond.k_a * _loop_bond.l_a * _loop_bond.l_a;
+            std::clog << "[seed " << t.seed << "] " << step << '\t' << "E: " << er / n << '\t' << "L: " << double(t.loops.loaded()) / n << '\t'
+                      << "G: " << double(t.glues.size()) / n << '\n';
+        }
+    }
+
+    void save_sample()
+    {
+        chk(gd_get_positions(_sys, _xyz.data()));
+        for (std::size_t r = 0; r < _replicas.size(); r++) {
+            auto &t = *_replicas[r];
+            std::vector<long long> loops;
+            for (auto const &l : t.loops.loops()) { loops.push_back((long long)l.start); loops.push_back((long long)l.end); loops.push_back((long long)l.id); }
+            t.store.save_snapshot(xyz(r), _n, loops);
+        }
+    }
+
+    static long next_multiple(long step, long interval) { return (step / interval + 1) * interval; }
+
+    void run_simulation()
+    {
+        auto const &s = _config.sampling;
+        for (long interval : {s.logging_interval, s.sampling_interval, s.loop_update_interval, s.glue_update_interval})
+            if (interval <= 0) throw std::runtime_error("intervals must be positive");
+        auto callback = [&](long step) {
+            if (step % s.logging_interval == 0) show_progress(step);
+            if (step % s.sampling_interval == 0) save_sample();
+            if (step % s.loop_update_interval == 0) step_loops(step);
+            if (step % s.glue_update_interval == 0) step_glues(step);
+        };
+        chk(gd_begin_phase(_sys, nullptr));
+        for (std::size_t r = 0; r < _replicas.size(); r++) upload_loops(r, -1);
+        callback(0);
+        std::vector<uint64_t> seeds;      // every trajectory's integrator seed, drawn where simulation draws it
+        for (auto &t : _replicas) {
+            seeds.push_back(t->random());
+            if (t->trace.is_open()) t->trace << "seed " << seeds.back() << '\n' << std::flush;
+        }
+        gd_run_desc run{};
+        run.temperature = s.temperature; run.timestep = s.timestep; run.seed = seeds[0]; run.noise_mode = GD_NOISE_PHILOX;
+        run.replica_seeds = seeds.data();
+        long step = 0;
+        while (step < s.steps) {
+            long const next = std::min<long>(s.steps, std::min({next_multiple(step, s.logging_interval), next_multiple(step, s.sampling_interval),
+                                                               next_multiple(step, s.loop_update_interval), next_multiple(step, s.glue_update_interval)}));
+            run.steps = next - step; chk(gd_run(_sys, &run)); step = next;
+            callback(step);
+        }
+    }
+
+    simulation_config _config;
+    std::vector<chain_assignment> _chains;
+    std::vector<std::unique_ptr<replica>> _replicas;
+    gd_system *_sys = nullptr;
+    std::size_t _n = 0;
+    gd_bond_params _loop_bond{}, _glue_bond{};
+    std::vector<double> _xyz;        // (K, N, 3)
+    bool _auto_skin = false;
+};
+
+// "s0,s1,...": distinct unsigned integers
+std::vector<std::uint64_t> parse_seeds(std::string const &text)
+{
+    std::vector<std::uint64_t> seeds;
+    std::size_t pos = 0;
+    while (pos <= text.size()) {
+        std::size_t const end = std::min(text.find(',', pos), text.size());
+        std::string const item = text.substr(pos, end - pos);
+        if (item.empty() || item.find_first_not_of("0123456789") != std::string::npos) throw std::runtime_error{"--seeds takes a comma-separated list of unsigned integers"};
+        std::uint64_t const seed = std::stoull(item);
+        if (std::find(seeds.begin(), seeds.end(), seed) != seeds.end()) throw std::runtime_error{"--seeds: seed " + item + " is listed twice"};
+        seeds.push_back(seed);
+        pos = end + 1;
+    }
+    return seeds;
+}
+
 void show_usage()
 {
     std::cerr << "Loop formation simulator\n"
@@ -315,6 +600,8 @@ void show_usage()
                  "  -C <config>  override chain definitions (config 'chains' key) by additional JSON file\n"
                  "  -o <output>  override output HDF5 filename (config 'output_filename' key)\n"
                  "  -s <seed>    override random seed (config 'random_seed' key)\n"
+                 "  --seeds <s0,s1,...> run one trajectory per seed as the replicas of one device handle; the output name\n"
+                 "               must contain {seed}; not with -s\n"
                  "  -d <device>  GPU index (default 0)\n"
                  "  --auto-skin  select the neighbour-list width from measured step times (faster on some models; the\n"
                  "               trajectory of a seed then depends on timing -- off by default)\n"
@@ -341,6 +628,7 @@ int main(int argc, char **argv)
         int device = 0;
         std::string trace_dir;
         bool auto_skin = false;
+        std::optional<std::vector<std::uint64_t>> seeds;
         for (int i = 1; i < argc; i++) {
             std::string const arg = argv[i];
             auto value = [&]() -> std::string { if (i + 1 >= argc) throw std::runtime_error{"bad option"}; return argv[++i]; };
@@ -348,6 +636,7 @@ int main(int argc, char **argv)
             else if (arg == "-C") chains_filename = value();
             else if (arg == "-o") output_filename = value();
             else if (arg == "-s") seed = std::stoull(value());
+            else if (arg == "--seeds") seeds = parse_seeds(value());
             else if (arg == "-d") device = std::stoi(value());
             else if (arg == "--trace") trace_dir = value();
             else if (arg == "--auto-skin") auto_skin = true;
@@ -374,6 +663,22 @@ int main(int argc, char **argv)
             }
         }
         if (output_filename) config.sampling.output_filename = *output_filename;
+        if (seeds) {
+            if (seed) throw std::runtime_error{"--seeds and -s exclude each other"};
+            std::string const &name = config.sampling.output_filename;
+            std::size_t const at = name.find("{seed}");
+            if (at == std::string::npos) throw std::runtime_error{"--seeds: the output name '" + name + "' must contain {seed}"};
+            std::vector<std::string> outputs;
+            for (auto s : *seeds) outputs.push_back(std::string{name}.replace(at, 6, std::to_string(s)));
+            if (seeds->size() == 1) { seed = seeds->front(); config.sampling.output_filename = outputs.front(); }      // exactly -s
+            else {
+                if (!gd_replica_pairs_define || !gd_replica_pairs_set)
+                    throw std::runtime_error{"--seeds with several seeds needs per-replica dynamic pair lists (gd_replica_pairs_*, gdyn_replica.h), "
+                                             "which this gdyn library does not have"};
+                ensemble{config, *seeds, outputs, device, trace_dir, auto_skin}.run();
+                return 0;
+            }
+        }
         if (seed) config.sampling.random_seed = *seed;
         simulation{config, device, trace_dir, auto_skin}.run();
         return 0;
