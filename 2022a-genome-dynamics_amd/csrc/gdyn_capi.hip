@@ -19,6 +19,7 @@
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_replica.h"
+#include "../../include/gdyn_ensemble.h"
 #include <hip/hip_fp16.h>
 
 #include "gdyn_types.h"
@@ -27,6 +28,7 @@
 #include "gdyn_list.hpp"
 #include "gdyn_live.hpp"
 #include "gdyn_replica_pairs.hpp"
+#include "gdyn_ensemble.hpp"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
 #endif
@@ -98,7 +100,8 @@ struct gd_system {
     hipStream_t stream = nullptr;
 
     // host model
-    std::vector<double> a, b, mob, bend;
+    gd::EnsembleAB ens;            // the (a, b) factors: the shared table and what single replicas carry instead (gdyn_ensemble.hpp)
+    std::vector<double> mob, bend;
     bool has_pair = false; gd_pair_softcore pair{};
     std::vector<gd_bond_params> btypes; std::vector<int> bterm;
     std::vector<Bond> bonds;
@@ -138,7 +141,8 @@ struct gd_system {
     gd_timing timing{};
 
     // device: static (bead order)
-    DevBuf<float2> ab_o; DevBuf<float> mob_o; DevBuf<float4> bendE_o; DevBuf<unsigned char> psmask_o, bdeg_o;
+    DevBuf<float2> ab_o; uint32_t ab_stride = 0;      // [N], stride 0: one table for all replicas; [R][N], stride N: one each (gdyn_ensemble.h)
+    DevBuf<float> mob_o; DevBuf<float4> bendE_o; DevBuf<unsigned char> psmask_o, bdeg_o;
     DevBuf<unsigned> badj_o; DevBuf<int4> chain_o; DevBuf<BondType> btab;
     // device: per slot
     DevBuf<float4> pos[2], xb, fout, snap;
@@ -217,7 +221,7 @@ extern "C" int gd_create_abi(int abi_version, const gd_desc *d, gd_system **out)
     s->Np = s->nblk * GD_BLOCK;
     s->cpb = (s->nblk + GD_XCDS - 1) / GD_XCDS;
     if (s->R % GD_XCDS == 0 && !dev_env("GDYN_SLICE_MAP")) s->cpb = 0;      // whole replicas per XCD (see block_map)
-    s->a.assign(s->N, 0.0); s->b.assign(s->N, 0.0); s->mob.assign(s->N, 1.0); s->bend.assign(s->N, 0.0);
+    s->ens.reset(s->N, s->R); s->mob.assign(s->N, 1.0); s->bend.assign(s->N, 0.0);
     s->hctx.assign(s->R, DevCtx{});
     for (auto &c : s->hctx) { c.bead_scale = 1; c.bond_scale = 1; }   // wall_semiaxes {0,0,0} until a wall is set (simulation_context.hpp:16)
     s->rp.reset(s->N, s->R);
@@ -354,8 +358,7 @@ extern "C" int gd_set_bead_params(gd_system *s, const double *a, const double *b
 {
     if (!s) return fail(GD_EINVAL, "gd_set_bead_params: NULL system");
     if (mob) for (uint32_t i = 0; i < s->N; i++) if (!(mob[i] >= 0)) return fail(GD_EINVAL, "gd_set_bead_params: negative mobility at %u", i);
-    if (a) s->a.assign(a, a + s->N);
-    if (b) s->b.assign(b, b + s->N);
+    s->ens.set_shared(a, b);      // (a column replaces that column of every replica, gdyn_ensemble.h)
     if (mob) s->mob.assign(mob, mob + s->N);
     if (bend) s->bend.assign(bend, bend + s->N);
     s->topo_dirty = true;
@@ -567,7 +570,7 @@ static void launch_replica_pairs(gd_system *s, const StepParams &p, int mode)
     q.base = (const uint4 *)(s->rp_dev.p + l.base); q.rec = (const BondType *)(s->rp_dev.p + l.rec);
     q.row_bead = s->rp_dev.p + l.row_bead; q.row_off = s->rp_dev.p + l.row_off; q.ent = s->rp_dev.p + l.ent;
     q.ctx = mode == 0 ? p.ctx_out : p.ctx_in;      // (a step's k_step has applied the pending callback and left the result there)
-    q.ab_o = s->ab_o.p;
+    q.ab_o = s->ab_o.p; q.ab_stride = s->ab_stride;
     q.mob_o = s->mob_uniform >= 0.f ? nullptr : s->mob_o.p; q.mob_uniform = s->mob_uniform; q.dt = p.dt;
     q.lo = p.lo; q.comp = p.comp;
     q.N = s->N; q.Np = s->Np; q.R = s->R; q.max_rows = l.max_rows;
@@ -605,6 +608,42 @@ extern "C" int gd_replica_pairs_count(gd_system *s, uint32_t slot, uint32_t repl
     if (replica >= s->R) return fail(GD_EINVAL, "gd_replica_pairs_count: replica %u out of range", replica);
     if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_replica_pairs_count: slot %u was never defined (gd_replica_pairs_define)", slot);
     *n = s->rp.count(slot, replica);
+    return GD_OK;
+}
+
+// ------------------------------------------------------------- per-replica A/B tables (include/gdyn_ensemble.h)
+
+extern "C" int gd_ensemble_abi_version(void) { return GD_ENSEMBLE_ABI_VERSION; }
+
+extern "C" int gd_ensemble_set_ab(gd_system *s, uint32_t replica, const double *a, const double *b)
+{
+    if (!s) return fail(GD_EINVAL, "gd_ensemble_set_ab: NULL system");
+    if (replica >= s->R) return fail(GD_EINVAL, "gd_ensemble_set_ab: replica %u out of range", replica);
+    if (!a && !b) return fail(GD_EINVAL, "gd_ensemble_set_ab: a and b are both NULL");
+    if (const size_t bad = s->ens.set(replica, a, b)) return fail(GD_EINVAL, "gd_ensemble_set_ab: non-finite factor at bead %zu", bad - 1);
+    // the factors enter the device state in the gather of the next list build and nowhere else: what pos.w carries and the resident
+    // list go, and finalize_topology decides again whether the bond records can be mixed on the host
+    s->topo_dirty = true; s->list.topology_changed();
+    return GD_OK;
+}
+
+extern "C" int gd_ensemble_get_ab(gd_system *s, uint32_t replica, double *a, double *b)
+{
+    if (!s) return fail(GD_EINVAL, "gd_ensemble_get_ab: NULL system");
+    if (replica >= s->R) return fail(GD_EINVAL, "gd_ensemble_get_ab: replica %u out of range", replica);
+    if (!a && !b) return fail(GD_EINVAL, "gd_ensemble_get_ab: a and b are both NULL");
+    s->ens.get(replica, a, b);
+    return GD_OK;
+}
+
+extern "C" int gd_ensemble_classes(gd_system *s, uint32_t *class_of, uint32_t *n_classes)
+{
+    if (!s) return fail(GD_EINVAL, "gd_ensemble_classes: NULL system");
+    if (!class_of && !n_classes) return fail(GD_EINVAL, "gd_ensemble_classes: class_of and n_classes are both NULL");
+    std::vector<uint32_t> c(s->R);
+    const uint32_t n = s->ens.classes(c.data());
+    if (class_of) std::copy(c.begin(), c.end(), class_of);
+    if (n_classes) *n_classes = n;
     return GD_OK;
 }
 
@@ -717,15 +756,17 @@ static int finalize_topology(gd_system *s)
     // have few distinct (a, b) per set -- the bead types are a handful of values -- so every bond gets the index of its own,
     // already mixed, parameter record and the kernels skip the per-bond mixing arithmetic.  More records than the table holds:
     // the sets stay as given and the kernels mix at run time.
+    // A handle whose replicas carry different tables (gdyn_ensemble.h) has no one (a, b) per bond: its sets stay as given as well.
+    const bool hetero = !s->ens.homogeneous();
     s->bonds_premixed = false;
-    {
+    if (!hetero) {
         std::vector<gd_bond_params> t2; std::vector<int> term2; std::vector<Bond> all2 = all;
         bool fits = true, any_mixed = false;
         for (auto &b : all2) {
             gd_bond_params q = types[b.type];
             if (q.mix) {
                 any_mixed = true;
-                const double a = 0.5 * (s->a[b.i] + s->a[b.j]), bb = 0.5 * (s->b[b.i] + s->b[b.j]);
+                const double a = 0.5 * (s->ens.a(0, b.i) + s->ens.a(0, b.j)), bb = 0.5 * (s->ens.b(0, b.i) + s->ens.b(0, b.j));
                 q.k_a = a * q.k_a + bb * q.k_b; q.l_a = a * q.l_a + bb * q.l_b; q.k_b = 0; q.l_b = 0; q.mix = 0;
             }
             int found = -1;
@@ -783,19 +824,20 @@ static int finalize_topology(gd_system *s)
     std::vector<unsigned char> psm(N, 0);
     for (size_t q = 0; q < s->psrc.size(); q++)
         for (uint32_t i = 0; i < N; i++) if (s->psrc[q].mask.empty() || s->psrc[q].mask[i]) psm[i] |= (unsigned char)(1u << q);
-    std::vector<float2> ab(N);
+    // the source table of k_scatter's gather: one for the handle, or one per replica
+    const uint32_t ab_tables = hetero ? s->R : 1u;
+    std::vector<float2> ab((size_t)ab_tables * N);
     std::vector<float> mob(N);
-    bool packable = true;
-    for (uint32_t i = 0; i < N; i++) {
-        ab[i] = make_float2((float)s->a[i], (float)s->b[i]); mob[i] = (float)s->mob[i];
-        // (a,b) ride in pos.w as two fp16 when that is exact (0, .5, 1, 5 ... are)
-        if ((double)__half2float(__float2half_rn(ab[i].x)) != s->a[i] || (double)__half2float(__float2half_rn(ab[i].y)) != s->b[i]) packable = false;
-    }
-    s->packed_ab = packable;
+    for (uint32_t r = 0; r < ab_tables; r++)
+        for (uint32_t i = 0; i < N; i++) ab[(size_t)r * N + i] = make_float2((float)s->ens.a(r, i), (float)s->ens.b(r, i));
+    for (uint32_t i = 0; i < N; i++) mob[i] = (float)s->mob[i];
+    // (a,b) ride in pos.w as two fp16 when that is exact (0, .5, 1, 5 ... are) for every replica
+    s->packed_ab = s->ens.fp16_exact();
+    s->ab_stride = hetero ? N : 0u;
 
-    HIPCHK(s->ab_o.resize(N)); HIPCHK(s->mob_o.resize(N)); HIPCHK(s->bendE_o.resize(N)); HIPCHK(s->psmask_o.resize(N));
+    HIPCHK(s->ab_o.resize(ab.size())); HIPCHK(s->mob_o.resize(N)); HIPCHK(s->bendE_o.resize(N)); HIPCHK(s->psmask_o.resize(N));
     HIPCHK(s->bdeg_o.resize(N)); HIPCHK(s->badj_o.resize(adj.size())); HIPCHK(s->chain_o.resize(N)); HIPCHK(s->btab.resize(GD_MAX_BOND_TYPES));   /* always the full table: k_step stages it with one DMA piece */
-    HIPCHK(hipMemcpy(s->ab_o.p, ab.data(), N * sizeof(float2), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->ab_o.p, ab.data(), ab.size() * sizeof(float2), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->mob_o.p, mob.data(), N * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->bendE_o.p, bendE.data(), N * sizeof(float4), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->psmask_o.p, psm.data(), N, hipMemcpyHostToDevice));
@@ -923,7 +965,7 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
     b.bbox = s->bbox.p; b.grid = s->grid.p;
     b.bbox_cur = s->bbox_enc.p + (size_t)s->list.bbox_cur * s->R * 6; b.bbox_next = s->bbox_enc.p + (size_t)(s->list.bbox_cur ^ 1) * s->R * 6;
     b.warm = (b.periodic || s->list.bbox_valid) ? 1 : 0; b.bbox_w = s->bbox_w.p;
-    b.ab_o = s->ab_o.p; b.mob_o = s->mob_o.p; b.bendE_o = s->bendE_o.p; b.psmask_o = s->psmask_o.p;
+    b.ab_o = s->ab_o.p; b.ab_stride = s->ab_stride; b.mob_o = s->mob_o.p; b.bendE_o = s->bendE_o.p; b.psmask_o = s->psmask_o.p;
     b.badj_o = s->badj_o.p; b.bdeg_o = s->bdeg_o.p; b.chain_o = s->has_bend ? s->chain_o.p : nullptr; b.WB = s->WB;
     b.ab = s->ab.p; b.mob = s->mobs.p; b.bendE = s->bendE.p; b.badj = s->badj.p; b.has_bend = s->has_bend ? 1 : 0;
     b.mob_is_uniform = s->mob_uniform >= 0.f ? 1 : 0;

@@ -1640,7 +1640,7 @@ __global__ __launch_bounds__(GD_BLOCK) void k_scatter(const BuildParams p)
     // (a,b) ride in pos.w and every kernel carries w along: only positions that came from the host (w = 0) need the per-bead
     // gather again
     float2 ab = make_float2(0.f, 0.f);
-    if (!p.packed_ab || !p.w_valid) ab = p.ab_o[o];
+    if (!p.packed_ab || !p.w_valid) ab = p.ab_o[(size_t)r * p.ab_stride + o];      // (the replica's own table, or the handle's: stride 0)
     if (p.packed_ab && !p.w_valid) x.w = pack_ab(ab);
     const size_t gn = rbase + ns;
     p.pos_out[gn] = x;
@@ -2420,7 +2420,8 @@ __global__ __launch_bounds__(256) void k_replica_pairs(const ReplicaPairsP p)
         const unsigned k0 = p.row_off[base.z + t], k1 = p.row_off[base.z + t + 1];
         const unsigned *__restrict__ ent = p.ent + base.w;
         const float4 xi = rpos[so[bead]];
-        const float2 abi = p.ab_o[bead];
+        const float2 *__restrict__ rab = p.ab_o + (size_t)r * p.ab_stride;      // the replica's own table, or the handle's (stride 0)
+        const float2 abi = rab[bead];
         const float bs = (float)p.ctx[r].bond_scale, inv_bs2 = __builtin_amdgcn_rcpf(bs * bs);      // (as fill_ctxf has them)
         for (unsigned k = k0; k < k1; k++) {
             const unsigned e = ent[k], j = e & GD_RP_PARTNER_MASK;
@@ -2431,7 +2432,7 @@ __global__ __launch_bounds__(256) void k_replica_pairs(const ReplicaPairsP p)
             const float r2 = d.x * d.x + d.y * d.y + d.z * d.z;
             float K = bt.ka, l = bt.la;
             if (bt.flags & 1) {
-                const float2 abj = p.ab_o[j];
+                const float2 abj = rab[j];
                 const float a = 0.5f * (abi.x + abj.x), b = 0.5f * (abi.y + abj.y);
                 K = a * bt.ka + b * bt.kb; l = a * bt.la + b * bt.lb;
             }

@@ -301,6 +301,7 @@ struct BuildParams {
     unsigned pool_cap;                  // KiB of the pool
     int predict;                        // 1: need_prev describes these beads (the build before ran at this radius and class mode)
     unsigned long long *dbg;            // section stamps of timing-only builds (the force-output buffer)
+    unsigned ab_stride;                 // ab_o of replica r starts at r * ab_stride: 0, one table for the handle; N, one per replica (gdyn_ensemble.h)
 };
 
 // launchers (gdyn_kernels.hip)
@@ -337,7 +338,7 @@ struct ReplicaPairsP {
     const BondType *rec;        // [4]: the slots' parameter records
     const unsigned *row_bead, *row_off, *ent;
     const DevCtx *ctx;          // the contexts the evaluation's k_step used (bond_scale)
-    const float2 *ab_o;         // (a, b) by bead id, for mixed sets
+    const float2 *ab_o;         // (a, b) by bead id, for mixed sets: replica r's table starts at r * ab_stride
     const float *mob_o;         // per-bead mobility, or NULL with mob_uniform
     float mob_uniform, dt;
     float4 *lo;
@@ -345,6 +346,7 @@ struct ReplicaPairsP {
     unsigned N, Np, R, max_rows;
     int periodic;
     float box[3], inv_box[3];
+    unsigned ab_stride;         // 0: one table for the handle; N: one per replica (gdyn_ensemble.h)
 };
 void gd_launch_replica_pairs(const ReplicaPairsP &p, int mode, hipStream_t st);
 // Unique pairs (bead ids i < j) of one replica closer than dcut, filtered from the RESIDENT Verlet list (k_pairs)

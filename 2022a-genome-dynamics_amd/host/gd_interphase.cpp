@@ -16,6 +16,13 @@
 // device from the contact tables each time they are dumped (gd_live_contacts, include/gdyn_live.h) and written at the end
 // exactly as `gd_gw_contact_matrix --rebin-rate RATE -o OUTPUT <the same files>` writes it from the stored maps afterwards.
 //
+// Files that differ in /metadata/ab_factors alone -- a genome model and its randomised controls (gd_randomize.py), other annotations of
+// one genome -- batch as well: replica r takes its (a, b) factors from file r (gd_ensemble_set_ab, include/gdyn_ensemble.h).  The
+// files with equal factors form a model, numbered by first appearance in file order and named on stderr, `[model k] file ...`.
+// --ensemble-matrix then pools per model: OUTPUT must contain {model}, which the model's number replaces, and model k's file holds
+// what `gd_gw_contact_matrix --rebin-rate RATE -o ... <the files of model k>` writes.  (A batch of one model: one matrix as before,
+// {model} -- if OUTPUT has it -- replaced by 0.)  The flow outputs are per replica and need nothing for this.
+//
 // --particle-flow OUTPUT, --grid-flow OUTPUT (not in the reference): the flow fields of the run's replicas.  Every frame stored under
 // snapshots/interphase is also recorded on the device (gd_live_history, include/gdyn_live.h), and at the end one gd_flow handle
 // works through the replicas in file order and writes exactly what `gd_particle_flow OUTPUT <flow options> <the same files>` and
@@ -39,9 +46,13 @@
 #include <vector>
 
 #include "../../include/gdyn.h"
+#include "../../include/gdyn_ensemble.h"
 #include "../../include/gdyn_live.h"
 // This program is also linked against libraries that implement gdyn.h alone (the fp64 oracle of the tests).  What
-// --ensemble-matrix and the flow options call is referenced weakly, and the options are refused where the symbols are absent.
+// --ensemble-matrix and the flow options call is referenced weakly, and the options are refused where the symbols are absent;
+// so are the per-replica A/B tables, without which a batch of differing models is refused.
+#pragma weak gd_ensemble_set_ab
+#pragma weak gd_ensemble_classes
 #pragma weak gd_cmap_create
 #pragma weak gd_cmap_destroy
 #pragma weak gd_cmap_add_binned
@@ -124,8 +135,79 @@ struct ensemble_matrix {
         dev.open();
         gd::cli::check(gd_cmap_add_binned(dev.h, rb.map.data(), (uint32_t)rb.map.size(), rb.n_bins, &target));
     }
-    void add(gd_system *sys) { gd::cli::check(gd_live_contacts(sys, GD_ALL_REPLICAS, dev.h)); }
+    void add(gd_system *sys, uint32_t replica) { gd::cli::check(gd_live_contacts(sys, replica, dev.h)); }
     void write() { gd::cmap::write_gw_matrix(output, head, rb, dev.fetch(target)); }
+};
+
+// The models of a batch: files whose /metadata/ab_factors are equal, numbered by first appearance in file order
+struct model_classes {
+    std::vector<uint32_t> of;      // by file
+    uint32_t n = 0;
+    std::vector<std::string> files_of(std::vector<std::string> const &files, uint32_t k) const
+    {
+        std::vector<std::string> v;
+        for (std::size_t r = 0; r < files.size(); r++) if (of[r] == k) v.push_back(files[r]);
+        return v;
+    }
+};
+
+// the factors of a prepared file, read before the stores open the files for writing
+std::vector<double> load_ab_factors(std::string const &path)
+{
+    H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    hid_t const file = H5Fopen(path.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT);
+    gd::h5::check(file >= 0, "cannot open " + path);
+    std::vector<double> ab;
+    try {
+        gd::h5::hid meta(H5Gopen2(file, "/metadata", H5P_DEFAULT));
+        gd::h5::check(meta >= 0, path + ": no /metadata");
+        ab = gd::h5::read_array<double>(meta, "ab_factors", 2, H5T_NATIVE_DOUBLE);
+    } catch (...) {
+        H5Fclose(file);
+        throw;
+    }
+    H5Fclose(file);
+    return ab;
+}
+
+model_classes classify_models(std::vector<std::string> const &files)
+{
+    model_classes m;
+    std::vector<std::vector<double>> first;      // the factors of every model's first file
+    for (auto const &f : files) {
+        auto ab = load_ab_factors(f);
+        std::size_t k = 0;
+        while (k < first.size() && first[k] != ab) k++;
+        if (k == first.size()) first.push_back(std::move(ab));
+        m.of.push_back((uint32_t)k);
+    }
+    m.n = (uint32_t)first.size();
+    return m;
+}
+
+// --ensemble-matrix of a run: one matrix over all replicas, or one per model, each fed from the replicas of its model
+struct ensemble_matrices {
+    std::vector<std::unique_ptr<ensemble_matrix>> of_model;
+    std::vector<uint32_t> model_of;      // by replica
+
+    static std::string output_name(std::string name, uint32_t model)
+    {
+        std::string const key = "{model}";
+        for (std::size_t at; (at = name.find(key)) != std::string::npos;) name.replace(at, key.size(), std::to_string(model));
+        return name;
+    }
+    ensemble_matrices(std::vector<std::string> const &files, model_classes const &models, long rate, std::string const &out, int device)
+        : model_of(models.of)
+    {
+        for (uint32_t k = 0; k < models.n; k++)
+            of_model.push_back(std::make_unique<ensemble_matrix>(models.files_of(files, k).front(), rate, output_name(out, k), device));
+    }
+    void add(gd_system *sys)
+    {
+        if (of_model.size() == 1) { of_model[0]->add(sys, GD_ALL_REPLICAS); return; }
+        for (std::size_t r = 0; r < model_of.size(); r++) of_model[model_of[r]]->add(sys, (uint32_t)r);
+    }
+    void write() { for (auto &m : of_model) m->write(); }
 };
 
 // --particle-flow / --grid-flow: the interphase frames recorded on the device as they are stored, and the two analyses of them
@@ -204,10 +286,10 @@ struct flow_outputs {
 // (gd_run_desc.replica_seeds), so a batched trajectory equals the solo one up to fp32 summation order.
 class simulation_driver {
 public:
-    simulation_driver(std::vector<std::unique_ptr<gd::trajectory_store>> &stores, int device, bool auto_skin = false, ensemble_matrix *ensemble = nullptr,
-                      flow_outputs *flow = nullptr)
+    simulation_driver(std::vector<std::unique_ptr<gd::trajectory_store>> &stores, int device, bool auto_skin = false, ensemble_matrices *ensemble = nullptr,
+                      flow_outputs *flow = nullptr, model_classes const *models = nullptr)
         : _stores(stores), _R(stores.size()), _config(gd::parse_simulation_config(stores[0]->load_config_text())), _auto_skin(auto_skin),
-          _ensemble(ensemble), _flow(flow)
+          _ensemble(ensemble), _flow(flow), _models(models)
     {
         // compatibility defaults of older runs (simulation_driver.cc:20-29)
         auto set_default = [](double &var, double def) { if (var == 0) var = def; };
@@ -253,11 +335,21 @@ private:
     void setup(int device)
     {
         _sys = gd::build_genome_system(*_stores[0], _config, device, /*loop_bonds=*/true, /*mixed_chain_bonds=*/true, _n, (uint32_t)_R);
+        auto const p0 = _stores[0]->load_particle_data();
+        bool tables = false;
         for (std::size_t r = 1; r < _R; r++) {
-            auto const p0 = _stores[0]->load_particle_data(), pr = _stores[r]->load_particle_data();
+            auto const pr = _stores[r]->load_particle_data();
             if (pr.size() != p0.size()) throw std::runtime_error("batched trajectories must hold the same model (bead count differs)");
-            for (std::size_t i = 0; i < p0.size(); i++)
-                if (pr[i].a != p0[i].a || pr[i].b != p0[i].b) throw std::runtime_error("batched trajectories must hold the same model (A/B factors differ)");
+            bool differ = false;
+            for (std::size_t i = 0; !differ && i < p0.size(); i++) differ = pr[i].a != p0[i].a || pr[i].b != p0[i].b;
+            if (differ) {      // the replica carries its own factors, where the library has per-replica tables
+                if (!gd_ensemble_set_ab || !gd_ensemble_classes)
+                    throw std::runtime_error("batched trajectories must hold the same model (A/B factors differ)");
+                std::vector<double> a(pr.size()), b(pr.size());
+                for (std::size_t i = 0; i < pr.size(); i++) { a[i] = pr[i].a; b[i] = pr[i].b; }
+                chk(gd_ensemble_set_ab(_sys, (uint32_t)r, a.data(), b.data()));
+                tables = true;
+            }
             // the topology the handle is built from is file 0's: chains, nucleolar ranges and bonds must agree as well
             auto const c0 = _stores[0]->load_chromosomes(), cr = _stores[r]->load_chromosomes();
             bool same = c0.size() == cr.size();
@@ -269,6 +361,12 @@ private:
             same = same && b0.size() == br.size();
             for (std::size_t i = 0; same && i < b0.size(); i++) same = b0[i].nor_index == br[i].nor_index && b0[i].nuc_index == br[i].nuc_index;
             if (!same) throw std::runtime_error("batched trajectories must hold the same model (chromosome / nucleolus tables differ)");
+        }
+        if (tables) {      // the models as the library sees them are those the command line was checked against
+            std::vector<uint32_t> of(_R);
+            uint32_t n = 0;
+            chk(gd_ensemble_classes(_sys, of.data(), &n));
+            if (_models && (n != _models->n || of != _models->of)) throw std::runtime_error("the models of the batch changed between the check of the command line and the set-up");
         }
         // setup_context (simulation_driver.cc:43-51)
         gd::context c{};
@@ -500,8 +598,9 @@ private:
     std::size_t _R;
     gd::simulation_config _config;
     bool _auto_skin = false;
-    ensemble_matrix *_ensemble = nullptr;
+    ensemble_matrices *_ensemble = nullptr;
     flow_outputs *_flow = nullptr;
+    model_classes const *_models = nullptr;
     bool _interphase = false;
     std::vector<gd::context> _context;
     double _contact_distance = 0;
@@ -532,9 +631,11 @@ int main(int argc, char **argv)
     // gd_interphase [--device d] <trajectory> <trajectory>...  R prepared files as R replicas of one handle
     // options: --timing (wall-time split on stderr at the end), --auto-skin (list width selected from measured chunk times: the
     // trajectory of a seed then depends on timing; off by default.  --fixed-skin, the former spelling of the default, is accepted),
-    // --ensemble-matrix RATE OUTPUT (the genome-wide contact matrix of the replicas, as gd_gw_contact_matrix --rebin-rate RATE writes it),
+    // --ensemble-matrix RATE OUTPUT (the genome-wide contact matrix of the replicas, as gd_gw_contact_matrix --rebin-rate RATE writes it;
+    // files that differ in their A/B factors form models: OUTPUT then needs {model}, and every model gets its own matrix),
     // --particle-flow OUTPUT / --grid-flow OUTPUT with the options of gd_particle_flow / gd_grid_flow: --scan-radius, --smoothing,
-    // --velocity-delay, --name, and for the grid --grid-interval, --x-range, --y-range, --z-range
+    // --velocity-delay, --name, and for the grid --grid-interval, --x-range, --y-range, --z-range (per replica: a batch of several
+    // models needs nothing else)
     std::vector<std::string> files, flow_args;
     std::string particle_output, grid_output;
     bool particle_asked = false, grid_asked = false;
@@ -590,7 +691,9 @@ int main(int argc, char **argv)
         device = std::stoi(files[1]); files.pop_back();
     }
     if (files.empty()) {
-        std::cerr << "usage: gd_interphase <trajectory> [device]\n       gd_interphase [--device d] <trajectory> <trajectory>...\n";
+        std::cerr << "usage: gd_interphase <trajectory> [device]\n       gd_interphase [--device d] <trajectory> <trajectory>...\n"
+                     "files that differ in their A/B factors alone run as the models of one batch; --ensemble-matrix RATE OUTPUT then writes one\n"
+                     "matrix per model and OUTPUT must contain {model}; --particle-flow / --grid-flow work per replica and need no change\n";
         return 1;
     }
     std::unique_ptr<flow_outputs> flow;
@@ -617,8 +720,24 @@ int main(int argc, char **argv)
         }
     }
     try {
-        std::unique_ptr<ensemble_matrix> ensemble;      // (reads the first file's chromosome table before the stores open the files)
-        if (!matrix_output.empty()) ensemble = std::make_unique<ensemble_matrix>(files[0], matrix_rate, matrix_output, device);
+        // the models of the batch, from the files' factors -- before a file is opened for writing, so that a refused command line leaves
+        // every file as it was
+        model_classes models;      // (one file: the reference's command line, one model)
+        if (files.size() > 1) models = classify_models(files);
+        else { models.of = {0}; models.n = 1; }
+        bool const per_model = models.n > 1 && gd_ensemble_set_ab && gd_ensemble_classes;      // (else: the set-up refuses the batch)
+        if (per_model && !matrix_output.empty() && matrix_output.find("{model}") == std::string::npos) {
+            std::cerr << "error: the files hold " << models.n << " models (their A/B factors differ): the output of --ensemble-matrix must contain {model}\n";
+            return 1;
+        }
+        if (per_model)
+            for (uint32_t k = 0; k < models.n; k++) {
+                std::clog << "[model " << k << "]";
+                for (auto const &f : models.files_of(files, k)) std::clog << " file " << f;
+                std::clog << '\n';
+            }
+        std::unique_ptr<ensemble_matrices> ensemble;      // (reads the chromosome tables before the stores open the files)
+        if (!matrix_output.empty()) ensemble = std::make_unique<ensemble_matrices>(files, models, matrix_rate, matrix_output, device);
         std::vector<std::unique_ptr<gd::trajectory_store>> stores;
         {
             TIMED("open_files");
@@ -626,7 +745,7 @@ int main(int argc, char **argv)
         }
         double bead_steps = 0;
         {
-            simulation_driver driver{stores, device, auto_skin, ensemble.get(), flow.get()};
+            simulation_driver driver{stores, device, auto_skin, ensemble.get(), flow.get(), &models};
             driver.run();
             bead_steps = driver.bead_steps();
             if (ensemble) { TIMED("ensemble_matrix"); ensemble->write(); }
