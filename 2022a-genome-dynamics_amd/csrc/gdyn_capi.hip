@@ -29,6 +29,9 @@
 #include "gdyn_live.hpp"
 #include "gdyn_replica_pairs.hpp"
 #include "gdyn_ensemble.hpp"
+#include "gdyn_glue.hpp"
+#include "gdyn_glue_types.h"
+#include "../../include/gdyn_glue.h"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
 #endif
@@ -129,6 +132,16 @@ struct gd_system {
     gd::ReplicaPairs rp; gd::ReplicaLayout rp_layout; gd_bond_params rp_params[gd::RP_SLOTS] = {};
     uint32_t *rp_stage = nullptr; size_t rp_stage_cap = 0; hipEvent_t rp_copied = nullptr;      // (rp_copied: the last upload has left the staging block)
     DevBuf<uint32_t> rp_dev; DevBuf<double> rp_esum;
+    // device glue kinetics (gdyn_glue.h): the sets as sorted pair words (the host copy is what fetch returns and what is installed in
+    // the managed slot; the device copy gl_keys[gl_cur], gl_kstride words a replica, feeds the next update and is laid out again from
+    // the host copy after gd_glue_set), the buffers of an update (grown, never shrunk), two pinned blocks (small: seeds, counters,
+    // segments; large: the sets on their way up or down)
+    bool gl_defined = false, gl_dev_dirty = true; uint32_t gl_slot = 0; gd_glue_params gl_par{};
+    std::vector<std::vector<uint64_t>> gl_sets;
+    DevBuf<unsigned long long> gl_keys[2], gl_merged, gl_fkey[2], gl_fsel[2], gl_seeds, gl_cand_count; DevBuf<uint2> gl_cand;
+    DevBuf<unsigned> gl_alive, gl_nkeys, gl_cnt, gl_seg; DevBuf<char> gl_tmp;
+    size_t gl_kstride[2] = {0, 0}, gl_fstride = 0; int gl_cur = 0;
+    unsigned long long *gl_small = nullptr, *gl_pin = nullptr; size_t gl_pin_cap = 0;
     float *h_stage = nullptr;      // pinned host staging for snapshot downloads (R*N*3 floats)
     char *h_chunk = nullptr;       // pinned host block for the per-chunk readback (flags, contexts, list counts): copies into pageable
                                    // memory are staged by the runtime and cost ~20 us each
@@ -270,6 +283,8 @@ extern "C" int gd_destroy(gd_system *s)
     if (s->h_stage) (void)hipHostFree(s->h_stage);
     if (s->h_chunk) (void)hipHostFree(s->h_chunk);
     if (s->rp_stage) (void)hipHostFree(s->rp_stage);
+    if (s->gl_small) (void)hipHostFree(s->gl_small);
+    if (s->gl_pin) (void)hipHostFree(s->gl_pin);
     delete s;
     return GD_OK;
 }
@@ -596,6 +611,7 @@ extern "C" int gd_replica_pairs_set(gd_system *s, uint32_t slot, uint32_t replic
     if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_set: slot %u out of range", slot);
     if (replica >= s->R) return fail(GD_EINVAL, "gd_replica_pairs_set: replica %u out of range", replica);
     if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_replica_pairs_set: slot %u was never defined (gd_replica_pairs_define)", slot);
+    if (s->gl_defined && slot == s->gl_slot) return fail(GD_ESTATE, "gd_replica_pairs_set: slot %u is managed by gd_glue_define (use gd_glue_set)", slot);
     if (const size_t bad = s->rp.set(slot, replica, pairs, n))
         return fail(GD_EINVAL, "gd_replica_pairs_set: bad pair %zu (%u,%u)", bad - 1, pairs[2 * (bad - 1)], pairs[2 * (bad - 1) + 1]);
     return GD_OK;
@@ -1506,6 +1522,222 @@ static unsigned contact_jbits(const gd_system *s)      // bits of a bead id
     return b;
 }
 
+// ------------------------------------------------------------- glue kinetics on the device (include/gdyn_glue.h)
+// The rule is in the header and in DESIGN.md section 7k, the kernels in gdyn_glue.hip.  The host keeps a copy of every set (at most
+// max_glues words a replica): it is what the managed slot is fed from, through the per-replica lists' own flattener.
+
+extern "C" int gd_glue_abi_version(void) { return GD_GLUE_ABI_VERSION; }
+
+// a replica's set into the managed slot, as gd_replica_pairs_set would install it
+static void glue_install(gd_system *s, uint32_t r)
+{
+    const std::vector<uint64_t> &keys = s->gl_sets[r];
+    std::vector<uint32_t> pairs(2 * keys.size());
+    for (size_t k = 0; k < keys.size(); k++) { pairs[2 * k] = gd::glue_i(keys[k]); pairs[2 * k + 1] = gd::glue_j(keys[k]); }
+    (void)s->rp.set(s->gl_slot, r, pairs.data(), (uint32_t)keys.size());      // (ids and i != j were checked when the set was made)
+}
+
+static int glue_pinned(gd_system *s, size_t words)
+{
+    if (words <= s->gl_pin_cap) return GD_OK;
+    const size_t cap = gd::grown_capacity(s->gl_pin_cap, words);
+    unsigned long long *h = nullptr;
+    HIPCHK(hipHostMalloc((void **)&h, cap * sizeof(unsigned long long), hipHostMallocDefault));
+    if (s->gl_pin) (void)hipHostFree(s->gl_pin);
+    s->gl_pin = h; s->gl_pin_cap = cap;
+    return GD_OK;
+}
+
+// the small pinned block: [R] seeds (64-bit), then 32-bit words: [R] set sizes, [4R] segments, [3R] counters
+static unsigned *glue_small_words(gd_system *s) { return (unsigned *)(s->gl_small + s->R); }
+
+extern "C" int gd_glue_define(gd_system *s, uint32_t slot, const gd_glue_params *p)
+{
+    if (!s || !p) return fail(GD_EINVAL, "gd_glue_define: NULL argument");
+    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_glue_define: slot %u out of range", slot);
+    if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_glue_define: slot %u was never defined (gd_replica_pairs_define)", slot);
+    if (s->gl_defined && slot != s->gl_slot) return fail(GD_ESTATE, "gd_glue_define: slot %u already holds the handle's glues (one glue slot per handle)", s->gl_slot);
+    if (const char *bad = gd::glue_check_params(p->reach, p->binding_rate, p->unbinding_rate)) return fail(GD_EINVAL, "gd_glue_define: %s", bad);
+    if (s->gl_defined)
+        for (uint32_t r = 0; r < s->R; r++)
+            if (s->gl_sets[r].size() > p->max_glues)
+                return fail(GD_EINVAL, "gd_glue_define: max_glues %u is below the %zu pairs replica %u holds", p->max_glues, s->gl_sets[r].size(), r);
+    if (!s->gl_defined) {
+        HIPCHK(hipSetDevice(s->device));
+        if (!s->gl_small) HIPCHK(hipHostMalloc((void **)&s->gl_small, (size_t)s->R * (sizeof(unsigned long long) + 8 * sizeof(unsigned)), hipHostMallocDefault));
+        HIPCHK(s->gl_seeds.resize(s->R, false)); HIPCHK(s->gl_nkeys.resize(s->R)); HIPCHK(s->gl_cnt.resize(3 * (size_t)s->R));
+        HIPCHK(s->gl_seg.resize(4 * (size_t)s->R));
+        s->gl_sets.assign(s->R, {});
+        s->gl_slot = slot; s->gl_defined = true; s->gl_dev_dirty = true;
+        for (uint32_t r = 0; r < s->R; r++) glue_install(s, r);      // (the slot holds the sets from here on: empty)
+    }
+    s->gl_par = *p;
+    return GD_OK;
+}
+
+extern "C" int gd_glue_set(gd_system *s, uint32_t replica, const uint32_t *pairs, uint32_t n)
+{
+    if (!s || (n && !pairs)) return fail(GD_EINVAL, "gd_glue_set: NULL argument");
+    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_set: no glue slot (gd_glue_define)");
+    if (replica >= s->R) return fail(GD_EINVAL, "gd_glue_set: replica %u out of range", replica);
+    if (const char *bad = gd::glue_normalise(pairs, n, s->N, s->gl_par.max_glues, s->gl_sets[replica])) return fail(GD_EINVAL, "gd_glue_set: %s", bad);
+    glue_install(s, replica);
+    s->gl_dev_dirty = true;
+    return GD_OK;
+}
+
+extern "C" int gd_glue_fetch(gd_system *s, uint32_t replica, uint32_t *pairs, uint32_t cap, uint32_t *n)
+{
+    if (!s || !n || (cap && !pairs)) return fail(GD_EINVAL, "gd_glue_fetch: NULL argument");
+    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_fetch: no glue slot (gd_glue_define)");
+    if (replica >= s->R) return fail(GD_EINVAL, "gd_glue_fetch: replica %u out of range", replica);
+    const std::vector<uint64_t> &keys = s->gl_sets[replica];
+    for (size_t k = 0; k < keys.size() && k < cap; k++) { pairs[2 * k] = gd::glue_i(keys[k]); pairs[2 * k + 1] = gd::glue_j(keys[k]); }
+    *n = (uint32_t)keys.size();
+    return GD_OK;
+}
+
+extern "C" int gd_glue_counts(gd_system *s, uint32_t *n)
+{
+    if (!s || !n) return fail(GD_EINVAL, "gd_glue_counts: NULL argument");
+    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_counts: no glue slot (gd_glue_define)");
+    for (uint32_t r = 0; r < s->R; r++) n[r] = (uint32_t)s->gl_sets[r].size();
+    return GD_OK;
+}
+
+// the host's sets onto the device (after gd_glue_define and gd_glue_set; an update leaves its result there itself)
+static int glue_upload(gd_system *s)
+{
+    if (!s->gl_dev_dirty) return GD_OK;
+    size_t most = 1;
+    for (auto &k : s->gl_sets) most = std::max(most, k.size());
+    const int c = s->gl_cur;
+    const size_t stride = gd::grown_capacity(s->gl_kstride[c], most);
+    if ((size_t)s->R * stride > 0xffffffffull) return fail(GD_ENOMEM, "gd_glue_update: %zu pairs a replica exceed the sort's 32-bit offsets", stride);
+    HIPCHK(s->gl_keys[c].resize((size_t)s->R * stride, false));
+    s->gl_kstride[c] = stride;
+    GDCHK(glue_pinned(s, (size_t)s->R * most));
+    unsigned *nk = glue_small_words(s);
+    for (uint32_t r = 0; r < s->R; r++) {
+        std::copy(s->gl_sets[r].begin(), s->gl_sets[r].end(), s->gl_pin + (size_t)r * most);
+        nk[r] = (unsigned)s->gl_sets[r].size();
+    }
+    HIPCHK(hipMemcpy2DAsync(s->gl_keys[c].p, stride * sizeof(unsigned long long), s->gl_pin, most * sizeof(unsigned long long),
+                            most * sizeof(unsigned long long), s->R, hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipMemcpyAsync(s->gl_nkeys.p, nk, s->R * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    s->gl_dev_dirty = false;
+    return GD_OK;
+}
+
+extern "C" int gd_glue_update(gd_system *s, double dt, uint64_t epoch, const uint64_t *seeds)
+{
+    if (!s || !seeds) return fail(GD_EINVAL, "gd_glue_update: NULL argument");
+    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_update: no glue slot (gd_glue_define)");
+    if (!(dt > 0) || !std::isfinite(dt)) return fail(GD_EINVAL, "gd_glue_update: dt must be positive and finite");
+    HIPCHK(hipSetDevice(s->device));
+    const uint32_t R = s->R;
+    const gd_glue_params &par = s->gl_par;
+    GDCHK(prepare(s));
+    GDCHK(glue_upload(s));
+    std::vector<unsigned long long> ccnt;
+    GDCHK(search_device(s, 0, R, par.reach, s->gl_cand, s->gl_cand_count, ccnt));
+    unsigned long long most_c = 0;
+    size_t most_k = 0;
+    for (uint32_t r = 0; r < R; r++) { most_c = std::max(most_c, ccnt[2 * r]); most_k = std::max(most_k, s->gl_sets[r].size()); }
+    const int c = s->gl_cur, o = c ^ 1;
+    if (s->gl_alive.n < s->gl_keys[c].n) HIPCHK(s->gl_alive.resize(s->gl_keys[c].n, false));
+
+    GlueP q;
+    memset(&q, 0, sizeof q);
+    q.pos = s->pos[s->pcur].p; q.slot_of = s->slot_of.p; q.N = s->N; q.Np = s->Np; q.R = R;
+    set_box(s, q);
+    q.dcut2 = (float)(par.reach * par.reach);      // (search_device's own bound)
+    q.thr_off = gd::glue_rate_threshold(par.unbinding_rate, dt); q.thr_on = gd::glue_rate_threshold(par.binding_rate, dt); q.epoch = epoch;
+    q.seeds = s->gl_seeds.p; q.keys = s->gl_keys[c].p; q.kstride = (unsigned)s->gl_kstride[c]; q.nkeys = s->gl_nkeys.p;
+    q.alive = s->gl_alive.p; q.cnt = s->gl_cnt.p; q.cand = s->gl_cand.p; q.cand_cap = s->gl_cand.n / R; q.cand_count = s->gl_cand_count.p;
+    q.seg = s->gl_seg.p;
+
+    unsigned *small = glue_small_words(s), *h_nk = small, *h_seg = small + R, *h_cnt = small + 5 * (size_t)R;
+    std::copy(seeds, seeds + R, s->gl_small);
+    HIPCHK(hipMemcpyAsync(s->gl_seeds.p, s->gl_small, R * sizeof(unsigned long long), hipMemcpyHostToDevice, s->stream));
+
+    // unbind and bind; the fired records' buffer is sized like the search's output: grown until every replica fits (the draws are
+    // counter-based: a second pass fires the same pairs)
+    {
+        const double p_on = -std::expm1(-par.binding_rate * dt);
+        const size_t want = (size_t)std::min<double>((double)most_c, (double)most_c * p_on * 1.25 + 1024.0);
+        if (want > s->gl_fstride) s->gl_fstride = gd::grown_capacity(s->gl_fstride, want);
+    }
+    for (int attempt = 0;; attempt++) {
+        if (attempt == 4) return fail(GD_ESTATE, "gd_glue_update: the fired pairs' buffer did not converge");
+        const size_t fs = std::max<size_t>(s->gl_fstride, 1);
+        if ((size_t)R * fs > 0xffffffffull) return fail(GD_ENOMEM, "gd_glue_update: %zu fired pairs a replica exceed the sort's 32-bit offsets", fs);
+        if (s->gl_fkey[0].n != (size_t)R * fs)
+            for (int k = 0; k < 2; k++) { HIPCHK(s->gl_fkey[k].resize((size_t)R * fs, false)); HIPCHK(s->gl_fsel[k].resize((size_t)R * fs, false)); }
+        s->gl_fstride = fs;
+        q.fkey = s->gl_fkey[0].p; q.fsel = s->gl_fsel[0].p; q.fstride = (unsigned)fs;
+        HIPCHK(hipMemsetAsync(s->gl_cnt.p, 0, 3 * (size_t)R * sizeof(unsigned), s->stream));
+        gd_launch_glue_unbind(q, (unsigned)most_k, s->stream);
+        gd_launch_glue_bind(q, most_c, s->stream);
+        HIPCHK(hipMemcpyAsync(h_cnt, s->gl_cnt.p, 2 * (size_t)R * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(hipGetLastError());
+        unsigned most_f = 0;
+        for (uint32_t r = 0; r < R; r++) most_f = std::max(most_f, h_cnt[R + r]);
+        if (most_f <= fs) break;
+        s->gl_fstride = (size_t)most_f + most_f / 8 + 64;
+    }
+
+    // who binds: everything that fired where it fits, else the smallest selection keys
+    size_t most_new = 0, most_rows = most_k;
+    bool select = false;
+    for (uint32_t r = 0; r < R; r++) {
+        const size_t alive = h_cnt[r], fired = h_cnt[R + r], free_r = par.max_glues > alive ? par.max_glues - alive : 0;
+        const size_t take = std::min(fired, free_r);
+        h_seg[r] = (unsigned)(r * s->gl_fstride); h_seg[R + r] = h_seg[r] + (fired > free_r ? (unsigned)fired : 0u);
+        select = select || fired > free_r;
+        h_nk[r] = (unsigned)(alive + take);
+        most_new = std::max<size_t>(most_new, h_nk[r]); most_rows = std::max(most_rows, take);
+    }
+    const size_t ms = gd::grown_capacity(s->gl_kstride[o], std::max<size_t>(most_new, 1));
+    if ((size_t)R * ms > 0xffffffffull) return fail(GD_ENOMEM, "gd_glue_update: %zu pairs a replica exceed the sort's 32-bit offsets", ms);
+    HIPCHK(s->gl_keys[o].resize((size_t)R * ms, false)); HIPCHK(s->gl_merged.resize((size_t)R * ms, false));
+    for (uint32_t r = 0; r < R; r++) { h_seg[2 * R + r] = (unsigned)(r * ms); h_seg[3 * R + r] = h_seg[2 * R + r] + h_nk[r]; }
+    q.merged = s->gl_merged.p; q.mstride = (unsigned)ms;
+    HIPCHK(hipMemcpyAsync(s->gl_seg.p, h_seg, 4 * (size_t)R * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
+    const unsigned key_bits = 32u + contact_jbits(s);
+    if (most_new) {
+        size_t tmp_sel = 0, tmp_keys = 0;
+        if (select) HIPCHK(gd_glue_sort_select(nullptr, &tmp_sel, s->gl_fkey[0].p, s->gl_fsel[0].p, s->gl_fkey[1].p, s->gl_fsel[1].p, s->gl_fkey[0].n, R,
+                                               s->gl_seg.p, s->gl_seg.p + R, key_bits, s->stream));
+        HIPCHK(gd_glue_sort_keys(nullptr, &tmp_keys, s->gl_merged.p, s->gl_keys[o].p, s->gl_merged.n, R, s->gl_seg.p + 2 * R, s->gl_seg.p + 3 * R, key_bits, s->stream));
+        size_t tmp_bytes = std::max<size_t>(std::max(tmp_sel, tmp_keys), 1);
+        if (tmp_bytes > s->gl_tmp.n) HIPCHK(s->gl_tmp.resize(tmp_bytes, false));
+        if (select) {
+            tmp_bytes = s->gl_tmp.n;
+            HIPCHK(gd_glue_sort_select(s->gl_tmp.p, &tmp_bytes, s->gl_fkey[0].p, s->gl_fsel[0].p, s->gl_fkey[1].p, s->gl_fsel[1].p, s->gl_fkey[0].n, R,
+                                       s->gl_seg.p, s->gl_seg.p + R, key_bits, s->stream));
+        }
+        gd_launch_glue_merge(q, (unsigned)most_rows, s->stream);
+        tmp_bytes = s->gl_tmp.n;
+        HIPCHK(gd_glue_sort_keys(s->gl_tmp.p, &tmp_bytes, s->gl_merged.p, s->gl_keys[o].p, s->gl_merged.n, R, s->gl_seg.p + 2 * R, s->gl_seg.p + 3 * R, key_bits, s->stream));
+        GDCHK(glue_pinned(s, (size_t)R * most_new));
+        HIPCHK(hipMemcpy2DAsync(s->gl_pin, most_new * sizeof(unsigned long long), s->gl_keys[o].p, ms * sizeof(unsigned long long),
+                                most_new * sizeof(unsigned long long), R, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIPCHK(hipMemcpyAsync(s->gl_nkeys.p, h_nk, R * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipGetLastError());
+    s->gl_kstride[o] = ms; s->gl_cur = o;
+    for (uint32_t r = 0; r < R; r++) {
+        s->gl_sets[r].assign(s->gl_pin + (size_t)r * most_new, s->gl_pin + (size_t)r * most_new + h_nk[r]);
+        glue_install(s, r);
+    }
+    return GD_OK;
+}
+
+// (the contact maps, continued)
 static ContactTab contact_tab(gd_system *s)
 {
     ContactTab t;

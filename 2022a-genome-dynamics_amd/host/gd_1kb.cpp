@@ -19,6 +19,10 @@
 // `-s s_r` would start, with its own generator, kinetics, output file (the output name holds the placeholder {seed}) and trace
 // (<dir>/seed-<s_r>/).  Its loops and glues are the per-replica pair lists of include/gdyn_replica.h, which only libgdyn has: the
 // symbols are referenced weakly, and two or more seeds are refused where they are absent.  One seed runs exactly as -s.
+// --device-glues (with --seeds, one seed or more): the glue kinetics of all trajectories in one device call per update
+// (gd_glue_update, include/gdyn_glue.h) instead of a position download, two pair searches and one generator
+// draw per candidate on the host for every trajectory.  The same stochastic process with counter-based draws keyed by the
+// trajectory's seed: deterministic, but not the reference's mt19937_64 sequence, which the default keeps draw for draw.
 // The program reads no environment variable.
 #include <algorithm>
 #include <cmath>
@@ -40,6 +44,11 @@
 // referenced weakly, and an ensemble is refused where the symbols are absent.
 #pragma weak gd_replica_pairs_define
 #pragma weak gd_replica_pairs_set
+#include "../../include/gdyn_glue.h"
+#pragma weak gd_glue_define
+#pragma weak gd_glue_update
+#pragma weak gd_glue_fetch
+#pragma weak gd_glue_counts
 #include "gd_1kb_config.hpp"
 #include "gd_1kb_kinetics.hpp"
 #include "gd_1kb_store.hpp"
@@ -321,8 +330,8 @@ private:
 class ensemble {
 public:
     ensemble(simulation_config const &config, std::vector<std::uint64_t> const &seeds, std::vector<std::string> const &outputs, int device,
-             std::string const &trace_dir, bool auto_skin)
-        : _config(config), _chains(make_chain_assignments(_config)), _auto_skin(auto_skin)
+             std::string const &trace_dir, bool auto_skin, bool device_glues = false)
+        : _config(config), _chains(make_chain_assignments(_config)), _auto_skin(auto_skin), _device_glues(device_glues)
     {
         for (auto const &c : _chains) _n += c.config->length;
         if (_n == 0) throw std::runtime_error("no monomers: the configuration defines no chains");
@@ -405,6 +414,13 @@ private:
         _glue_bond.p = 8; _glue_bond.q = 3; _glue_bond.minimum_image = 1;
         chk(gd_replica_pairs_define(_sys, 0, &_loop_bond));
         chk(gd_replica_pairs_define(_sys, 1, &_glue_bond));
+        if (_device_glues && _config.glue.max_glues != 0) {      // slot 1's lists come from the device kinetics
+            gd_glue_params glue{};
+            glue.max_glues = (uint32_t)_config.glue.max_glues; glue.reach = _config.glue.glue_distance;
+            glue.binding_rate = _config.glue.glue_binding_rate; glue.unbinding_rate = _config.glue.glue_unbinding_rate;
+            chk(gd_glue_define(_sys, 1, &glue));
+            _glue_counts.assign(_replicas.size(), 0);
+        }
     }
 
     double *xyz(std::size_t r) { return _xyz.data() + 3 * _n * r; }
@@ -494,6 +510,7 @@ private:
         if (!_replicas[0]->glues.enabled()) return;
         auto const &s = _config.sampling;
         double const leap = s.timestep * double(s.glue_update_interval);
+        if (_device_glues) { step_glues_on_device(step, leap); return; }
         chk(gd_get_positions(_sys, _xyz.data()));
         for (std::size_t r = 0; r < _replicas.size(); r++) {
             auto &t = *_replicas[r];
@@ -503,6 +520,24 @@ private:
             if (n) chk(gd_search_pairs(_sys, (uint32_t)r, t.glues.reach(), candidates.data(), n, &n));
             t.glues.update(leap, xyz(r), candidates, t.random);
             upload_glues(r, step);
+        }
+    }
+
+    // --device-glues: one update of every trajectory on the device, keyed by the trajectory's seed and the update's number; the new
+    // lists are in slot 1 when it returns.  Only the set sizes come back, and the sets themselves when a trace is written.
+    void step_glues_on_device(long step, double leap)
+    {
+        std::vector<uint64_t> seeds;
+        for (auto const &t : _replicas) seeds.push_back(t->seed);
+        chk(gd_glue_update(_sys, leap, uint64_t(step / _config.sampling.glue_update_interval), seeds.data()));
+        chk(gd_glue_counts(_sys, _glue_counts.data()));
+        for (std::size_t r = 0; r < _replicas.size(); r++) {
+            auto &t = *_replicas[r];
+            if (!t.trace.is_open()) continue;
+            std::vector<uint32_t> pairs(2 * std::size_t(_glue_counts[r]));
+            uint32_t n = 0;
+            chk(gd_glue_fetch(_sys, (uint32_t)r, pairs.data(), _glue_counts[r], &n));
+            trace(t, "glues", step, pairs);
         }
     }
 
@@ -516,7 +551,7 @@ private:
             auto const &t = *_replicas[r];
             double const er = e[r] + double(t.zero_length_loops) * 0.5 * _loop_bond.k_a * _loop_bond.l_a * _loop_bond.l_a;
             std::clog << "[seed " << t.seed << "] " << step << '\t' << "E: " << er / n << '\t' << "L: " << double(t.loops.loaded()) / n << '\t'
-                      << "G: " << double(t.glues.size()) / n << '\n';
+                      << "G: " << double(_glue_counts.empty() ? t.glues.size() : std::size_t(_glue_counts[r])) / n << '\n';
         }
     }
 
@@ -572,6 +607,8 @@ private:
     gd_bond_params _loop_bond{}, _glue_bond{};
     std::vector<double> _xyz;        // (K, N, 3)
     bool _auto_skin = false;
+    bool _device_glues = false;
+    std::vector<uint32_t> _glue_counts;      // --device-glues: the set sizes after the last update (gd_glue_counts)
 };
 
 // "s0,s1,...": distinct unsigned integers
@@ -602,6 +639,9 @@ void show_usage()
                  "  -s <seed>    override random seed (config 'random_seed' key)\n"
                  "  --seeds <s0,s1,...> run one trajectory per seed as the replicas of one device handle; the output name\n"
                  "               must contain {seed}; not with -s\n"
+                 "  --device-glues  with --seeds: glue binding and unbinding of all trajectories on the device, one call per\n"
+                 "               update, with counter-based draws keyed by each seed (deterministic; not the host's mt19937_64\n"
+                 "               sequence)\n"
                  "  -d <device>  GPU index (default 0)\n"
                  "  --auto-skin  select the neighbour-list width from measured step times (faster on some models; the\n"
                  "               trajectory of a seed then depends on timing -- off by default)\n"
@@ -629,6 +669,7 @@ int main(int argc, char **argv)
         std::string trace_dir;
         bool auto_skin = false;
         std::optional<std::vector<std::uint64_t>> seeds;
+        bool device_glues = false;
         for (int i = 1; i < argc; i++) {
             std::string const arg = argv[i];
             auto value = [&]() -> std::string { if (i + 1 >= argc) throw std::runtime_error{"bad option"}; return argv[++i]; };
@@ -639,12 +680,18 @@ int main(int argc, char **argv)
             else if (arg == "--seeds") seeds = parse_seeds(value());
             else if (arg == "-d") device = std::stoi(value());
             else if (arg == "--trace") trace_dir = value();
+            else if (arg == "--device-glues") device_glues = true;
             else if (arg == "--auto-skin") auto_skin = true;
             else if (arg == "--fixed-skin") auto_skin = false;
             else if (arg.size() > 1 && arg[0] == '-') throw std::runtime_error{"bad option"};
             else positional.push_back(arg);
         }
         if (positional.size() != 1) throw std::runtime_error{"config file is not specified"};
+        if (device_glues) {      // (refused here: before the configuration is read and before any output or trace file exists)
+            if (!seeds) throw std::runtime_error{"--device-glues needs --seeds (one seed or more)"};
+            if (!gd_glue_define || !gd_glue_update || !gd_glue_fetch || !gd_glue_counts || !gd_replica_pairs_define || !gd_replica_pairs_set)
+                throw std::runtime_error{"--device-glues needs the device glue kinetics (gd_glue_*, gdyn_glue.h), which this gdyn library does not have"};
+        }
         simulation_config config;
         {
             auto const text = load_text(positional[0]);
@@ -670,12 +717,12 @@ int main(int argc, char **argv)
             if (at == std::string::npos) throw std::runtime_error{"--seeds: the output name '" + name + "' must contain {seed}"};
             std::vector<std::string> outputs;
             for (auto s : *seeds) outputs.push_back(std::string{name}.replace(at, 6, std::to_string(s)));
-            if (seeds->size() == 1) { seed = seeds->front(); config.sampling.output_filename = outputs.front(); }      // exactly -s
+            if (seeds->size() == 1 && !device_glues) { seed = seeds->front(); config.sampling.output_filename = outputs.front(); }      // exactly -s
             else {
                 if (!gd_replica_pairs_define || !gd_replica_pairs_set)
                     throw std::runtime_error{"--seeds with several seeds needs per-replica dynamic pair lists (gd_replica_pairs_*, gdyn_replica.h), "
                                              "which this gdyn library does not have"};
-                ensemble{config, *seeds, outputs, device, trace_dir, auto_skin}.run();
+                ensemble{config, *seeds, outputs, device, trace_dir, auto_skin, device_glues}.run();
                 return 0;
             }
         }
