@@ -383,6 +383,27 @@ class System:
         t = Tuning(skin, rebuild_interval, adapt_interval, list_width, kernel_path, near_fraction, auto_skin)
         self.lib.check(self.lib.dll.gd_set_tuning(self._h, C.byref(t)))
 
+    def _groups_fn(self, name):
+        f = getattr(self.lib.dll, name, None)
+        if f is None:
+            raise GdynError(6, f"{name}: not in this library (include/gdyn_groups.h: csrc/libgdyn.so only)")
+        return f
+
+    def set_step_groups(self, mode=0):
+        """Replica groups of the step launches (include/gdyn_groups.h): 0 the library's rule, 1 one launch per step, 2 two groups
+        wherever the results allow it.  Results do not depend on the mode."""
+        f = self._groups_fn("gd_set_step_groups")
+        f.argtypes = [C.c_void_p, C.c_uint32]
+        self.lib.check(f(self._h, mode))
+
+    def step_groups(self):
+        """(mode set, groups the step launches of the last run ran in: 1 or 2)."""
+        f = self._groups_fn("gd_get_step_groups")
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        mode, last = C.c_uint32(0), C.c_uint32(0)
+        self.lib.check(f(self._h, C.byref(mode), C.byref(last)))
+        return mode.value, last.value
+
     def timing(self):
         t = Timing()
         self.lib.check(self.lib.dll.gd_get_timing(self._h, C.byref(t)))

@@ -20,6 +20,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_replica.h"
 #include "../../include/gdyn_ensemble.h"
+#include "../../include/gdyn_groups.h"
 #include <hip/hip_fp16.h>
 
 #include "gdyn_types.h"
@@ -193,9 +194,17 @@ struct gd_system {
     bool comp_last = false;        // the last gd_run stepped with the compensated update (diagnostics)
     double mob_max = 1.0;
     std::vector<hipEvent_t> events;
+    // Replica groups of the step launches (gdyn_groups.h, gd::step_group_split): the second stream and the two events that fork it off
+    // the handle's stream in front of a span of steps and join it behind -- created on first use; between two calls nothing is in flight
+    // on it that the handle's stream does not wait for.
+    hipStream_t stream2 = nullptr; hipEvent_t grp_fork = nullptr, grp_join = nullptr;
+    uint32_t group_mode = gd::STEP_GROUPS_RULE, groups_last = 1;      // gd_set_step_groups; groups of the step launches of the last gd_run
     ~gd_system()
     {
         for (auto e : events) (void)hipEventDestroy(e);
+        if (grp_fork) (void)hipEventDestroy(grp_fork);
+        if (grp_join) (void)hipEventDestroy(grp_join);
+        if (stream2) (void)hipStreamDestroy(stream2);
         if (rp_copied) (void)hipEventDestroy(rp_copied);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -737,6 +746,22 @@ extern "C" int gd_set_tuning(gd_system *s, const gd_tuning *t)
     return GD_OK;
 }
 extern "C" int gd_get_timing(gd_system *s, gd_timing *o) { if (!s || !o) return fail(GD_EINVAL, "gd_get_timing: NULL"); *o = s->timing; return GD_OK; }
+// ---- replica groups of the step launches (include/gdyn_groups.h)
+extern "C" int gd_groups_abi_version(void) { return GD_GROUPS_ABI_VERSION; }
+extern "C" int gd_set_step_groups(gd_system *s, uint32_t mode)
+{
+    if (!s) return fail(GD_EINVAL, "gd_set_step_groups: NULL system");
+    if (mode > gd::STEP_GROUPS_TWO) return fail(GD_EINVAL, "gd_set_step_groups: mode must be 0 (rule), 1 (one launch) or 2 (two groups wherever results allow)");
+    s->group_mode = mode;
+    return GD_OK;
+}
+extern "C" int gd_get_step_groups(gd_system *s, uint32_t *mode, uint32_t *last_groups)
+{
+    if (!s) return fail(GD_EINVAL, "gd_get_step_groups: NULL system");
+    if (mode) *mode = s->group_mode;
+    if (last_groups) *last_groups = s->groups_last;
+    return GD_OK;
+}
 extern "C" int gd_get_stream(gd_system *s, void **st) { if (!s || !st) return fail(GD_EINVAL, "gd_get_stream: NULL"); *st = (void *)s->stream; return GD_OK; }
 
 // --------------------------------------------------------------- topology
@@ -897,6 +922,7 @@ static void fill_common(gd_system *s, StepParams &p)
 {
     memset(&p, 0, sizeof p);
     p.N = s->N; p.Np = s->Np; p.R = s->R; p.nblk = s->nblk; p.stride = (size_t)s->R * s->Np;
+    p.r0 = 0; p.nrep = s->R;      // (all replicas in one launch; gd_run's step groups narrow it, enqueue_chunk)
     set_box(s, p);
     p.pos_in = s->pos[s->pcur].p; p.pos_out = s->pos[s->pcur ^ 1].p; p.xb = s->xb.p; p.orig = s->orig[s->ocur].p;
     p.ab = s->ab.p; p.mob = s->mobs.p; p.bendE = s->bendE.p; p.mob_uniform = s->mob_uniform; p.WB = s->WB;
@@ -1173,6 +1199,39 @@ extern "C" int gd_apply_callback(gd_system *s)
     return apply_pending(s);
 }
 
+// Replica groups (gd::step_group_split, gdyn_policy.hpp): group B's launches of a span go to a second stream that is forked off the
+// handle's stream by an event in front of the span and joined to it by one behind, ahead of the span's end event -- so the span's
+// time covers both groups, and everything behind the span (builds, finalize, readback, the caller's own work on gd_get_stream) sees one
+// stream as before.  Between fork and join only kernels are launched: no call in there can return early and leave the streams apart.
+static int fork_groups(gd_system *s)
+{
+    if (!s->stream2) HIPCHK(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
+    if (!s->grp_fork) HIPCHK(hipEventCreateWithFlags(&s->grp_fork, hipEventDisableTiming));
+    if (!s->grp_join) HIPCHK(hipEventCreateWithFlags(&s->grp_join, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(s->grp_fork, s->stream));
+    HIPCHK(hipStreamWaitEvent(s->stream2, s->grp_fork, 0));
+    return GD_OK;
+}
+static int join_groups(gd_system *s)
+{
+    hipError_t e = hipEventRecord(s->grp_join, s->stream2);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->grp_join, 0);
+    if (e != hipSuccess) {      // (no event to wait on: the host waits for group B, so that the streams are joined on this way out too)
+        (void)hipStreamSynchronize(s->stream2);
+        return fail(GD_EHIP, "gd_run: joining the step groups failed: %s", hipGetErrorString(e));
+    }
+    return GD_OK;
+}
+
+static gd::StepGroupState group_state(const gd_system *s, bool host_noise)
+{
+    gd::StepGroupState st;
+    st.R = s->R; st.nblk = s->nblk; st.tiled = s->list.valid && s->list.tiled; st.post_step = post_step_active(s);
+    st.device_noise = !host_noise; st.whole_replica_map = s->cpb == 0;
+    st.fast_pair = s->has_pair && s->pair.p_a == 2 && s->pair.q_a == 3 && s->pair.p_b == 8 && s->pair.q_b == 3;      // (fill_common's pk != 0)
+    return st;
+}
+
 static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, bool comp, bool host_noise, Chunk &c)
 {
     const size_t RN = (size_t)s->R * s->N;
@@ -1215,6 +1274,12 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
         }
         const int64_t n = std::min<int64_t>((int64_t)s->pol.K - s->list.steps_since_build, chunk - k);
         hipEvent_t e1 = get_event(s, nev++);
+        // replicas of group A of this span's launches (0: one launch per step), decided on the list in use
+        uint32_t min_blocks = gd::STEP_GROUPS_MIN_BLOCKS, a16 = gd::STEP_GROUPS_A16;
+        if (const char *e = dev_env("GDYN_GROUP_MIN_BLOCKS")) min_blocks = (uint32_t)atoi(e);      // (timing experiments)
+        if (const char *e = dev_env("GDYN_GROUP_A16")) a16 = (uint32_t)atoi(e);
+        const uint32_t ra = gd::step_group_split(s->group_mode, group_state(s, host_noise), min_blocks, a16);
+        if (ra) { GDCHK(fork_groups(s)); s->groups_last = 2; }
         for (int64_t q = 0; q < n; q++) {
             fill_common(s, p);
             p.dt_d = run->timestep; p.dt = (float)run->timestep; p.kT = (float)run->temperature; p.seed = run->seed;
@@ -1226,11 +1291,15 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
             // evaluation of a COMPLETE interval only (a chunk that ends mid-interval records nothing and adapts nothing)
             p.record_disp = (s->list.steps_since_build + (uint32_t)q + 1u == s->pol.K);
             c.full_interval |= p.record_disp != 0;
-            gd_launch_step(p, GD_MODE_STEP, s->stream);
+            if (ra) {      // (same parameters, same buffers: the groups differ in the replicas they cover)
+                p.r0 = 0; p.nrep = ra; gd_launch_step(p, GD_MODE_STEP, s->stream);
+                p.r0 = ra; p.nrep = s->R - ra; gd_launch_step(p, GD_MODE_STEP, s->stream2);
+            } else gd_launch_step(p, GD_MODE_STEP, s->stream);
             if (s->sw_n) launch_softwell(s, p, 0);
             if (s->rp.any()) launch_replica_pairs(s, p, 0);      // (a step evaluates every term: GD_TERM_DYNAMIC is in its mask)
             s->pcur ^= 1; s->ccur ^= 1;
         }
+        if (ra) GDCHK(join_groups(s));
         HIPCHK(hipEventRecord(e1, s->stream));
         c.spans.push_back({nev - 1, 0});
         s->timing.step_launches += (uint64_t)n;
@@ -1332,6 +1401,7 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
     const bool with_list = pair_cutoff(s) > 0;
     const size_t RN = (size_t)s->R * s->N;
     memset(&s->timing, 0, sizeof s->timing);
+    s->groups_last = 1;
 
     // injected noise lives on the device as float (R,N,3) per step
     const bool host_noise = run->noise_mode == GD_NOISE_HOST && run->temperature > 0;

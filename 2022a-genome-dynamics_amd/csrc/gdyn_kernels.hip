@@ -572,6 +572,10 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
 
     unsigned r, blk;
     if (!block_map(blockIdx.x, p.nblk, p.cpb, r, blk)) return;
+    // a launch of one replica group (launch_step_mode, gd::step_group_split): the global replica from here on -- one scalar add, nothing of
+    // r0 stays live.  Only the variants the groups run on carry it: tiled stepping with the specialised pair form (the runtime-power
+    // variants sit on their SGPR budget: the add costs them two more spills, so they stay on the single path)
+    if (MODE == GD_MODE_STEP && TILED && PK != 0) r += p.r0;
     if (TILED && SPLIT) {      // a step split by tile size (launch_step_mode): this launch takes the blocks of one LDS class
                                // (an instantiation of its own: the unsplit kernel carries no trace of it)
         const unsigned held = p.tiles[(size_t)r * p.nblk + blk].total;
@@ -1132,7 +1136,7 @@ static StepKernel step_kernel(bool periodic, bool tiled, int pk, bool s16)
 template <int MODE>
 static void launch_step_mode(const StepParams &p, hipStream_t st)
 {
-    const dim3 grid(p.cpb ? GD_XCDS * p.cpb * p.R : p.R * p.nblk), block(GD_BLOCK);
+    const dim3 grid(p.cpb ? GD_XCDS * p.cpb * p.nrep : p.nrep * p.nblk), block(GD_BLOCK);      // (nrep: the replicas of this launch, r0 .. r0 + nrep - 1)
     const size_t lds = p.tiled ? (size_t)p.tile_cap * sizeof(float4) : 0;
     // (more than 64 KB of dynamic LDS: opted in per device at gd_create, gd_kernels_init_device below)
     const bool s16 = p.tiled && gd_tile_s16(p.tile_cap);

@@ -72,6 +72,41 @@ inline PoolPlan plan_pool(size_t pool_used, size_t pool_kib, size_t waves, uint3
     return pl;
 }
 
+// ---- Replica groups of the step launches between two builds (gd_run, enqueue_chunk).  Replicas are independent:
+// the k_step launches of an interval may run as two launches per step, replicas [0, A) on the handle's stream and [A, R) on a second
+// one, so that the blocks of one group fill the CUs the other leaves idle while its rounds drain.  Results do not depend on it: every
+// word a stepping launch reads or writes is addressed by the global replica or by a bead of it.  The rule is a function of the state
+// alone, never of a clock.
+enum : uint32_t { STEP_GROUPS_RULE = 0, STEP_GROUPS_ONE = 1, STEP_GROUPS_TWO = 2 };      // gd_set_step_groups (include/gdyn_groups.h)
+struct StepGroupState {
+    uint32_t R = 0, nblk = 0;           // replicas of the handle, blocks per replica
+    bool tiled = false;                 // the list in use is tiled
+    bool post_step = false;             // a kernel runs behind k_step (droplet term, per-replica pairs): it covers all replicas of a step
+    bool device_noise = true;           // the noise is drawn on the device (injected noise is staged per step for all replicas)
+    bool whole_replica_map = false;     // the handle maps whole replicas to XCDs (StepParams.cpb == 0)
+    bool fast_pair = false;             // the pair form has a specialised kernel (StepParams.pk != 0): only those variants take a group offset
+};
+// blocks the smaller group must have for mode 0 to split, and group A's share of the replicas in sixteenths.  384 = half a round of the
+// device (256 CUs x 3 resident blocks): a launch that splits is more than one round, a one-round grid stays on one launch.  Measured
+// (DESIGN.md section 7l, 16 replicas in 8 + 8): groups of 472 blocks (30 000 beads) gain 9 %, groups of 240 gain 5 % -- a one-round
+// grid, kept on one launch all the same --, groups of 120 and of 48 lose 10 %; the equal split against 7 : 9 and 9 : 7 sixteenths there
+constexpr uint32_t STEP_GROUPS_MIN_BLOCKS = 384u;
+constexpr uint32_t STEP_GROUPS_A16 = 8u;
+// Replicas of group A (group B: the rest), or 0: one launch.  Both sizes are multiples of 8, so that each group keeps the block map
+// it would have alone (block_map with cpb == 0: XCD x runs replicas x, x + 8, ... of the group).
+inline uint32_t step_group_split(uint32_t mode, const StepGroupState &st, uint32_t min_blocks = STEP_GROUPS_MIN_BLOCKS, uint32_t a16 = STEP_GROUPS_A16)
+{
+    if (mode != STEP_GROUPS_RULE && mode != STEP_GROUPS_TWO) return 0;
+    if (!st.tiled || st.post_step || !st.device_noise || !st.whole_replica_map || !st.fast_pair) return 0;
+    if (st.R < 2 * GD_XCDS || st.R % GD_XCDS != 0 || st.nblk == 0) return 0;
+    a16 = std::min(std::max(a16, 1u), 15u);
+    uint32_t ra = (uint32_t)(((uint64_t)st.R * a16 + 8u * GD_XCDS) / (16u * GD_XCDS)) * GD_XCDS;      // the multiple of 8 nearest to R a16 / 16
+    ra = std::min(std::max(ra, (uint32_t)GD_XCDS), st.R - GD_XCDS);
+    const uint32_t small = std::min(ra, st.R - ra);
+    if (mode == STEP_GROUPS_RULE && (uint64_t)small * st.nblk < min_blocks) return 0;
+    return ra;
+}
+
 struct ListPolicy {
     // developer hooks (gd_create)
     std::vector<unsigned> tile_caps = {3312u, 4080u, 5072u, 8192u};      // (4080: the largest tile with byte-offset list entries)

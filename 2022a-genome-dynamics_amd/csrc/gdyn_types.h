@@ -152,6 +152,10 @@ struct StepParams {
     size_t stride;                      // R*Np, ELL column stride
     int periodic;
     float box[3], inv_box[3];
+    // replica group of a stepping launch (gd_run's two groups, gdyn_policy.hpp step_group_split): the launch covers replicas r0 ..
+    // r0 + nrep - 1 and its grid is sized from nrep (further down); every index the kernel forms is the global replica's.  Every other
+    // launch: r0 = 0, nrep = R.  (Both fields sit in what was alignment padding: the layout of everything else is as it was.)
+    unsigned r0;
     // per-slot state
     const float4 *pos_in;
     float4 *pos_out;
@@ -211,6 +215,7 @@ struct StepParams {
     float rn;                           // near-class radius of the tiled list in use
     unsigned *dmax;                     // [R] largest squared displacement since the build, float bits (monotone between builds)
     int record_disp;
+    unsigned nrep;                      // replicas of this launch (see r0)
     // compensated position update (small-dt / T = 0 runs: mu F dt below the ulp of an fp32 coordinate): the true position of a bead is
     // pos + lo with lo the fp32 residual the rounded sums left behind, [R][N] by BEAD index (it does not take part in the cell sort)
     float4 *lo;
