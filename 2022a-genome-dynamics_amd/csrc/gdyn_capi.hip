@@ -1032,6 +1032,9 @@ static int enqueue_build(gd_system *s, float rv, bool with_list, bool allow_tile
             fprintf(stderr, "[gdyn] build %llu: %s, rows used %u KiB, pool %zu KiB, rv %.4f\n", (unsigned long long)s->rebuilds, predict ? "predicted" : "no history", s->list.pool_used, pool_kib(), rv);
         built.pool_guess = (uint32_t)std::min<size_t>(plan.used, 0xffffffffu);
         b.predict = predict ? 1 : 0; b.nbr16 = s->nbr16.p; b.pool_cap = (unsigned)std::min<size_t>(pool_kib(), 0xffffffffu);
+        // k_fill orders k_step's threads by len_prev, and the order decides the last digits of a block's wall-reaction partial: a key
+        // left by a refused build, or by another state of the handle, is cleared (threads in slot order, as in a handle's first build)
+        if (!s->list.orders_by_history()) HIPCHK(hipMemsetAsync(s->len_prev.p, 0, s->len_prev.n, s->stream));
     }
     s->list.build_enqueued(built);
     gd_launch_build(b, s->stream);
@@ -1106,6 +1109,7 @@ static int build_now(gd_system *s, float rv, bool with_list, bool allow_tiled = 
         GDCHK(enqueue_build(s, rv_try, with_list, allow_tiled));
         GDCHK(read_chunk(s, c));
         if (!s->pol.on_report(list_state(s), c.rep)) return clear_flags(s);
+        s->list.build_refused();
     }
     return fail(GD_ENOMEM, "neighbour list width did not converge (W=%u)", s->pol.W);
 }

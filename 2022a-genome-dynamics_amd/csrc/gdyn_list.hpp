@@ -30,19 +30,25 @@ struct ResidentList {
     bool bbox_valid = false;            // open boxes: that half holds the bounding box of the positions the last build sorted
     bool need_valid = false;            // the row history describes the state about to be listed well enough to predict row widths from it
     float need_rv = 0; bool need_all_near = false;      // list radius / class mode the history was counted at
+    bool order_valid = false;           // the thread-order key (len_prev) was left by a tiled build of this trajectory that no rollback or
+                                        // retry has refused since: the next tiled build may order k_step's threads by it (else by slot)
     uint32_t pool_used = 0;             // KiB of the row pool the last build took (its cursor's final value: the need, when the pool was full)
     uint32_t repairs = 0;               // k_step waves the last build read back had to repair (diagnostics)
 
     // ---- transitions: one per event
     // the model, the cutoff, a scale or the tuning changed; a timing sweep moved the skin; a pair search met a bead beyond the margin
     void drop() { valid = false; }
-    // positions from the caller: pos.w is plain, the box and what the beads needed before say nothing about them
-    void positions_set() { valid = false; w_packed = false; bbox_valid = false; need_valid = false; }
+    // positions from the caller: pos.w is plain, the box, what the beads needed before and the order key say nothing about them
+    void positions_set() { valid = false; w_packed = false; bbox_valid = false; need_valid = false; order_valid = false; }
     // new topology: pos.w is repacked by the next build; the beads are where they were (box and history stay)
     void topology_changed() { valid = false; w_packed = false; }
     // a chunk was rolled back to its snapshot: pos.w is what it was before the chunk; the box the abandoned builds recorded may be that
-    // of positions stepped on incomplete lists; the history and the pool's use stay (an overflow has counted the need into it)
-    void rolled_back(bool w_packed_before) { valid = false; bbox_valid = false; w_packed = w_packed_before; }
+    // of positions stepped on incomplete lists; the history and the pool's use stay (an overflow has counted the need into it).  The
+    // order key does not: a build whose repairs were refused stored list lengths clamped to the rows of whichever waves the repair
+    // queue or the pool happened to turn away, and the builds behind it listed positions stepped on those lists
+    void rolled_back(bool w_packed_before) { valid = false; bbox_valid = false; w_packed = w_packed_before; order_valid = false; }
+    // a build outside gd_run was refused and is run again on the same positions (build_now): its order key is as above
+    void build_refused() { order_valid = false; }
 
     struct Build {
         float rv = 0, rn = 0;
@@ -58,6 +64,7 @@ struct ResidentList {
         if (b.tiled) {
             if (!b.predicted) pool_used = b.pool_guess;      // (the guess stands in until a chunk's readback brings the real use)
             need_valid = true; need_rv = b.rv; need_all_near = b.all_near;
+            order_valid = true;      // (this build writes the key of the next one; rolled_back / build_refused take it back)
         }
         bbox_cur ^= 1; bbox_valid = b.tiled;      // (the box of the positions this build sorted, reduced by k_tiles: the next build's grid)
         tiled = b.tiled; tile_cap = b.tile_cap;
@@ -87,6 +94,9 @@ struct ResidentList {
     {
         return need_valid && need_all_near == all_near && need_rv > 0 && std::fabs(rv_new / need_rv - 1.f) <= 0.02f;
     }
+    // a tiled build orders k_step's threads by the key in memory (false: the key is cleared first -- threads in slot order, as in a
+    // handle's first build: what a handle computes from given positions and context does not depend on what it ran before)
+    bool orders_by_history() const { return order_valid; }
     // an observation (energy, forces) needs no build: nothing has stepped on the list, or the last run verified it
     bool fresh(uint64_t state_serial) const { return valid && (steps_since_build == 0 || verified_serial == state_serial); }
     // a pair search at dcut is served from the list (W == 0: the handle has built without a list so far)

@@ -22,7 +22,8 @@ static bool same(const ResidentList &a, const ResidentList &b)
     return a.valid == b.valid && a.tiled == b.tiled && a.W == b.W && a.tile_cap == b.tile_cap && a.rv == b.rv && a.rn == b.rn &&
            a.steps_since_build == b.steps_since_build && a.search_list == b.search_list && a.verified_serial == b.verified_serial &&
            a.w_packed == b.w_packed && a.bbox_cur == b.bbox_cur && a.bbox_valid == b.bbox_valid && a.need_valid == b.need_valid &&
-           a.need_rv == b.need_rv && a.need_all_near == b.need_all_near && a.pool_used == b.pool_used && a.repairs == b.repairs;
+           a.need_rv == b.need_rv && a.need_all_near == b.need_all_near && a.order_valid == b.order_valid && a.pool_used == b.pool_used &&
+           a.repairs == b.repairs;
 }
 
 static ResidentList::Build tiled_build(float rv = 0.525f, bool predicted = false)
@@ -56,6 +57,7 @@ static void test_initial_state()
     const ResidentList l;
     CHECK(!l.valid && !l.tiled && l.W == 0 && l.tile_cap == 0 && l.rv == 0 && l.rn == 0 && l.steps_since_build == 0 && !l.search_list);
     CHECK(l.verified_serial == 0 && !l.w_packed && l.bbox_cur == 0 && !l.bbox_valid && !l.need_valid && l.pool_used == 0 && l.repairs == 0);
+    CHECK(!l.order_valid && !l.orders_by_history());      // (a handle's first build orders k_step's threads by slot)
     CHECK(!l.fresh(0) && !l.fresh(1) && !l.serves_search(0.1) && !l.predicts(0.5f, false));
 }
 
@@ -63,23 +65,25 @@ static void test_initial_state()
 static void test_drop()
 {
     const ResidentList l0 = list_in_use();
-    CHECK(l0.valid && l0.search_list && l0.w_packed && l0.bbox_valid && l0.need_valid && l0.verified_serial == 7);
+    CHECK(l0.valid && l0.search_list && l0.w_packed && l0.bbox_valid && l0.need_valid && l0.order_valid && l0.verified_serial == 7);
     ResidentList l = l0, want = l0;
     l.drop();
     want.valid = false;
     CHECK(same(l, want));
+    CHECK(l.orders_by_history());      // (the same beads where they were: the order key still describes them)
     l.drop();      // (idempotent)
     CHECK(same(l, want));
 }
 
-// positions from the caller: not valid; w_packed, box and row history cleared
+// positions from the caller: not valid; w_packed, box, row history and order key cleared
 static void test_positions_set()
 {
     const ResidentList l0 = list_in_use();
     ResidentList l = l0, want = l0;
     l.positions_set();
-    want.valid = false; want.w_packed = false; want.bbox_valid = false; want.need_valid = false;
+    want.valid = false; want.w_packed = false; want.bbox_valid = false; want.need_valid = false; want.order_valid = false;
     CHECK(same(l, want));
+    CHECK(!l.orders_by_history());         // (... and orders its threads by slot: nothing of the handle's earlier state decides a result)
     CHECK(l.need_rv == l0.need_rv && l.pool_used == 640 && l.bbox_cur == l0.bbox_cur);
     CHECK(!l.predicts(l0.rv, false));      // (the next tiled build has no history)
 }
@@ -92,19 +96,25 @@ static void test_topology_changed()
     l.topology_changed();
     want.valid = false; want.w_packed = false;
     CHECK(same(l, want));
-    CHECK(l.bbox_valid && l.need_valid && l.predicts(l0.rv, false));
+    CHECK(l.bbox_valid && l.need_valid && l.predicts(l0.rv, false) && l.orders_by_history());
 }
 
-// rollback: not valid; box cleared; w_packed restored to the value before the chunk; history and pool_used kept
+// rollback: not valid; box and order key cleared; w_packed restored to the value before the chunk; history and pool_used kept
 static void test_rolled_back()
 {
     for (int before = 0; before < 2; before++) {
         const ResidentList l0 = list_in_use();
         ResidentList l = l0, want = l0;
         l.rolled_back(before != 0);
-        want.valid = false; want.bbox_valid = false; want.w_packed = before != 0;
+        want.valid = false; want.bbox_valid = false; want.w_packed = before != 0; want.order_valid = false;
         CHECK(same(l, want));
         CHECK(l.need_valid && l.pool_used == 640 && l.repairs == 2 && l.steps_since_build == 3);
+        CHECK(l.predicts(l0.rv, false) && !l.orders_by_history());      // (rows from the history, threads by slot)
+        // the retry's build writes a key again; a second rollback takes it back again
+        l.build_enqueued(tiled_build(0.525f, true));
+        CHECK(l.orders_by_history());
+        l.rolled_back(before != 0);
+        CHECK(!l.orders_by_history());
     }
     {   // the value before the chunk, whatever the chunk's builds made of it: plain positions stay plain
         ResidentList l;
@@ -114,6 +124,24 @@ static void test_rolled_back()
         l.rolled_back(snap);
         CHECK(!l.w_packed);
     }
+}
+
+// a build outside gd_run refused, to be run again on the same positions: the order key it wrote is not used; nothing else
+static void test_build_refused()
+{
+    ResidentList l;
+    l.build_enqueued(tiled_build());
+    CHECK(l.orders_by_history());
+    ResidentList want = l;
+    l.build_refused();
+    want.order_valid = false;
+    CHECK(same(l, want));
+    CHECK(l.need_valid && l.predicts(0.525f, false) && l.pool_used == 720);      // (the retry's rows are predicted from what the refused build counted)
+    l.build_refused();      // (idempotent)
+    CHECK(same(l, want));
+    l.build_enqueued(tiled_build(0.525f, true));      // the retry: accepted, in use, and the build after it is ordered by its key
+    l.enter_use(false);
+    CHECK(l.orders_by_history());
 }
 
 // a build enqueued
@@ -128,6 +156,7 @@ static void test_build_enqueued()
         CHECK(l.rv == b.rv && l.rn == b.rn && l.tiled && l.tile_cap == 3312 && l.W == 96 && l.w_packed);
         CHECK(l.bbox_cur == 1 && l.bbox_valid && l.steps_since_build == 0);
         CHECK(l.need_valid && l.need_rv == b.rv && !l.need_all_near && l.pool_used == 720);
+        CHECK(l.order_valid);      // (it writes the key the next build orders by)
         CHECK(!l.search_list && l.verified_serial == 0 && l.repairs == 0);
     }
     {   // a predicted tiled build keeps the pool use that was read back; the history moves to its radius and class mode
@@ -145,6 +174,14 @@ static void test_build_enqueued()
         l.build_enqueued(generic_build(0.6f));
         CHECK(!l.tiled && l.W == 104 && l.rv == 0.6f && l.rn == 0.6f && !l.w_packed && l.bbox_cur == 0 && !l.bbox_valid);
         CHECK(l.need_valid && l.need_rv == 0.525f && l.pool_used == 640 && l.steps_since_build == 0);
+        CHECK(l.order_valid);      // (a generic build writes no key: the one of the last tiled build stands, as it was ...)
+        ResidentList n;
+        n.build_enqueued(generic_build());
+        CHECK(!n.order_valid);     // (... also when there is none)
+        ResidentList r = list_in_use();
+        r.rolled_back(true);
+        r.build_enqueued(generic_build());
+        CHECK(!r.order_valid);     // (a key taken back stays taken back across a generic build)
     }
     {   // without a list (no pair term): the counting sort alone -- the row width of the list before stays, everything else as above
         ResidentList l = list_in_use();
@@ -152,7 +189,7 @@ static void test_build_enqueued()
         b.rv = 1.f; b.rn = 1.f; b.with_list = false; b.tiled = false; b.W = 0; b.tile_cap = 3312; b.packed_ab = true;
         l.build_enqueued(b);
         CHECK(l.W == 96 && !l.tiled && l.rv == 1.f && l.rn == 1.f && l.w_packed && !l.bbox_valid && l.bbox_cur == 0 && l.steps_since_build == 0);
-        CHECK(l.need_valid && l.pool_used == 640);
+        CHECK(l.need_valid && l.pool_used == 640 && l.order_valid);
         ResidentList l1;
         l1.build_enqueued(b);
         CHECK(l1.W == 0 && !l1.serves_search(0.5));      // (W == 0: a search builds a list first, whatever the radius)
@@ -386,6 +423,7 @@ int main()
     test_positions_set();
     test_topology_changed();
     test_rolled_back();
+    test_build_refused();
     test_build_enqueued();
     test_enter_use();
     test_stepped();

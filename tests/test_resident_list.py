@@ -56,7 +56,7 @@ def test_capi_assigns_no_member_of_the_resident_list():
     members it replaced, and no statement assigns, increments or takes a reference to a member of it."""
     members = _members()
     assert set(members) >= {"valid", "tiled", "W", "tile_cap", "rv", "rn", "steps_since_build", "search_list", "verified_serial", "w_packed",
-                            "bbox_cur", "bbox_valid", "need_valid", "need_rv", "need_all_near", "pool_used", "repairs"}, members
+                            "bbox_cur", "bbox_valid", "need_valid", "need_rv", "need_all_near", "order_valid", "pool_used", "repairs"}, members
     src = open(os.path.join(CSRC, "gdyn_capi.hip")).read()
     code = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
     assert len(re.findall(r"\bgd::ResidentList\s+\w+\s*;", code)) == 1

@@ -13,10 +13,10 @@ replica's context, rollbacks and launch counts --
     one group reported, results those of mode 1;
     and for energy(), forces() and positions() right after a grouped run.
 
-The states are ones at which two ONE-launch handles agree bit for bit among themselves.  That is not so everywhere: at 33 280 x 16 beads
-(and at 62 178 x 16 with skin 1.1) two handles built and run alike end with semiaxes that differ by a few dozen ulp in one or a few
-replicas about every other time, positions and final reaction bit-equal, with one launch per step and with the library before the groups
-as well.  1 500 x 16 and 62 178 x 16 at the library's own width agreed in eight handles each, four per mode.
+Two ONE-launch handles built and run alike agree bit for bit among themselves, which is what makes the comparison of the modes
+meaningful: tests/test_state_alone_gpu.py holds equal handles to that through builds whose repairs are refused and through rolled-back
+chunks, the states at which they once did not (33 280 x 16 beads, 62 178 x 16 at skin 1.1: the thread order of a retry's first build
+followed what the rejected builds had left; DESIGN.md section 7l, "Equal handles").
 """
 import importlib
 
@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import stressed_states as ss
+from bit_identity import assert_identical as _assert_identical
 from util import CASES, g
 
 pytestmark = pytest.mark.gpu
@@ -52,23 +53,6 @@ def _handle(hip, mode, n=N, nrep=R, tune=TUNE, prepare=None):
 
 def _run(s, steps):
     return s.run(steps, DT, KT, flags=FLAGS, replica_seeds=_seeds(s.R))
-
-
-def _ctx(s):
-    out = []
-    for r in range(s.R):
-        c = s.context(r)
-        out.append((c.step, c.time, c.bead_scale, c.bond_scale, tuple(c.semiaxes), tuple(c.axial_reaction), c.rollbacks, c.rebuilds,
-                    c.rebuild_interval, c.list_path, c.callback_pending))
-    return out
-
-
-def _assert_identical(a, b, ta=None, tb=None):
-    """Handles a and b (and the timing of their last runs) hold the same state, bit for bit."""
-    assert np.array_equal(a.positions(), b.positions())
-    assert _ctx(a) == _ctx(b)
-    if ta is not None:
-        assert (ta.step_launches, ta.rebuild_launches) == (tb.step_launches, tb.rebuild_launches)
 
 
 def _both(hip, runs, expect_groups, **kw):
