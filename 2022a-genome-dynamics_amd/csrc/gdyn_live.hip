@@ -140,6 +140,16 @@ struct gd_live_history : gd::handle {
     }
 };
 
+// ---- the seams of an analysis that reads the blocks itself (gdyn_live.hpp)
+gd_live_history_shape gd_live_history_shape_of(const gd_live_history *h)
+{
+    return {h->device, h->N, h->frames, h->frames_per_block, (size_t)h->slots * h->frame_floats()};
+}
+
+int gd_live_history_slot(const gd_live_history *h, const char *who, uint32_t replica, uint32_t *slot) { return h->slot_of(who, replica, slot); }
+
+const float *gd_live_history_frame(const gd_live_history *h, uint32_t f, uint32_t slot) { return h->frame(f, slot); }
+
 extern "C" {
 
 int gd_live_abi_version(void) { return GD_LIVE_ABI_VERSION; }

@@ -3,12 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_cmap.h"
 #include "../../include/gdyn_flow.h"
 #include "../../include/gdyn_lamina.h"
+#include "../../include/gdyn_live.h"
 #include "../../include/gdyn_rdf.h"
 #include "gdyn_types.h"
 
@@ -48,3 +50,15 @@ GD_SEAM int gd_flow_device(const gd_flow *h);
 // idle: the handle holds the history, or none when the caller found it unusable (ok == false).
 GD_SEAM int gd_flow_history_begin(gd_flow *h, const char *who, uint32_t frames, uint32_t n_beads, double **x, hipStream_t *stream);
 GD_SEAM void gd_flow_history_end(gd_flow *h, uint32_t frames, uint32_t n_beads, bool ok);
+
+// ---- the recorder (gdyn_live.hip), for an analysis that takes its frames as recorded (gdyn_msd.hip): float32, frame f of a slot
+// at gd_live_history_frame(h, f, slot), the frames of one block frame_stride floats apart.  The blocks are not written while the
+// recorder's stream is idle, which every gd_live_history_* call leaves it.
+struct gd_live_history_shape {
+    int device;
+    uint32_t N, frames, frames_per_block;
+    size_t frame_stride;
+};
+GD_SEAM gd_live_history_shape gd_live_history_shape_of(const gd_live_history *h);
+GD_SEAM int gd_live_history_slot(const gd_live_history *h, const char *who, uint32_t replica, uint32_t *slot);
+GD_SEAM const float *gd_live_history_frame(const gd_live_history *h, uint32_t f, uint32_t slot);

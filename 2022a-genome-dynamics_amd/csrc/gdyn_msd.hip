@@ -1,0 +1,634 @@
+// gdyn_msd.hip -- the lag statistics of a trajectory history (include/gdyn_msd.h): MSD(tau) along the frame axis and R2(s) along
+// the chains, one kernel family for both.  Beyond the reference, which has neither.
+//
+// A *sequence* is a run of items (3 coordinates each) a fixed stride apart: along time one bead's trajectory (item stride 3 N
+// elements, neighbouring beads 3 elements apart), along the chain one chain in one frame (item stride 3, the same chain in the
+// next frame 3 N elements on).  A *tile* is kSeqs = 16 sequences that lie side by side: 16 consecutive beads, or one chain in 16
+// consecutive frames of the window.
+//
+//   k_msd_lag<T>     one block per (tile, origin range of kRange = 4096 origins).  It stages windows of W items of its 16 sequences
+//                    in LDS, [item][sequence][3] in the stored type T with one element of padding per item row, and evaluates
+//                    every requested lag from there: lane = (sequence, lag), 16 x 64 per block, so the 16 lanes of a lag read
+//                    items 3 elements apart (conflict-free) and run the same trip count.  When the whole sequence fits (F <= W:
+//                    835 float32 items in 160 KiB) the history is read from HBM once per call whatever the number of lags.
+//                    Otherwise the block walks origin windows A and, for each, only the partner windows B = A + d W that a
+//                    requested lag connects (lags are sorted, so the lags of one d are a range found by bisection).
+//                    Every (sequence, lag, range) sum is ONE lane's serial sum over ascending origins, carried from window
+//                    pair to window pair in its slot of `partial` (always the same lane's): no bit depends on W.
+//   k_msd_reduce1/2  the sums of a group: per fixed chunk of 256 sequences, serially over ascending sequences (each the serial sum
+//                    of its ranges), then serially over the chunks.  The order depends on the shapes alone.
+//   k_msd_per_seq    gd_msd_time_per_bead: the serial sum of a sequence's ranges.
+//   k_msd_first_bad  the lowest index of a non-finite coordinate (integer atomicMin, reached by no lane of a finite history)
+// fp64 throughout, -ffp-contract=off (csrc/Makefile), no fast-math, no floating-point atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "../../include/gdyn.h"
+#include "../../include/gdyn_msd.h"
+#include "gdyn_analysis.hpp"
+#include "gdyn_live.hpp"
+#include "gdyn_once.hpp"
+
+using namespace gd;
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kLagBlock = 1024;              // k_msd_lag: a tile of F = 701 float32 frames leaves room for one block per CU, so the
+                                             // block brings the waves that hide the LDS latency itself (four per SIMD)
+constexpr unsigned kSeqs = 16;               // sequences of a tile
+constexpr unsigned kSlots = kLagBlock / kSeqs;  // lags evaluated side by side
+constexpr unsigned kRow = 3 * kSeqs + 1;     // elements of an item row in LDS: odd, so consecutive items start on different banks
+constexpr unsigned kRange = 4096;            // origins of one serial sum: fixed, so that the order of summation is
+constexpr unsigned kChunk = 256;             // sequences of one serial group sum: likewise
+constexpr unsigned long long kNoBadIndex = ~0ull;
+constexpr size_t kPartialBytes = (size_t)1 << 30;      // lags are evaluated in batches whose partial sums fit this
+
+struct LagArgs {
+    const void *x;                  // the history, (F, N, 3) of T
+    const uint32_t *chains;         // (C, 2) on the device: along the chain; NULL: along time
+    const uint32_t *lags;           // ascending
+    double2 *partial;               // (ranges, sequences, lags): (sum of t2, sum of t4)
+    unsigned N, F, C;
+    unsigned f0, nf, ftiles;        // along the chain: the frame window and its tiles of kSeqs frames
+    unsigned n_lags, W, windows;    // W items per window; windows: 1 (the longest sequence fits in one) or 2
+    size_t n_seqs;
+};
+
+__device__ inline unsigned lower_bound_dev(const uint32_t *__restrict__ v, unsigned n, unsigned long long key)      // first index with v[i] >= key
+{
+    unsigned lo = 0, hi = n;
+    while (lo < hi) {
+        unsigned const mid = (lo + hi) / 2;
+        if (v[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// items [i0, i0 + n) of the tile's sequences into dst ([item][sequence][3]); sequences beyond `valid` read as zeros
+template <typename T>
+__device__ inline void stage(T *dst, const T *__restrict__ base, size_t seq_stride, size_t item_stride, unsigned valid, size_t i0, unsigned n)
+{
+    unsigned const total = n * kSeqs * 3;
+    if (item_stride >= seq_stride) {      // along time: an item row of the tile is contiguous in memory
+        for (unsigned idx = threadIdx.x; idx < total; idx += kLagBlock) {
+            unsigned const w = idx / (3 * kSeqs), e = idx % (3 * kSeqs), s = e / 3;
+            dst[w * kRow + e] = s < valid ? base[(i0 + w) * item_stride + (size_t)s * seq_stride + e % 3] : T(0);
+        }
+    } else {      // along the chain: the items of a sequence are contiguous
+        for (unsigned idx = threadIdx.x; idx < total; idx += kLagBlock) {
+            unsigned const s = idx / (3 * n), e = idx % (3 * n), w = e / 3;
+            dst[w * kRow + 3 * s + e % 3] = s < valid ? base[(size_t)s * seq_stride + (i0 + w) * item_stride + e % 3] : T(0);
+        }
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kLagBlock) k_msd_lag(LagArgs p)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    T *A = reinterpret_cast<T *>(smem);
+    T *B = A + (size_t)(p.windows - 1) * p.W * kRow;      // one window: partners lie in A
+    const T *x = static_cast<const T *>(p.x);
+
+    // the tile: where its sequences lie, how long they are, and which rows of `partial` are theirs
+    size_t base, seq_stride, item_stride, q0, q_stride;
+    unsigned valid, L;
+    if (p.chains) {
+        unsigned const c = blockIdx.x / p.ftiles, ft = blockIdx.x % p.ftiles;
+        unsigned const start = p.chains[2 * c];
+        L = p.chains[2 * c + 1] - start;
+        base = ((size_t)p.f0 + (size_t)ft * kSeqs) * p.N * 3 + (size_t)start * 3;
+        seq_stride = (size_t)p.N * 3;
+        item_stride = 3;
+        valid = min(kSeqs, p.nf - ft * kSeqs);
+        q0 = (size_t)ft * kSeqs * p.C + c;
+        q_stride = p.C;
+    } else {
+        L = p.F;
+        base = (size_t)blockIdx.x * kSeqs * 3;
+        seq_stride = 3;
+        item_stride = (size_t)p.N * 3;
+        valid = min(kSeqs, p.N - blockIdx.x * kSeqs);
+        q0 = (size_t)blockIdx.x * kSeqs;
+        q_stride = 1;
+    }
+    unsigned const s = threadIdx.x % kSeqs, slot = threadIdx.x / kSeqs;
+    long long const W = p.W;
+    if (L < 2) return;
+    unsigned const ranges = (L - 1 + kRange - 1) / kRange;      // origins 0 .. L-2
+    for (unsigned g = blockIdx.y; g < ranges; g += gridDim.y) {
+        long long const O0 = (long long)g * kRange, O1 = min(O0 + (long long)kRange, (long long)L - 1);
+        double2 *mine = p.partial + ((size_t)g * p.n_seqs + q0 + (size_t)s * q_stride) * p.n_lags;
+        for (long long A0 = O0; A0 < O1; A0 += W) {
+            long long const nO = min(W, O1 - A0), nA = min(W, (long long)L - A0);      // origins; items staged
+            __syncthreads();      // the last window pair has been read
+            stage(A, x + base, seq_stride, item_stride, valid, (size_t)A0, (unsigned)nA);
+            for (long long d = 0;;) {      // partner windows [A0 + d W, A0 + (d + 1) W): the lags of d lie in ((d - 1) W, (d + 1) W)
+                unsigned const lo = d ? lower_bound_dev(p.lags, p.n_lags, (unsigned long long)((d - 1) * W + 1)) : 0;
+                unsigned const hi = lower_bound_dev(p.lags, p.n_lags, (unsigned long long)((d + 1) * W));
+                if (lo == hi) {
+                    if (hi >= p.n_lags) break;
+                    d = p.lags[hi] / W;      // >= d + 1
+                    continue;
+                }
+                long long const B0 = A0 + d * W;
+                if (B0 >= (long long)L) break;
+                long long const nB = d ? min(W, (long long)L - B0) : nA;
+                const T *Bw = A;
+                if (d) {
+                    __syncthreads();      // the last partner window has been read
+                    stage(B, x + base, seq_stride, item_stride, valid, (size_t)B0, (unsigned)nB);
+                    Bw = B;
+                }
+                __syncthreads();
+                if (s < valid)
+                    for (unsigned k = lo / kSlots * kSlots + slot; k < hi; k += kSlots) {      // lag k is always this lane's
+                        if (k < lo) continue;
+                        long long const shift = (long long)p.lags[k] - d * W;      // partner's place in B = origin's place in A + shift
+                        long long const r0 = max(0ll, -shift), r1 = min(nO, nB - shift);
+                        if (r1 <= r0) continue;
+                        const T *pa = A + r0 * kRow + 3 * s, *pb = Bw + (r0 + shift) * kRow + 3 * s;
+                        double2 acc = mine[k];
+#pragma unroll 4
+                        for (long long r = r0; r < r1; r++, pa += kRow, pb += kRow) {
+                            double const dx = (double)pb[0] - (double)pa[0], dy = (double)pb[1] - (double)pa[1], dz = (double)pb[2] - (double)pa[2];
+                            double const t2 = (dx * dx + dy * dy) + dz * dz;
+                            acc.x += t2;
+                            acc.y += t2 * t2;
+                        }
+                        mine[k] = acc;
+                    }
+                d++;
+            }
+        }
+    }
+}
+
+// how a sequence's group is found: gmod > 0: q % gmod; else group[q] (NULL: group 0)
+struct GroupMap {
+    const int32_t *group;
+    unsigned gmod;
+};
+
+__device__ inline double2 sum_ranges(const double2 *__restrict__ partial, unsigned ranges, size_t n_seqs, unsigned n_lags, size_t q, unsigned k)
+{
+    double2 r = partial[q * n_lags + k];
+    for (unsigned g = 1; g < ranges; g++) {
+        double2 const v = partial[((size_t)g * n_seqs + q) * n_lags + k];
+        r.x += v.x;
+        r.y += v.y;
+    }
+    return r;
+}
+
+// tmp[chunk][group][lag]: the sums of the chunk's sequences of a group, in ascending order
+__global__ void __launch_bounds__(kBlock) k_msd_reduce1(const double2 *__restrict__ partial, unsigned ranges, size_t n_seqs, unsigned n_lags,
+                                                        GroupMap m, unsigned G, double2 *__restrict__ tmp)
+{
+    size_t const q0 = (size_t)blockIdx.x * kChunk, q1 = min(q0 + kChunk, n_seqs);
+    size_t const tasks = (size_t)G * n_lags;
+    for (size_t e = threadIdx.x; e < tasks; e += kBlock) {
+        unsigned const grp = (unsigned)(e / n_lags), k = (unsigned)(e % n_lags);
+        double2 acc = make_double2(0.0, 0.0);
+        if (m.gmod) {
+            size_t q = q0 + (grp + m.gmod - q0 % m.gmod) % m.gmod;
+            for (; q < q1; q += m.gmod) {
+                double2 const v = sum_ranges(partial, ranges, n_seqs, n_lags, q, k);
+                acc.x += v.x;
+                acc.y += v.y;
+            }
+        } else {
+            for (size_t q = q0; q < q1; q++) {
+                if ((m.group ? m.group[q] : 0) != (int)grp) continue;
+                double2 const v = sum_ranges(partial, ranges, n_seqs, n_lags, q, k);
+                acc.x += v.x;
+                acc.y += v.y;
+            }
+        }
+        tmp[(size_t)blockIdx.x * tasks + e] = acc;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_msd_reduce2(const double2 *__restrict__ tmp, unsigned chunks, size_t tasks, double2 *__restrict__ out)
+{
+    size_t const e = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= tasks) return;
+    double2 acc = tmp[e];
+    for (unsigned c = 1; c < chunks; c++) {
+        double2 const v = tmp[(size_t)c * tasks + e];
+        acc.x += v.x;
+        acc.y += v.y;
+    }
+    out[e] = acc;
+}
+
+__global__ void __launch_bounds__(kBlock) k_msd_per_seq(const double2 *__restrict__ partial, unsigned ranges, size_t n_seqs, double2 *__restrict__ out)
+{
+    size_t const q = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q < n_seqs) out[q] = sum_ranges(partial, ranges, n_seqs, 1, q, 0);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_msd_first_bad(const T *__restrict__ x, size_t n, unsigned long long *first_bad)
+{
+    unsigned long long bad = kNoBadIndex;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+        if (!isfinite(x[i])) bad = min(bad, (unsigned long long)i);
+    if (bad != kNoBadIndex) atomicMin(first_bad, bad);
+}
+
+// The dynamic LDS a block of k_msd_lag may ask for on a device: all 160 KiB of a gfx950 CU where the opt-in is granted (once per
+// device, gdyn_once.hpp), else 128 KiB, else the 64 KiB that need none.  A refusal only makes the windows smaller.
+int lds_budget(int device)
+{
+    static DeviceOnce<> once;
+    int const bytes = once.run(device, [](int) {
+        for (int want : {160 * 1024, 128 * 1024}) {
+            hipError_t const a = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_lag<float>), hipFuncAttributeMaxDynamicSharedMemorySize, want);
+            hipError_t const b = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_lag<double>), hipFuncAttributeMaxDynamicSharedMemorySize, want);
+            if (a == hipSuccess && b == hipSuccess) return want;
+            (void)hipGetLastError();
+        }
+        return 64 * 1024;
+    });
+    return bytes > 0 ? bytes : 64 * 1024;
+}
+
+}  // namespace
+
+struct gd_msd : gd::handle {
+    unsigned knob = 0;
+    int lds_bytes = 64 * 1024;
+    unsigned F = 0, N = 0;         // F == 0: no history; N stays, for the groups and chains that belong to it
+    bool is_f64 = false;
+    dbuf<float> xf;
+    dbuf<double> xd;
+    dbuf<unsigned long long> first_bad;
+    // groups and chains
+    unsigned G = 1;
+    bool have_groups = false;      // false: one group of all beads
+    std::vector<int32_t> group;
+    dbuf<int32_t> group_dev;
+    std::vector<uint32_t> chains;  // (C, 2)
+    dbuf<uint32_t> chains_dev;
+    // per call
+    dbuf<uint32_t> lags_dev;
+    dbuf<double2> partial, tmp, out;
+
+    const void *x() const { return is_f64 ? (const void *)xd.p : (const void *)xf.p; }
+    size_t elem() const { return is_f64 ? sizeof(double) : sizeof(float); }
+};
+
+namespace {
+
+int check_groups(const char *who, const int32_t *group, unsigned N, unsigned G)
+{
+    for (unsigned i = 0; i < N; i++)
+        if (group[i] < -1 || group[i] >= (int64_t)G) return fail(GD_EINVAL, "%s: group[%u] = %d is not in [-1, %u)", who, i, group[i], G);
+    return GD_OK;
+}
+
+int check_chains(const char *who, const uint32_t *r, unsigned C, unsigned N)
+{
+    for (unsigned c = 0; c < C; c++) {
+        if (r[2 * c] > r[2 * c + 1]) return fail(GD_EINVAL, "%s: chain %u is reversed: [%u, %u)", who, c, r[2 * c], r[2 * c + 1]);
+        if (r[2 * c + 1] > N) return fail(GD_EINVAL, "%s: chain %u ends at %u, beyond the %u beads", who, c, r[2 * c + 1], N);
+        if (c && r[2 * c] < r[2 * c - 1]) return fail(GD_EINVAL, "%s: chain %u starts at %u, before chain %u ends (%u)", who, c, r[2 * c], c - 1, r[2 * c - 1]);
+    }
+    return GD_OK;
+}
+
+// the history is on the device: the non-finite check, then the handle holds it (or none)
+int finish_history(gd_msd *h, const char *who, unsigned frames, unsigned n_beads, bool is_f64)
+{
+    size_t const n = (size_t)frames * n_beads * 3;
+    HIPCHK(h->first_bad.ensure(1));
+    HIPCHK(hipMemsetAsync(h->first_bad.p, 0xff, sizeof(unsigned long long), h->stream));
+    unsigned const blocks = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 8192);
+    if (is_f64) hipLaunchKernelGGL(k_msd_first_bad<double>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xd.p, n, h->first_bad.p);
+    else hipLaunchKernelGGL(k_msd_first_bad<float>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xf.p, n, h->first_bad.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = kNoBadIndex;
+    HIPCHK(hipMemcpyAsync(&bad, h->first_bad.p, sizeof bad, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bad != kNoBadIndex) return fail(GD_EINVAL, "%s: non-finite coordinate at %llu", who, bad);
+    if (n_beads != h->N) {      // groups and chains belonged to another N
+        h->have_groups = false;
+        h->G = 1;
+        h->group.clear();
+        h->chains.clear();
+    }
+    h->F = frames;
+    h->N = n_beads;
+    h->is_f64 = is_f64;
+    return GD_OK;
+}
+
+int check_shape(const char *who, uint32_t frames, uint32_t n_beads)
+{
+    if (frames == 0 || n_beads == 0) return fail(GD_EINVAL, "%s: empty history (%u frames of %u beads)", who, frames, n_beads);
+    if (n_beads > (1u << 28)) return fail(GD_EINVAL, "%s: %u beads exceed 2^28", who, n_beads);
+    return GD_OK;
+}
+
+// lags: distinct and >= 1; order: their indices by ascending lag
+int check_lags(const char *who, const char *what, const uint32_t *lags, uint32_t n, std::vector<uint32_t> &order)
+{
+    order.resize(n);
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lags[a] < lags[b]; });
+    if (n && lags[order[0]] == 0) return fail(GD_EINVAL, "%s: %s 0", who, what);
+    for (uint32_t k = 1; k < n; k++)
+        if (lags[order[k]] == lags[order[k - 1]]) return fail(GD_EINVAL, "%s: %s %u is listed twice", who, what, lags[order[k]]);
+    return GD_OK;
+}
+
+struct Plan {      // one axis of one call
+    bool along_chain;
+    unsigned f0, nf, ftiles;
+    size_t n_seqs, tiles;
+    unsigned longest;      // items of the longest sequence
+    unsigned ranges;
+};
+
+// evaluates the sorted lags [k0, k0 + nl) into h->partial ((ranges, n_seqs, nl), zero where nothing is summed)
+int run_lags(gd_msd *h, const Plan &pl, const uint32_t *sorted_lags_dev, unsigned nl)
+{
+    size_t const row = (size_t)kRow * h->elem();
+    unsigned const fit = (unsigned)std::min<size_t>((size_t)h->lds_bytes / row, 1u << 28);
+    unsigned W, windows;
+    unsigned const want = h->knob ? std::min(h->knob, pl.longest) : pl.longest;
+    if (want <= fit) {
+        W = std::max(want, 1u);
+        windows = W >= pl.longest ? 1 : 2;
+        if (windows == 2 && 2 * (size_t)W > fit) W = std::max(fit / 2, 1u);
+    } else {
+        W = std::max(fit / 2, 1u);
+        windows = 2;
+    }
+    size_t const cells = (size_t)pl.ranges * pl.n_seqs * nl;
+    HIPCHK(h->partial.ensure(cells));
+    HIPCHK(hipMemsetAsync(h->partial.p, 0, cells * sizeof(double2), h->stream));
+    LagArgs a;
+    a.x = h->x();
+    a.chains = pl.along_chain ? h->chains_dev.p : nullptr;
+    a.lags = sorted_lags_dev;
+    a.partial = h->partial.p;
+    a.N = h->N;
+    a.F = h->F;
+    a.C = (unsigned)(h->chains.size() / 2);
+    a.f0 = pl.f0;
+    a.nf = pl.nf;
+    a.ftiles = pl.ftiles;
+    a.n_lags = nl;
+    a.W = W;
+    a.windows = windows;
+    a.n_seqs = pl.n_seqs;
+    dim3 const grid((unsigned)pl.tiles, std::min(pl.ranges, 65535u));
+    size_t const lds = (size_t)windows * W * row;
+    if (h->is_f64) hipLaunchKernelGGL(k_msd_lag<double>, grid, dim3(kLagBlock), lds, h->stream, a);
+    else hipLaunchKernelGGL(k_msd_lag<float>, grid, dim3(kLagBlock), lds, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return GD_OK;
+}
+
+// the group sums of every lag of `lags` (in the caller's order) along one axis: sum2 / sum4 (G, n) on the host
+int group_sums(gd_msd *h, const Plan &pl, const uint32_t *lags, const std::vector<uint32_t> &order, GroupMap m, unsigned G, double *sum2, double *sum4)
+{
+    unsigned const n = (unsigned)order.size();
+    std::vector<uint32_t> sorted(n);
+    for (unsigned k = 0; k < n; k++) sorted[k] = lags[order[k]];
+    HIPCHK(h->lags_dev.upload(sorted.data(), n));
+    size_t const per_lag = (size_t)pl.ranges * pl.n_seqs * sizeof(double2);
+    unsigned const batch = (unsigned)std::min<size_t>(std::max<size_t>(kPartialBytes / std::max<size_t>(per_lag, 1), 1), n);
+    unsigned const chunks = (unsigned)((pl.n_seqs + kChunk - 1) / kChunk);
+    std::vector<double2> host;
+    for (unsigned k0 = 0; k0 < n; k0 += batch) {
+        unsigned const nl = std::min(batch, n - k0);
+        if (int rc = run_lags(h, pl, h->lags_dev.p + k0, nl)) return rc;
+        size_t const tasks = (size_t)G * nl;
+        HIPCHK(h->tmp.ensure((size_t)chunks * tasks));
+        HIPCHK(h->out.ensure(tasks));
+        hipLaunchKernelGGL(k_msd_reduce1, dim3(chunks), dim3(kBlock), 0, h->stream, h->partial.p, pl.ranges, pl.n_seqs, nl, m, G, h->tmp.p);
+        hipLaunchKernelGGL(k_msd_reduce2, dim3(blocks_for(tasks, kBlock)), dim3(kBlock), 0, h->stream, h->tmp.p, chunks, tasks, h->out.p);
+        HIPCHK(hipGetLastError());
+        host.resize(tasks);
+        HIPCHK(hipMemcpyAsync(host.data(), h->out.p, tasks * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (unsigned g = 0; g < G; g++)
+            for (unsigned k = 0; k < nl; k++) {
+                size_t const at = (size_t)g * n + order[k0 + k];
+                sum2[at] = host[(size_t)g * nl + k].x;
+                if (sum4) sum4[at] = host[(size_t)g * nl + k].y;
+            }
+    }
+    return GD_OK;
+}
+
+Plan time_plan(const gd_msd *h)
+{
+    Plan pl{};
+    pl.along_chain = false;
+    pl.n_seqs = h->N;
+    pl.tiles = (h->N + kSeqs - 1) / kSeqs;
+    pl.longest = h->F;
+    pl.ranges = h->F > 1 ? (h->F - 1 + kRange - 1) / kRange : 1;
+    return pl;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gd_msd_abi_version(void) { return GD_MSD_ABI_VERSION; }
+
+int gd_msd_create(const gd_msd_desc *desc, gd_msd **out)
+{
+    if (int rc = gd::open("gd_msd_create", desc, out)) return rc;
+    (*out)->knob = desc->max_items_per_tile;
+    (*out)->lds_bytes = lds_budget(desc->device);
+    return GD_OK;
+}
+
+int gd_msd_destroy(gd_msd *h) { return gd::close(h); }
+
+int gd_msd_set_history(gd_msd *h, const void *xyz, uint32_t frames, uint32_t n_beads, int is_f64)
+{
+    const char *who = "gd_msd_set_history";
+    if (!h || !xyz) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (int rc = check_shape(who, frames, n_beads)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    size_t const n = (size_t)frames * n_beads * 3;
+    h->F = 0;      // the buffer is about to be overwritten
+    if (is_f64) HIPCHK(h->xd.upload(static_cast<const double *>(xyz), n));
+    else HIPCHK(h->xf.upload(static_cast<const float *>(xyz), n));
+    return finish_history(h, who, frames, n_beads, is_f64 != 0);
+}
+
+int gd_msd_set_history_live(gd_msd *h, gd_live_history *history, uint32_t replica)
+{
+    const char *who = "gd_msd_set_history_live";
+    if (!h || !history) return fail(GD_EINVAL, "%s: NULL handle", who);
+    gd_live_history_shape const v = gd_live_history_shape_of(history);
+    uint32_t slot = 0;
+    if (int rc = gd_live_history_slot(history, who, replica, &slot)) return rc;
+    if (v.device != h->device) return fail(GD_EINVAL, "%s: the recorder is on device %d, the analysis handle on device %d", who, v.device, h->device);
+    if (!v.frames) return fail(GD_ESTATE, "%s: no frame recorded", who);
+    if (int rc = check_shape(who, v.frames, v.N)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    size_t const M = (size_t)v.N * 3;
+    h->F = 0;
+    HIPCHK(h->xf.ensure((size_t)v.frames * M));
+    for (uint32_t f0 = 0; f0 < v.frames; f0 += v.frames_per_block) {      // one strided copy per block of the recorder
+        uint32_t const nf = std::min(v.frames_per_block, v.frames - f0);
+        HIPCHK(hipMemcpy2DAsync(h->xf.p + (size_t)f0 * M, M * sizeof(float), gd_live_history_frame(history, f0, slot), v.frame_stride * sizeof(float),
+                                M * sizeof(float), nf, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return finish_history(h, who, v.frames, v.N, false);
+}
+
+int gd_msd_set_groups(gd_msd *h, const int32_t *group, uint32_t n_groups)
+{
+    const char *who = "gd_msd_set_groups";
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the groups are N values of its beads)", who);
+    if (!group) {
+        if (n_groups > 1) return fail(GD_EINVAL, "%s: %u groups without a group array", who, n_groups);
+        h->have_groups = false;
+        h->G = 1;
+        h->group.clear();
+        return GD_OK;
+    }
+    if (n_groups == 0 || n_groups > (1u << 20)) return fail(GD_EINVAL, "%s: %u groups (1 to 2^20)", who, n_groups);
+    if (int rc = check_groups(who, group, h->N, n_groups)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    dbuf<int32_t> dev;
+    HIPCHK(dev.upload(group, h->N));
+    h->group_dev = std::move(dev);
+    h->group.assign(group, group + h->N);
+    h->G = n_groups;
+    h->have_groups = true;
+    return GD_OK;
+}
+
+int gd_msd_set_chains(gd_msd *h, const uint32_t *ranges, uint32_t n_chains)
+{
+    const char *who = "gd_msd_set_chains";
+    if (!h || (!ranges && n_chains)) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the chains are ranges of its beads)", who);
+    if (n_chains > (1u << 24)) return fail(GD_EINVAL, "%s: %u chains exceed 2^24", who, n_chains);
+    if (int rc = check_chains(who, ranges, n_chains, h->N)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    dbuf<uint32_t> dev;
+    HIPCHK(dev.upload(ranges, 2 * (size_t)n_chains));
+    h->chains_dev = std::move(dev);
+    h->chains.assign(ranges, ranges + 2 * (size_t)n_chains);
+    return GD_OK;
+}
+
+int gd_msd_time(gd_msd *h, const uint32_t *lags, uint32_t n_lags, double *sum2, double *sum4, uint64_t *count)
+{
+    const char *who = "gd_msd_time";
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (n_lags && (!lags || !sum2 || !count)) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (n_lags > (1u << 28)) return fail(GD_EINVAL, "%s: %u lags exceed 2^28", who, n_lags);
+    std::vector<uint32_t> order;
+    if (int rc = check_lags(who, "lag", lags, n_lags, order)) return rc;
+    if (h->have_groups)
+        if (int rc = check_groups(who, h->group.data(), h->N, h->G)) return rc;
+    if (n_lags == 0) return GD_OK;
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> s2((size_t)h->G * n_lags), s4((size_t)h->G * n_lags);
+    GroupMap const m{h->have_groups ? h->group_dev.p : nullptr, 0};
+    if (int rc = group_sums(h, time_plan(h), lags, order, m, h->G, s2.data(), s4.data())) return rc;
+    std::vector<uint64_t> members(h->G, h->have_groups ? 0 : h->N);
+    if (h->have_groups)
+        for (int32_t g : h->group)
+            if (g >= 0) members[g]++;
+    for (unsigned g = 0; g < h->G; g++)
+        for (unsigned l = 0; l < n_lags; l++) count[(size_t)g * n_lags + l] = members[g] * (lags[l] < h->F ? h->F - lags[l] : 0);
+    std::memcpy(sum2, s2.data(), s2.size() * sizeof(double));
+    if (sum4) std::memcpy(sum4, s4.data(), s4.size() * sizeof(double));
+    return GD_OK;
+}
+
+int gd_msd_time_per_bead(gd_msd *h, uint32_t lag, double *m2, double *m4)
+{
+    const char *who = "gd_msd_time_per_bead";
+    if (!h || !m2) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (lag == 0 || lag >= h->F) return fail(GD_EINVAL, "%s: lag %u of %u frames (1 to F - 1)", who, lag, h->F);
+    HIPCHK(hipSetDevice(h->device));
+    Plan const pl = time_plan(h);
+    HIPCHK(h->lags_dev.upload(&lag, 1));
+    if (int rc = run_lags(h, pl, h->lags_dev.p, 1)) return rc;
+    HIPCHK(h->out.ensure(h->N));
+    hipLaunchKernelGGL(k_msd_per_seq, dim3(blocks_for(h->N, kBlock)), dim3(kBlock), 0, h->stream, h->partial.p, pl.ranges, pl.n_seqs, h->out.p);
+    HIPCHK(hipGetLastError());
+    std::vector<double2> host(h->N);
+    HIPCHK(hipMemcpyAsync(host.data(), h->out.p, host.size() * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (unsigned i = 0; i < h->N; i++) {
+        m2[i] = host[i].x;
+        if (m4) m4[i] = host[i].y;
+    }
+    return GD_OK;
+}
+
+int gd_msd_chain(gd_msd *h, const uint32_t *seps, uint32_t n_seps, uint32_t first_frame, uint32_t n_frames, double *sum2, double *sum4,
+                 uint64_t *count)
+{
+    const char *who = "gd_msd_chain";
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    unsigned const C = (unsigned)(h->chains.size() / 2);
+    if (n_seps && C && (!seps || !sum2 || !count)) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (n_seps > (1u << 28)) return fail(GD_EINVAL, "%s: %u separations exceed 2^28", who, n_seps);
+    if ((uint64_t)first_frame + n_frames > h->F)
+        return fail(GD_EINVAL, "%s: frames %u to %llu of %u", who, first_frame, (unsigned long long)first_frame + n_frames, h->F);
+    std::vector<uint32_t> order;
+    if (int rc = check_lags(who, "separation", seps, n_seps, order)) return rc;
+    if (int rc = check_chains(who, h->chains.data(), C, h->N)) return rc;
+    if (n_seps == 0 || C == 0) return GD_OK;
+    size_t const cells = (size_t)C * n_seps;
+    unsigned longest = 0;
+    for (unsigned c = 0; c < C; c++) longest = std::max(longest, h->chains[2 * c + 1] - h->chains[2 * c]);
+    for (unsigned c = 0; c < C; c++)
+        for (unsigned l = 0; l < n_seps; l++) {
+            uint64_t const len = h->chains[2 * c + 1] - h->chains[2 * c];
+            count[(size_t)c * n_seps + l] = (uint64_t)n_frames * (seps[l] < len ? len - seps[l] : 0);
+        }
+    if (n_frames == 0 || longest < 2) {
+        std::fill(sum2, sum2 + cells, 0.0);
+        if (sum4) std::fill(sum4, sum4 + cells, 0.0);
+        return GD_OK;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    Plan pl{};
+    pl.along_chain = true;
+    pl.f0 = first_frame;
+    pl.nf = n_frames;
+    pl.ftiles = (n_frames + kSeqs - 1) / kSeqs;
+    pl.n_seqs = (size_t)n_frames * C;
+    pl.tiles = (size_t)C * pl.ftiles;
+    pl.longest = longest;
+    pl.ranges = (longest - 1 + kRange - 1) / kRange;
+    if (pl.tiles > 0x7fffffffu) return fail(GD_EINVAL, "%s: %zu tiles of %u chains in %u frames exceed 2^31", who, pl.tiles, C, n_frames);
+    std::vector<double> s2(cells), s4(cells);
+    GroupMap const m{nullptr, C};
+    if (int rc = group_sums(h, pl, seps, order, m, C, s2.data(), s4.data())) return rc;
+    std::memcpy(sum2, s2.data(), cells * sizeof(double));
+    if (sum4) std::memcpy(sum4, s4.data(), cells * sizeof(double));
+    return GD_OK;
+}
+
+}  // extern "C"

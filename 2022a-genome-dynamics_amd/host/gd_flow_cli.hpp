@@ -149,15 +149,15 @@ inline std::string sha256_hex(std::string const &msg)
 
 inline std::string analysis_name(options const &o, std::string const &config) { return o.name.empty() ? sha256_hex(config).substr(0, 7) : o.name; }
 
-// load_positions: /snapshots/interphase/<step>/positions for the steps of .steps in stored order, as float32 (F, N, 3)
-inline std::vector<float> load_history(std::string const &path, uint32_t &frames, uint32_t &beads)
+// load_positions: /snapshots/<phase>/<step>/positions for the steps of .steps in stored order, as float32 (F, N, 3)
+inline std::vector<float> load_history(std::string const &path, uint32_t &frames, uint32_t &beads, std::string const &phase_name = "interphase")
 {
     h5::hid file(H5Fopen(path.c_str(), H5F_ACC_RDONLY, H5P_DEFAULT));
     h5::check(file >= 0, "cannot open " + path);
-    h5::hid phase(H5Gopen2(file, "/snapshots/interphase", H5P_DEFAULT));
-    h5::check(phase >= 0, path + ": no /snapshots/interphase");
+    h5::hid phase(H5Gopen2(file, ("/snapshots/" + phase_name).c_str(), H5P_DEFAULT));
+    h5::check(phase >= 0, path + ": no /snapshots/" + phase_name);
     auto const steps = h5::read_string_list(phase, ".steps");
-    h5::check(!steps.empty(), path + ": no interphase snapshots");
+    h5::check(!steps.empty(), path + ": no " + phase_name + " snapshots");
     std::vector<float> out;
     std::size_t n0 = 0;
     for (auto const &s : steps) {
