@@ -9,8 +9,17 @@ the total and the branches kernels get wrong are reached:
   pressed_genome(lib, n_beads, n_replicas)
                          the perturbed genome inside a tighter wall with three unequal semiaxes per replica: hundreds of beads on the
                          wall, on both sides of the surface, and an axial reaction of the size of spring * semiaxes
-  composite(lib)         an open-box model with all six terms (pair, bond, bend, point, wall, dynamic), R = 2
-  chromatin_1kb_images(lib, shifted, shape)
+  composite(lib)         an open-box model with all six terms (pair, bond, bend, point, wall, dynamic), R = 2; with `powers` the
+                         pair term takes runtime soft-core powers (the kernels' runtime-power pair form) and the wall WALL_POWERS
+  spindle_driver(lib)    perturbed(lib, "spindle") with the pair form as host/gd_spindle.cpp sets it: (2, 3, 2, 3), eps_b = sigma_b = 0
+  inner_sphere(lib)      the excluded-core model of test_parity_gpu.py::test_inner_sphere_wall_matches_oracle, runtime inner-wall powers
+  isolated_pairs(lib, form)
+                         one handle of two-bead systems at known separations, for the closed-form soft-core answers of every (P, Q)
+  runtime_blob(lib, n_beads, compress), runtime_box(lib, n_beads, compress)
+                         dense blobs of chains (open) and the compressed 1 kb model (periodic) with runtime pair powers: local density,
+                         and with it the tile class of the LDS-tiled lists, set by `compress`; clear_of_edge() conditions such a state
+  spindle_coarse(lib)    the coarse model host/gd_spindle.cpp builds, through the Python API
+  chromatin_1kb_images(lib, shifted, shape, powers)
                          the 1 kb force field with beads shifted by whole periods, so that pair neighbours and glue pairs straddle
                          the box faces in raw coordinates (and unflagged chain bonds become long: they must NOT be minimum-imaged);
                          also in a box with three different periods
@@ -242,8 +251,14 @@ def softcore_bond_pairs():
     return np.array(out, dtype=np.uint32)
 
 
-def composite(lib, terms=ALL, seed=11, n_replicas=2):
-    """Open-box model in which all six terms act at once (only the terms in `terms` are configured).
+RUNTIME_POWERS = ((4, 2, 12, 1), (6, 4, 2, 3))      # (p_a, q_a, p_b, q_b) of the runtime-power composite models
+WALL_POWERS = (4, 2, 6, 4)                          # ... and the powers of their ellipsoid wall
+
+
+def composite(lib, terms=ALL, seed=11, n_replicas=2, powers=None):
+    """Open-box model in which all six terms act at once (only the terms in `terms` are configured).  powers = (p_a, q_a, p_b, q_b):
+    the pair term with these soft-core powers instead of (2, 3, 8, 3) -- the runtime-power pair form of the kernels, still mixed,
+    scaled and with fp16-exact factors, so the tiled path stays available -- and the wall with WALL_POWERS instead of the default.
 
     pair:    AB soft-core (p 2/8, q 3), mixed, scaled with bead_scale
     bond:    mixed and scaled harmonic (i, i+2) bonds, mixed semispring chains, spring chains, unmixed softcore (i, i+2) bonds
@@ -260,7 +275,8 @@ def composite(lib, terms=ALL, seed=11, n_replicas=2):
     bend_e = 0.5 + (np.arange(n) % 5) * 0.25
     s.set_bead_params(a=a, b=b, mobility=mob, bending_energy=bend_e)
     if terms & g.TERM_PAIR:
-        s.set_pair_softcore(**PAIR, mix=True, scale_by_bead_scale=True)
+        pair = dict(PAIR) if powers is None else dict(PAIR, **dict(zip(("p_a", "q_a", "p_b", "q_b"), powers)))
+        s.set_pair_softcore(**pair, mix=True, scale_by_bead_scale=True)
     if terms & g.TERM_BOND:
         for k in SEMISPRING_CHAINS:
             s.add_bond_range(SEMISPRING_MIXED, *_chain_range(k), 1)
@@ -282,8 +298,9 @@ def composite(lib, terms=ALL, seed=11, n_replicas=2):
         for kind, K, bb, pt, tg in POINT_SOURCES:
             s.add_point_source(kind, K, bb, pt, targets=source_targets(tg))
     if terms & g.TERM_WALL:
+        wp = {} if powers is None else dict(zip(("p_a", "q_a", "p_b", "q_b"), WALL_POWERS))
         s.set_ellipsoid_wall(2.0, WALL_SIGMA[0], 2.0, WALL_SIGMA[1], wall_a_factor=1.0, wall_b_factor=1.0, packing_spring=PACKING,
-                             semiaxes_spring=(1e4,) * 3, mobility=1e-4, init_semiaxes=SEMI)
+                             semiaxes_spring=(1e4,) * 3, mobility=1e-4, init_semiaxes=SEMI, **wp)
     if terms & g.TERM_DYNAMIC:
         s.set_dynamic_pairs(0, LOOP, loop_pairs())
         s.set_dynamic_pairs(1, GLUE, glue_pairs())
@@ -304,19 +321,20 @@ def on_grid(x):
     return np.round(np.asarray(x, dtype=np.float64) / GRID) * GRID
 
 
-def chromatin_1kb_images(lib, shifted=True, shape=(1.0, 1.0, 1.0), n_beads=3000, n_replicas=2, seed=5, frac=0.3):
+def chromatin_1kb_images(lib, shifted=True, shape=(1.0, 1.0, 1.0), n_beads=3000, n_replicas=2, seed=5, frac=0.3, powers=None):
     """The 1 kb force field of workloads.chromatin_1kb (repulsion + attraction, spring chain, per-bead bending, spring loops in dynamic
     slot 0, minimum-image softcore glue in slot 1) with the jittered random walk of its initial state, in a box of periods
     shape x L (L the workload's period, put on the 2^-16 grid).  shifted=True moves `frac` of the beads by whole periods per axis
     (+-L), after the rounding: pair neighbours and glue pairs then straddle the box faces in raw coordinates, and so do chain bonds and
-    loops, which are NOT minimum-imaged (simulation.cpp:126-140: only the glue is) and so become long."""
+    loops, which are NOT minimum-imaged (simulation.cpp:126-140: only the glue is) and so become long.  powers = (p_a, q_a, p_b, q_b)
+    replaces the pair term's (2, 3, 8, 3): the runtime-power pair form, unmixed, with the attractive B channel."""
     s0, info = g_wl().chromatin_1kb(lib, n_beads=n_beads, n_replicas=1, n_loops=30, n_glues=60)
     x0 = s0.positions()[0]
     s0.close()
     box = tuple(float(on_grid(info["box"] * f)) for f in shape)
     s = g.System(lib, n_beads, n_replicas, box=box)
     s.set_bead_params(mobility=np.ones(n_beads), bending_energy=np.full(n_beads, 1.0))
-    s.set_pair_softcore(*KB_PAIR, mix=False)
+    s.set_pair_softcore(*kb_pair(powers), mix=False)
     s.add_bond_range(P(g.POT_SPRING, k_a=100.0, l_a=1.0), 0, n_beads, 1)
     s.add_bending_range(0, n_beads, 0.0, per_bead=True)
     loops, glues = kb_pairs(n_beads, seed)
@@ -335,8 +353,14 @@ def chromatin_1kb_images(lib, shifted=True, shape=(1.0, 1.0, 1.0), n_beads=3000,
 
 
 KB_PAIR = (2.0, 1.0, -0.2, 1.5, 2, 3, 8, 3)          # (eps_a, sigma_a, eps_b, sigma_b, p_a, q_a, p_b, q_b) of chromatin_1kb
+KB_RUNTIME_POWERS = (2, 1, 8, 4)
 KB_LOOP = P(g.POT_SPRING, k_a=10.0, l_a=1.0)
 KB_GLUE = P(g.POT_SOFTCORE, k_a=-1.0, l_a=1.5, p=8, q=3, minimum_image=True)
+
+
+def kb_pair(powers=None):
+    """KB_PAIR with its powers replaced"""
+    return KB_PAIR if powers is None else KB_PAIR[:4] + tuple(powers)
 
 
 def kb_pairs(n_beads, seed):
@@ -348,11 +372,245 @@ def kb_pairs(n_beads, seed):
     return loops, np.stack([j, j + 3], axis=1).astype(np.uint32)
 
 
+# ------------------------------------------------------------------------------------------------ the spindle driver's pair form
+
+SPINDLE_PAIR = (5.0, 0.2)         # workloads.spindle: init_bead_repulsion, init_bead_diameter
+
+
+def spindle_driver(lib, specialised=False, **kw):
+    """perturbed(lib, "spindle") with the pair form exactly as host/gd_spindle.cpp:80-83 sets it: (eps, sigma, 0, 0, 2, 3, 2, 3), unmixed
+    -- an unused B channel with sigma_b = 0 and runtime powers, where workloads.spindle writes (2, 3, 8, 3).  specialised=True: the
+    (2, 3, 8, 3), eps_b = 0 form of the same state -- the same function of the positions, evaluated by the specialised kernels."""
+    s = perturbed(lib, "spindle", **kw)
+    s.set_pair_softcore(*SPINDLE_PAIR, 0.0, 0.0, 2, 3, *((8, 3) if specialised else (2, 3)), mix=False)
+    return s
+
+
+# ------------------------------------------------------------------------------------------------ the excluded core
+
+INNER = dict(radius=0.6, eps=3.0, sigma=(0.30, 0.24), spring=40.0, outer=1.7, fill=1.6)
+INNER_POWERS = (6, 4, 4, 2)
+
+
+def inner_sphere(lib, powers=INNER_POWERS, n_beads=3000, n_replicas=2, seed=11):
+    """The model of test_parity_gpu.py::test_inner_sphere_wall_matches_oracle at its size (3 000 A or B beads uniform in a ball of
+    radius 1.6 around an excluded core of radius 0.6, inside a fixed spherical wall of radius 1.7), every replica drawn on its own, the
+    inner wall's soft cores with the runtime powers `powers` (None: the default (2, 3, 8, 3))."""
+    rng = np.random.default_rng(seed)
+    x = rng.normal(size=(n_replicas, n_beads, 3))
+    x *= (rng.random((n_replicas, n_beads)) ** (1 / 3) * INNER["fill"] / np.linalg.norm(x, axis=-1))[..., None]
+    a = (rng.random(n_beads) < 0.5).astype(float)
+    s = g.System(lib, n_beads, n_replicas)
+    s.set_bead_params(a=a, b=1.0 - a, mobility=np.ones(n_beads))
+    s.set_pair_softcore(2.0, 0.30, 2.0, 0.24, 2, 3, 8, 3, mix=True)
+    s.set_ellipsoid_wall(4.0, 0.30, 4.0, 0.24, 0.0, 1.0, 50.0, (0.0,) * 3, 0.0, (INNER["outer"],) * 3, scale_by_bead_scale=False)
+    pw = {} if powers is None else dict(zip(("p_a", "q_a", "p_b", "q_b"), powers))
+    s.set_inner_sphere_wall(INNER["radius"], INNER["eps"], INNER["sigma"][0], INNER["eps"], INNER["sigma"][1], 0.0, 1.0, INNER["spring"], **pw)
+    s.set_positions(f32(x))
+    return s
+
+
+# ------------------------------------------------------------------------------------------------ isolated pairs: known answers
+
+FORMS = tuple((p, q) for p in (2, 4, 6, 8, 12) for q in (1, 2, 3, 4))      # what valid_pq admits
+# separations of the pairs as multiples of sigma_a: coincident, tiny, inside, just inside, on the edge, the next fp32 above it, outside
+# (0.9 and 0.999 rounded to fp32, so that u sigma_a is a position fp32 holds)
+U_GRID = tuple(float(np.float32(u)) for u in (0.0, 2.0 ** -10, 0.25, 0.5, 0.9, 0.999, 1.0, np.nextafter(np.float32(1.0), np.float32(2.0)), 1.5))
+PAIR_KINDS = (((1, 0), (1, 0)), ((0, 1), (0, 1)), ((1, 0), (0, 1)), ((.5, .5), (.5, .5)), ((1, 0), (.5, .5)), ((0, 1), (.5, .5)))
+# channel A carries the form under test at sigma_a = 2^-2 (u sigma_a is then exact in fp32 for every fp32 u); channel B a second
+# form at sigma_b = 5/16: it reaches further than A, so A's edge u = 1 lies inside the pair cutoff, and B's own edge (u = 1.25) is
+# not on the grid
+ISO = dict(eps_a=2.5, sigma_a=0.25, eps_b=1.5, sigma_b=0.3125)
+ISO_SPACING = 1.0                 # lattice spacing of the pairs: beyond any list radius (cutoff 0.3125; lists reach under twice that)
+
+
+def second_form(form):
+    """The form of channel B next to `form` in channel A: twelve places on in FORMS, so that (2, 3) meets (8, 3) -- that one handle is
+    the specialised pair form, the other nineteen are runtime-power forms -- and every form serves once as the second."""
+    return FORMS[(FORMS.index(tuple(form)) + 12) % len(FORMS)]
+
+
+def isolated_pairs_layout():
+    """(x (N, 3) fp32-exact, a, b, pairs (n, 2), u (n,), axis (n,)): one pair per (u, kind), bead 2k at a lattice point and bead 2k+1
+    u sigma_a further along axis k % 3; the lattice point's coordinate on that axis is 0, so both positions are exact in fp32."""
+    combos = [(u, kind) for u in U_GRID for kind in PAIR_KINDS]
+    n = len(combos)
+    x, a, b = np.zeros((2 * n, 3)), np.zeros(2 * n), np.zeros(2 * n)
+    side = int(np.ceil(np.sqrt(n)))
+    for k, (u, ((ai, bi), (aj, bj))) in enumerate(combos):
+        ax = k % 3
+        others = [c for c in range(3) if c != ax]
+        x[2 * k, others] = x[2 * k + 1, others] = ISO_SPACING * (1 + k % side), ISO_SPACING * (1 + k // side)
+        x[2 * k + 1, ax] = u * ISO["sigma_a"]
+        a[2 * k], b[2 * k], a[2 * k + 1], b[2 * k + 1] = ai, bi, aj, bj
+    assert np.array_equal(x, f32(x))
+    pairs = np.arange(2 * n).reshape(n, 2)
+    return x, a, b, pairs, np.array([u for u, _ in combos]), np.arange(n) % 3
+
+
+def isolated_pairs(lib, form):
+    """One handle (R = 1) of the isolated pairs: `form` in channel A, second_form(form) in channel B, mixed, non-uniform mobility."""
+    x, a, b, *_ = isolated_pairs_layout()
+    s = g.System(lib, len(x), 1)
+    s.set_bead_params(a=a, b=b, mobility=np.array(MOBILITY)[np.arange(len(x)) % 3])
+    s.set_pair_softcore(ISO["eps_a"], ISO["sigma_a"], ISO["eps_b"], ISO["sigma_b"], *form, *second_form(form), mix=True)
+    s.set_positions(x[None])
+    return s
+
+
+def softcore_closed_form(eps, sigma, P, Q, r):
+    """(U, -dU/dr) of U = eps (1 - (r/sigma)^P)^Q for r < sigma, 0 beyond, in numpy fp64 (tests/test_oracle_kat.py:61-62)."""
+    u = np.asarray(r, dtype=np.float64) / sigma
+    inside = u < 1
+    ui = np.where(inside, u, 0.0)
+    e = np.where(inside, eps * (1 - ui ** P) ** Q, 0.0)
+    f = np.where(inside, eps * P * Q / sigma * (1 - ui ** P) ** (Q - 1) * ui ** (P - 1), 0.0)
+    return e, f
+
+
+def isolated_pairs_reference(form):
+    """(F (N, 3), e (n,) per pair) of isolated_pairs(lib, form) from the closed form with the mixing weights (a_i + a_j) / 2, (b_i + b_j) / 2."""
+    x, a, b, pairs, _, axis = isolated_pairs_layout()
+    i, j = pairs[:, 0], pairs[:, 1]
+    r = np.linalg.norm(x[j] - x[i], axis=-1)
+    wa, wb = 0.5 * (a[i] + a[j]), 0.5 * (b[i] + b[j])
+    ea, fa = softcore_closed_form(ISO["eps_a"], ISO["sigma_a"], *form, r)
+    eb, fb = softcore_closed_form(ISO["eps_b"], ISO["sigma_b"], *second_form(form), r)
+    f = wa * fa + wb * fb                                   # bead j is pushed along +axis, bead i along -axis
+    F = np.zeros_like(x)
+    F[j, axis] = f
+    F[i, axis] = -f
+    return F, wa * ea + wb * eb
+
+
+# ------------------------------------------------------------------------------------------------ dense blobs: the tile classes
+
+BLOB_POWERS = (4, 2, 12, 1)
+BLOB_BOND = P(g.POT_SPRING, k_a=600.0, l_a=0.25)     # (the walks' bonds are 0.2 x compress long: compressed at every member of the family)
+
+
+def runtime_blob(lib, n_beads, compress, powers=BLOB_POWERS, n_replicas=2, seed=3):
+    """A uniform blob of chains (the genome workload's confined random walks, one draw per replica) scaled by `compress` about the
+    origin: local density, and with it the size of the list tiles, grows as compress^-3 at a fixed bead count.  Mixed pair term with
+    the runtime powers `powers` on the three fp16-exact types, spring chains, non-uniform mobility; open box."""
+    wl = g_wl()
+    lens = wl.chain_lengths(n_beads)
+    radius = 0.27 * (n_beads / (8 * 0.30)) ** (1 / 3)
+    x = np.stack([wl.confined_random_walks(lens, radius, 0.2, np.random.default_rng(seed + r)) for r in range(n_replicas)])
+    s = g.System(lib, n_beads, n_replicas)
+    a, b, _ = _types(n_beads)
+    s.set_bead_params(a=a, b=b, mobility=np.array(MOBILITY)[np.arange(n_beads) % 3])
+    s.set_pair_softcore(2.0, 0.30, 2.0, 0.24, *powers, mix=True)
+    st = 0
+    for n in lens:
+        s.add_bond_range(BLOB_BOND, st, st + int(n), 1)
+        st += int(n)
+    s.set_positions(f32(x * compress))
+    return s
+
+
+def runtime_box(lib, n_beads, compress, powers=BLOB_POWERS, n_replicas=2, seed=5):
+    """The periodic counterpart: the 1 kb force field (chromatin_1kb_images, unshifted) with positions and periods scaled by
+    `compress`, pair term with the runtime powers `powers` and the attractive B channel, unmixed.  At compress well below 1 the box
+    is a few list radii wide and a block's tile wraps around it."""
+    s0 = chromatin_1kb_images(lib, shifted=False, n_beads=n_beads, n_replicas=n_replicas, seed=seed, powers=powers)
+    box = tuple(float(on_grid(L * compress)) for L in s0.box)
+    x = on_grid(s0.positions() * compress)
+    s0.close()
+    s = g.System(lib, n_beads, n_replicas, box=box)
+    s.set_bead_params(mobility=np.ones(n_beads), bending_energy=np.full(n_beads, 1.0))
+    s.set_pair_softcore(*kb_pair(powers), mix=False)
+    s.add_bond_range(P(g.POT_SPRING, k_a=100.0, l_a=1.0), 0, n_beads, 1)
+    s.add_bending_range(0, n_beads, 0.0, per_bead=True)
+    loops, glues = kb_pairs(n_beads, seed)
+    s.set_dynamic_pairs(0, KB_LOOP, loops)
+    s.set_dynamic_pairs(1, KB_GLUE, glues)
+    s.set_positions(x)
+    s.box = box
+    return s
+
+
+EDGE_MARGIN = 2.0 ** -19
+
+
+def clear_of_edge(so, sigma, margin=EDGE_MARGIN, grid=None):
+    """Positions of the ORACLE handle `so` (left set on it) with no pair within margin x sigma of the separation sigma.
+
+    A soft core with Q = 1 has a force that jumps at r = sigma (by eps P / sigma), and fp32 r^2 / sigma^2 may fall on either side of 1
+    for a pair within a few 1e-7 sigma of it: there a device-oracle difference measures the conditioning of the state, not the
+    kernel.  One bead of every such pair is moved along the pair's axis by 8 margin sigma (at least one step of `grid`), the
+    result rounded to fp32 (to `grid`), until no pair is left in the band.  A function of the positions and the oracle's pair search
+    alone."""
+    x = so.positions()
+    box = getattr(so, "box", None)
+    step = max(8 * margin * sigma, grid or 0.0)
+    for _ in range(10):
+        found = 0
+        for r in range(so.R):
+            hi, lo = (so.search_pairs(sigma * f, replica=r).astype(np.int64) for f in (1 + margin, 1 - margin))
+            code = lambda p: np.minimum(p[:, 0], p[:, 1]) * so.N + np.maximum(p[:, 0], p[:, 1])
+            band = np.setdiff1d(code(hi), code(lo))
+            found += len(band)
+            for i, j in zip(band // so.N, band % so.N):
+                d = x[r, j] - x[r, i]
+                if box is not None:
+                    d -= np.array(box) * np.rint(d / np.array(box))
+                x[r, j] += step * d / np.linalg.norm(d)
+        if not found:
+            return x
+        x = f32(x) if grid is None else on_grid(x)
+        so.set_positions(x)
+    raise AssertionError("pairs left on the edge")
+
+
+# ------------------------------------------------------------------------------------------------ the spindle driver's coarse model
+
+SPINDLE_COARSE = dict(n_fine=1500, coarse=2, init_bend_energy=1.0, init_start_stddev=0.5)
+
+
+def spindle_coarse(lib, n_replicas=2, seed=2024):
+    """The coarse model host/gd_spindle.cpp builds (setup_chains, setup_system, add_spindle_forcefield, run_initialization) through
+    the Python API: the workloads' chain lengths at 1 500 fine beads coarse-grained by 2, default bead factors, uniform mobility,
+    the pair form (eps, sigma, 0, 0, 2, 3, 2, 3) unmixed, semispring chains with bending, the harmonic spindle source on the three
+    beads around every centromere, randomly directed straight rods around init_start_point -- one draw per replica."""
+    wl = g_wl()
+    cfg = dict(wl.DEFAULT_CONFIG)
+    cfg.update({k: v for k, v in SPINDLE_COARSE.items() if k.startswith("init_")})
+    chains, start = [], 0
+    for n in wl.chain_lengths(SPINDLE_COARSE["n_fine"]):
+        size = (int(n) + SPINDLE_COARSE["coarse"] - 1) // SPINDLE_COARSE["coarse"]
+        chains.append((start, start + size, start + (int(n) // 2) // SPINDLE_COARSE["coarse"]))
+        start += size
+    n = start
+    s = g.System(lib, n, n_replicas)
+    s.set_bead_params(mobility=np.full(n, cfg["init_mobility"]))
+    s.set_pair_softcore(cfg["init_bead_repulsion"], cfg["init_bead_diameter"], 0.0, 0.0, 2, 3, 2, 3, mix=False)
+    bond = P(g.POT_SEMISPRING, k_a=cfg["init_bond_spring"], l_a=cfg["init_bond_length"])
+    for c0, c1, _ in chains:
+        s.add_bond_range(bond, c0, c1, 1)
+        s.add_bending_range(c0, c1, cfg["init_bend_energy"])
+    s.add_point_source(g.POT_HARMONIC, cfg["init_spindle_spring"], 0.0, cfg["init_spindle_point"],
+                       targets=[c + d for (_, _, c) in chains for d in (-1, 0, 1)])
+    x = np.empty((n_replicas, n, 3))
+    for r in range(n_replicas):
+        rng = np.random.default_rng(seed + r)
+        for c0, c1, _ in chains:
+            centroid = np.array(cfg["init_start_point"]) + cfg["init_start_stddev"] * rng.normal(size=3)
+            d = rng.normal(size=3)
+            d *= cfg["init_bond_length"] / np.linalg.norm(d)
+            x[r, c0:c1] = centroid - d * (c1 - c0) / 2 + np.arange(c1 - c0)[:, None] * d
+    s.set_positions(f32(x))
+    s.cfg = cfg
+    return s
+
+
 # ------------------------------------------------------------------------------------------------ what the states reach
 
 # the terms each builder configures
 CONFIGURED = {"genome": ("pair", "bond", "wall"), "spindle": ("pair", "bond", "bend", "point"), "ab_box": ("pair", "bond"),
-              "chromatin_1kb": ("pair", "bond", "bend", "dynamic"), "composite": TERM_NAMES, "1kb_images": ("pair", "bond", "bend", "dynamic")}
+              "chromatin_1kb": ("pair", "bond", "bend", "dynamic"), "composite": TERM_NAMES, "1kb_images": ("pair", "bond", "bend", "dynamic"),
+              "spindle_driver": ("pair", "bond", "bend", "point"), "inner_sphere": ("pair", "wall"), "runtime_blob": ("pair", "bond"),
+              "runtime_box": ("pair", "bond", "bend", "dynamic")}
 COVERAGE = 1e-2      # every configured term: max|F_t| >= COVERAGE * max|F_all|, in every replica
 
 

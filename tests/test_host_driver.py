@@ -503,6 +503,8 @@ def test_spindle_driver_on_oracle(tmp_path, oracle):
     _check_spindle(tmp_path, oracle, oracle, drv, atol=0, env=_env(os.path.join(ROOT, "oracle")))
 
 
+# (the driver's pair form (2, 3, 2, 3) runs the runtime-power pair kernels; its forces are held to the oracle at FORCE_RTOL on both list
+# paths by tests/test_runtime_pair_gpu.py::test_spindle_driver_model_forces_match_oracle -- here: the program, end to end)
 @pytest.mark.gpu
 def test_spindle_driver_on_gpu(tmp_path, hip, oracle):
     _check_spindle(tmp_path, oracle, oracle, _make("gd_spindle", ".", "../csrc", "gdyn"), atol=2e-4)

@@ -66,6 +66,28 @@ def test_softcore_two_bead_analytic(oracle, P, Q):
         assert F[0, 0] == pytest.approx(-f_ref, rel=1e-12, abs=1e-14)
 
 
+def test_softcore_known_answers_of_every_valid_form(oracle):
+    """All 20 (P, Q) that valid_pq admits, on the isolated pairs of tests/stressed_states.py (separations 0, 2^-10, ..., 1, the next
+    fp32 above 1, 1.5 times sigma_a; six pairings of the bead types; a second form in channel B): the oracle against the closed form
+    with the mixing weights, 1e-12 -- the two references the device test of these forms (test_runtime_pair_gpu.py) is read against."""
+    import stressed_states as ss
+    assert len(ss.FORMS) == 20 and sorted(ss.second_form(f) for f in ss.FORMS) == sorted(ss.FORMS)
+    assert [f for f in ss.FORMS if (f, ss.second_form(f)) == ((2, 3), (8, 3))] == [(2, 3)]
+    x, a, b, pairs, u, axis = ss.isolated_pairs_layout()
+    assert len(pairs) == len(ss.U_GRID) * len(ss.PAIR_KINDS) and (u == 0).sum() == 6 and (u == 1).sum() == 6
+    for form in ss.FORMS:
+        with pytest.raises(g.GdynError):
+            g.System(oracle, 2, 1).set_pair_softcore(1.0, 1.0, p_a=form[0] + 1, q_a=form[1])      # (odd P: not a form)
+        s = ss.isolated_pairs(oracle, form)
+        F_ref, e_ref = ss.isolated_pairs_reference(form)
+        assert np.abs(F_ref).max() > 1.0 and (e_ref > 0).sum() > len(e_ref) // 2
+        F = s.forces()[0]
+        assert np.abs(F - F_ref).max() <= 1e-12 * np.abs(F_ref).max(), form
+        assert np.all(F[pairs[u == 0]] == 0)                                           # coincident beads: exactly no force
+        assert abs(s.energy()[0] - e_ref.sum()) <= 1e-12 * np.abs(e_ref).sum(), form
+        assert np.array_equal(s.forces(g.TERM_PAIR), s.forces())
+
+
 def test_ab_mixture_weights(oracle):
     # a = (a_i+a_j)/2, b = (b_i+b_j)/2 (simulation_driver_forcefield.cc:32-33,44)
     def setup(s):

@@ -8,7 +8,10 @@
    The wall's axial reaction: the production-size initial states leave it at zero (the record of why pressed_genome exists), the pressed
    genome presses on the wall from both sides, and the oracle's reaction equals its numpy restatement (tests/wall_restatement.py) --
    the reference tests/test_wall_context_gpu.py holds the device to.
-3. The softcore-bond rule (include/gdyn.h): mix / scale_by_bond_scale are rejected; the accepted form is k_a (1-(r/l_a)^p)^q."""
+3. The softcore-bond rule (include/gdyn.h): mix / scale_by_bond_scale are rejected; the accepted form is k_a (1-(r/l_a)^p)^q.
+4. The runtime-power states (any soft-core powers but (2, 3, 8, 3): another pair kernel on the device): the spindle driver's form is
+   the specialised form's function, the runtime composite, 1 kb, excluded-core, blob and box states reach every configured term with
+   the pair term a sizeable part, and their forces are -grad U."""
 import numpy as np
 import pytest
 
@@ -130,6 +133,168 @@ def test_1kb_images_straddle_the_box_faces(oracle, shape):
     for term in (g.TERM_PAIR,):
         assert np.abs(s.forces(term) - base.forces(term)).max() <= 1e-9 * np.abs(base.forces(term)).max()
     assert np.abs(s.forces(g.TERM_BOND)).max() > 100 * np.abs(base.forces(g.TERM_BOND)).max()
+
+
+# ------------------------------------------------------------------------------------------------ the runtime-power states
+
+def _pair_share(s):
+    """max|F_pair| / max|F_all| per replica"""
+    return ss.term_ratios(s)["pair"]
+
+
+def test_spindle_driver_form_is_the_specialised_form_on_the_oracle(oracle):
+    """host/gd_spindle.cpp's pair form (2, 3, 2, 3) with eps_b = sigma_b = 0 against (2, 3, 8, 3) with eps_b = 0 at the same state: one
+    function of the positions (the B channel carries no energy), 1e-12 on the oracle -- so a difference between the two on the device
+    (test_term_parity_gpu.py) is a difference between two kernels."""
+    s, t = ss.spindle_driver(oracle), ss.spindle_driver(oracle, specialised=True)
+    x = s.positions()
+    assert np.array_equal(x, t.positions()) and np.array_equal(x, ss.f32(x)) and x.shape[0] == 2 and np.abs(x[0] - x[1]).max() > 0.05
+    _assert_covered(s, ss.CONFIGURED["spindle_driver"])
+    assert np.all(_pair_share(s) >= 0.3)
+    F, Ft = s.forces(g.TERM_PAIR), t.forces(g.TERM_PAIR)
+    assert np.abs(F - Ft).max() <= 1e-12 * np.abs(Ft).max()
+    E, Et = s.energy(g.TERM_PAIR), t.energy(g.TERM_PAIR)
+    assert np.all(E > 0) and np.all(np.abs(E - Et) <= 1e-12 * np.abs(Et))
+    assert np.isfinite(s.forces()).all() and np.isfinite(s.energy()).all()
+
+
+@pytest.mark.parametrize("powers", ss.RUNTIME_POWERS)
+def test_runtime_power_composite_reaches_every_term(oracle, powers):
+    s, d = ss.composite(oracle, powers=powers), ss.composite(oracle)
+    _assert_covered(s, ss.TERM_NAMES)
+    assert np.all(_pair_share(s) >= 0.3)
+    x = s.positions()
+    assert np.array_equal(x, d.positions()) and np.array_equal(x, ss.f32(x)) and np.abs(x[0] - x[1]).max() > 0.1
+    assert [(s.context(r).bead_scale, s.context(r).bond_scale) for r in range(2)] == list(ss.COMPOSITE_SCALES)
+    # the powers are seen: pair and wall forces differ from the default model's by far more than any tolerance; the rest is untouched
+    for t in ("pair", "wall"):
+        Fs, Fd = s.forces(ss.TERM_BITS[t]), d.forces(ss.TERM_BITS[t])
+        assert np.abs(Fs - Fd).max() > 0.05 * np.abs(Fd).max(), t
+    for t in ("bond", "bend", "point", "dynamic"):
+        assert np.array_equal(s.forces(ss.TERM_BITS[t]), d.forces(ss.TERM_BITS[t])), t
+    # both channels and the mixing act: pairs of every kind (AA, BB, AB, uu, Au, Bu) inside the cutoff in each replica
+    a, b, _ = ss._types(s.N)
+    ss._composite_free_types(a, b)
+    for r in range(2):
+        pairs = s.search_pairs(ss.PAIR["sigma_b"] * ss.COMPOSITE_SCALES[r][0], replica=r).astype(np.int64)
+        kinds = {tuple(sorted([(a[i], b[i]), (a[j], b[j])])) for i, j in pairs}
+        assert len(kinds) == 6, kinds
+    # the wall's soft inside acts on both channels (beads with a > 0 and with b > 0 inside the surface, under force)
+    Fw = np.linalg.norm(s.forces(g.TERM_WALL), axis=-1)
+    C = np.sum((x / np.array(ss.SEMI)) ** 2, axis=-1) - 1
+    for r in range(2):
+        assert ((C[r] < 0) & (Fw[r] > 0)).sum() >= 5 and ((C[r] > 0) & (Fw[r] > 0)).sum() >= 5
+
+
+@pytest.mark.parametrize("term", ["pair", "wall"])
+@pytest.mark.parametrize("powers", ss.RUNTIME_POWERS)
+def test_runtime_power_composite_force_is_minus_gradient(oracle, powers, term):
+    s = ss.composite(oracle, powers=powers)
+    if term == "wall":      # on a sphere, as test_composite_force_is_minus_gradient_per_term
+        for r, (bs, os_) in enumerate(ss.COMPOSITE_SCALES):
+            s.set_context(r, 0, bs, os_, semiaxes=(ss.SEMI[1],) * 3)
+    beads = list(range(ss.N_CHAINS * ss.CHAIN_LEN, ss.N_COMPOSITE)) + [5, 77, 200]
+    if powers[3] == 1 and term == "pair":
+        # Q = 1: the force jumps at r = sigma_b, and a central difference across the jump is not the derivative -- the probe beads
+        # whose B-channel partner sits within 2 h of it are left out (none is expected: asserted to be few)
+        x, keep = s.positions(), []
+        a, b, _ = ss._types(s.N)
+        ss._composite_free_types(a, b)
+        for i in beads:
+            d = np.linalg.norm(x[:, :, :] - x[:, i:i + 1, :], axis=-1)
+            edge = np.stack([np.abs(d[r] - ss.PAIR["sigma_b"] * ss.COMPOSITE_SCALES[r][0]) < 1e-5 for r in range(2)])
+            if not edge.any():
+                keep.append(i)
+        assert len(keep) >= len(beads) - 2
+        beads = keep
+    _fd_check(s, ss.TERM_BITS[term], beads)
+
+
+@pytest.mark.parametrize("shape", [(1.0, 1.0, 1.0), (0.8, 1.0, 1.25)])
+def test_runtime_power_1kb_images(oracle, shape):
+    pw = ss.KB_RUNTIME_POWERS
+    base = ss.chromatin_1kb_images(oracle, shifted=False, shape=shape, powers=pw)
+    _assert_covered(base, ss.CONFIGURED["1kb_images"])
+    assert np.all(_pair_share(base) >= 0.1)
+    s, d = ss.chromatin_1kb_images(oracle, shape=shape, powers=pw), ss.chromatin_1kb_images(oracle, shape=shape)
+    x = s.positions()
+    assert np.array_equal(x, d.positions()) and np.array_equal(x, ss.f32(x)) and np.abs(x[0] - x[1]).max() > 0.05
+    Fs, Fd = s.forces(g.TERM_PAIR), d.forces(g.TERM_PAIR)
+    assert np.abs(Fs - Fd).max() > 0.05 * np.abs(Fd).max()
+    # both channels act, with opposite signs, and pair neighbours straddle the faces (as test_1kb_images_straddle_the_box_faces)
+    p = ss.kb_pair(pw)
+    for ch, sign in (((p[0], p[1], 0.0, 0.0), 1), ((0.0, 0.0, p[2], p[3]), -1)):
+        s.set_pair_softcore(*ch, *pw, mix=False)
+        e = s.energy(g.TERM_PAIR)
+        assert np.all(sign * e > 0) and np.all(np.abs(s.forces(g.TERM_PAIR)).max(axis=(1, 2)) >= 0.1 * np.abs(Fs).max(axis=(1, 2)))
+    s.set_pair_softcore(*p, mix=False)
+    L = np.array(s.box)
+    for r in range(2):
+        nb = s.search_pairs(1.5, replica=r).astype(np.int64)
+        assert (np.abs(x[r, nb[:, 0]] - x[r, nb[:, 1]]) > L / 2).any(axis=-1).sum() > 100
+    assert np.abs(Fs - base.forces(g.TERM_PAIR)).max() <= 1e-9 * np.abs(Fs).max()
+
+
+def test_inner_sphere_state_presses_on_both_sides_of_the_core(oracle):
+    s, d = ss.inner_sphere(oracle), ss.inner_sphere(oracle, powers=None)
+    _assert_covered(s, ss.CONFIGURED["inner_sphere"])
+    assert np.all(_pair_share(s) >= 0.3)
+    x = s.positions()
+    assert np.array_equal(x, ss.f32(x)) and x.shape[0] == 2 and np.abs(x[0] - x[1]).max() > 0.05
+    rad = np.linalg.norm(x, axis=-1)
+    Fw, Fd = s.forces(g.TERM_WALL), d.forces(g.TERM_WALL)
+    reach = ss.INNER["radius"] + 0.5 * max(ss.INNER["sigma"])
+    for r in range(2):
+        inside, gap = rad[r] < ss.INNER["radius"], (rad[r] > ss.INNER["radius"]) & (rad[r] < reach)
+        assert inside.sum() >= 50 and gap.sum() >= 50
+        # in the gap the force is the soft cores' (runtime powers: it differs from the default's), pointing outwards
+        acted = gap & (np.linalg.norm(Fw[r], axis=-1) > 0)
+        assert acted.sum() >= 30 and np.all(np.sum(Fw[r][acted] * x[r][acted], axis=-1) > 0)
+        assert np.abs(Fw[r][gap] - Fd[r][gap]).max() > 0.05 * np.abs(Fd[r][gap]).max()
+        assert np.array_equal(Fw[r][inside], Fd[r][inside])                          # the harmonic core has no powers
+        # ... and it is a sizeable part of the wall term (the outer wall is the other)
+        assert np.abs(Fw[r][gap]).max() >= 0.05 * np.abs(Fw[r]).max()
+    _fd_check(s, g.TERM_WALL, list(np.nonzero((rad[0] < reach) & (rad[1] < reach))[0][:12]))
+
+
+@pytest.mark.parametrize("family,n_beads,compress,edge", [("runtime_blob", 1500, 0.7, 0.24), ("runtime_blob", 6000, 0.4, 0.24),
+                                                          ("runtime_box", 3000, 0.6, 1.5), ("runtime_box", 6000, 0.4, 1.5)])
+def test_dense_runtime_power_families(oracle, family, n_beads, compress, edge):
+    """The blobs and boxes test_runtime_pair_gpu.py compresses into the tile classes: every configured term acts, density grows as
+    compress^-3, and clear_of_edge leaves no pair where the (12, 1) channel's force jumps, moving a handful of beads by a few 1e-6."""
+    make = getattr(ss, family)
+    s = make(oracle, n_beads, compress)
+    _assert_covered(s, ss.CONFIGURED[family])
+    assert np.all(_pair_share(s) >= 0.3)
+    x = s.positions()
+    assert np.array_equal(x, ss.f32(x)) and x.shape[0] == 2 and np.abs(x[0] - x[1]).max() > 0.05
+    loose = make(oracle, n_beads, 2 * compress)
+    assert len(s.search_pairs(edge)) > 4 * len(loose.search_pairs(edge))
+    grid = ss.GRID if family == "runtime_box" else None
+    if grid:
+        assert np.array_equal(x, ss.on_grid(x)) and min(s.box) < 8 * edge * 1.75      # a few list radii wide
+    y = ss.clear_of_edge(s, edge, grid=grid)
+    assert np.array_equal(y, s.positions()) and np.array_equal(y, ss.f32(y))
+    moved = np.abs(y - x).max(axis=-1) > 0
+    assert moved.sum() <= 40 and np.abs(y - x).max() <= max(16 * ss.EDGE_MARGIN * edge, 2 * (grid or 0))
+    for r in range(2):
+        n_in, n_out = (len(s.search_pairs(edge * f, replica=r)) for f in (1 - ss.EDGE_MARGIN, 1 + ss.EDGE_MARGIN))
+        assert n_in == n_out > 0
+
+
+def test_spindle_coarse_model_is_the_drivers(oracle):
+    """ss.spindle_coarse against what host/gd_spindle.cpp configures: the pair form's energy and forces are those of the (2, 3, 8, 3),
+    eps_b = 0 form; at the rods only the pair term and the spindle source act, 40 steps on bonds and bending do as well."""
+    s = ss.spindle_coarse(oracle)
+    x = s.positions()
+    assert 300 <= s.N <= 1000 and np.array_equal(x, ss.f32(x)) and np.abs(x[0] - x[1]).max() > 0.05
+    assert ss.idle_terms(s, ("pair", "point")) == [] and sorted(ss.idle_terms(s, ("bond", "bend"))) == ["bend", "bond"]
+    F, E = s.forces(g.TERM_PAIR), s.energy(g.TERM_PAIR)
+    s.set_pair_softcore(s.cfg["init_bead_repulsion"], s.cfg["init_bead_diameter"], 0.0, 0.0, 2, 3, 8, 3, mix=False)
+    assert np.abs(F - s.forces(g.TERM_PAIR)).max() <= 1e-12 * np.abs(F).max() and np.all(np.abs(E - s.energy(g.TERM_PAIR)) <= 1e-12 * E)
+    s.begin_phase()
+    s.run(40, s.cfg["init_timestep"], s.cfg["init_temperature"], seed=20220101)
+    assert ss.idle_terms(s, ("pair", "bond", "bend", "point")) == []
 
 
 # ------------------------------------------------------------------------------------------------ the wall's axial reaction

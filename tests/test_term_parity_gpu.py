@@ -12,7 +12,10 @@ channel, attractive B channel) and the dynamic term of the 1 kb and composite mo
 glue in slot 1) -- S_t is the sum of the magnitudes of its one-signed parts, each evaluated on the oracle alone: a sum of cancelling
 parts carries the rounding of the parts, not of their difference.
 
-Both kernel paths (generic global-gather lists, LDS-tiled lists) run every comparison, and the test asserts which one ran."""
+Both kernel paths (generic global-gather lists, LDS-tiled lists) run every comparison, and the test asserts which one ran.
+
+The workloads all set the soft-core powers (2, 3, 8, 3), which the kernels specialise; the states named *_runtime, composite_P_Q_P_Q,
+spindle_driver and inner_sphere carry other powers (pair term, ellipsoid wall, inner wall) and run the runtime-power forms."""
 import numpy as np
 import pytest
 
@@ -28,9 +31,9 @@ def _assert_path(s, path):
 
 
 # name -> (builder(lib), the terms it configures, {term: [modifiers that leave one one-signed part]} for the mixed-sign terms)
-def _pair_channel(a):
+def _pair_channel(a, powers=None):
     def mod(s):
-        p = ss.KB_PAIR
+        p = ss.kb_pair(powers)
         s.set_pair_softcore(*((p[0], p[1], 0.0, 0.0) if a else (0.0, 0.0, p[2], p[3])), *p[4:], mix=False)
     return mod
 
@@ -40,16 +43,33 @@ def _only_slot(keep):
 
 
 KB_PARTS = {"pair": [_pair_channel(True), _pair_channel(False)], "dynamic": [_only_slot(0), _only_slot(1)]}
+KB_RT = ss.KB_RUNTIME_POWERS
+KB_PARTS_RT = {"pair": [_pair_channel(True, KB_RT), _pair_channel(False, KB_RT)], "dynamic": KB_PARTS["dynamic"]}
+COMPOSITE_PARTS = {"dynamic": [_only_slot(0), _only_slot(1)]}
+
+
+def _powers_id(powers):
+    return "_".join(str(k) for k in powers)
+
+
 STATES = {
     "genome": (lambda lib: ss.perturbed(lib, "genome"), ss.CONFIGURED["genome"], {}),
     "genome_30k": (lambda lib: ss.perturbed(lib, "genome", seed=8, n_beads=30000), ss.CONFIGURED["genome"], {}),
     "spindle": (lambda lib: ss.perturbed(lib, "spindle"), ss.CONFIGURED["spindle"], {}),
     "ab_box": (lambda lib: ss.perturbed(lib, "ab_box"), ss.CONFIGURED["ab_box"], {}),
     "chromatin_1kb": (lambda lib: ss.perturbed(lib, "chromatin_1kb"), ss.CONFIGURED["chromatin_1kb"], KB_PARTS),
-    "composite": (ss.composite, ss.TERM_NAMES, {"dynamic": [_only_slot(0), _only_slot(1)]}),
+    "composite": (ss.composite, ss.TERM_NAMES, COMPOSITE_PARTS),
     "1kb_images": (lambda lib: ss.chromatin_1kb_images(lib), ss.CONFIGURED["1kb_images"], KB_PARTS),
     "1kb_images_aniso": (lambda lib: ss.chromatin_1kb_images(lib, shape=(0.8, 1.0, 1.25)), ss.CONFIGURED["1kb_images"], KB_PARTS),
+    # the runtime-power pair form (and runtime wall powers): tests/stressed_states.py, asserted in tests/test_stressed_states.py
+    "spindle_driver": (ss.spindle_driver, ss.CONFIGURED["spindle_driver"], {}),
+    "1kb_images_runtime": (lambda lib: ss.chromatin_1kb_images(lib, powers=KB_RT), ss.CONFIGURED["1kb_images"], KB_PARTS_RT),
+    "1kb_images_aniso_runtime": (lambda lib: ss.chromatin_1kb_images(lib, shape=(0.8, 1.0, 1.25), powers=KB_RT), ss.CONFIGURED["1kb_images"],
+                                 KB_PARTS_RT),
+    "inner_sphere": (ss.inner_sphere, ss.CONFIGURED["inner_sphere"], {}),
 }
+for _pw in ss.RUNTIME_POWERS:
+    STATES["composite_" + _powers_id(_pw)] = (lambda lib, pw=_pw: ss.composite(lib, powers=pw), ss.TERM_NAMES, COMPOSITE_PARTS)
 
 
 def _energy_scale(oracle, make, term, parts):
@@ -100,10 +120,15 @@ def test_every_term_on_its_own_scale(hip, oracle, state, path):
     _assert_path(sh, path)
 
 
-@pytest.mark.parametrize("path", list(PATHS))
-def test_every_term_mask_on_the_composite_model(hip, oracle, path):
+# (powers, path): the default model keeps the ids it had; the runtime-power models are named by their powers
+MASK_CASES = [(None, p) for p in PATHS] + [(pw, p) for pw in ss.RUNTIME_POWERS for p in PATHS]
+MASK_IDS = [p if pw is None else f"{_powers_id(pw)}-{p}" for pw, p in MASK_CASES]
+
+
+@pytest.mark.parametrize("powers,path", MASK_CASES, ids=MASK_IDS)
+def test_every_term_mask_on_the_composite_model(hip, oracle, powers, path):
     """All 63 masks: the per-bond-type term bits (static bonds vs dynamic pairs in one adjacency) and every section's skip logic."""
-    sh, so = ss.composite(hip), ss.composite(oracle)
+    sh, so = ss.composite(hip, powers=powers), ss.composite(oracle, powers=powers)
     sh.set_tuning(kernel_path=PATHS[path])
     for m in range(1, 64):
         _compare_forces(sh.forces(m), so.forces(m), m)
@@ -113,15 +138,18 @@ def test_every_term_mask_on_the_composite_model(hip, oracle, path):
 # the kernel path is a property of the pair list: for the other terms in isolation there is no pair term, so no list whose tiles the
 # bonded, bending, point and wall sections could share -- a path has no meaning for them, they run once with the library's choice
 # and the path is not asserted
-STEP_CASES = [("pair", "generic"), ("pair", "tiled")] + [(t, None) for t in ss.TERM_NAMES if t != "pair"]
+STEP_CASES = [("pair", "generic", None), ("pair", "tiled", None)] + [(t, None, None) for t in ss.TERM_NAMES if t != "pair"]
+# ... and the terms the runtime powers reach, with them: the pair term on both paths, the wall
+STEP_CASES += [c for pw in ss.RUNTIME_POWERS for c in (("pair", "generic", pw), ("pair", "tiled", pw), ("wall", None, pw))]
+STEP_IDS = [f"{t}-{p}" + ("" if pw is None else "-" + _powers_id(pw)) for t, p, pw in STEP_CASES]
 
 
-@pytest.mark.parametrize("term,path", STEP_CASES)
-def test_step_mode_per_term(hip, oracle, term, path):
+@pytest.mark.parametrize("term,path,powers", STEP_CASES, ids=STEP_IDS)
+def test_step_mode_per_term(hip, oracle, term, path, powers):
     """k_step in STEP mode (what trajectories run) against the oracle's F_t: one zero-noise, T = 0, compensated step of a term-isolated
     copy of the composite model with non-uniform mobility and no scale or wall update; (x1 - x0) / (mu dt) is the force the step used."""
     m = ss.TERM_BITS[term]
-    sh, so = ss.composite(hip, terms=m), ss.composite(oracle, terms=m)
+    sh, so = ss.composite(hip, terms=m, powers=powers), ss.composite(oracle, terms=m, powers=powers)
     if path:
         sh.set_tuning(kernel_path=PATHS[path])
     x0 = so.positions()
@@ -134,6 +162,32 @@ def test_step_mode_per_term(hip, oracle, term, path):
     _compare_forces((sh.positions() - x0) / (mu * dt), Fo, term)
     if path:
         _assert_path(sh, path)
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+def test_spindle_driver_form_against_the_specialised_kernels(hip, path):
+    """The spindle driver's pair form, (2, 3, 2, 3) with eps_b = sigma_b = 0, runs the runtime-power pair kernels; (2, 3, 8, 3) with
+    eps_b = 0 is the same function of the positions (1e-12 on the oracle: tests/test_stressed_states.py) and runs the specialised ones.
+    Two kernels, one function: forces (evaluated, and as one compensated zero-noise step used them) and energies agree."""
+    out = []
+    for specialised in (False, True):
+        s = ss.spindle_driver(hip, specialised=specialised)
+        s.set_tuning(kernel_path=PATHS[path])
+        F, E, x0 = s.forces(g.TERM_PAIR), s.energy(g.TERM_PAIR), s.positions()
+        assert np.isfinite(F).all() and np.isfinite(E).all() and np.isfinite(s.forces()).all()
+        _assert_path(s, path)
+        t = ss.spindle_driver(hip, specialised=specialised)
+        t.set_tuning(kernel_path=PATHS[path])
+        dt = 1e-5
+        t.run(1, dt, 0.0, noise=g.NOISE_ZERO, flags=g.RUN_COMPENSATED)
+        assert t.context().compensated == 1 and t.context().step == 1
+        _assert_path(t, path)
+        out.append((F, E, (t.positions() - x0) / dt, s.forces()))
+    (F, E, Fstep, Fall), (Fs, Es, Fstep_s, Fall_s) = out
+    _compare_forces(F, Fs, "pair")
+    _compare_forces(Fstep, Fstep_s, "step")
+    _compare_forces(Fstep, Fall_s, "step vs forces")
+    assert np.all(np.abs(E - Es) <= ENERGY_RTOL * np.abs(Es)), (E - Es) / Es
 
 
 @pytest.mark.parametrize("path", list(PATHS))
