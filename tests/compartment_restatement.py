@@ -34,6 +34,32 @@ def dense(bin1, bin2, count, chrom, weights=None):
     return out
 
 
+def dense_fast(bin1, bin2, count, chrom, weights=None):
+    """dense() with np.add.at on float32 in the place of the loop: the same adds in the same order, so the same bytes (the host
+    test holds the two together); for tables the loop would take seconds on."""
+    chrom = np.asarray(chrom)
+    b1, b2, c = np.asarray(bin1, np.int64), np.asarray(bin2, np.int64), np.asarray(count, np.float64)
+    inside = (b1 >= 0) & (b1 < len(chrom)) & (b2 >= 0) & (b2 < len(chrom))
+    i, j, c = np.minimum(b1, b2)[inside], np.maximum(b1, b2)[inside], c[inside]
+    first = np.zeros(len(chrom), np.int64)
+    for b, e in runs(chrom):
+        first[b:e] = b
+    cis = (chrom[i] == chrom[j]) & (first[i] == first[j])
+    i, j, c = i[cis], j[cis], c[cis]
+    with np.errstate(all="ignore"):
+        v = (c if weights is None else c / (np.asarray(weights, np.float64)[i] * np.asarray(weights, np.float64)[j])).astype(np.float32)
+        out = {}
+        for b, e in runs(chrom):
+            m = np.zeros((e - b, e - b), np.float32)
+            mine = first[i] == b
+            # one unbuffered pass over [li, lj], [lj, li], [li, lj], ...: the order of the loop
+            rows = np.stack([i[mine] - b, j[mine] - b], axis=1).ravel()
+            cols = np.stack([j[mine] - b, i[mine] - b], axis=1).ravel()
+            np.add.at(m, (rows, cols), np.repeat(v[mine], 2))
+            out[int(chrom[b])] = m
+    return out
+
+
 def profile(matrices, valid=None):
     """(contacts, counts, mean): fp64 sums of the float32 cells of the upper diagonals, zero and NaN cells skipped."""
     size = max(m.shape[0] for m in matrices.values())
@@ -79,6 +105,19 @@ def pca(matrix, mask=None, k=3):
         axes[j, mask] = sign * vh[j]
         pcs[mask, j] = sign * u[:, j] * np.sqrt(m - 1)
     return pcs, s[:k] ** 2, axes, s
+
+
+def split_rule(m):
+    """The shape of the device solver at m valid bins (csrc/gdyn_hic.hip, pca_run), only to assert on the CPU which branch a size
+    reaches: xblocks (stripes of 64 columns), splits = min(32, ceil(1024 / xblocks), ceil(m / 16)), rows_per_split, the rows
+    (i0, i1) of every split (i0 > i1: the split starts past the last row and adds nothing), the trips of the wave loop (16 rows a
+    trip) in the longest split, and the blocks of 128 and of 256 rows."""
+    xblocks = -(-m // 64)
+    splits = max(1, min(32, -(-1024 // xblocks), -(-m // 16)))
+    rows_per_split = -(-m // splits)
+    rows = [(s * rows_per_split, min((s + 1) * rows_per_split, m)) for s in range(splits)]
+    return dict(xblocks=xblocks, splits=splits, rows_per_split=rows_per_split, rows=rows, trips=-(-rows_per_split // 16),
+                rblocks=-(-m // 128), blocks256=-(-m // 256), ld=(m + 1) // 2 * 2)
 
 
 def pca_bounds(singular, k):

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import compartment_edge_cases as E
 import compartment_restatement as R
 from conftest import ROOT
 
@@ -102,6 +103,142 @@ def test_contact_pca_refuses_what_the_reference_refuses():
         hic.contact_pca(np.eye(3), [True, False, False], 1)
     with pytest.raises(ValueError):
         hic.contact_pca(np.eye(3), None, 4)
+
+
+# ---- the inputs of tests/test_compartment_edges_gpu.py are what they claim to be, and hic.py's numpy functions at those sizes
+
+def test_dense_fast_equals_the_loop_byte_for_byte():
+    """On the toy fixture (either order of the ids, ids outside the table) and on table A, RAW and weighted."""
+    b1 = np.concatenate([np.where(np.arange(len(BIN1)) % 3 == 0, BIN2, BIN1), [-1, 5, len(CHROM), 2 ** 40]])
+    b2 = np.concatenate([np.where(np.arange(len(BIN1)) % 3 == 0, BIN1, BIN2), [3, len(CHROM), 7, 0]])
+    c = np.concatenate([COUNT, [9, 9, 9, 9]])
+    t = E.table_a()
+    for args in ((b1, b2, c, CHROM), (t.bin1, t.bin2, t.count, t.chrom)):
+        for w in (None, WEIGHT if args[3] is CHROM else t.weight):
+            slow, fast = R.dense(*args, w), R.dense_fast(*args, w)
+            assert slow.keys() == fast.keys()
+            for code in slow:
+                assert fast[code].dtype == np.float32 and np.array_equal(np.nan_to_num(slow[code], nan=-1.0).tobytes(), np.nan_to_num(fast[code], nan=-1.0).tobytes()), code
+                assert np.array_equal(np.isnan(slow[code]), np.isnan(fast[code]))
+    # a diagonal pixel and a repeated pixel: two adds each, in the loop's order
+    chrom = np.zeros(3, np.int32)
+    args = ([0, 0, 1, 0], [0, 2, 2, 2], [5, 7, 3, 7], chrom, np.array([0.7, 0.0, 1.3]))
+    assert np.array_equal(R.dense(*args)[0], R.dense_fast(*args)[0])
+
+
+def test_table_a_reaches_the_second_block_and_the_second_trip():
+    t = E.table_a()
+    assert np.bincount(t.chrom).tolist() == [300, 1, 64, 65, 257, 2, 330] and len(t.chrom) == 1019 and 30000 < len(t.count) < 45000
+    pairs = np.stack([t.bin1, t.bin2], axis=1)
+    assert (t.bin1 <= t.bin2).all() and len(np.unique(pairs, axis=0)) == len(pairs) and np.array_equal(pairs, pairs[np.lexsort((t.bin2, t.bin1))])
+    assert (t.chrom[t.bin1] == t.chrom[t.bin2]).all() and t.count.dtype == np.int32 and t.count.min() >= 1 and t.count.max() <= 900
+    assert all(c % 4 for c in E.CUTS_A[1:]) and E.CUTS_A[-1] < len(t.count)
+    # the excluded chromosome is the largest: max_size = 330 exceeds every counted n, so the profile ends in distances no cell has
+    assert t.excluded.sum() == 330 and t.chrom[t.excluded.astype(bool)].tolist() == [6] * 330 and max(E.SIZES[c] for c in E.COUNTED) == 300
+    assert 257 % 64 == 1 and -(-330 // 256) == 2                   # chromosome 4: a last row block of one row; two blocks of distances
+    touching = lambda b: [(int(i), int(j)) for i, j in pairs if b in (i, j)]
+    assert touching(E.ONLY_FAR) == [(40, 299)] and touching(E.EMPTY) == [] and touching(E.NAN_WEIGHT) == [(42, 280)] and len(touching(E.PARTNER)) > 2
+    assert np.isnan(t.weight[E.NAN_WEIGHT]) and np.isnan(t.weight).sum() == 1 and np.nanmin(t.weight) >= 0.4 and np.nanmax(t.weight) <= 1.6
+    raw, weighted = E.expected_a("RAW"), E.expected_a("weight")
+    for x in (raw, weighted):
+        assert len(x.mean) == 330 and (x.counts[256:300] > 0).any() and (x.counts[300:] == 0).all() and np.isnan(x.mean[300:]).all() and not np.isnan(x.mean[:300]).any()
+    delta = raw.counts - weighted.counts                           # the one NaN cell of the weighted target, (42, 280), is not counted
+    assert delta[238] == 1 and delta.sum() == 1
+    assert max(m.max() for m in raw.matrices.values()) < 2 ** 24 and not any(np.isnan(m).any() for m in raw.matrices.values())
+    # the planted rows: what only columns from 256 on can tell
+    row = raw.matrices[0][E.ONLY_FAR]
+    assert np.flatnonzero(row).tolist() == [299] and not raw.matrices[0][E.EMPTY].any()
+    row = weighted.matrices[0][E.PARTNER]
+    assert np.flatnonzero(np.isnan(row)).tolist() == [280] and np.isfinite(np.delete(row, 280)).all() and np.delete(row, 280)[:256].any()
+    assert np.flatnonzero(weighted.matrices[0][E.NAN_WEIGHT]).tolist() == [42] and np.isnan(weighted.matrices[0][280, 42])
+    assert np.flatnonzero(~raw.valid).tolist() == [E.EMPTY] and np.flatnonzero(~weighted.valid).tolist() == [E.EMPTY, E.PARTNER, E.NAN_WEIGHT]
+    # the excluded chromosome's enrichment is NaN exactly beyond the longest counted distance
+    assert np.array_equal(np.isnan(raw.enrichment[6]), raw.distance[6] >= 300)
+    for code in (0, 4):
+        assert np.array_equal(raw.enrichment[code], R.enrichment(raw.matrices[code], raw.mean), equal_nan=True)      # the vectorised form of expected_a
+
+
+@pytest.mark.parametrize("norm", ["RAW", "weight"])
+def test_numpy_path_on_table_a(norm):
+    """hic.py's functions on seven chromosomes by the rules of the device tests: matrices byte for byte, RAW profile and
+    enrichment exactly, weighted at rtol counts 2^-52 (+ 2^-52 for the division), the valid bins equal."""
+    t, x = E.table_a(), E.expected_a(norm)
+    b1, b2 = E.shuffled_ids(t.bin1, t.bin2)
+    got = hic.dense_matrices(b1, b2, t.count, t.chrom, None if norm == "RAW" else t.weight)
+    for code in range(len(E.SIZES)):
+        assert got[code].dtype == np.float32 and np.array_equal(got[code], x.matrices[code], equal_nan=True), code
+    contacts, counts, mean = hic.mean_contact_profile(got, E.COUNTED)
+    assert np.array_equal(counts, x.counts) and np.array_equal(np.isnan(mean), np.isnan(x.mean))
+    live = counts > 0
+    bound = counts[live] * (0.0 if norm == "RAW" else 2.0 ** -52)
+    assert (np.abs(contacts[live] - x.contacts[live]) <= bound * x.contacts[live]).all() and (np.abs(mean[live] - x.mean[live]) <= bound * x.mean[live]).all()
+    assert not contacts[300:].any()
+    for code in (0, 4, 6):
+        e, want = hic.enrichment(got[code], x.mean), x.enrichment[code]
+        assert np.array_equal(np.isnan(e), np.isnan(want))
+        ok = ~np.isnan(want)
+        assert (np.abs(e[ok] - want[ok]) <= (0.0 if norm == "RAW" else 2.0 ** -52) * np.abs(want[ok])).all()
+    assert np.array_equal(np.concatenate([hic.dense_valid(got[code]) for code in range(len(E.SIZES))]), x.valid)
+
+
+def test_colliding_tables_are_what_they_claim():
+    one, two = E.split_counts()
+    assert len(one[2]) == 200 and len(two[2]) == 400 and min(two[2]) >= 1 and one[0].max() < 8 and len(set(zip(one[0].tolist(), one[1].tolist()))) < 200
+    a, b = R.dense(*one, E.CHROM_B)[0], R.dense(*two, E.CHROM_B)[0]
+    assert np.array_equal(a, b) and a.max() < 2 ** 24 and a.sum(dtype=np.float64) == 2.0 * one[2].sum()
+    assert all(abs(w * 2 ** 20 - round(w * 2 ** 20)) > 1e-3 for w in E.WEIGHT_B[:8])             # no weight is dyadic
+    b1, b2, c = E.PIXELS_ZERO
+    m = R.dense(b1, b2, c, E.CHROM_ZERO, E.WEIGHT_ZERO)
+    contacts, counts, mean = R.profile(m)
+    assert E.WEIGHT_ZERO[E.ZERO_BIN] == 0 and sum(E.ZERO_BIN in p for p in zip(b1.tolist(), b2.tolist())) == 2
+    assert np.isinf(m[0]).sum() == 4 and counts.tolist() == [2, 4, 3, 1, 0] and np.isinf(mean).tolist() == [False, True, True, False, False]
+    for fn in (hic.mean_contact_profile,):
+        got = fn(m)
+        assert np.array_equal(got[1], counts) and np.array_equal(got[0], contacts) and np.array_equal(got[2], mean, equal_nan=True)
+    e = hic.enrichment(m[0], mean)
+    assert np.array_equal(e, R.enrichment(m[0], mean), equal_nan=True) and np.isnan(e[1, 2]) and e[0, 1] == 0 and e[3, 4] == 0
+    valid = R.valid(m[0])
+    assert valid.tolist() == [True, False, False, True, False] and np.array_equal(hic.dense_valid(m[0]), valid)
+
+
+def test_layered_matrices_are_well_conditioned_at_every_size():
+    """The device is not asked for a badly conditioned case: the block's convergence ratio lam[k + 8] / lam[k - 1] is at most
+    1e-3 and the smallest gap of the wanted components at least 1e-3 lam_0, for every size and k the device tests use."""
+    cases = [(m, True) for m in E.PCA_SIZES] + [(m, False) for m in E.PCA_UNSYMMETRIC]
+    for m, sym in cases:
+        matrix, mask, (pcs, var, axes, singular) = E.pca_reference(m, sym)
+        assert mask.sum() == m and np.array_equal(mask, np.any(matrix != 0, axis=1)) and len(singular) == m
+        assert np.array_equal(matrix, matrix.T) == sym
+        for k in (1, 3):
+            ratio, gap = E.conditioning(singular, m, k)
+            assert ratio <= 1e-3 and gap >= 1e-3, (m, sym, k, ratio, gap)
+    assert set(E.PCA_TWICE) <= set(E.PCA_SIZES) and set(E.PCA_UNSYMMETRIC) <= set(E.PCA_SIZES)
+
+
+def test_sizes_reach_the_branches_of_the_solver():
+    s = {m: R.split_rule(m) for m in E.PCA_SIZES}
+    assert s[513]["splits"] == 32 and s[513]["rows_per_split"] == 17 and s[513]["rows"][31] == (527, 513) and s[513]["rows"][30] == (510, 513) and s[513]["trips"] == 2
+    assert s[600]["splits"] == 32 and s[600]["rows_per_split"] == 19 and s[600]["rows_per_split"] % 4 != 0 and all(a < b for a, b in s[600]["rows"])
+    assert s[1030]["splits"] == 32 and s[1030]["rows_per_split"] == 33 and s[1030]["trips"] == 3 and 33 - 32 == 1
+    assert s[512]["splits"] == 32 and s[512]["rows_per_split"] == 16 and s[512]["trips"] == 1
+    assert all(s[m]["trips"] == 1 for m in E.PCA_SIZES if m <= 512) and all(s[m]["splits"] < 32 for m in E.PCA_SIZES if m < 512)
+    assert s[16]["splits"] == 1 and s[17]["splits"] == 2 and s[9]["splits"] == 1
+    assert [s[m]["xblocks"] for m in (63, 64, 65)] == [1, 1, 2] and [s[m]["rblocks"] for m in (127, 128, 129)] == [1, 1, 2]
+    assert [s[m]["blocks256"] for m in (255, 256, 257)] == [1, 1, 2]
+    assert [s[m]["ld"] - m for m in (63, 64, 65, 127, 128, 129, 255, 256, 257, 512, 513)] == [1, 0, 1, 1, 0, 1, 1, 0, 1, 0, 1]      # the pad column
+    assert min(9, 1 + 8) == 9 and min(9, 3 + 8) == 9               # m = 9: the block is the whole space for k = 1 and k = 3
+    # the rule covers the rows once, whatever the size
+    for m in list(E.PCA_SIZES) + [2, 3, 293, 2490]:
+        r = R.split_rule(m)
+        covered = [i for a, b in r["rows"] for i in range(a, b)]
+        assert covered == list(range(m)) and len(r["rows"]) == r["splits"] <= 32, m
+
+
+@pytest.mark.parametrize("m,sym", [(65, True), (513, True), (65, False), (513, False)])
+def test_contact_pca_on_layered_matrices(m, sym):
+    matrix, mask, (pcs, var, axes, singular) = E.pca_reference(m, sym)
+    got = hic.contact_pca(matrix, None, 3)
+    R.check_pca(got, pcs, var, axes, singular, mask, f"hic.py, m = {m}" + ("" if sym else ", unsymmetric"))
 
 
 def test_header_defines_version_2_and_the_new_symbols():
