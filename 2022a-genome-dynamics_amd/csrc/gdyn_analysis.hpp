@@ -1,6 +1,7 @@
 // gdyn_analysis.hpp -- the host-side plumbing that the device analyses (gdyn_flow, gdyn_rdf, gdyn_lamina, gdyn_cmap,
-// gdyn_hic) share: error reporting, owned device buffers, the device and stream of a handle with its create prologue and
-// destroy epilogue, and the grid size of a one-lane-per-element launch.  Nothing here is extern "C" or device code.
+// gdyn_hic) share: error reporting, owned device and pinned host buffers, the device and stream of a handle with its create
+// prologue and destroy epilogue, and the grid size of a one-lane-per-element launch.  The stepper's host files (gdyn_system.hpp)
+// take the error reporting and the buffers from here too.  Nothing here is extern "C" or device code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +18,7 @@ namespace gd {
 
 static int fail(int code, const char *fmt, ...)
 {
-    char buf[512];
+    char buf[1024];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
@@ -28,6 +29,11 @@ static int fail(int code, const char *fmt, ...)
     do {                                                                                                \
         hipError_t e_ = (call);                                                                         \
         if (e_ != hipSuccess) return gd::fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define GDCHK(call)              \
+    do {                         \
+        int rc_ = (call);        \
+        if (rc_ != GD_OK) return rc_; \
     } while (0)
 
 // blocks of `block` lanes for n elements; no caller comes near the cap, which keeps the count inside a grid dimension
@@ -66,6 +72,27 @@ struct dbuf {
         if (e == hipSuccess) n = count;
         return e;
     }
+    // exactly `count` elements: as it is when it has them, else freed and allocated anew (the content is lost).  zero: the new block
+    // is cleared, and the device idle, when this returns
+    hipError_t resize(size_t count, bool zero = true)
+    {
+        if (count == n) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+        if (count == 0) return hipSuccess;
+        hipError_t e = hipMalloc(&p, count * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            return e;
+        }
+        n = count;
+        if (zero) {
+            e = hipMemset(p, 0, count * sizeof(T));
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+        }
+        return e;
+    }
     hipError_t upload(const T *src, size_t count)
     {
         hipError_t e = ensure(count);
@@ -73,6 +100,43 @@ struct dbuf {
         return e;
     }
     hipError_t zero(hipStream_t st) { return n ? hipMemsetAsync(p, 0, n * sizeof(T), st) : hipSuccess; }
+};
+
+// pinned host memory, freed with its owner.  Grow-only like dbuf::ensure; a block that grows geometrically is asked for
+// gd::grown_capacity(n, need) elements (gdyn_replica_pairs.hpp)
+template <typename T>
+struct pinned {
+    T *p = nullptr;
+    size_t n = 0;
+
+    pinned() = default;
+    pinned(pinned &&o) noexcept : p(o.p), n(o.n)
+    {
+        o.p = nullptr;
+        o.n = 0;
+    }
+    pinned &operator=(pinned &&o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~pinned()
+    {
+        if (p) (void)hipHostFree(p);
+    }
+    // room for `count` elements; grows by reallocation (the content is lost), never shrinks; unchanged after a failure
+    hipError_t ensure(size_t count)
+    {
+        if (count <= n) return hipSuccess;
+        T *q = nullptr;
+        hipError_t e = hipHostMalloc((void **)&q, count * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        if (p) (void)hipHostFree(p);
+        p = q;
+        n = count;
+        return hipSuccess;
+    }
 };
 
 // what every gd_<x> handle starts with.  The stream goes after the derived handle's members, so after its buffers.

@@ -7,9 +7,10 @@
 // the fixed build cadence never changes results (only the summation order of pair terms).
 // What the host knows about the list in use is one gd::ResidentList (gdyn_list.hpp): this file calls its transitions -- a build, the
 // caller's positions, a new topology, a rollback, a dropped list -- and assigns none of its members ("Resident list").
+// The handle itself (gd_system) and the features that live in files of their own -- the kernels behind k_step, the contact maps and
+// pair search, the glue kinetics -- are in gdyn_system.hpp.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,51 +18,24 @@
 #include <string>
 #include <vector>
 
-#include "../../include/gdyn.h"
-#include "../../include/gdyn_replica.h"
-#include "../../include/gdyn_ensemble.h"
-#include "../../include/gdyn_groups.h"
 #include <hip/hip_fp16.h>
 
-#include "gdyn_types.h"
+#include "gdyn_system.hpp"
 #include "gdyn_once.hpp"
-#include "gdyn_policy.hpp"
-#include "gdyn_list.hpp"
-#include "gdyn_live.hpp"
-#include "gdyn_replica_pairs.hpp"
-#include "gdyn_ensemble.hpp"
-#include "gdyn_glue.hpp"
-#include "gdyn_glue_types.h"
-#include "../../include/gdyn_glue.h"
 #ifdef GD_DEV
 #include "gdyn_dev.h"
 #endif
 
 // ------------------------------------------------------------------ errors
+// (gd::fail, HIPCHK and GDCHK of gdyn_analysis.hpp write the message here, as every other file of the library does)
 
 static thread_local char g_err[1024];
-static int fail(int code, const char *fmt, ...)
+extern "C" const char *gd_last_error(void) { return g_err; }
+int gd_report_error(int code, const char *msg)
 {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
+    snprintf(g_err, sizeof g_err, "%s", msg);
     return code;
 }
-#define HIPCHK(call)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) return fail(GD_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define GDCHK(call)              \
-    do {                         \
-        int rc_ = (call);        \
-        if (rc_ != GD_OK) return rc_; \
-    } while (0)
-
-extern "C" const char *gd_last_error(void) { return g_err; }
-// the flow analyses (gdyn_flow.hip, include/gdyn_flow.h) report through the same message
-int gd_report_error(int code, const char *msg) { return fail(code, "%s", msg); }
 
 // Experiment hooks (environment variables, debug prints, the kernel micro-benchmark) exist in developer builds only
 // (make dev -> libgdyn_dev.so, -DGD_DEV); the product library reads no environment variable.
@@ -71,144 +45,6 @@ static const char *dev_env(const char *name) { return getenv(name); }
 static const char *dev_env(const char *) { return nullptr; }
 #endif
 extern "C" const char *gd_backend_name(void) { return "hip"; }
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t resize(size_t count, bool zero = true)
-    {
-        if (count == n && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        n = count;
-        if (zero) { e = hipMemset(p, 0, count * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
-        return e;
-    }
-};
-
-// ------------------------------------------------------------------ system
-
-struct Bond { uint32_t i, j; int type; };
-struct BendRange { uint32_t start, end; double energy; int per_bead; };
-struct PointSource { int kind; double k, b, p[3]; std::vector<uint8_t> mask; };
-struct DynSet { bool used = false; gd_bond_params p; std::vector<uint32_t> pairs; };
-
-struct gd_system {
-    uint32_t N = 0, R = 0, Np = 0, nblk = 0;
-    int device = 0, box_kind = 0;
-    double box[3] = {0, 0, 0};
-    hipStream_t stream = nullptr;
-
-    // host model
-    gd::EnsembleAB ens;            // the (a, b) factors: the shared table and what single replicas carry instead (gdyn_ensemble.hpp)
-    std::vector<double> mob, bend;
-    bool has_pair = false; gd_pair_softcore pair{};
-    std::vector<gd_bond_params> btypes; std::vector<int> bterm;
-    std::vector<Bond> bonds;
-    DynSet dyn[4];
-    std::vector<BendRange> bends;
-    std::vector<PointSource> psrc;
-    bool has_wall = false; gd_wall wall{};
-    bool has_scaling = false; double bs_init = 1, bs_tau = 1, bo_init = 1, bo_tau = 1;
-    std::vector<DevCtx> hctx;      // host mirror of the device context
-
-    bool topo_dirty = true, ctx_dirty = true;
-    bool has_bend = false, has_bonds = false;
-    uint32_t WB = 0, ncell_cap = 0;
-    int pcur = 0, ccur = 0;
-    uint32_t kernel_path = 0;      // 0 auto, 1 generic, 2 tiled
-    bool packed_ab = false;
-    bool has_inner = false; gd_inner_sphere inner{};
-    bool has_softcore_bonds = false;
-    bool bonds_premixed = false;   // every bond parameter record is unmixed (AB mixing resolved per bond by finalize_topology)
-    bool bonds_all_scaled = false; // every bond parameter record has scale_by_bond_scale set
-    uint32_t sw_n = 0; double sw_eps = 0, sw_decay = 1, sw_cut = 0;     // droplet attraction (gd_set_pair_softwell)
-    DevBuf<unsigned> sw_targets; DevBuf<double> sw_esum;
-    // per-replica dynamic pairs (gdyn_replica.h): what the caller set, the block of the last upload (layout, pinned staging, device
-    // copy; both grown geometrically, never shrunk), the slots' parameters, the energy sums
-    gd::ReplicaPairs rp; gd::ReplicaLayout rp_layout; gd_bond_params rp_params[gd::RP_SLOTS] = {};
-    uint32_t *rp_stage = nullptr; size_t rp_stage_cap = 0; hipEvent_t rp_copied = nullptr;      // (rp_copied: the last upload has left the staging block)
-    DevBuf<uint32_t> rp_dev; DevBuf<double> rp_esum;
-    // device glue kinetics (gdyn_glue.h): the sets as sorted pair words (the host copy is what fetch returns and what is installed in
-    // the managed slot; the device copy gl_keys[gl_cur], gl_kstride words a replica, feeds the next update and is laid out again from
-    // the host copy after gd_glue_set), the buffers of an update (grown, never shrunk), two pinned blocks (small: seeds, counters,
-    // segments; large: the sets on their way up or down)
-    bool gl_defined = false, gl_dev_dirty = true; uint32_t gl_slot = 0; gd_glue_params gl_par{};
-    std::vector<std::vector<uint64_t>> gl_sets;
-    DevBuf<unsigned long long> gl_keys[2], gl_merged, gl_fkey[2], gl_fsel[2], gl_seeds, gl_cand_count; DevBuf<uint2> gl_cand;
-    DevBuf<unsigned> gl_alive, gl_nkeys, gl_cnt, gl_seg; DevBuf<char> gl_tmp;
-    size_t gl_kstride[2] = {0, 0}, gl_fstride = 0; int gl_cur = 0;
-    unsigned long long *gl_small = nullptr, *gl_pin = nullptr; size_t gl_pin_cap = 0;
-    float *h_stage = nullptr;      // pinned host staging for snapshot downloads (R*N*3 floats)
-    char *h_chunk = nullptr;       // pinned host block for the per-chunk readback (flags, contexts, list counts): copies into pageable
-                                   // memory are staged by the runtime and cost ~20 us each
-    uint32_t cpb = 1;
-    gd::ListPolicy pol;            // list width, rebuild interval, tile class, list path of the builds to come (gdyn_policy.hpp)
-    gd::ResidentList list;         // the list in use and what its build left for the next one (gdyn_list.hpp)
-    uint64_t rebuilds = 0, rollbacks = 0;
-    uint32_t n_bond_types = 0;
-    std::vector<unsigned long long> lcount;
-    gd_timing timing{};
-
-    // device: static (bead order)
-    DevBuf<float2> ab_o; uint32_t ab_stride = 0;      // [N], stride 0: one table for all replicas; [R][N], stride N: one each (gdyn_ensemble.h)
-    DevBuf<float> mob_o; DevBuf<float4> bendE_o; DevBuf<unsigned char> psmask_o, bdeg_o;
-    DevBuf<unsigned> badj_o; DevBuf<int4> chain_o; DevBuf<BondType> btab;
-    // device: per slot
-    DevBuf<float4> pos[2], xb, fout, snap;
-    DevBuf<unsigned> orig[2], slot_of, rank, members, cell_cnt, cell_start, nbr, meta, badj, flags;
-    DevBuf<float> bbox_enc, bbox_w;      // box of the last build's positions (two halves: read / written), k_scatter's per-wave partials
-    DevBuf<unsigned short> nbr16; DevBuf<TileDesc> tiles;
-    DevBuf<float4> rec_x0; DevBuf<uint2> rec_mo; DevBuf<unsigned char> len_prev;
-    // Ragged rows of the tiled lists (BuildParams): per-wave row table, what every bead needed at the last build, the pool's cursor.
-    // nbr16 IS the pool: pool KiB = nbr16.n / 512 entries.
-    DevBuf<uint2> wtab, rqueue; DevBuf<unsigned short> need_prev; DevBuf<unsigned> pool;
-    DevBuf<float> bbox;
-    DevBuf<float2> ab; DevBuf<float> mobs; DevBuf<float4> bendE; DevBuf<int4> chain;
-    float mob_uniform = -1.f;
-    DevBuf<GridP> grid; DevBuf<DevCtx> ctx[2]; DevBuf<float4> react_part[2]; DevBuf<double> epart;   // react_part ping-pongs with ctx
-    DevBuf<unsigned long long> lcount_d; DevBuf<float> noise;
-    DevBuf<unsigned long long> seeds_d;     // gd_run_desc.replica_seeds of the run in progress
-    DevBuf<unsigned> dmax;          // [R] largest squared displacement since the list build (k_step keeps it; zeroed by the build)
-    double last_dt = 0, last_kT = -1;
-    int last_flags = 0;             // flags of the last gd_run (the look-ahead of a list built between runs, gd_search_pairs)
-    double pend_dt = 0; int pend_flags = 0;      // timestep and flags of the run that left its last callback pending (GD_RUN_DEFER_CALLBACK)
-    double near_frac = 0.65;        // near-class radius = cutoff + near_frac x (list radius - cutoff)
-    // gd_search_pairs: device output, counters, and the cached result of the last call
-    DevBuf<uint2> sp_out; DevBuf<unsigned long long> sp_count; std::vector<uint2> sp_host;
-    bool sp_valid = false; uint32_t sp_r = 0; double sp_dcut = 0; uint64_t sp_serial = 0;
-    // gd_contacts_*: per-replica count tables (ContactTab), the pair buffer of an update, dump buffers
-    DevBuf<unsigned long long> ct_words; DevBuf<unsigned> ct_distinct; size_t ct_cap = 0;
-    DevBuf<uint2> ct_pairs; DevBuf<unsigned long long> ct_count; std::vector<unsigned> ct_distinct_h;
-    DevBuf<unsigned long long> ct_ck[2]; DevBuf<unsigned> ct_cv[2], ct_n; DevBuf<char> ct_tmp;
-    uint64_t state_serial = 1;     // bumped by everything that changes positions or the model (invalidates the cache)
-    int ocur = 0;   // which orig[] buffer is current
-    // Compensated positions (small-dt / T = 0 runs, k_step's p.comp): fp32 residuals by bead index, so that the position of a bead is
-    // pos + lo.  gd_set_positions fills them from the fp64 input, a compensated run keeps them, any other run invalidates them.
-    DevBuf<float4> lo, snap_lo;
-    bool lo_valid = false;         // lo describes the current positions (else: taken as zero)
-    bool comp_last = false;        // the last gd_run stepped with the compensated update (diagnostics)
-    double mob_max = 1.0;
-    std::vector<hipEvent_t> events;
-    // Replica groups of the step launches (gdyn_groups.h, gd::step_group_split): the second stream and the two events that fork it off
-    // the handle's stream in front of a span of steps and join it behind -- created on first use; between two calls nothing is in flight
-    // on it that the handle's stream does not wait for.
-    hipStream_t stream2 = nullptr; hipEvent_t grp_fork = nullptr, grp_join = nullptr;
-    uint32_t group_mode = gd::STEP_GROUPS_RULE, groups_last = 1;      // gd_set_step_groups; groups of the step launches of the last gd_run
-    ~gd_system()
-    {
-        for (auto e : events) (void)hipEventDestroy(e);
-        if (grp_fork) (void)hipEventDestroy(grp_fork);
-        if (grp_join) (void)hipEventDestroy(grp_join);
-        if (stream2) (void)hipStreamDestroy(stream2);
-        if (rp_copied) (void)hipEventDestroy(rp_copied);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
 
 static int valid_pq(int p, int q) { return (p == 2 || p == 4 || p == 6 || p == 8 || p == 12) && q >= 1 && q <= 4; }
 
@@ -289,11 +125,6 @@ extern "C" int gd_destroy(gd_system *s)
     if (!s) return GD_OK;
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->h_chunk) (void)hipHostFree(s->h_chunk);
-    if (s->rp_stage) (void)hipHostFree(s->rp_stage);
-    if (s->gl_small) (void)hipHostFree(s->gl_small);
-    if (s->gl_pin) (void)hipHostFree(s->gl_pin);
     delete s;
     return GD_OK;
 }
@@ -346,11 +177,11 @@ static int fetch_xyz(gd_system *s, const float **out, int quantize)
 {
     HIPCHK(hipSetDevice(s->device));
     const size_t n3 = (size_t)s->R * s->N * 3;
-    if (!s->h_stage) HIPCHK(hipHostMalloc((void **)&s->h_stage, n3 * sizeof(float), hipHostMallocDefault));
+    HIPCHK(s->h_stage.ensure(n3));
     gd_launch_gather_xyz(s->pos[s->pcur].p, s->slot_of.p, (float *)s->fout.p, s->N, s->Np, s->R, quantize, s->stream);   // fout: R*N float4 >= n3 floats
-    HIPCHK(hipMemcpyAsync(s->h_stage, s->fout.p, n3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_stage.p, s->fout.p, n3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
-    *out = s->h_stage;
+    *out = s->h_stage.p;
     return GD_OK;
 }
 
@@ -398,7 +229,7 @@ extern "C" int gd_set_pair_softcore(gd_system *s, const gd_pair_softcore *p)
     return GD_OK;
 }
 
-static int check_bond_params(const gd_bond_params *p)
+int check_bond_params(const gd_bond_params *p)
 {
     if (p->kind < GD_POT_HARMONIC || p->kind > GD_POT_SOFTCORE) return fail(GD_EINVAL, "bond params: bad kind %d", p->kind);
     if (p->kind == GD_POT_SOFTCORE && !valid_pq(p->p, p->q)) return fail(GD_EINVAL, "bond params: unsupported softcore powers");
@@ -491,148 +322,6 @@ extern "C" int gd_set_ellipsoid_wall(gd_system *s, const gd_wall *w)
     s->wall = *w; s->has_wall = true;
     for (auto &c : s->hctx) memcpy(c.semi, w->init_semiaxes, sizeof c.semi);
     s->ctx_dirty = true;
-    return GD_OK;
-}
-
-extern "C" int gd_set_pair_softwell(gd_system *s, double energy, double decay, double cutoff, const uint32_t *targets, uint32_t n)
-{
-    if (!s || (n && !targets)) return fail(GD_EINVAL, "gd_set_pair_softwell: NULL argument");
-    if (n > 4096) return fail(GD_EINVAL, "gd_set_pair_softwell: at most 4096 targets");
-    if (n && (!(decay > 0) || !(cutoff > 0))) return fail(GD_EINVAL, "gd_set_pair_softwell: decay and cutoff must be positive");
-    for (uint32_t k = 0; k < n; k++) if (targets[k] >= s->N) return fail(GD_EINVAL, "gd_set_pair_softwell: target %u out of range", k);
-    {   // set_neighbor_targets takes a set of particles: a repeated index would make two threads update one bead
-        std::vector<uint32_t> t(targets, targets + n);
-        std::sort(t.begin(), t.end());
-        for (uint32_t k = 1; k < n; k++) if (t[k] == t[k - 1]) return fail(GD_EINVAL, "gd_set_pair_softwell: target %u listed twice", t[k]);
-    }
-    HIPCHK(hipSetDevice(s->device));
-    s->sw_n = 0;
-    if (n) {
-        HIPCHK(s->sw_targets.resize(n, false));
-        HIPCHK(hipMemcpy(s->sw_targets.p, targets, n * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIPCHK(s->sw_esum.resize(s->R));
-        s->sw_n = n; s->sw_eps = energy; s->sw_decay = decay; s->sw_cut = cutoff;
-    }
-    return GD_OK;
-}
-
-// the box of a kernel's parameter block: periodic flag, periods and their inverses
-template <class P>
-static void set_box(const gd_system *s, P &p)
-{
-    p.periodic = s->box_kind == GD_BOX_PERIODIC;
-    for (int k = 0; k < 3; k++) { p.box[k] = (float)s->box[k]; p.inv_box[k] = s->box[k] > 0 ? (float)(1.0 / s->box[k]) : 0.f; }
-}
-
-// the droplet term of the step / force / energy evaluation that `p` describes (same positions, same buffers)
-static void launch_softwell(gd_system *s, const StepParams &p, int mode)
-{
-    SoftwellP q;
-    memset(&q, 0, sizeof q);
-    q.pos_in = p.pos_in; q.pos_out = p.pos_out; q.fout = s->fout.p; q.esum = s->sw_esum.p;
-    q.slot_of = s->slot_of.p; q.targets = s->sw_targets.p;
-    q.mob_o = s->mob_uniform >= 0.f ? nullptr : s->mob_o.p; q.mob_uniform = s->mob_uniform; q.dt = p.dt;
-    q.lo = p.lo; q.comp = p.comp;      // (a compensated step keeps the droplet's share of mu F dt in the residuals too)
-    q.eps = (float)s->sw_eps; q.inv_d2 = (float)(1.0 / (s->sw_decay * s->sw_decay)); q.rc2 = (float)(s->sw_cut * s->sw_cut);
-    q.N = s->N; q.Np = s->Np; q.R = s->R; q.M = s->sw_n;
-    set_box(s, q);
-    gd_launch_softwell(q, mode, s->stream);
-}
-
-// ---- per-replica dynamic pairs (include/gdyn_replica.h)
-static_assert(gd::RP_SLOT_SHIFT == GD_RP_SLOT_SHIFT && gd::RP_PARTNER_MASK == GD_RP_PARTNER_MASK && GD_ADJ_MASK <= GD_RP_PARTNER_MASK, "entry format");
-static_assert(gd::RP_RECORD_WORDS * sizeof(uint32_t) == gd::RP_SLOTS * sizeof(BondType), "record words");
-
-// A kernel behind k_step moves beads after k_step has bounded their displacement (the droplet term, the per-replica pairs): the running
-// bound then covers no step's output, so both list classes are walked and the list serves no observation after the run.
-static bool post_step_active(const gd_system *s) { return s->sw_n != 0 || s->rp.any(); }
-
-static BondType bond_record(const gd_bond_params &p, int term)
-{
-    const bool harmonic = p.kind == GD_POT_HARMONIC;     // U = K r^2 / 2 is the spring with rest length 0
-    return BondType{(float)p.k_a, (float)p.k_b, harmonic ? 0.f : (float)p.l_a, harmonic ? 0.f : (float)p.l_b,
-                    (p.mix ? 1 : 0) | (p.scale_by_bond_scale ? 2 : 0) | (p.minimum_image ? 4 : 0) | (term << 8),
-                    p.kind == GD_POT_SEMISPRING ? 0.f : -3.0e38f, p.kind, p.p | (p.q << 8)};
-}
-
-// The lists the caller set since the last evaluation: flattened, packed into the pinned block and sent with one asynchronous copy.
-// (Every evaluation ends behind a stream synchronisation, so the copy before has left the block by now: the wait on its event returns
-// at once, except after an evaluation that ended early on an error.)
-static int sync_replica_pairs(gd_system *s)
-{
-    if (!s->rp.dirty()) return GD_OK;
-    const gd::ReplicaLayout l = s->rp.flatten();
-    if (l.words > 0xffffffffull) return fail(GD_ENOMEM, "per-replica pair lists: %zu words exceed the table's 32-bit offsets", l.words);
-    if (!s->rp_copied) HIPCHK(hipEventCreateWithFlags(&s->rp_copied, hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(s->rp_copied));
-    if (l.words > s->rp_stage_cap) {
-        const size_t cap = gd::grown_capacity(s->rp_stage_cap, l.words);
-        uint32_t *h = nullptr;
-        HIPCHK(hipHostMalloc((void **)&h, cap * sizeof(uint32_t), hipHostMallocDefault));
-        if (s->rp_stage) (void)hipHostFree(s->rp_stage);
-        s->rp_stage = h; s->rp_stage_cap = cap;
-    }
-    if (l.words > s->rp_dev.n) HIPCHK(s->rp_dev.resize(gd::grown_capacity(s->rp_dev.n, l.words), false));
-    if (!s->rp_esum.p) HIPCHK(s->rp_esum.resize(s->R));
-    s->rp.pack(l, s->rp_stage);
-    BondType rec[gd::RP_SLOTS];
-    for (uint32_t k = 0; k < gd::RP_SLOTS; k++) rec[k] = s->rp.defined(k) ? bond_record(s->rp_params[k], GD_TERM_DYNAMIC) : BondType{};
-    memcpy(s->rp_stage + l.rec, rec, sizeof rec);
-    HIPCHK(hipMemcpyAsync(s->rp_dev.p, s->rp_stage, l.words * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipEventRecord(s->rp_copied, s->stream));
-    s->rp_layout = l;
-    return GD_OK;
-}
-
-// the per-replica pairs of the step / force / energy evaluation that `p` describes (same positions, same buffers)
-static void launch_replica_pairs(gd_system *s, const StepParams &p, int mode)
-{
-    const gd::ReplicaLayout &l = s->rp_layout;
-    ReplicaPairsP q;
-    memset(&q, 0, sizeof q);
-    q.pos_in = p.pos_in; q.pos_out = p.pos_out; q.fout = s->fout.p; q.esum = s->rp_esum.p; q.slot_of = s->slot_of.p;
-    q.base = (const uint4 *)(s->rp_dev.p + l.base); q.rec = (const BondType *)(s->rp_dev.p + l.rec);
-    q.row_bead = s->rp_dev.p + l.row_bead; q.row_off = s->rp_dev.p + l.row_off; q.ent = s->rp_dev.p + l.ent;
-    q.ctx = mode == 0 ? p.ctx_out : p.ctx_in;      // (a step's k_step has applied the pending callback and left the result there)
-    q.ab_o = s->ab_o.p; q.ab_stride = s->ab_stride;
-    q.mob_o = s->mob_uniform >= 0.f ? nullptr : s->mob_o.p; q.mob_uniform = s->mob_uniform; q.dt = p.dt;
-    q.lo = p.lo; q.comp = p.comp;
-    q.N = s->N; q.Np = s->Np; q.R = s->R; q.max_rows = l.max_rows;
-    set_box(s, q);
-    gd_launch_replica_pairs(q, mode, s->stream);
-}
-
-extern "C" int gd_replica_abi_version(void) { return GD_REPLICA_ABI_VERSION; }
-
-extern "C" int gd_replica_pairs_define(gd_system *s, uint32_t slot, const gd_bond_params *p)
-{
-    if (!s || !p) return fail(GD_EINVAL, "gd_replica_pairs_define: NULL argument");
-    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_define: slot %u out of range", slot);
-    GDCHK(check_bond_params(p));
-    s->rp_params[slot] = *p;
-    s->rp.define(slot);
-    return GD_OK;
-}
-
-extern "C" int gd_replica_pairs_set(gd_system *s, uint32_t slot, uint32_t replica, const uint32_t *pairs, uint32_t n)
-{
-    if (!s || (n && !pairs)) return fail(GD_EINVAL, "gd_replica_pairs_set: NULL argument");
-    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_set: slot %u out of range", slot);
-    if (replica >= s->R) return fail(GD_EINVAL, "gd_replica_pairs_set: replica %u out of range", replica);
-    if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_replica_pairs_set: slot %u was never defined (gd_replica_pairs_define)", slot);
-    if (s->gl_defined && slot == s->gl_slot) return fail(GD_ESTATE, "gd_replica_pairs_set: slot %u is managed by gd_glue_define (use gd_glue_set)", slot);
-    if (const size_t bad = s->rp.set(slot, replica, pairs, n))
-        return fail(GD_EINVAL, "gd_replica_pairs_set: bad pair %zu (%u,%u)", bad - 1, pairs[2 * (bad - 1)], pairs[2 * (bad - 1) + 1]);
-    return GD_OK;
-}
-
-extern "C" int gd_replica_pairs_count(gd_system *s, uint32_t slot, uint32_t replica, uint32_t *n)
-{
-    if (!s || !n) return fail(GD_EINVAL, "gd_replica_pairs_count: NULL argument");
-    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_replica_pairs_count: slot %u out of range", slot);
-    if (replica >= s->R) return fail(GD_EINVAL, "gd_replica_pairs_count: replica %u out of range", replica);
-    if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_replica_pairs_count: slot %u was never defined (gd_replica_pairs_define)", slot);
-    *n = s->rp.count(slot, replica);
     return GD_OK;
 }
 
@@ -1073,25 +762,25 @@ static int read_chunk(gd_system *s, Chunk &c)
 {
     HIPCHK(hipGetLastError());
     const size_t nf = (size_t)s->R * GD_NFLAGS * sizeof(unsigned), nc = s->R * sizeof(DevCtx), nl = 2 * (size_t)s->R * sizeof(unsigned long long), nd = s->R * sizeof(float);
-    if (!s->h_chunk) HIPCHK(hipHostMalloc((void **)&s->h_chunk, nf + nc + nl + nd + 16, hipHostMallocDefault));
-    HIPCHK(hipMemcpyAsync(s->h_chunk + nf + nc + nl + nd, s->pool.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(s->h_chunk, s->flags.p, nf, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(s->h_chunk + nf, s->ctx[s->ccur].p, nc, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(s->h_chunk + nf + nc, s->lcount_d.p, nl, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpy2DAsync(s->h_chunk + nf + nc + nl, sizeof(float), s->dmax.p, GD_DMAX_STRIDE * sizeof(unsigned), sizeof(float), s->R,
+    HIPCHK(s->h_chunk.ensure(nf + nc + nl + nd + 16));
+    HIPCHK(hipMemcpyAsync(s->h_chunk.p + nf + nc + nl + nd, s->pool.p, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_chunk.p, s->flags.p, nf, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_chunk.p + nf, s->ctx[s->ccur].p, nc, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(s->h_chunk.p + nf + nc, s->lcount_d.p, nl, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpy2DAsync(s->h_chunk.p + nf + nc + nl, sizeof(float), s->dmax.p, GD_DMAX_STRIDE * sizeof(unsigned), sizeof(float), s->R,
                             hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
-    c.rep = gd::summarize((const unsigned *)s->h_chunk, s->R);
-    c.ctx.resize(s->R); memcpy(c.ctx.data(), s->h_chunk + nf, nc); memcpy(s->lcount.data(), s->h_chunk + nf + nc, nl);
-    c.dmax2 = 0; for (uint32_t r = 0; r < s->R; r++) { float d2; memcpy(&d2, s->h_chunk + nf + nc + nl + r * sizeof(float), 4); c.dmax2 = std::max(c.dmax2, d2); }
-    unsigned used[4]; memcpy(used, s->h_chunk + nf + nc + nl + nd, 16);
+    c.rep = gd::summarize((const unsigned *)s->h_chunk.p, s->R);
+    c.ctx.resize(s->R); memcpy(c.ctx.data(), s->h_chunk.p + nf, nc); memcpy(s->lcount.data(), s->h_chunk.p + nf + nc, nl);
+    c.dmax2 = 0; for (uint32_t r = 0; r < s->R; r++) { float d2; memcpy(&d2, s->h_chunk.p + nf + nc + nl + r * sizeof(float), 4); c.dmax2 = std::max(c.dmax2, d2); }
+    unsigned used[4]; memcpy(used, s->h_chunk.p + nf + nc + nl + nd, 16);
     s->list.chunk_read(used);
     if (c.rep.tile_over && dev_env("GDYN_DEBUG")) {      // (developer builds: the grids of a tile overflow)
         std::vector<GridP> gp(s->R);
         (void)hipMemcpy(gp.data(), s->grid.p, s->R * sizeof(GridP), hipMemcpyDeviceToHost);
         for (uint32_t r = 0; r < std::min(s->R, 3u); r++)
             fprintf(stderr, "[gdyn] grid r%u: nc %d %d %d ncell %d org %g %g %g inv %g flags need_t %u\n", r, gp[r].nc[0], gp[r].nc[1], gp[r].nc[2],
-                    gp[r].ncell, gp[r].org[0], gp[r].org[1], gp[r].org[2], gp[r].inv[0], ((const unsigned *)s->h_chunk)[r * GD_NFLAGS + GD_FLAG_NEED_TILE]);
+                    gp[r].ncell, gp[r].org[0], gp[r].org[1], gp[r].org[2], gp[r].inv[0], ((const unsigned *)s->h_chunk.p)[r * GD_NFLAGS + GD_FLAG_NEED_TILE]);
     }
     return GD_OK;
 }
@@ -1114,7 +803,7 @@ static int build_now(gd_system *s, float rv, bool with_list, bool allow_tiled = 
     return fail(GD_ENOMEM, "neighbour list width did not converge (W=%u)", s->pol.W);
 }
 
-static int prepare(gd_system *s)
+int prepare(gd_system *s)
 {
     HIPCHK(hipSetDevice(s->device));
     GDCHK(finalize_topology(s));
@@ -1299,7 +988,7 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
                 p.r0 = 0; p.nrep = ra; gd_launch_step(p, GD_MODE_STEP, s->stream);
                 p.r0 = ra; p.nrep = s->R - ra; gd_launch_step(p, GD_MODE_STEP, s->stream2);
             } else gd_launch_step(p, GD_MODE_STEP, s->stream);
-            if (s->sw_n) launch_softwell(s, p, 0);
+            if (s->sw.n) launch_softwell(s, p, 0);
             if (s->rp.any()) launch_replica_pairs(s, p, 0);      // (a step evaluates every term: GD_TERM_DYNAMIC is in its mask)
             s->pcur ^= 1; s->ccur ^= 1;
         }
@@ -1467,18 +1156,18 @@ extern "C" int gd_compute_energy(gd_system *s, uint32_t mask, double *energy)
     fill_common(s, p);
     p.term_mask = mask;
     gd_launch_step(p, GD_MODE_ENERGY, s->stream);
-    const bool droplet = s->sw_n && (mask & GD_TERM_PAIR);
+    const bool droplet = s->sw.n && (mask & GD_TERM_PAIR);
     const bool replica_pairs = s->rp.any() && (mask & GD_TERM_DYNAMIC);
     std::vector<double> esw(s->R, 0.0), erp(s->R, 0.0);
     if (replica_pairs) {
-        HIPCHK(hipMemsetAsync(s->rp_esum.p, 0, s->R * sizeof(double), s->stream));
+        HIPCHK(hipMemsetAsync(s->rp_up.esum.p, 0, s->R * sizeof(double), s->stream));
         launch_replica_pairs(s, p, 2);
-        HIPCHK(hipMemcpyAsync(erp.data(), s->rp_esum.p, s->R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(erp.data(), s->rp_up.esum.p, s->R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
     if (droplet) {
-        HIPCHK(hipMemsetAsync(s->sw_esum.p, 0, s->R * sizeof(double), s->stream));
+        HIPCHK(hipMemsetAsync(s->sw.esum.p, 0, s->R * sizeof(double), s->stream));
         launch_softwell(s, p, 2);
-        HIPCHK(hipMemcpyAsync(esw.data(), s->sw_esum.p, s->R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(esw.data(), s->sw.esum.p, s->R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     }
     std::vector<double> part((size_t)s->R * s->nblk);
     HIPCHK(hipMemcpyAsync(part.data(), s->epart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -1502,7 +1191,7 @@ extern "C" int gd_compute_forces(gd_system *s, uint32_t mask, double *forces)
     p.term_mask = mask;
     HIPCHK(hipMemsetAsync(p.react_out, 0, s->react_part[0].n * sizeof(float4), s->stream));
     gd_launch_step(p, GD_MODE_FORCE, s->stream);
-    if (s->sw_n && (mask & GD_TERM_PAIR)) launch_softwell(s, p, 1);
+    if (s->sw.n && (mask & GD_TERM_PAIR)) launch_softwell(s, p, 1);
     if (s->rp.any() && (mask & GD_TERM_DYNAMIC)) launch_replica_pairs(s, p, 1);
     // (a mask without the wall leaves axial_reaction as the last evaluation of the wall set it: no fold of the zeroed partials)
     const bool fold = s->has_wall && (mask & GD_TERM_WALL);
@@ -1518,8 +1207,8 @@ extern "C" int gd_compute_forces(gd_system *s, uint32_t mask, double *forces)
 
 // Pairs within dcut of replicas r0 .. r0 + nrep - 1, one launch: replica r0 + y's pairs at out + y * (out.n / nrep), their number in
 // cnt[2 y] (and left on the device in `count`).  The buffer grows until every replica fits.
-static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, DevBuf<uint2> &out, DevBuf<unsigned long long> &count,
-                         std::vector<unsigned long long> &cnt)
+int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, gd::dbuf<uint2> &out, gd::dbuf<unsigned long long> &count,
+                  std::vector<unsigned long long> &cnt)
 {
     const bool with_list = pair_cutoff(s) > 0;
     if (!out.p || out.n % nrep) HIPCHK(out.resize((size_t)nrep * std::max<size_t>((size_t)s->N * 8, 4096), false));
@@ -1562,348 +1251,10 @@ static int search_device(gd_system *s, uint32_t r0, uint32_t nrep, double dcut, 
     return fail(GD_ESTATE, "pair search: did not converge");
 }
 
-// md::neighbor_searcher{box, dcut}.search(): served on the device from the resident Verlet list when that list is
-// complete for dcut (dcut + 2 x largest displacement since the build <= list radius), after ONE list build otherwise -- a
-// build at radius max(force-list radius, dcut), so the force list stays valid either way and the next gd_run does not rebuild.
-// The result is cached for the repeated call of the count-then-fetch idiom.
-extern "C" int gd_search_pairs(gd_system *s, uint32_t r, double dcut, uint32_t *pairs, uint64_t cap, uint64_t *n_pairs)
-{
-    if (!s || !n_pairs || (cap && !pairs)) return fail(GD_EINVAL, "gd_search_pairs: NULL argument");
-    if (r >= s->R || !(dcut > 0)) return fail(GD_EINVAL, "gd_search_pairs: bad replica or cutoff");
-    GDCHK(prepare(s));
-    if (!(s->sp_valid && s->sp_r == r && s->sp_dcut == dcut && s->sp_serial == s->state_serial)) {
-        std::vector<unsigned long long> cnt;
-        GDCHK(search_device(s, r, 1, dcut, s->sp_out, s->sp_count, cnt));
-        s->sp_host.resize((size_t)cnt[0]);
-        if (cnt[0]) HIPCHK(hipMemcpy(s->sp_host.data(), s->sp_out.p, (size_t)cnt[0] * sizeof(uint2), hipMemcpyDeviceToHost));
-        s->sp_valid = true; s->sp_r = r; s->sp_dcut = dcut; s->sp_serial = s->state_serial;
-    }
-    const uint64_t n = s->sp_host.size();
-    for (uint64_t k = 0; k < n && k < cap; k++) { pairs[2 * k] = s->sp_host[k].x; pairs[2 * k + 1] = s->sp_host[k].y; }
-    *n_pairs = n;
-    return GD_OK;
-}
-
-// ------------------------------------------------------------- contact maps
-// contact_map (simulation_interphase/contact_map.cc:26-91) on the device, for all replicas of the handle at once: update() = one
-// pair search over every replica + one insert launch into the per-replica count tables; nothing but R pair counts crosses PCIe
-// until a map is dumped.  The tables share one capacity (a power of two) and are grown AHEAD of an update so that no table is more
-// than half full after it, whatever the update adds (the search has already counted the pairs when the tables are sized).
-static unsigned contact_jbits(const gd_system *s)      // bits of a bead id
-{
-    unsigned b = 1;
-    while (((uint64_t)(s->N - 1) >> b) != 0) b++;
-    return b;
-}
-
-// ------------------------------------------------------------- glue kinetics on the device (include/gdyn_glue.h)
-// The rule is in the header and in DESIGN.md section 7k, the kernels in gdyn_glue.hip.  The host keeps a copy of every set (at most
-// max_glues words a replica): it is what the managed slot is fed from, through the per-replica lists' own flattener.
-
-extern "C" int gd_glue_abi_version(void) { return GD_GLUE_ABI_VERSION; }
-
-// a replica's set into the managed slot, as gd_replica_pairs_set would install it
-static void glue_install(gd_system *s, uint32_t r)
-{
-    const std::vector<uint64_t> &keys = s->gl_sets[r];
-    std::vector<uint32_t> pairs(2 * keys.size());
-    for (size_t k = 0; k < keys.size(); k++) { pairs[2 * k] = gd::glue_i(keys[k]); pairs[2 * k + 1] = gd::glue_j(keys[k]); }
-    (void)s->rp.set(s->gl_slot, r, pairs.data(), (uint32_t)keys.size());      // (ids and i != j were checked when the set was made)
-}
-
-static int glue_pinned(gd_system *s, size_t words)
-{
-    if (words <= s->gl_pin_cap) return GD_OK;
-    const size_t cap = gd::grown_capacity(s->gl_pin_cap, words);
-    unsigned long long *h = nullptr;
-    HIPCHK(hipHostMalloc((void **)&h, cap * sizeof(unsigned long long), hipHostMallocDefault));
-    if (s->gl_pin) (void)hipHostFree(s->gl_pin);
-    s->gl_pin = h; s->gl_pin_cap = cap;
-    return GD_OK;
-}
-
-// the small pinned block: [R] seeds (64-bit), then 32-bit words: [R] set sizes, [4R] segments, [3R] counters
-static unsigned *glue_small_words(gd_system *s) { return (unsigned *)(s->gl_small + s->R); }
-
-extern "C" int gd_glue_define(gd_system *s, uint32_t slot, const gd_glue_params *p)
-{
-    if (!s || !p) return fail(GD_EINVAL, "gd_glue_define: NULL argument");
-    if (slot >= gd::RP_SLOTS) return fail(GD_EINVAL, "gd_glue_define: slot %u out of range", slot);
-    if (!s->rp.defined(slot)) return fail(GD_ESTATE, "gd_glue_define: slot %u was never defined (gd_replica_pairs_define)", slot);
-    if (s->gl_defined && slot != s->gl_slot) return fail(GD_ESTATE, "gd_glue_define: slot %u already holds the handle's glues (one glue slot per handle)", s->gl_slot);
-    if (const char *bad = gd::glue_check_params(p->reach, p->binding_rate, p->unbinding_rate)) return fail(GD_EINVAL, "gd_glue_define: %s", bad);
-    if (s->gl_defined)
-        for (uint32_t r = 0; r < s->R; r++)
-            if (s->gl_sets[r].size() > p->max_glues)
-                return fail(GD_EINVAL, "gd_glue_define: max_glues %u is below the %zu pairs replica %u holds", p->max_glues, s->gl_sets[r].size(), r);
-    if (!s->gl_defined) {
-        HIPCHK(hipSetDevice(s->device));
-        if (!s->gl_small) HIPCHK(hipHostMalloc((void **)&s->gl_small, (size_t)s->R * (sizeof(unsigned long long) + 8 * sizeof(unsigned)), hipHostMallocDefault));
-        HIPCHK(s->gl_seeds.resize(s->R, false)); HIPCHK(s->gl_nkeys.resize(s->R)); HIPCHK(s->gl_cnt.resize(3 * (size_t)s->R));
-        HIPCHK(s->gl_seg.resize(4 * (size_t)s->R));
-        s->gl_sets.assign(s->R, {});
-        s->gl_slot = slot; s->gl_defined = true; s->gl_dev_dirty = true;
-        for (uint32_t r = 0; r < s->R; r++) glue_install(s, r);      // (the slot holds the sets from here on: empty)
-    }
-    s->gl_par = *p;
-    return GD_OK;
-}
-
-extern "C" int gd_glue_set(gd_system *s, uint32_t replica, const uint32_t *pairs, uint32_t n)
-{
-    if (!s || (n && !pairs)) return fail(GD_EINVAL, "gd_glue_set: NULL argument");
-    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_set: no glue slot (gd_glue_define)");
-    if (replica >= s->R) return fail(GD_EINVAL, "gd_glue_set: replica %u out of range", replica);
-    if (const char *bad = gd::glue_normalise(pairs, n, s->N, s->gl_par.max_glues, s->gl_sets[replica])) return fail(GD_EINVAL, "gd_glue_set: %s", bad);
-    glue_install(s, replica);
-    s->gl_dev_dirty = true;
-    return GD_OK;
-}
-
-extern "C" int gd_glue_fetch(gd_system *s, uint32_t replica, uint32_t *pairs, uint32_t cap, uint32_t *n)
-{
-    if (!s || !n || (cap && !pairs)) return fail(GD_EINVAL, "gd_glue_fetch: NULL argument");
-    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_fetch: no glue slot (gd_glue_define)");
-    if (replica >= s->R) return fail(GD_EINVAL, "gd_glue_fetch: replica %u out of range", replica);
-    const std::vector<uint64_t> &keys = s->gl_sets[replica];
-    for (size_t k = 0; k < keys.size() && k < cap; k++) { pairs[2 * k] = gd::glue_i(keys[k]); pairs[2 * k + 1] = gd::glue_j(keys[k]); }
-    *n = (uint32_t)keys.size();
-    return GD_OK;
-}
-
-extern "C" int gd_glue_counts(gd_system *s, uint32_t *n)
-{
-    if (!s || !n) return fail(GD_EINVAL, "gd_glue_counts: NULL argument");
-    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_counts: no glue slot (gd_glue_define)");
-    for (uint32_t r = 0; r < s->R; r++) n[r] = (uint32_t)s->gl_sets[r].size();
-    return GD_OK;
-}
-
-// the host's sets onto the device (after gd_glue_define and gd_glue_set; an update leaves its result there itself)
-static int glue_upload(gd_system *s)
-{
-    if (!s->gl_dev_dirty) return GD_OK;
-    size_t most = 1;
-    for (auto &k : s->gl_sets) most = std::max(most, k.size());
-    const int c = s->gl_cur;
-    const size_t stride = gd::grown_capacity(s->gl_kstride[c], most);
-    if ((size_t)s->R * stride > 0xffffffffull) return fail(GD_ENOMEM, "gd_glue_update: %zu pairs a replica exceed the sort's 32-bit offsets", stride);
-    HIPCHK(s->gl_keys[c].resize((size_t)s->R * stride, false));
-    s->gl_kstride[c] = stride;
-    GDCHK(glue_pinned(s, (size_t)s->R * most));
-    unsigned *nk = glue_small_words(s);
-    for (uint32_t r = 0; r < s->R; r++) {
-        std::copy(s->gl_sets[r].begin(), s->gl_sets[r].end(), s->gl_pin + (size_t)r * most);
-        nk[r] = (unsigned)s->gl_sets[r].size();
-    }
-    HIPCHK(hipMemcpy2DAsync(s->gl_keys[c].p, stride * sizeof(unsigned long long), s->gl_pin, most * sizeof(unsigned long long),
-                            most * sizeof(unsigned long long), s->R, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->gl_nkeys.p, nk, s->R * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->gl_dev_dirty = false;
-    return GD_OK;
-}
-
-extern "C" int gd_glue_update(gd_system *s, double dt, uint64_t epoch, const uint64_t *seeds)
-{
-    if (!s || !seeds) return fail(GD_EINVAL, "gd_glue_update: NULL argument");
-    if (!s->gl_defined) return fail(GD_ESTATE, "gd_glue_update: no glue slot (gd_glue_define)");
-    if (!(dt > 0) || !std::isfinite(dt)) return fail(GD_EINVAL, "gd_glue_update: dt must be positive and finite");
-    HIPCHK(hipSetDevice(s->device));
-    const uint32_t R = s->R;
-    const gd_glue_params &par = s->gl_par;
-    GDCHK(prepare(s));
-    GDCHK(glue_upload(s));
-    std::vector<unsigned long long> ccnt;
-    GDCHK(search_device(s, 0, R, par.reach, s->gl_cand, s->gl_cand_count, ccnt));
-    unsigned long long most_c = 0;
-    size_t most_k = 0;
-    for (uint32_t r = 0; r < R; r++) { most_c = std::max(most_c, ccnt[2 * r]); most_k = std::max(most_k, s->gl_sets[r].size()); }
-    const int c = s->gl_cur, o = c ^ 1;
-    if (s->gl_alive.n < s->gl_keys[c].n) HIPCHK(s->gl_alive.resize(s->gl_keys[c].n, false));
-
-    GlueP q;
-    memset(&q, 0, sizeof q);
-    q.pos = s->pos[s->pcur].p; q.slot_of = s->slot_of.p; q.N = s->N; q.Np = s->Np; q.R = R;
-    set_box(s, q);
-    q.dcut2 = (float)(par.reach * par.reach);      // (search_device's own bound)
-    q.thr_off = gd::glue_rate_threshold(par.unbinding_rate, dt); q.thr_on = gd::glue_rate_threshold(par.binding_rate, dt); q.epoch = epoch;
-    q.seeds = s->gl_seeds.p; q.keys = s->gl_keys[c].p; q.kstride = (unsigned)s->gl_kstride[c]; q.nkeys = s->gl_nkeys.p;
-    q.alive = s->gl_alive.p; q.cnt = s->gl_cnt.p; q.cand = s->gl_cand.p; q.cand_cap = s->gl_cand.n / R; q.cand_count = s->gl_cand_count.p;
-    q.seg = s->gl_seg.p;
-
-    unsigned *small = glue_small_words(s), *h_nk = small, *h_seg = small + R, *h_cnt = small + 5 * (size_t)R;
-    std::copy(seeds, seeds + R, s->gl_small);
-    HIPCHK(hipMemcpyAsync(s->gl_seeds.p, s->gl_small, R * sizeof(unsigned long long), hipMemcpyHostToDevice, s->stream));
-
-    // unbind and bind; the fired records' buffer is sized like the search's output: grown until every replica fits (the draws are
-    // counter-based: a second pass fires the same pairs)
-    {
-        const double p_on = -std::expm1(-par.binding_rate * dt);
-        const size_t want = (size_t)std::min<double>((double)most_c, (double)most_c * p_on * 1.25 + 1024.0);
-        if (want > s->gl_fstride) s->gl_fstride = gd::grown_capacity(s->gl_fstride, want);
-    }
-    for (int attempt = 0;; attempt++) {
-        if (attempt == 4) return fail(GD_ESTATE, "gd_glue_update: the fired pairs' buffer did not converge");
-        const size_t fs = std::max<size_t>(s->gl_fstride, 1);
-        if ((size_t)R * fs > 0xffffffffull) return fail(GD_ENOMEM, "gd_glue_update: %zu fired pairs a replica exceed the sort's 32-bit offsets", fs);
-        if (s->gl_fkey[0].n != (size_t)R * fs)
-            for (int k = 0; k < 2; k++) { HIPCHK(s->gl_fkey[k].resize((size_t)R * fs, false)); HIPCHK(s->gl_fsel[k].resize((size_t)R * fs, false)); }
-        s->gl_fstride = fs;
-        q.fkey = s->gl_fkey[0].p; q.fsel = s->gl_fsel[0].p; q.fstride = (unsigned)fs;
-        HIPCHK(hipMemsetAsync(s->gl_cnt.p, 0, 3 * (size_t)R * sizeof(unsigned), s->stream));
-        gd_launch_glue_unbind(q, (unsigned)most_k, s->stream);
-        gd_launch_glue_bind(q, most_c, s->stream);
-        HIPCHK(hipMemcpyAsync(h_cnt, s->gl_cnt.p, 2 * (size_t)R * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(hipGetLastError());
-        unsigned most_f = 0;
-        for (uint32_t r = 0; r < R; r++) most_f = std::max(most_f, h_cnt[R + r]);
-        if (most_f <= fs) break;
-        s->gl_fstride = (size_t)most_f + most_f / 8 + 64;
-    }
-
-    // who binds: everything that fired where it fits, else the smallest selection keys
-    size_t most_new = 0, most_rows = most_k;
-    bool select = false;
-    for (uint32_t r = 0; r < R; r++) {
-        const size_t alive = h_cnt[r], fired = h_cnt[R + r], free_r = par.max_glues > alive ? par.max_glues - alive : 0;
-        const size_t take = std::min(fired, free_r);
-        h_seg[r] = (unsigned)(r * s->gl_fstride); h_seg[R + r] = h_seg[r] + (fired > free_r ? (unsigned)fired : 0u);
-        select = select || fired > free_r;
-        h_nk[r] = (unsigned)(alive + take);
-        most_new = std::max<size_t>(most_new, h_nk[r]); most_rows = std::max(most_rows, take);
-    }
-    const size_t ms = gd::grown_capacity(s->gl_kstride[o], std::max<size_t>(most_new, 1));
-    if ((size_t)R * ms > 0xffffffffull) return fail(GD_ENOMEM, "gd_glue_update: %zu pairs a replica exceed the sort's 32-bit offsets", ms);
-    HIPCHK(s->gl_keys[o].resize((size_t)R * ms, false)); HIPCHK(s->gl_merged.resize((size_t)R * ms, false));
-    for (uint32_t r = 0; r < R; r++) { h_seg[2 * R + r] = (unsigned)(r * ms); h_seg[3 * R + r] = h_seg[2 * R + r] + h_nk[r]; }
-    q.merged = s->gl_merged.p; q.mstride = (unsigned)ms;
-    HIPCHK(hipMemcpyAsync(s->gl_seg.p, h_seg, 4 * (size_t)R * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
-    const unsigned key_bits = 32u + contact_jbits(s);
-    if (most_new) {
-        size_t tmp_sel = 0, tmp_keys = 0;
-        if (select) HIPCHK(gd_glue_sort_select(nullptr, &tmp_sel, s->gl_fkey[0].p, s->gl_fsel[0].p, s->gl_fkey[1].p, s->gl_fsel[1].p, s->gl_fkey[0].n, R,
-                                               s->gl_seg.p, s->gl_seg.p + R, key_bits, s->stream));
-        HIPCHK(gd_glue_sort_keys(nullptr, &tmp_keys, s->gl_merged.p, s->gl_keys[o].p, s->gl_merged.n, R, s->gl_seg.p + 2 * R, s->gl_seg.p + 3 * R, key_bits, s->stream));
-        size_t tmp_bytes = std::max<size_t>(std::max(tmp_sel, tmp_keys), 1);
-        if (tmp_bytes > s->gl_tmp.n) HIPCHK(s->gl_tmp.resize(tmp_bytes, false));
-        if (select) {
-            tmp_bytes = s->gl_tmp.n;
-            HIPCHK(gd_glue_sort_select(s->gl_tmp.p, &tmp_bytes, s->gl_fkey[0].p, s->gl_fsel[0].p, s->gl_fkey[1].p, s->gl_fsel[1].p, s->gl_fkey[0].n, R,
-                                       s->gl_seg.p, s->gl_seg.p + R, key_bits, s->stream));
-        }
-        gd_launch_glue_merge(q, (unsigned)most_rows, s->stream);
-        tmp_bytes = s->gl_tmp.n;
-        HIPCHK(gd_glue_sort_keys(s->gl_tmp.p, &tmp_bytes, s->gl_merged.p, s->gl_keys[o].p, s->gl_merged.n, R, s->gl_seg.p + 2 * R, s->gl_seg.p + 3 * R, key_bits, s->stream));
-        GDCHK(glue_pinned(s, (size_t)R * most_new));
-        HIPCHK(hipMemcpy2DAsync(s->gl_pin, most_new * sizeof(unsigned long long), s->gl_keys[o].p, ms * sizeof(unsigned long long),
-                                most_new * sizeof(unsigned long long), R, hipMemcpyDeviceToHost, s->stream));
-    }
-    HIPCHK(hipMemcpyAsync(s->gl_nkeys.p, h_nk, R * sizeof(unsigned), hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipGetLastError());
-    s->gl_kstride[o] = ms; s->gl_cur = o;
-    for (uint32_t r = 0; r < R; r++) {
-        s->gl_sets[r].assign(s->gl_pin + (size_t)r * most_new, s->gl_pin + (size_t)r * most_new + h_nk[r]);
-        glue_install(s, r);
-    }
-    return GD_OK;
-}
-
-// (the contact maps, continued)
-static ContactTab contact_tab(gd_system *s)
-{
-    ContactTab t;
-    t.words = s->ct_words.p; t.distinct = s->ct_distinct.p; t.cap = s->ct_cap; t.jbits = contact_jbits(s);
-    return t;
-}
-
-extern "C" int gd_contacts_update(gd_system *s, double distance)
-{
-    if (!s) return fail(GD_EINVAL, "gd_contacts_update: NULL argument");
-    if (!(distance > 0)) return fail(GD_EINVAL, "gd_contacts_update: the contact distance must be positive");
-    if (contact_jbits(s) > 20) return fail(GD_EINVAL, "gd_contacts_update: contact maps take at most 1 048 576 beads (the count shares a 64-bit word with the pair)");
-    GDCHK(prepare(s));
-    std::vector<unsigned long long> cnt;
-    GDCHK(search_device(s, 0, s->R, distance, s->ct_pairs, s->ct_count, cnt));
-    if (s->ct_distinct_h.size() != s->R) s->ct_distinct_h.assign(s->R, 0u);
-    unsigned long long need = 0, most = 0;
-    for (uint32_t r = 0; r < s->R; r++) { need = std::max(need, s->ct_distinct_h[r] + cnt[2 * r]); most = std::max(most, cnt[2 * r]); }
-    size_t cap = std::max<size_t>(s->ct_cap, 1024);
-    while (cap < 2 * need) cap *= 2;
-    if (cap != s->ct_cap) {
-        DevBuf<unsigned long long> words;
-        HIPCHK(words.resize((size_t)s->R * cap, false));
-        HIPCHK(hipMemsetAsync(words.p, 0xff, words.n * sizeof(unsigned long long), s->stream));
-        if (s->ct_cap) {
-            ContactTab to = contact_tab(s), from = to;
-            to.words = words.p; to.cap = cap;
-            HIPCHK(hipMemsetAsync(s->ct_distinct.p, 0, s->R * sizeof(unsigned), s->stream));      // (recounted by the rehash)
-            gd_launch_contacts_rehash(from, to, s->R, s->stream);
-            HIPCHK(hipStreamSynchronize(s->stream));      // the old tables are freed below
-        } else HIPCHK(s->ct_distinct.resize(s->R));
-        std::swap(s->ct_words.p, words.p); std::swap(s->ct_words.n, words.n);
-        s->ct_cap = cap;
-    }
-    gd_launch_contacts_insert(contact_tab(s), s->ct_pairs.p, s->ct_pairs.n / s->R, s->ct_count.p, most, s->R, s->stream);
-    HIPCHK(hipMemcpyAsync(s->ct_distinct_h.data(), s->ct_distinct.p, s->R * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipGetLastError());
-    return GD_OK;
-}
-
-extern "C" int gd_contacts_fetch(gd_system *s, uint32_t r, uint32_t *rows, uint64_t cap, uint64_t *n_rows)
-{
-    if (!s || !n_rows || (cap && !rows)) return fail(GD_EINVAL, "gd_contacts_fetch: NULL argument");
-    if (r >= s->R) return fail(GD_EINVAL, "gd_contacts_fetch: bad replica");
-    const uint64_t n = s->ct_cap ? s->ct_distinct_h[r] : 0;
-    *n_rows = n;
-    if (!n || !cap) return GD_OK;       // (the count of the count-then-fetch idiom costs nothing: the host mirrors the occupancy)
-    HIPCHK(hipSetDevice(s->device));
-    for (int k = 0; k < 2; k++)
-        if (s->ct_ck[k].n < n) { HIPCHK(s->ct_ck[k].resize((size_t)(n + n / 4), false)); HIPCHK(s->ct_cv[k].resize((size_t)(n + n / 4), false)); }
-    HIPCHK(s->ct_n.resize(1));
-    HIPCHK(hipMemsetAsync(s->ct_n.p, 0, sizeof(unsigned), s->stream));
-    gd_launch_contacts_compact(contact_tab(s), r, s->ct_ck[0].p, s->ct_cv[0].p, s->ct_n.p, s->stream);
-    const unsigned jb = contact_jbits(s), bits = 2 * jb;      // key = i << jb | j
-    size_t tmp_bytes = 0;
-    HIPCHK(gd_sort_contacts(nullptr, &tmp_bytes, s->ct_ck[0].p, s->ct_ck[1].p, s->ct_cv[0].p, s->ct_cv[1].p, (size_t)n, bits, s->stream));
-    if (s->ct_tmp.n < tmp_bytes) HIPCHK(s->ct_tmp.resize(tmp_bytes + tmp_bytes / 4, false));
-    tmp_bytes = s->ct_tmp.n;
-    HIPCHK(gd_sort_contacts(s->ct_tmp.p, &tmp_bytes, s->ct_ck[0].p, s->ct_ck[1].p, s->ct_cv[0].p, s->ct_cv[1].p, (size_t)n, bits, s->stream));
-    std::vector<unsigned long long> hk((size_t)n); std::vector<unsigned> hv((size_t)n);
-    unsigned found = 0;
-    HIPCHK(hipMemcpyAsync(hk.data(), s->ct_ck[1].p, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(hv.data(), s->ct_cv[1].p, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipMemcpyAsync(&found, s->ct_n.p, sizeof found, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipGetLastError());
-    if (found != n) return fail(GD_ESTATE, "gd_contacts_fetch: table occupancy %u differs from the %llu entries counted", found, (unsigned long long)n);
-    for (uint64_t k = 0; k < n && k < cap; k++) {
-        rows[3 * k] = (uint32_t)(hk[k] >> jb); rows[3 * k + 1] = (uint32_t)(hk[k] & ((1ull << jb) - 1ull)); rows[3 * k + 2] = hv[k];
-    }
-    return GD_OK;
-}
-
-extern "C" int gd_contacts_clear(gd_system *s, uint32_t r)
-{
-    if (!s) return fail(GD_EINVAL, "gd_contacts_clear: NULL argument");
-    if (r != GD_ALL_REPLICAS && r >= s->R) return fail(GD_EINVAL, "gd_contacts_clear: bad replica");
-    if (!s->ct_cap) return GD_OK;
-    HIPCHK(hipSetDevice(s->device));
-    const uint32_t r0 = r == GD_ALL_REPLICAS ? 0 : r, nr = r == GD_ALL_REPLICAS ? s->R : 1;
-    HIPCHK(hipMemsetAsync(s->ct_words.p + (size_t)r0 * s->ct_cap, 0xff, (size_t)nr * s->ct_cap * sizeof(unsigned long long), s->stream));
-    HIPCHK(hipMemsetAsync(s->ct_distinct.p + r0, 0, nr * sizeof(unsigned), s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    for (uint32_t k = r0; k < r0 + nr; k++) s->ct_distinct_h[k] = 0;
-    return GD_OK;
-}
-
 // ------------------------------------------------------------- live seams (gdyn_live.hpp)
-// What the live bridge reads of a handle.  Neither call needs prepare(): the tables and the positions are what gd_contacts_fetch
-// and gd_get_positions_f32 read, which do not prepare either.  Both end with the stream idle, so no chunk of a gd_run and no
-// update is in flight when an analysis stream reads the buffers.
+// What the live bridge reads of a handle (the contact tables: gd_live_contact_tab, gdyn_capi_contacts.hip).  No call needs prepare():
+// the tables and the positions are what gd_contacts_fetch and gd_get_positions_f32 read, which do not prepare either.  Each ends with
+// the stream idle, so no chunk of a gd_run and no update is in flight when an analysis stream reads the buffers.
 gd_live_shape gd_live_shape_of(const gd_system *s)
 {
     gd_live_shape v{};
@@ -1911,15 +1262,6 @@ gd_live_shape gd_live_shape_of(const gd_system *s)
     v.periodic = s->box_kind == GD_BOX_PERIODIC; v.has_wall = s->has_wall;
     memcpy(v.box, s->box, sizeof v.box);
     return v;
-}
-
-int gd_live_contact_tab(gd_system *s, ContactTab *tab, const unsigned **occupancy)
-{
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    *tab = contact_tab(s);
-    *occupancy = s->ct_cap ? s->ct_distinct_h.data() : nullptr;
-    return GD_OK;
 }
 
 int gd_live_positions(gd_system *s, int quantize, const float **xyz)

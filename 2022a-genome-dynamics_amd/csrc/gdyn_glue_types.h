@@ -1,4 +1,4 @@
-// gdyn_glue_types.h -- what gdyn_capi.hip and gdyn_glue.hip share of the device glue kinetics: the kernels' parameter block, the
+// gdyn_glue_types.h -- what gdyn_capi_glue.hip and gdyn_glue.hip share of the device glue kinetics: the kernels' parameter block, the
 // launchers and the sorts.  (A header of its own: gdyn_types.h describes the timed kernels' source.)
 #ifndef GDYN_GLUE_TYPES_H
 #define GDYN_GLUE_TYPES_H

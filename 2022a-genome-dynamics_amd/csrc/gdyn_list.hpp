@@ -1,7 +1,7 @@
 // gdyn_list.hpp -- the resident list of a handle: what the host knows about the neighbour list in use, and every event that changes it.
 //
 // One struct, one named transition per event (the table in DESIGN.md, "Resident list"), the questions the stepper asks of it as const
-// queries.  Plain C++ (no HIP runtime, handle or environment): gdyn_capi.hip calls the transitions and never assigns a member;
+// queries.  Plain C++ (no HIP runtime, handle or environment): the handle's host files (gdyn_capi*.hip) call the transitions and never assign a member;
 // tests/native/test_resident_list.cpp drives it alone.  Buffers, the position / order cursors and the counters of the handle
 // (rebuilds, the per-replica entry counts) stay with the handle and are passed in where a query needs them.
 #pragma once

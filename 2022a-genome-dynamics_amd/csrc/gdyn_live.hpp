@@ -16,7 +16,7 @@
 
 #define GD_SEAM __attribute__((visibility("hidden")))
 
-// ---- the stepper (gdyn_capi.hip).  Each call makes the system's device current and returns with its stream idle: what it
+// ---- the stepper (gdyn_capi.hip; the contact tables: gdyn_capi_contacts.hip).  Each call makes the system's device current and returns with its stream idle: what it
 // hands out is not written again until the next call on the system.
 struct gd_live_shape {
     int device;

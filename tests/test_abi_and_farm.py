@@ -266,20 +266,23 @@ def test_bench_two_rccl_ranks_on_one_device_or_the_refusal_recorded(hip):
 
 
 def test_every_entry_point_makes_its_device_current_before_its_first_hip_call():
-    """include/gdyn.h: independent handles may live on different threads AND devices.  Audit of csrc/gdyn_capi.hip: every extern "C"
-    entry point that reaches the HIP runtime sets the handle's device first -- hipSetDevice itself or one of the helpers that start
-    with it (prepare, fetch_xyz, apply_pending, finalize_topology)."""
+    """include/gdyn.h: independent handles may live on different threads AND devices.  Audit of the handle's host files (csrc/gdyn_capi.hip
+    and the gdyn_capi_*.hip of the features): every extern "C" entry point that reaches the HIP runtime sets the handle's device first --
+    hipSetDevice itself or one of the helpers that start with it (prepare, fetch_xyz, apply_pending, finalize_topology)."""
+    import glob
     import re
-    src = open(os.path.join(ROOT, PKG_DIR, "csrc", "gdyn_capi.hip")).read()
+    files = sorted(glob.glob(os.path.join(ROOT, PKG_DIR, "csrc", "gdyn_capi*.hip")))
+    assert len(files) == 4, files      # the stepper, the kernels behind k_step, the contact maps and pair search, the glue kinetics
+    src = "\n".join(open(f).read() for f in files)
     src = re.sub(r"//[^\n]*", "", src)
     starts = [m.start() for m in re.finditer(r'^extern "C" ', src, re.M)] + [len(src)]
     helpers = r"hipSetDevice|prepare\(s\)|fetch_xyz\(s|apply_pending\(s\)|finalize_topology\(s\)"
     for h in ("prepare", "fetch_xyz", "apply_pending", "finalize_topology"):      # the helpers do start with it (apply_pending: once something is pending)
-        body = src[src.index("static int " + h + "("):]
+        body = src[re.search(r"^(?:static )?int " + h + r"\(", src, re.M).start():]      # (prepare crosses files: not static)
         body = body[:body.index("\n}\n")]
         first_hip = re.search(r"\bhip[A-Z]\w+\s*\(|gd_launch_", body)
         assert first_hip and (first_hip.group(0).startswith("hipSetDevice") or re.search(helpers, body[:first_hip.start()])), h
-    checked = 0
+    checked = set()
     for a, b in zip(starts, starts[1:]):
         fn = src[a:b]
         first_line = fn.split("\n", 1)[0]
@@ -290,8 +293,11 @@ def test_every_entry_point_makes_its_device_current_before_its_first_hip_call():
             continue
         sets = re.search(helpers, fn)
         assert sets and sets.start() <= uses.start(), name
-        checked += 1
-    assert checked >= 12
+        checked.add(name)
+    # sixteen entry points reach the runtime, those of the feature files among them
+    assert len(checked) >= 16, sorted(checked)
+    assert checked >= {"gd_set_pair_softwell", "gd_search_pairs", "gd_contacts_update", "gd_contacts_fetch", "gd_contacts_clear",
+                       "gd_glue_define", "gd_glue_update"}, sorted(checked)
 
 
 def test_committed_pmc_traffic_describes_the_kernel_source_in_the_tree():

@@ -1,6 +1,7 @@
 """The resident list of a handle (csrc/gdyn_list.hpp) on the CPU: tests/native/test_resident_list.cpp drives gd::ResidentList alone
 through every event that changes it (the transition table of DESIGN.md) and checks its queries -- row-width prediction, freshness for an
-observation, pair searches, the list fields of gd_context.  Two source checks hold gdyn_capi.hip to calling the transitions."""
+observation, pair searches, the list fields of gd_context.  Two source checks hold the handle's host files to calling the transitions."""
+import glob
 import os
 import re
 import subprocess
@@ -52,12 +53,15 @@ def _members():
 
 
 def test_capi_assigns_no_member_of_the_resident_list():
-    """gdyn_capi.hip changes the list state through the named transitions only: the handle has one ResidentList, none of the loose
+    """The handle's host files (gdyn_capi.hip, the gdyn_capi_*.hip of the features) and the header that declares the handle
+    (gdyn_system.hpp) change the list state through the named transitions only: the handle has one ResidentList, none of the loose
     members it replaced, and no statement assigns, increments or takes a reference to a member of it."""
     members = _members()
     assert set(members) >= {"valid", "tiled", "W", "tile_cap", "rv", "rn", "steps_since_build", "search_list", "verified_serial", "w_packed",
                             "bbox_cur", "bbox_valid", "need_valid", "need_rv", "need_all_near", "order_valid", "pool_used", "repairs"}, members
-    src = open(os.path.join(CSRC, "gdyn_capi.hip")).read()
+    files = sorted(glob.glob(os.path.join(CSRC, "gdyn_capi*.hip")))
+    assert len(files) == 4, files
+    src = "\n".join(open(f).read() for f in files + [os.path.join(CSRC, "gdyn_system.hpp")])
     code = re.sub(r"//[^\n]*|/\*.*?\*/", "", src, flags=re.S)
     assert len(re.findall(r"\bgd::ResidentList\s+\w+\s*;", code)) == 1
     alt = "|".join(members)
