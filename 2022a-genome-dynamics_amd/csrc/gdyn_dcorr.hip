@@ -1,0 +1,868 @@
+// gdyn_dcorr.hip -- the spatial correlation of bead displacements (include/gdyn_dcorr.h): per origin frame, pair class and
+// distance bin, the number of pairs and the fixed-point sum of D_i . D_j.  Beyond the reference, which has no such analysis.
+// The pair rules are gdyn_rdf.hip's, the history handling gdyn_msd.hip's.
+//
+// Per call:
+//   k_dcorr_tmax   the largest squared displacement t2 of the selected beads over all origins of the call (integer atomicMax on the
+//                  bit pattern of the non-negative double).  The host turns it into the scale S and refuses an illegal one before
+//                  any pair is walked.
+//   k_dcorr_self   per origin and label, the sum of llrint(t2 * 2^S) (LDS integer atomics per block, one global one per label).
+// Per batch of origins (max_frames_per_launch; no result depends on it):
+//   k_dcorr_bbox   open box: the bounding box of each origin frame's selected beads (block reduction, integer atomicMin / atomicMax
+//                  on an order-preserving image of the double)
+//   k_dcorr_grid   the cells of each origin: of side >= max_distance (1 + kCellSlack), of the periodic box or of the frame's own
+//                  bounding box, coarsened until an origin has at most `cap` cells.  An axis of zero extent has one cell.
+//   k_dcorr_disp   gathers the selected beads of each origin, computes D in fp64 and keys the bead (origin, cell)
+//   gd_sort_contacts, k_dcorr_sorted, k_dcorr_starts   as gdyn_rdf.hip: the beads in key order as 64-byte records (position, D,
+//                  label, chain) and the first sorted index of every cell
+//   k_dcorr_work   one work item per kChunk centres of a non-empty cell (their order is arbitrary: the sums are integers)
+//   k_dcorr_pairs  the hot path.  A block owns one work item: up to kChunk centres of one cell, held in registers.  Every bead of a
+//                  cell wants the same 27 cells (fewer at an open edge, every cell once where an axis has fewer than 3), so the
+//                  block stages them through LDS in tiles, one x-row span at a time, as seven arrays of 8-byte words (structure of
+//                  arrays: x y z Dx Dy Dz and label|chain).  Lane = (centre, slice): the kBlock / centres (a power of two) lanes of
+//                  a centre walk the tile interleaved, so the lanes of a wave read a few consecutive words of an array (no bank
+//                  conflict for 8-byte reads, identical addresses broadcast) and small cells still fill the block.  Only partners
+//                  later in sorted order count, so every unordered pair is seen once.  The positions are read first and D and the
+//                  labels only for the ~15 % of partners inside the cutoff.  Pairs go to a block histogram in LDS (uint32 counts,
+//                  64-bit sums, ds integer atomics) whose non-zero cells are flushed with one 64-bit integer global atomic each (a
+//                  signed sum added as two's complement through the unsigned atomic is exact); above GD_DCORR_LDS_BINS cells every
+//                  pair goes to global memory directly.
+// fp64 throughout, -ffp-contract=off (csrc/Makefile), no fast-math, no floating-point atomics: every table is an integer sum.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "../../include/gdyn.h"
+#include "../../include/gdyn_dcorr.h"
+#include "gdyn_analysis.hpp"
+#include "gdyn_live.hpp"
+#include "gdyn_once.hpp"
+#include "gdyn_types.h"
+
+using namespace gd;
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr unsigned kChunk = kBlock;          // centres of one work item
+constexpr unsigned kTilePad = 2;             // words between the arrays of a tile: staging writes 8 fields of 2 records per 16 lanes
+constexpr unsigned kTileWords = 7;           // x y z Dx Dy Dz label|chain
+constexpr unsigned kUnroll = 4;              // partners of a lane whose positions are read together
+constexpr double kCellSlack = 1e-9;          // cells are this much wider than max_distance, against the rounding of the cell assignment
+constexpr unsigned long long kNoBadIndex = ~0ull;
+
+struct Rec {      // one selected bead of one origin
+    double p[3];
+    double d[3];
+    int label;
+    unsigned chain;
+    unsigned pad[2];
+};
+static_assert(sizeof(Rec) == 64, "a record is 64 bytes");
+
+struct Grid {      // the cells of one origin
+    double lo[3];            // open: the low corner of the bounding box; periodic: 0
+    double box[3];           // periodic: the periods
+    double inv_side[3];      // cells per unit length (0 along an axis of zero extent)
+    int n[3];                // cells per axis (>= 1)
+    unsigned cells;
+};
+
+struct Origins {      // first + k * stride, k < count
+    unsigned first, stride, count;
+};
+
+struct Space {
+    int periodic;
+    double box[3];
+    double cell_side;        // max_distance (1 + kCellSlack)
+};
+
+// an image of a double under which unsigned order is numeric order
+__device__ inline unsigned long long ordered(double x)
+{
+    unsigned long long const u = (unsigned long long)__double_as_longlong(x);
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__device__ inline double unordered(unsigned long long o)
+{
+    return __longlong_as_double((long long)((o >> 63) ? (o & ~(1ull << 63)) : ~o));
+}
+
+__device__ inline double wave_min(double v)
+{
+    for (int m = 32; m; m >>= 1) v = fmin(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ inline double wave_max(double v)
+{
+    for (int m = 32; m; m >>= 1) v = fmax(v, __shfl_xor(v, m));
+    return v;
+}
+
+// the same over the block (every lane calls; sh: kBlock / 64 doubles)
+__device__ inline double block_min(double v, double *sh)
+{
+    v = wave_min(v);
+    __syncthreads();      // sh is free again
+    if (threadIdx.x % 64 == 0) sh[threadIdx.x / 64] = v;
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) v = fmin(v, sh[w]);
+    return v;
+}
+__device__ inline double block_max(double v, double *sh)
+{
+    v = wave_max(v);
+    __syncthreads();
+    if (threadIdx.x % 64 == 0) sh[threadIdx.x / 64] = v;
+    __syncthreads();
+    for (int w = 0; w < kBlock / 64; w++) v = fmax(v, sh[w]);
+    return v;
+}
+
+__device__ inline double wrap(double x, double L)      // gdyn_rdf.hip
+{
+    double const w = fmod(x, L);
+    return w < 0.0 ? w + L : w;
+}
+
+__device__ inline int cell_of(double w, double inv_side, int n) { return (int)fmin(fmax(floor(w * inv_side), 0.0), (double)(n - 1)); }
+
+__device__ inline double min_image(double d, double L)     // DESIGN.md 7b; |d| <= L/2 already gives nearbyint(d/L) = 0
+{
+    return fabs(d) > 0.5 * L ? d - L * nearbyint(d / L) : d;
+}
+
+__device__ inline void load3(const void *__restrict__ xyz, int is_f64, size_t at, double p[3])
+{
+    for (int a = 0; a < 3; a++) p[a] = is_f64 ? static_cast<const double *>(xyz)[at + a] : (double)static_cast<const float *>(xyz)[at + a];
+}
+
+// t2 of selected bead k at origin o (and D)
+__device__ inline double disp_of(const void *__restrict__ xyz, int is_f64, unsigned N, unsigned bead, unsigned f, unsigned lag, double p[3], double d[3])
+{
+    double q[3];
+    load3(xyz, is_f64, ((size_t)f * N + bead) * 3, p);
+    load3(xyz, is_f64, ((size_t)(f + lag) * N + bead) * 3, q);
+    for (int a = 0; a < 3; a++) d[a] = q[a] - p[a];
+    return (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+}
+
+__global__ void __launch_bounds__(kBlock) k_dcorr_tmax(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
+                                                       unsigned n_sel, unsigned lag, Origins og, unsigned long long *__restrict__ tmax)
+{
+    __shared__ double sh[kBlock / 64];
+    double t2 = 0.0;
+    for (size_t idx = (size_t)blockIdx.x * kBlock + threadIdx.x; idx < (size_t)og.count * n_sel; idx += (size_t)gridDim.x * kBlock) {
+        unsigned const o = (unsigned)(idx / n_sel), k = (unsigned)(idx % n_sel);
+        double p[3], d[3];
+        t2 = fmax(t2, disp_of(xyz, is_f64, N, sel[k], og.first + o * og.stride, lag, p, d));
+    }
+    t2 = block_max(t2, sh);      // (finite coordinates: never NaN; an overflow is +inf, the largest pattern)
+    if (threadIdx.x == 0 && t2 > 0.0) atomicMax(tmax, (unsigned long long)__double_as_longlong(t2));
+}
+
+// self_sum[o, label] += llrint(t2 * scale); grid (blocks over the selection, origins of this launch)
+__global__ void __launch_bounds__(kBlock) k_dcorr_self(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
+                                                       const int *__restrict__ label, unsigned n_sel, unsigned lag, Origins og, unsigned o0,
+                                                       double scale, unsigned K, unsigned long long *__restrict__ self_sum)
+{
+    __shared__ unsigned long long acc[GD_DCORR_MAX_LABELS];
+    if (threadIdx.x < GD_DCORR_MAX_LABELS) acc[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned const o = o0 + blockIdx.y, k = blockIdx.x * kBlock + threadIdx.x;
+    if (k < n_sel) {
+        unsigned const bead = sel[k];
+        double p[3], d[3];
+        double const t2 = disp_of(xyz, is_f64, N, bead, og.first + o * og.stride, lag, p, d);
+        atomicAdd(&acc[label ? label[bead] : 0], (unsigned long long)llrint(t2 * scale));
+    }
+    __syncthreads();
+    if (threadIdx.x < K && acc[threadIdx.x]) atomicAdd(&self_sum[(size_t)o * K + threadIdx.x], acc[threadIdx.x]);
+}
+
+// bbox[o]: ordered images of (min x, y, z, max x, y, z), preset to (~0, ~0, ~0, 0, 0, 0); grid (a few blocks that stride over the selection, B)
+__global__ void __launch_bounds__(kBlock) k_dcorr_bbox(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
+                                                       unsigned n_sel, Origins og, unsigned o0, unsigned long long *__restrict__ bbox)
+{
+    __shared__ double sh[kBlock / 64];
+    unsigned const o = blockIdx.y;
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (unsigned k = blockIdx.x * kBlock + threadIdx.x; k < n_sel; k += gridDim.x * kBlock) {
+        double p[3];
+        load3(xyz, is_f64, ((size_t)(og.first + (o0 + o) * og.stride) * N + sel[k]) * 3, p);
+        for (int a = 0; a < 3; a++) {
+            lo[a] = fmin(lo[a], p[a]);
+            hi[a] = fmax(hi[a], p[a]);
+        }
+    }
+    for (int a = 0; a < 3; a++) {
+        lo[a] = block_min(lo[a], sh);
+        hi[a] = block_max(hi[a], sh);
+    }
+    if (threadIdx.x == 0 && lo[0] <= hi[0])
+        for (int a = 0; a < 3; a++) {
+            atomicMin(&bbox[6 * (size_t)o + a], ordered(lo[a]));
+            atomicMax(&bbox[6 * (size_t)o + 3 + a], ordered(hi[a]));
+        }
+}
+
+__global__ void __launch_bounds__(kBlock) k_dcorr_grid(const unsigned long long *__restrict__ bbox, unsigned B, Space sp, unsigned cap,
+                                                       Grid *__restrict__ grids)
+{
+    unsigned const o = blockIdx.x * kBlock + threadIdx.x;
+    if (o >= B) return;
+    Grid g;
+    double n[3], ext[3];
+    for (int a = 0; a < 3; a++) {
+        g.lo[a] = sp.periodic ? 0.0 : unordered(bbox[6 * (size_t)o + a]);
+        g.box[a] = sp.periodic ? sp.box[a] : 0.0;
+        ext[a] = sp.periodic ? sp.box[a] : unordered(bbox[6 * (size_t)o + 3 + a]) - g.lo[a];
+        n[a] = fmin(fmax(1.0, floor(ext[a] / sp.cell_side)), 1048576.0);
+    }
+    while (n[0] * n[1] * n[2] > (double)cap) {
+        int const a = (n[0] >= n[1] && n[0] >= n[2]) ? 0 : (n[1] >= n[2] ? 1 : 2);
+        n[a] = fmax(1.0, floor(n[a] * 0.9));
+    }
+    g.cells = 1;
+    for (int a = 0; a < 3; a++) {
+        g.n[a] = (int)n[a];
+        g.inv_side[a] = ext[a] > 0.0 ? n[a] / ext[a] : 0.0;
+        g.cells *= (unsigned)g.n[a];
+    }
+    grids[o] = g;
+}
+
+__global__ void __launch_bounds__(kBlock) k_dcorr_disp(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
+                                                       const int *__restrict__ label, const unsigned *__restrict__ chain, unsigned n_sel,
+                                                       unsigned lag, Origins og, unsigned o0, unsigned B, const Grid *__restrict__ grids, int periodic,
+                                                       unsigned cap, unsigned long long *__restrict__ keys, unsigned *__restrict__ vals,
+                                                       Rec *__restrict__ grec)
+{
+    size_t const idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= (size_t)B * n_sel) return;
+    unsigned const o = (unsigned)(idx / n_sel), k = (unsigned)(idx % n_sel), bead = sel[k];
+    Rec r;
+    (void)disp_of(xyz, is_f64, N, bead, og.first + (o0 + o) * og.stride, lag, r.p, r.d);
+    r.label = label ? label[bead] : 0;
+    r.chain = chain ? chain[bead] : 0u;
+    r.pad[0] = r.pad[1] = 0u;
+    Grid const g = grids[o];
+    int c[3];
+    for (int a = 0; a < 3; a++) c[a] = cell_of(periodic ? wrap(r.p[a], g.box[a]) : r.p[a] - g.lo[a], g.inv_side[a], g.n[a]);
+    unsigned const cell = ((unsigned)c[2] * (unsigned)g.n[1] + (unsigned)c[1]) * (unsigned)g.n[0] + (unsigned)c[0];
+    keys[idx] = (unsigned long long)o * cap + cell;
+    vals[idx] = (unsigned)idx;
+    grec[idx] = r;
+}
+
+__global__ void __launch_bounds__(kBlock) k_dcorr_sorted(const Rec *__restrict__ grec, const unsigned *__restrict__ vals, size_t n, Rec *__restrict__ srec)
+{
+    size_t const s = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s < n) srec[s] = grec[vals[s]];
+}
+
+// starts[t] = first sorted index whose key >= t, t in [0, count)
+__global__ void __launch_bounds__(kBlock) k_dcorr_starts(const unsigned long long *__restrict__ keys, size_t n, size_t count, unsigned *__restrict__ starts)
+{
+    size_t const t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= count) return;
+    size_t lo = 0, hi = n;
+    while (lo < hi) {
+        size_t const mid = (lo + hi) / 2;
+        if (keys[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    starts[t] = (unsigned)lo;
+}
+
+// work items (cell slot, chunk of kChunk centres) of the non-empty cells; slots = B * cap
+__global__ void __launch_bounds__(kBlock) k_dcorr_work(const unsigned *__restrict__ starts, size_t slots, uint2 *__restrict__ work, unsigned *__restrict__ n_work)
+{
+    size_t const t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= slots) return;
+    unsigned const c = starts[t + 1] - starts[t];
+    if (!c) return;
+    unsigned const items = (c + kChunk - 1) / kChunk, base = atomicAdd(n_work, items);
+    for (unsigned k = 0; k < items; k++) work[base + k] = make_uint2((unsigned)t, k);
+}
+
+// the distinct cells of one axis that the neighbours of cell c lie in: first and count
+__device__ inline void axis_cells(int c, int n, int periodic, int &first, int &count)
+{
+    if (periodic) {
+        first = n < 3 ? 0 : (c + n - 1) % n;
+        count = n < 3 ? n : 3;
+    } else {
+        first = max(c - 1, 0);
+        count = min(c + 1, n - 1) - first + 1;
+    }
+}
+
+struct PairArgs {
+    double md2, inv_bw, scale;
+    unsigned n_bins, K, split, cells;      // cells = P * n_bins
+    unsigned tile, cap;
+    unsigned long long *counts, *sums;     // (B, P, n_bins)
+};
+
+template <bool kPeriodic, bool kLds>
+__global__ void __launch_bounds__(kBlock) k_dcorr_pairs(const Rec *__restrict__ srec, const unsigned *__restrict__ starts, const uint2 *__restrict__ work,
+                                                        const Grid *__restrict__ grids, PairArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
+    unsigned const stride = a.tile + kTilePad;
+    double *tx = reinterpret_cast<double *>(smem);      // [kTileWords][stride]
+    unsigned long long *tmeta = smem + 6 * (size_t)stride;
+    unsigned long long *hsum = smem + kTileWords * (size_t)stride;
+    unsigned *hcount = reinterpret_cast<unsigned *>(hsum + (kLds ? a.cells : 0));
+
+    uint2 const w = work[blockIdx.x];
+    unsigned const o = w.x / a.cap, cell = w.x % a.cap;
+    Grid const g = grids[o];
+    const unsigned *st = starts + (size_t)o * a.cap;
+    unsigned const s_begin = st[cell] + w.y * kChunk, nc = min(st[cell + 1] - s_begin, kChunk);
+    unsigned gs = 1;      // lanes per centre
+    while (2 * gs * nc <= (unsigned)kBlock) gs *= 2;
+    unsigned const ci = threadIdx.x / gs, sl = threadIdx.x % gs;
+    bool const active = ci < nc;
+    unsigned const s = s_begin + ci;
+    Rec q;
+    if (active) q = srec[s];
+    if (kLds) {
+        for (unsigned e = threadIdx.x; e < a.cells; e += kBlock) {
+            hsum[e] = 0ull;
+            hcount[e] = 0u;
+        }
+    }
+    unsigned long long *gcount = a.counts + (size_t)o * a.cells, *gsum = a.sums + (size_t)o * a.cells;
+
+    int const cx = (int)(cell % (unsigned)g.n[0]), cy = (int)(cell / (unsigned)g.n[0] % (unsigned)g.n[1]),
+              cz = (int)(cell / ((unsigned)g.n[0] * (unsigned)g.n[1]));
+    int x0, nx, y0, ny, z0, nz;
+    axis_cells(cx, g.n[0], kPeriodic, x0, nx);
+    axis_cells(cy, g.n[1], kPeriodic, y0, ny);
+    axis_cells(cz, g.n[2], kPeriodic, z0, nz);
+    int const xa1 = min(x0 + nx, g.n[0]), xb1 = x0 + nx - xa1;      // [x0, x0 + nx) split where it wraps past the last cell
+    for (int iz = 0; iz < nz; iz++) {
+        int const pz = (z0 + iz) % g.n[2];
+        for (int iy = 0; iy < ny; iy++) {
+            int const py = (y0 + iy) % g.n[1];
+            unsigned const row = ((unsigned)pz * (unsigned)g.n[1] + (unsigned)py) * (unsigned)g.n[0];
+            for (int span = 0; span < 2; span++) {
+                unsigned const j_begin = max(span ? st[row] : st[row + x0], s_begin + 1u);      // partners later in sorted order only
+                unsigned const j_end = span ? st[row + xb1] : st[row + xa1];
+                for (unsigned j0 = j_begin; j0 < j_end; j0 += a.tile) {
+                    unsigned const nt = min(a.tile, j_end - j0);
+                    __syncthreads();      // the last tile has been read (and, the first time, the histogram is clear)
+                    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(srec + j0);
+                    for (unsigned e = threadIdx.x; e < nt * 8; e += kBlock) {
+                        unsigned const field = e % 8;
+                        if (field < kTileWords) smem[field * stride + e / 8] = src[e];
+                    }
+                    __syncthreads();
+                    if (!active) continue;
+                    for (unsigned k0 = sl; k0 < nt; k0 += kUnroll * gs) {
+                        // the positions of kUnroll partners first, so that their LDS reads are in flight together
+                        double r2[kUnroll];
+#pragma unroll
+                        for (unsigned u = 0; u < kUnroll; u++) {
+                            unsigned const k = k0 + u * gs, kc = min(k, nt - 1u);
+                            double dx = q.p[0] - tx[kc], dy = q.p[1] - tx[stride + kc], dz = q.p[2] - tx[2 * stride + kc];
+                            if (kPeriodic) {
+                                dx = min_image(dx, g.box[0]);
+                                dy = min_image(dy, g.box[1]);
+                                dz = min_image(dz, g.box[2]);
+                            }
+                            r2[u] = k < nt && j0 + k > s ? (dx * dx + dy * dy) + dz * dz : INFINITY;
+                        }
+#pragma unroll
+                        for (unsigned u = 0; u < kUnroll; u++) {
+                            if (!(r2[u] < a.md2)) continue;
+                            unsigned const k = k0 + u * gs;
+                            unsigned long long const bin = (unsigned long long)(sqrt(r2[u]) * a.inv_bw);
+                            if (bin >= a.n_bins) continue;
+                            double const dot = (q.d[0] * tx[3 * stride + k] + q.d[1] * tx[4 * stride + k]) + q.d[2] * tx[5 * stride + k];
+                            unsigned long long const term = (unsigned long long)llrint(dot * a.scale);
+                            unsigned long long const meta = tmeta[k];
+                            unsigned const lj = (unsigned)(meta & 0xffffffffu), chj = (unsigned)(meta >> 32);
+                            unsigned const la = min((unsigned)q.label, lj), lb = max((unsigned)q.label, lj);
+                            unsigned p = la * a.K - la * (la - 1u) / 2u + (lb - la);      // (la = 0: 0 * 0xffffffff / 2 = 0)
+                            if (a.split) p = 2u * p + (q.chain != chj ? 1u : 0u);
+                            unsigned const e = p * a.n_bins + (unsigned)bin;
+                            if (kLds) {
+                                atomicAdd(&hcount[e], 1u);
+                                atomicAdd(&hsum[e], term);
+                            } else {
+                                atomicAdd(&gcount[e], 1ull);
+                                atomicAdd(&gsum[e], term);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (kLds) {
+        __syncthreads();
+        for (unsigned e = threadIdx.x; e < a.cells; e += kBlock) {
+            unsigned const c = hcount[e];
+            if (c) {
+                atomicAdd(&gcount[e], (unsigned long long)c);
+                if (hsum[e]) atomicAdd(&gsum[e], hsum[e]);
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kBlock) k_dcorr_first_bad(const T *__restrict__ x, size_t n, unsigned long long *first_bad)
+{
+    unsigned long long bad = kNoBadIndex;
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
+        if (!isfinite(x[i])) bad = min(bad, (unsigned long long)i);
+    if (bad != kNoBadIndex) atomicMin(first_bad, bad);
+}
+
+// The dynamic LDS a block of k_dcorr_pairs may ask for on a device: all 160 KiB of a gfx950 CU where the opt-in is granted (once per
+// device, gdyn_once.hpp), else 128 KiB, else the 64 KiB that need none.  A refusal only makes the tiles and the LDS histogram smaller.
+int lds_budget(int device)
+{
+    static DeviceOnce<> once;
+    int const bytes = once.run(device, [](int) {
+        const void *kernels[] = {reinterpret_cast<const void *>(&k_dcorr_pairs<false, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<false, true>),
+                                 reinterpret_cast<const void *>(&k_dcorr_pairs<true, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<true, true>)};
+        for (int want : {160 * 1024, 128 * 1024}) {
+            bool ok = true;
+            for (const void *k : kernels) ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess && ok;
+            if (ok) return want;
+            (void)hipGetLastError();
+        }
+        return 64 * 1024;
+    });
+    return bytes > 0 ? bytes : 64 * 1024;
+}
+
+size_t tile_bytes(unsigned tile) { return (size_t)kTileWords * (tile + kTilePad) * 8; }
+
+// max(n (n - 1) / 2, 1) * (M * 2^S + 1) < 2^62, exactly (M = m * 2^e with a 53-bit integer m)
+bool scale_legal(uint64_t n, double M, int S)
+{
+    if (!(M >= 0.0) || !std::isfinite(M)) return false;
+    typedef unsigned __int128 u128;
+    u128 const lim = (u128)1 << 62, pairs = std::max<u128>((u128)n * (n ? n - 1 : 0) / 2, 1);
+    if (M == 0.0) return pairs < lim;
+    int e = 0;
+    uint64_t const m = (uint64_t)std::ldexp(std::frexp(M, &e), 53);
+    int const sh = e - 53 + S;
+    if (sh >= 0) {
+        if (sh >= 62) return false;
+        u128 const v = (u128)m << sh;
+        return v < lim && pairs * (v + 1) < lim;
+    }
+    int const k = -sh;
+    if (k >= 64) return pairs * 2 < lim;      // M * 2^S < 2^-11
+    return pairs * ((u128)m + ((u128)1 << k)) < (lim << k);
+}
+
+}  // namespace
+
+struct gd_dcorr : gd::handle {
+    unsigned max_frames = 0;
+    int lds_bytes = 64 * 1024;
+    unsigned F = 0, N = 0;         // F == 0: no history; N stays, for the labels and chains that belong to it
+    bool is_f64 = false;
+    dbuf<float> xf;
+    dbuf<double> xd;
+    dbuf<unsigned long long> first_bad;
+    // selection: labels and chains
+    unsigned K = 1, n_sel = 0;
+    bool have_labels = false, have_chains = false;
+    std::vector<uint64_t> members;      // beads per label
+    dbuf<unsigned> sel;                 // the selected beads, ascending
+    dbuf<int> label_dev;
+    dbuf<unsigned> chain_dev;
+    // per call
+    dbuf<unsigned long long> tmax, self_sum;
+    // per batch
+    dbuf<unsigned long long> bbox;
+    dbuf<Grid> grids;
+    dbuf<Rec> grec, srec;
+    dbuf<unsigned long long> keys[2];
+    dbuf<unsigned> vals[2], starts, n_work;
+    dbuf<uint2> work;
+    dbuf<char> sort_tmp;
+    dbuf<unsigned long long> counts, sums;
+
+    const void *x() const { return is_f64 ? (const void *)xd.p : (const void *)xf.p; }
+    unsigned P() const { return K * (K + 1) / 2 * (have_chains ? 2u : 1u); }
+};
+
+namespace {
+
+int select_all(gd_dcorr *h, unsigned N)
+{
+    std::vector<unsigned> all(N);
+    std::iota(all.begin(), all.end(), 0u);
+    dbuf<unsigned> dev;
+    HIPCHK(dev.upload(all.data(), N));
+    h->sel = std::move(dev);
+    h->n_sel = N;
+    h->K = 1;
+    h->have_labels = false;
+    h->members.assign(1, N);
+    return GD_OK;
+}
+
+// the history is on the device: the non-finite check, then the handle holds it (or none)
+int finish_history(gd_dcorr *h, const char *who, unsigned frames, unsigned n_beads, bool is_f64)
+{
+    size_t const n = (size_t)frames * n_beads * 3;
+    HIPCHK(h->first_bad.ensure(1));
+    HIPCHK(hipMemsetAsync(h->first_bad.p, 0xff, sizeof(unsigned long long), h->stream));
+    unsigned const blocks = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 8192);
+    if (is_f64) hipLaunchKernelGGL(k_dcorr_first_bad<double>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xd.p, n, h->first_bad.p);
+    else hipLaunchKernelGGL(k_dcorr_first_bad<float>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xf.p, n, h->first_bad.p);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = kNoBadIndex;
+    HIPCHK(hipMemcpyAsync(&bad, h->first_bad.p, sizeof bad, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bad != kNoBadIndex) return fail(GD_EINVAL, "%s: non-finite coordinate at %llu", who, bad);
+    if (n_beads != h->N || !h->sel.p) {      // labels and chains belonged to another N
+        if (int rc = select_all(h, n_beads)) return rc;
+        h->have_chains = false;
+    }
+    h->F = frames;
+    h->N = n_beads;
+    h->is_f64 = is_f64;
+    return GD_OK;
+}
+
+int check_shape(const char *who, uint32_t frames, uint32_t n_beads)
+{
+    if (frames == 0 || n_beads == 0) return fail(GD_EINVAL, "%s: empty history (%u frames of %u beads)", who, frames, n_beads);
+    if (n_beads > (1u << 28)) return fail(GD_EINVAL, "%s: %u beads exceed 2^28", who, n_beads);
+    return GD_OK;
+}
+
+uint32_t origins_of(const gd_dcorr *h, uint32_t lag, uint32_t first, uint32_t n_origins, uint32_t stride)
+{
+    if (!h || !h->F || !stride || !lag) return 0;
+    if (n_origins) return n_origins;
+    if ((uint64_t)first + lag >= h->F) return 0;
+    return (h->F - lag - first - 1) / stride + 1;
+}
+
+struct Call {      // what a batch needs of its call
+    unsigned lag;
+    Origins og;
+    Space sp;
+    double bin_width, md, scale;
+    unsigned n_bins, cap;
+    bool lds;
+    unsigned tile;
+};
+
+int run_batch(gd_dcorr *h, const Call &c, unsigned o0, unsigned B, uint64_t *count_out, int64_t *sum_out)
+{
+    hipStream_t st = h->stream;
+    unsigned const n = h->n_sel;
+    size_t const nb = (size_t)B * n, slots = (size_t)B * c.cap, cells = (size_t)h->P() * c.n_bins;
+    HIPCHK(h->bbox.ensure(6 * (size_t)B));
+    HIPCHK(h->grids.ensure(B));
+    HIPCHK(h->grec.ensure(nb));
+    HIPCHK(h->srec.ensure(nb));
+    for (int k = 0; k < 2; k++) {
+        HIPCHK(h->keys[k].ensure(nb));
+        HIPCHK(h->vals[k].ensure(nb));
+    }
+    HIPCHK(h->starts.ensure(slots + 1));
+    HIPCHK(h->work.ensure(nb / kChunk + std::min(nb, slots) + 1));
+    HIPCHK(h->n_work.ensure(1));
+    HIPCHK(h->counts.ensure((size_t)B * cells));
+    HIPCHK(h->sums.ensure((size_t)B * cells));
+    const int *label = h->have_labels ? h->label_dev.p : nullptr;
+    const unsigned *chain = h->have_chains ? h->chain_dev.p : nullptr;
+    int const is64 = h->is_f64;
+    if (!c.sp.periodic) {
+        std::vector<unsigned long long> init(6 * (size_t)B);
+        for (size_t k = 0; k < init.size(); k++) init[k] = k % 6 < 3 ? ~0ull : 0ull;
+        HIPCHK(hipMemcpyAsync(h->bbox.p, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));      // init is about to go out of scope
+        hipLaunchKernelGGL(k_dcorr_bbox, dim3(std::min(blocks_for(n, kBlock), 16u), B), dim3(kBlock), 0, st, h->x(), is64, h->N, h->sel.p, n, c.og, o0, h->bbox.p);
+    }
+    hipLaunchKernelGGL(k_dcorr_grid, dim3(blocks_for(B, kBlock)), dim3(kBlock), 0, st, h->bbox.p, B, c.sp, c.cap, h->grids.p);
+    hipLaunchKernelGGL(k_dcorr_disp, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->x(), is64, h->N, h->sel.p, label, chain, n, c.lag, c.og, o0, B,
+                       h->grids.p, c.sp.periodic, c.cap, h->keys[0].p, h->vals[0].p, h->grec.p);
+    HIPCHK(hipGetLastError());
+    unsigned bits = 1;
+    while (bits < 64 && ((unsigned long long)slots >> bits)) bits++;
+    size_t tmp_bytes = 0;
+    HIPCHK(gd_sort_contacts(nullptr, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
+    HIPCHK(h->sort_tmp.ensure(tmp_bytes));
+    HIPCHK(gd_sort_contacts(h->sort_tmp.p, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
+    hipLaunchKernelGGL(k_dcorr_sorted, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->grec.p, h->vals[1].p, nb, h->srec.p);
+    hipLaunchKernelGGL(k_dcorr_starts, dim3(blocks_for(slots + 1, kBlock)), dim3(kBlock), 0, st, h->keys[1].p, nb, slots + 1, h->starts.p);
+    HIPCHK(hipMemsetAsync(h->n_work.p, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_dcorr_work, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, st, h->starts.p, slots, h->work.p, h->n_work.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(h->counts.p, 0, (size_t)B * cells * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(h->sums.p, 0, (size_t)B * cells * sizeof(unsigned long long), st));
+    unsigned n_work = 0;
+    HIPCHK(hipMemcpyAsync(&n_work, h->n_work.p, sizeof n_work, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (n_work > h->work.n) return fail(GD_EHIP, "gd_dcorr_pairs: %u work items for %zu", n_work, h->work.n);
+    if (n_work) {
+        PairArgs a;
+        a.md2 = c.md * c.md;
+        a.inv_bw = 1 / c.bin_width;
+        a.scale = c.scale;
+        a.n_bins = c.n_bins;
+        a.K = h->K;
+        a.split = h->have_chains;
+        a.cells = (unsigned)cells;
+        a.tile = c.tile;
+        a.cap = c.cap;
+        a.counts = h->counts.p;
+        a.sums = h->sums.p;
+        size_t const shmem = tile_bytes(c.tile) + (c.lds ? cells * 12 : 0);
+        dim3 const grid(n_work), block(kBlock);
+        if (c.sp.periodic && c.lds)
+            hipLaunchKernelGGL((k_dcorr_pairs<true, true>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+        else if (c.sp.periodic)
+            hipLaunchKernelGGL((k_dcorr_pairs<true, false>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+        else if (c.lds)
+            hipLaunchKernelGGL((k_dcorr_pairs<false, true>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+        else
+            hipLaunchKernelGGL((k_dcorr_pairs<false, false>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(count_out, h->counts.p, (size_t)B * cells * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(sum_out, h->sums.p, (size_t)B * cells * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gd_dcorr_abi_version(void) { return GD_DCORR_ABI_VERSION; }
+
+uint32_t gd_dcorr_bins(double bin_width, double max_distance)
+{
+    if (!(bin_width > 0.0) || !(max_distance > 0.0) || !std::isfinite(bin_width) || !std::isfinite(max_distance)) return 0;
+    double const n = std::ceil(max_distance / bin_width);
+    return n >= 1.0 && n <= (double)GD_DCORR_MAX_BINS ? (uint32_t)n : 0u;
+}
+
+int gd_dcorr_create(const gd_dcorr_desc *desc, gd_dcorr **out)
+{
+    if (int rc = gd::open("gd_dcorr_create", desc, out)) return rc;
+    (*out)->max_frames = desc->max_frames_per_launch;
+    (*out)->lds_bytes = lds_budget(desc->device);
+    return GD_OK;
+}
+
+int gd_dcorr_destroy(gd_dcorr *h) { return gd::close(h); }
+
+int gd_dcorr_set_history(gd_dcorr *h, const void *xyz, uint32_t frames, uint32_t n_beads, int is_f64)
+{
+    const char *who = "gd_dcorr_set_history";
+    if (!h || !xyz) return fail(GD_EINVAL, "%s: NULL argument", who);
+    if (int rc = check_shape(who, frames, n_beads)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    size_t const n = (size_t)frames * n_beads * 3;
+    h->F = 0;      // the buffer is about to be overwritten
+    if (is_f64) HIPCHK(h->xd.upload(static_cast<const double *>(xyz), n));
+    else HIPCHK(h->xf.upload(static_cast<const float *>(xyz), n));
+    return finish_history(h, who, frames, n_beads, is_f64 != 0);
+}
+
+int gd_dcorr_set_history_live(gd_dcorr *h, gd_live_history *history, uint32_t replica)
+{
+    const char *who = "gd_dcorr_set_history_live";
+    if (!h || !history) return fail(GD_EINVAL, "%s: NULL handle", who);
+    gd_live_history_shape const v = gd_live_history_shape_of(history);
+    uint32_t slot = 0;
+    if (int rc = gd_live_history_slot(history, who, replica, &slot)) return rc;
+    if (v.device != h->device) return fail(GD_EINVAL, "%s: the recorder is on device %d, the analysis handle on device %d", who, v.device, h->device);
+    if (!v.frames) return fail(GD_ESTATE, "%s: no frame recorded", who);
+    if (int rc = check_shape(who, v.frames, v.N)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    size_t const M = (size_t)v.N * 3;
+    h->F = 0;
+    HIPCHK(h->xf.ensure((size_t)v.frames * M));
+    for (uint32_t f0 = 0; f0 < v.frames; f0 += v.frames_per_block) {      // one strided copy per block of the recorder
+        uint32_t const nf = std::min(v.frames_per_block, v.frames - f0);
+        HIPCHK(hipMemcpy2DAsync(h->xf.p + (size_t)f0 * M, M * sizeof(float), gd_live_history_frame(history, f0, slot), v.frame_stride * sizeof(float),
+                                M * sizeof(float), nf, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return finish_history(h, who, v.frames, v.N, false);
+}
+
+int gd_dcorr_set_labels(gd_dcorr *h, const int32_t *label, uint32_t n_labels)
+{
+    const char *who = "gd_dcorr_set_labels";
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the labels are N values of its beads)", who);
+    if (!label) {
+        if (n_labels > 1) return fail(GD_EINVAL, "%s: %u labels without a label array", who, n_labels);
+        HIPCHK(hipSetDevice(h->device));
+        return select_all(h, h->N);
+    }
+    if (n_labels == 0 || n_labels > GD_DCORR_MAX_LABELS) return fail(GD_EINVAL, "%s: %u labels (1 to %d)", who, n_labels, GD_DCORR_MAX_LABELS);
+    std::vector<unsigned> chosen;
+    std::vector<uint64_t> members(n_labels, 0);
+    for (unsigned i = 0; i < h->N; i++) {
+        if (label[i] < -1 || label[i] >= (int64_t)n_labels) return fail(GD_EINVAL, "%s: label[%u] = %d is not in [-1, %u)", who, i, label[i], n_labels);
+        if (label[i] >= 0) {
+            chosen.push_back(i);
+            members[label[i]]++;
+        }
+    }
+    HIPCHK(hipSetDevice(h->device));
+    dbuf<unsigned> sel;
+    dbuf<int> dev;
+    HIPCHK(sel.upload(chosen.data(), chosen.size()));
+    HIPCHK(dev.upload(label, h->N));
+    h->sel = std::move(sel);
+    h->label_dev = std::move(dev);
+    h->n_sel = (unsigned)chosen.size();
+    h->K = n_labels;
+    h->have_labels = true;
+    h->members = std::move(members);
+    return GD_OK;
+}
+
+int gd_dcorr_set_chains(gd_dcorr *h, const uint32_t *chain_id)
+{
+    const char *who = "gd_dcorr_set_chains";
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the chains are N values of its beads)", who);
+    if (!chain_id) {
+        h->have_chains = false;
+        return GD_OK;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    dbuf<unsigned> dev;
+    HIPCHK(dev.upload(chain_id, h->N));
+    h->chain_dev = std::move(dev);
+    h->have_chains = true;
+    return GD_OK;
+}
+
+uint32_t gd_dcorr_classes(const gd_dcorr *h) { return h ? h->P() : 0u; }
+
+uint32_t gd_dcorr_origins(const gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_origins, uint32_t origin_stride)
+{
+    return origins_of(h, lag, first_origin, n_origins, origin_stride);
+}
+
+int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_origins, uint32_t origin_stride, const double *box, double bin_width,
+                   double max_distance, int32_t scale_bits, int32_t *scale_used, uint64_t *count_out, int64_t *sum_out, uint64_t *self_count_out,
+                   int64_t *self_sum_out)
+{
+    const char *who = "gd_dcorr_pairs";
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (lag == 0) return fail(GD_EINVAL, "%s: lag 0", who);
+    if (origin_stride == 0) return fail(GD_EINVAL, "%s: origin stride 0", who);
+    if (n_origins && (uint64_t)first_origin + (uint64_t)(n_origins - 1) * origin_stride + lag >= h->F)
+        return fail(GD_EINVAL, "%s: origin %llu with lag %u lies beyond the %u frames", who,
+                    (unsigned long long)first_origin + (unsigned long long)(n_origins - 1) * origin_stride, lag, h->F);
+    if (box)
+        for (int a = 0; a < 3; a++)
+            if (!(box[a] > 0.0) || !std::isfinite(box[a])) return fail(GD_EINVAL, "%s: box[%d] = %g is not positive and finite", who, a, box[a]);
+    unsigned const n_bins = gd_dcorr_bins(bin_width, max_distance);
+    if (!n_bins)
+        return fail(GD_EINVAL, "%s: bin width %g and max distance %g must be positive and finite, with at most %u bins", who, bin_width, max_distance,
+                    GD_DCORR_MAX_BINS);
+    if (scale_bits != 0 && scale_bits != GD_DCORR_SCALE_UNIT && (scale_bits < 0 || scale_bits > GD_DCORR_MAX_SCALE_BITS))
+        return fail(GD_EINVAL, "%s: scale_bits %d (0: automatic, 1 to %d, or GD_DCORR_SCALE_UNIT)", who, scale_bits, GD_DCORR_MAX_SCALE_BITS);
+    size_t const cells = (size_t)h->P() * n_bins;
+    if (cells > (1u << 30)) return fail(GD_EINVAL, "%s: %u classes of %u bins exceed 2^30 cells", who, h->P(), n_bins);
+    Origins const og{first_origin, origin_stride, origins_of(h, lag, first_origin, n_origins, origin_stride)};
+    if (og.count && (!count_out || !sum_out)) return fail(GD_EINVAL, "%s: NULL output", who);
+    if ((self_count_out == nullptr) != (self_sum_out == nullptr)) return fail(GD_EINVAL, "%s: one self output without the other", who);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    unsigned const n = h->n_sel, K = h->K;
+    const int *label = h->have_labels ? h->label_dev.p : nullptr;
+
+    // the largest t2 of the call, then the scale
+    double M = 0.0;
+    if (og.count && n) {
+        HIPCHK(h->tmax.ensure(1));
+        HIPCHK(hipMemsetAsync(h->tmax.p, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_dcorr_tmax, dim3(std::min(blocks_for((size_t)og.count * n, kBlock), 2048u)), dim3(kBlock), 0, st, h->x(), (int)h->is_f64, h->N, h->sel.p, n, lag,
+                           og, h->tmax.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&M, h->tmax.p, sizeof M, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    int S = scale_bits == GD_DCORR_SCALE_UNIT ? 0 : scale_bits;
+    if (scale_bits == 0) {
+        S = GD_DCORR_MAX_SCALE_BITS;
+        while (S >= 0 && !scale_legal(n, M, S)) S--;
+        if (S < 0) return fail(GD_EINVAL, "%s: the largest squared displacement %g of %u beads overflows the sums at every scale", who, M, n);
+    } else if (!scale_legal(n, M, S)) {
+        return fail(GD_EINVAL, "%s: scale 2^%d overflows the sums of %u beads whose largest squared displacement is %g", who, S, n, M);
+    }
+    if (scale_used) *scale_used = S;
+    if (!og.count) return GD_OK;
+    double const scale = std::ldexp(1.0, S);
+
+    if (self_sum_out) {
+        for (unsigned o = 0; o < og.count; o++)
+            for (unsigned l = 0; l < K; l++) self_count_out[(size_t)o * K + l] = h->members[l];
+        std::memset(self_sum_out, 0, (size_t)og.count * K * sizeof(int64_t));
+        if (n) {
+            HIPCHK(h->self_sum.ensure((size_t)og.count * K));
+            HIPCHK(hipMemsetAsync(h->self_sum.p, 0, (size_t)og.count * K * sizeof(unsigned long long), st));
+            for (unsigned o0 = 0; o0 < og.count; o0 += 65535u)
+                hipLaunchKernelGGL(k_dcorr_self, dim3(blocks_for(n, kBlock), std::min(65535u, og.count - o0)), dim3(kBlock), 0, st, h->x(), (int)h->is_f64,
+                                   h->N, h->sel.p, label, n, lag, og, o0, scale, K, h->self_sum.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(self_sum_out, h->self_sum.p, (size_t)og.count * K * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
+    if (n < 2) {      // nothing to pair
+        std::memset(count_out, 0, (size_t)og.count * cells * sizeof(uint64_t));
+        std::memset(sum_out, 0, (size_t)og.count * cells * sizeof(int64_t));
+        return GD_OK;
+    }
+
+    Call c;
+    c.lag = lag;
+    c.og = og;
+    c.sp.periodic = box != nullptr;
+    for (int a = 0; a < 3; a++) c.sp.box[a] = box ? box[a] : 0.0;
+    c.sp.cell_side = max_distance * (1.0 + kCellSlack);
+    c.bin_width = bin_width;
+    c.md = max_distance;
+    c.scale = scale;
+    c.n_bins = n_bins;
+    c.cap = std::max(4096u, n);
+    // the histogram in LDS: a block adds at most kChunk * n to one uint32 counter; the tile takes what the table leaves, 64 to 256 records
+    c.tile = 256;
+    c.lds = cells <= GD_DCORR_LDS_BINS && n < (1u << 24) && cells * 12 + tile_bytes(64) <= (size_t)h->lds_bytes;
+    while (c.tile > 64 && tile_bytes(c.tile) + (c.lds ? cells * 12 : 0) > (size_t)h->lds_bytes) c.tile /= 2;
+    size_t const want = h->max_frames ? h->max_frames : ((size_t)1 << 20) / n + 1;      // ~1M beads per launch
+    // sorted indices stay 32-bit, origins fit gridDim.y, the cell starts of a batch stay below 2^26 entries
+    size_t const limit = std::min<size_t>(std::min<size_t>(65535, ((size_t)1 << 26) / c.cap), ((size_t)1 << 30) / n);
+    unsigned const B = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(want, limit), og.count));
+    for (unsigned o0 = 0; o0 < og.count; o0 += B) {
+        unsigned const b = std::min(B, og.count - o0);
+        if (int rc = run_batch(h, c, o0, b, count_out + (size_t)o0 * cells, sum_out + (size_t)o0 * cells)) return rc;
+    }
+    return GD_OK;
+}
+
+}  // extern "C"
