@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr) share: loading libgdyn with a check of
+"""What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap) share: loading libgdyn with a check of
 one module's symbols and ABI version, the life cycle of a ``gd_<x>`` handle, and the normalisation of frames."""
 from __future__ import annotations
 

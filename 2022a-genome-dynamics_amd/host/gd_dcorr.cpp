@@ -31,17 +31,6 @@ struct options {
     std::vector<std::string> trajfiles;
 };
 
-bool parse_box(std::string const &v, double box[3])
-{
-    std::size_t at = 0;
-    for (int a = 0; a < 3; a++) {
-        auto const comma = a < 2 ? v.find(',', at) : v.size();
-        if (comma == std::string::npos || !gd::cli::parse_float(v.substr(at, comma - at), box[a]) || !(box[a] > 0) || !std::isfinite(box[a])) return false;
-        at = comma + 1;
-    }
-    return true;
-}
-
 int parse(int argc, char **argv, options &o, std::string &err)
 {
     std::vector<std::string> pos;

@@ -1,0 +1,281 @@
+// gd_distance_map -- distance and contact-frequency maps of trajectories on the device (include/gdyn_dmap.h): for every trajectory
+// file, the sums behind the mean and rms spatial distance of every pair of bins and the number of bead pairs closer than each
+// threshold, over the frames of a phase.  The reference has no such analysis.  Per input sample, under /dmap/<name>/<sample>/ of the
+// output file, with S the selected bins:
+//   bins (S, 2) uint32, bin_chain (S) uint32, chain_names (C) fixed-length strings, thresholds (T) float64,
+//   sum1, sum2 (S, S) float64, hits (T, S, S) uint64, count (S, S) uint64       mean distance = sum1 / count, frequency = hits / count
+//   gd_distance_map [--name PHASE] [--rebin-rate K] [--by-chain] [--chains a,b,...] [--thresholds t1,t2,...] [--frames FIRST:COUNT]
+//                   [--box Lx,Ly,Lz] [--dry-run] outfile trajfiles...
+// --name: the phase whose frames are read (/snapshots/PHASE, default interphase) and the name of the output group.  Chains: the
+// phase's chromosome_ranges, else the file's, else one chain of all beads, as gd_msd reads them.  Bins: K consecutive beads of a chain
+// (default 1; the last bin of a chain is shorter, no bin spans two chains: tests/dmap_restatement.py, bins_from_chains), or with
+// --by-chain every non-empty chain as one bin.  --chains restricts rows and columns to the bins of the chains named.  --dry-run prints
+// the plan and, for every trajectory file given, its shape and bins; no device is used.
+#include "../../include/gdyn_dmap.h"
+#include "gd_lag_cli.hpp"
+
+using namespace gd::lagcli;
+
+namespace {
+
+struct options {
+    std::string name = "interphase";
+    long rate = 1;
+    bool by_chain = false, has_box = false, has_frames = false, dry_run = false;
+    std::vector<std::string> chains;
+    std::vector<double> thresholds;
+    long first_frame = 0, n_frames = 0;
+    double box[3] = {0, 0, 0};
+    std::string outfile;
+    std::vector<std::string> trajfiles;
+};
+
+std::vector<std::string> split(std::string const &v)
+{
+    std::vector<std::string> out;
+    std::size_t at = 0;
+    while (at <= v.size()) {
+        auto const comma = std::min(v.find(',', at), v.size());
+        out.push_back(v.substr(at, comma - at));
+        at = comma + 1;
+    }
+    return out;
+}
+
+bool parse_thresholds(std::string const &v, std::vector<double> &out)
+{
+    out.clear();
+    for (auto const &s : split(v)) {
+        double t = 0;
+        if (!gd::cli::parse_float(s, t) || !(t > 0) || !std::isfinite(t)) return false;
+        out.push_back(t);
+    }
+    return out.size() <= GD_DMAP_MAX_THRESHOLDS;
+}
+
+bool parse_chains(std::string const &v, std::vector<std::string> &out)
+{
+    out = split(v);
+    for (auto const &s : out)
+        if (s.empty() || std::count(out.begin(), out.end(), s) != 1) return false;
+    return true;
+}
+
+bool parse_frames(std::string const &v, long &first, long &count)
+{
+    auto const colon = v.find(':');
+    return colon != std::string::npos && gd::cli::parse_int(v.substr(0, colon), first) && gd::cli::parse_int(v.substr(colon + 1), count) && first >= 0 &&
+           count >= 1 && first <= 0xffffffffl && count <= 0xffffffffl;
+}
+
+int parse(int argc, char **argv, options &o, std::string &err)
+{
+    std::vector<std::string> pos;
+    for (int k = 1; k < argc; k++) {
+        std::string a = argv[k], v;
+        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
+            if (a == "--dry-run") { o.dry_run = true; continue; }
+            if (a == "--by-chain") { o.by_chain = true; continue; }
+            auto eq = a.find('=');
+            bool const inline_value = eq != std::string::npos;
+            std::string const key = inline_value ? a.substr(0, eq) : a;
+            if (key != "--name" && key != "--rebin-rate" && key != "--chains" && key != "--thresholds" && key != "--frames" && key != "--box") {
+                err = "unrecognized arguments: " + a;
+                return 2;
+            }
+            if (inline_value) v = a.substr(eq + 1);
+            else if (k + 1 < argc) v = argv[++k];
+            else { err = "argument " + key + ": expected one argument"; return 2; }
+            bool ok = true;
+            if (key == "--name") ok = !(o.name = v).empty() && v.find('/') == std::string::npos;
+            else if (key == "--rebin-rate") ok = gd::cli::parse_int(v, o.rate) && o.rate >= 1 && o.rate <= (1l << 28);
+            else if (key == "--chains") ok = parse_chains(v, o.chains);
+            else if (key == "--thresholds") ok = parse_thresholds(v, o.thresholds);
+            else if (key == "--frames") ok = o.has_frames = parse_frames(v, o.first_frame, o.n_frames);
+            else ok = o.has_box = parse_box(v, o.box);
+            if (!ok) { err = "argument " + key + ": invalid value: '" + v + "'"; return 2; }
+        } else {
+            pos.push_back(a);
+        }
+    }
+    if (o.by_chain && o.rate != 1) { err = "argument --by-chain: not allowed with argument --rebin-rate"; return 2; }
+    if (o.dry_run && pos.empty()) return 0;
+    if (pos.size() < 2) { err = "the following arguments are required: outfile, trajfiles"; return 2; }
+    o.outfile = pos[0];
+    o.trajfiles.assign(pos.begin() + 1, pos.end());
+    return 0;
+}
+
+struct plan {      // the bins of one trajectory file and the ones selected
+    std::vector<uint32_t> bins, bin_chain;      // (B, 2), (B)
+    std::vector<uint32_t> selected;             // ascending bin indices
+    uint32_t first_frame = 0, n_frames = 0;
+};
+
+// `rate` consecutive beads per bin within each chain; the last bin of a chain is shorter (Dmap.bins_from_chains)
+void bins_from_chains(std::vector<uint32_t> const &chains, uint32_t rate, plan &p)
+{
+    for (std::size_t c = 0; c < chains.size() / 2; c++)
+        for (uint32_t a = chains[2 * c]; a < chains[2 * c + 1]; a += rate) {
+            p.bins.push_back(a);
+            p.bins.push_back(std::min<uint64_t>((uint64_t)a + rate, chains[2 * c + 1]));
+            p.bin_chain.push_back((uint32_t)c);
+        }
+}
+
+plan make_plan(options const &o, layout const &l, std::string const &path, uint32_t F)
+{
+    plan p;
+    if (o.by_chain) {
+        for (std::size_t c = 0; c < l.chains.size() / 2; c++)
+            if (l.chains[2 * c] < l.chains[2 * c + 1]) {
+                p.bins.push_back(l.chains[2 * c]);
+                p.bins.push_back(l.chains[2 * c + 1]);
+                p.bin_chain.push_back((uint32_t)c);
+            }
+    } else {
+        bins_from_chains(l.chains, (uint32_t)o.rate, p);
+    }
+    std::vector<char> wanted(l.chain_names.size(), o.chains.empty());
+    for (auto const &name : o.chains) {
+        auto const it = std::find(l.chain_names.begin(), l.chain_names.end(), name);
+        gd::h5::check(it != l.chain_names.end(), path + ": no chain named " + name);
+        wanted[it - l.chain_names.begin()] = 1;
+    }
+    for (uint32_t b = 0; b < p.bin_chain.size(); b++)
+        if (wanted[p.bin_chain[b]]) p.selected.push_back(b);
+    gd::h5::check(!p.selected.empty(), path + ": no bin selected");
+    p.first_frame = o.has_frames ? (uint32_t)o.first_frame : 0;
+    p.n_frames = o.has_frames ? (uint32_t)o.n_frames : F;
+    gd::h5::check((uint64_t)p.first_frame + p.n_frames <= F, path + ": --frames " + std::to_string(p.first_frame) + ":" + std::to_string(p.n_frames) + " of " +
+                                                                 std::to_string(F) + " frames");
+    return p;
+}
+
+// the runs of consecutive bin indices of `selected`: (place in selected, first bin, length)
+struct run {
+    std::size_t at;
+    uint32_t first, n;
+};
+
+std::vector<run> runs_of(std::vector<uint32_t> const &selected)
+{
+    std::vector<run> out;
+    for (std::size_t k = 0; k < selected.size(); k++) {
+        if (!out.empty() && out.back().first + out.back().n == selected[k]) out.back().n++;
+        else out.push_back({k, selected[k], 1});
+    }
+    return out;
+}
+
+std::string join_doubles(std::vector<double> const &v)
+{
+    std::string s;
+    for (std::size_t k = 0; k < v.size(); k++) s += (k ? "," : "") + gd::cli::py_float(v[k]);
+    return s;
+}
+
+struct device {      // one gd_dmap handle; every failure of the library ends the program with its message
+    gd_dmap *h = nullptr;
+    device()
+    {
+        gd_dmap_desc d{0, 0};
+        gd::cli::check(gd_dmap_create(&d, &h));
+    }
+    ~device() { gd_dmap_destroy(h); }
+};
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    options o;
+    std::string err;
+    if (parse(argc, argv, o, err)) {
+        std::fprintf(stderr,
+                     "usage: gd_distance_map [--name PHASE] [--rebin-rate K] [--by-chain] [--chains a,b,...] [--thresholds t1,t2,...] [--frames FIRST:COUNT] "
+                     "[--box Lx,Ly,Lz] [--dry-run] outfile trajfiles ...\ngd_distance_map: error: %s\n",
+                     err.c_str());
+        return 2;
+    }
+    try {
+        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+        if (o.dry_run) {
+            std::string chains;
+            for (std::size_t k = 0; k < o.chains.size(); k++) chains += (k ? "," : "") + o.chains[k];
+            std::printf("name\t%s\nbins\t%s\nchains\t%s\nthresholds\t%s\nframes\t%s\nbox\t%s\n", o.name.c_str(),
+                        o.by_chain ? "by chain" : ("rate " + std::to_string(o.rate)).c_str(), o.chains.empty() ? "all" : chains.c_str(),
+                        o.thresholds.empty() ? "none" : join_doubles(o.thresholds).c_str(),
+                        o.has_frames ? (std::to_string(o.first_frame) + ":" + std::to_string(o.n_frames)).c_str() : "all",
+                        o.has_box ? join_doubles({o.box[0], o.box[1], o.box[2]}).c_str() : "open");
+            for (auto const &path : o.trajfiles) {
+                uint32_t F = 0, N = 0;
+                gd::flow::load_history(path, F, N, o.name);
+                layout const l = read_layout(path, o.name, "all", N);
+                plan const p = make_plan(o, l, path, F);
+                std::printf("sample\t%s\tframes %u\tbeads %u\tchains %zu\tbins %zu\tselected %zu\n", gd::cli::sample_name(path).c_str(), F, N, l.chains.size() / 2,
+                            p.bin_chain.size(), p.selected.size());
+            }
+            return 0;
+        }
+        device dev;
+        gd::h5::hid out(gd::cli::open_output(o.outfile));
+        gd::cli::stopwatch sw;
+        for (auto const &path : o.trajfiles) {
+            uint32_t F = 0, N = 0;
+            auto const hist = gd::flow::load_history(path, F, N, o.name);
+            layout const l = read_layout(path, o.name, "all", N);
+            plan const p = make_plan(o, l, path, F);
+            sw.read += sw.lap();
+            std::size_t const S = p.selected.size(), T = o.thresholds.size();
+            std::vector<double> sum1(S * S), sum2(S * S);
+            std::vector<uint64_t> hits(T * S * S), count(S * S);
+            gd::cli::check(gd_dmap_set_history(dev.h, hist.data(), F, N, 0));
+            gd::cli::check(gd_dmap_set_bins(dev.h, p.bins.data(), (uint32_t)p.bin_chain.size()));
+            auto const runs = runs_of(p.selected);
+            std::vector<double> r1, r2;
+            std::vector<uint64_t> rh, rc;
+            for (run const &a : runs)
+                for (run const &b : runs) {      // one rectangle per pair of runs of selected bins: a cell does not know its region
+                    std::size_t const cells = (std::size_t)a.n * b.n;
+                    r1.resize(cells), r2.resize(cells), rc.resize(cells), rh.resize(T * cells);
+                    gd::cli::check(gd_dmap_map(dev.h, a.first, a.n, b.first, b.n, p.first_frame, p.n_frames, o.has_box ? o.box : nullptr, o.thresholds.data(),
+                                               (uint32_t)T, r1.data(), r2.data(), T ? rh.data() : nullptr, rc.data()));
+                    for (std::size_t i = 0; i < a.n; i++)
+                        for (std::size_t j = 0; j < b.n; j++) {
+                            std::size_t const to = (a.at + i) * S + b.at + j, from = i * b.n + j;
+                            sum1[to] = r1[from];
+                            sum2[to] = r2[from];
+                            count[to] = rc[from];
+                            for (std::size_t t = 0; t < T; t++) hits[t * S * S + to] = rh[t * cells + from];
+                        }
+                }
+            sw.compute += sw.lap();
+            std::vector<uint32_t> bins(2 * S), bin_chain(S);
+            for (std::size_t k = 0; k < S; k++) {
+                bins[2 * k] = p.bins[2 * (std::size_t)p.selected[k]];
+                bins[2 * k + 1] = p.bins[2 * (std::size_t)p.selected[k] + 1];
+                bin_chain[k] = p.bin_chain[p.selected[k]];
+            }
+            gd::h5::hid group(gd::cli::require_group(out, "/dmap/" + o.name + "/" + gd::cli::sample_name(path)));
+            gd::cli::filters const f;
+            hsize_t const s = S, t = T;
+            gd::cli::put_dataset(group, "bins", bins.data(), {s, 2}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, &f);
+            gd::cli::put_dataset(group, "bin_chain", bin_chain.data(), {s}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, &f);
+            gd::cli::put_dataset(group, "thresholds", o.thresholds.data(), {t}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
+            gd::cli::put_dataset(group, "sum1", sum1.data(), {s, s}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
+            gd::cli::put_dataset(group, "sum2", sum2.data(), {s, s}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
+            gd::cli::put_dataset(group, "hits", hits.data(), {t, s, s}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
+            gd::cli::put_dataset(group, "count", count.data(), {s, s}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
+            gd::h5::unlink_if_present(group, "chain_names");
+            gd::h5::write_fixed_string_list(group, "chain_names", l.chain_names);
+            H5Fflush(out, H5F_SCOPE_GLOBAL);
+            sw.write += sw.lap();
+        }
+        sw.report("gd_distance_map");
+    } catch (std::exception const &e) {
+        std::fprintf(stderr, "gd_distance_map: error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

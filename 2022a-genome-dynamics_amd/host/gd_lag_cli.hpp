@@ -1,5 +1,6 @@
-// gd_lag_cli.hpp -- what gd_msd and gd_dcorr share: the lag lists of their command lines (--lags a,b,... / --log-lags K) and what a
-// trajectory file says about its beads (the chains of chromosome_ranges, the groups of particle_types).
+// gd_lag_cli.hpp -- what gd_msd, gd_dcorr and gd_distance_map share: the lag lists of their command lines (--lags a,b,... /
+// --log-lags K), the periods of --box, and what a trajectory file says about its beads (the chains of chromosome_ranges, the groups
+// of particle_types).
 #pragma once
 #include <json.hpp>   // nlohmann/json single header
 
@@ -29,6 +30,18 @@ inline bool parse_list(std::string const &v, std::vector<uint32_t> &out)
         at = comma + 1;
     }
     return !out.empty();
+}
+
+// --box Lx,Ly,Lz: three positive finite periods
+inline bool parse_box(std::string const &v, double box[3])
+{
+    std::size_t at = 0;
+    for (int a = 0; a < 3; a++) {
+        auto const comma = a < 2 ? v.find(',', at) : v.size();
+        if (comma == std::string::npos || !gd::cli::parse_float(v.substr(at, comma - at), box[a]) || !(box[a] > 0) || !std::isfinite(box[a])) return false;
+        at = comma + 1;
+    }
+    return true;
 }
 
 // --log-lags K over a sequence whose largest lag is `longest`: K values spaced geometrically over [1, longest], each rounded
