@@ -404,6 +404,17 @@ class System:
         self.lib.check(f(self._h, C.byref(mode), C.byref(last)))
         return mode.value, last.value
 
+    def ctx_prepared(self):
+        """Preparation launches of the last run (include/gdyn_prep.h): one per group and step of the spans whose steps ran on
+        prepared contexts, 0 when every step computed its context in the step kernel.  Results do not depend on it."""
+        f = getattr(self.lib.dll, "gd_get_ctx_prepared", None)
+        if f is None:
+            raise GdynError(6, "gd_get_ctx_prepared: not in this library (include/gdyn_prep.h: csrc/libgdyn.so only)")
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        n = C.c_uint64(0)
+        self.lib.check(f(self._h, C.byref(n)))
+        return n.value
+
     def timing(self):
         t = Timing()
         self.lib.check(self.lib.dll.gd_get_timing(self._h, C.byref(t)))

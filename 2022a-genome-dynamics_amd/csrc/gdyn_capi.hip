@@ -101,6 +101,7 @@ extern "C" int gd_create_abi(int abi_version, const gd_desc *d, gd_system **out)
         ok = ok && s->pos[k].resize(RNp) == hipSuccess && s->orig[k].resize(RNp) == hipSuccess && s->ctx[k].resize(s->R) == hipSuccess &&
              s->react_part[k].resize((size_t)s->R * s->nblk) == hipSuccess;
     }
+    ok = ok && s->ctxf.resize(s->R) == hipSuccess;      // (prepared contexts of grouped spans: 128 bytes a replica)
     ok = ok && s->xb.resize(RNp) == hipSuccess && s->slot_of.resize(RN) == hipSuccess && s->bbox_enc.resize((size_t)2 * s->R * 6) == hipSuccess && s->bbox_w.resize((size_t)s->R * s->nblk * (GD_BLOCK / 64) * 6) == hipSuccess &&
          s->rank.resize(RNp) == hipSuccess && s->members.resize(RNp) == hipSuccess && s->cell_cnt.resize((size_t)s->R * (s->ncell_cap + 1)) == hipSuccess &&
          s->cell_start.resize((size_t)s->R * (s->ncell_cap + 1)) == hipSuccess && s->meta.resize(RNp) == hipSuccess &&
@@ -449,6 +450,14 @@ extern "C" int gd_get_step_groups(gd_system *s, uint32_t *mode, uint32_t *last_g
     if (!s) return fail(GD_EINVAL, "gd_get_step_groups: NULL system");
     if (mode) *mode = s->group_mode;
     if (last_groups) *last_groups = s->groups_last;
+    return GD_OK;
+}
+// ---- prepared contexts of grouped spans (include/gdyn_prep.h)
+extern "C" int gd_prep_abi_version(void) { return GD_PREP_ABI_VERSION; }
+extern "C" int gd_get_ctx_prepared(gd_system *s, uint64_t *launches)
+{
+    if (!s) return fail(GD_EINVAL, "gd_get_ctx_prepared: NULL system");
+    if (launches) *launches = s->prep_last;
     return GD_OK;
 }
 extern "C" int gd_get_stream(gd_system *s, void **st) { if (!s || !st) return fail(GD_EINVAL, "gd_get_stream: NULL"); *st = (void *)s->stream; return GD_OK; }
@@ -972,6 +981,11 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
         if (const char *e = dev_env("GDYN_GROUP_MIN_BLOCKS")) min_blocks = (uint32_t)atoi(e);      // (timing experiments)
         if (const char *e = dev_env("GDYN_GROUP_A16")) a16 = (uint32_t)atoi(e);
         const uint32_t ra = gd::step_group_split(s->group_mode, group_state(s, host_noise), min_blocks, a16);
+        // ... and whether its steps run on prepared contexts: k_ctx_prep -> k_step on each group's stream (gd::ctx_prepared)
+        uint32_t prep_mode = gd::CTX_PREP_RULE, prep_min_blocks = gd::CTX_PREP_MIN_BLOCKS;
+        if (const char *e = dev_env("GDYN_CTX_PREP")) prep_mode = (uint32_t)atoi(e);                   // (the threshold table: 0 never, 1 the rule, 2 every grouped span)
+        if (const char *e = dev_env("GDYN_CTX_PREP_MIN_BLOCKS")) prep_min_blocks = (uint32_t)atoi(e);
+        const bool prepared = gd::ctx_prepared(s->group_mode, ra, group_state(s, host_noise), prep_mode, prep_min_blocks);
         if (ra) { GDCHK(fork_groups(s)); s->groups_last = 2; }
         for (int64_t q = 0; q < n; q++) {
             fill_common(s, p);
@@ -985,8 +999,14 @@ static int enqueue_chunk(gd_system *s, const gd_run_desc *run, int64_t done, boo
             p.record_disp = (s->list.steps_since_build + (uint32_t)q + 1u == s->pol.K);
             c.full_interval |= p.record_disp != 0;
             if (ra) {      // (same parameters, same buffers: the groups differ in the replicas they cover)
-                p.r0 = 0; p.nrep = ra; gd_launch_step(p, GD_MODE_STEP, s->stream);
-                p.r0 = ra; p.nrep = s->R - ra; gd_launch_step(p, GD_MODE_STEP, s->stream2);
+                if (prepared) p.ctxf = s->ctxf.p;
+                p.r0 = 0; p.nrep = ra;
+                if (prepared) gd_launch_ctx_prep(p, s->stream);
+                gd_launch_step(p, GD_MODE_STEP, s->stream);
+                p.r0 = ra; p.nrep = s->R - ra;
+                if (prepared) gd_launch_ctx_prep(p, s->stream2);
+                gd_launch_step(p, GD_MODE_STEP, s->stream2);
+                if (prepared) s->prep_last += 2;
             } else gd_launch_step(p, GD_MODE_STEP, s->stream);
             if (s->sw.n) launch_softwell(s, p, 0);
             if (s->rp.any()) launch_replica_pairs(s, p, 0);      // (a step evaluates every term: GD_TERM_DYNAMIC is in its mask)
@@ -1094,7 +1114,7 @@ extern "C" int gd_run(gd_system *s, const gd_run_desc *run)
     const bool with_list = pair_cutoff(s) > 0;
     const size_t RN = (size_t)s->R * s->N;
     memset(&s->timing, 0, sizeof s->timing);
-    s->groups_last = 1;
+    s->groups_last = 1; s->prep_last = 0;
 
     // injected noise lives on the device as float (R,N,3) per step
     const bool host_noise = run->noise_mode == GD_NOISE_HOST && run->temperature > 0;

@@ -554,7 +554,15 @@ __device__ __forceinline__ float integrate(const StepParams &p, const CtxF &s_ct
 // with / without AB mixing (compile-time), PK=0: runtime powers.
 // S16 (tiled lists only): entries are BYTE offsets into the tile (tile capacity < 4096 entries), one decode
 // instruction per entry instead of mask + shift-add
-template <int MODE, bool PERIODIC, bool TILED, int PK, bool S16, bool SPLIT = false>
+// PREP (tiled stepping with a specialised pair form only -- the variants replica groups run on): the replica's context was prepared by
+// k_ctx_prep in front of this launch.  Wave 0 copies the block's float constants from p.ctxf[r] into LDS with one DMA piece; no wave
+// loads the full context or the reaction partials, no block stores the context, and wave 0 draws its noise in front of the barrier
+// like the other seven.  A compile-time parameter: the variant carries no trace of the context code.
+template <int MODE, bool PERIODIC, bool TILED, int PK, bool S16, bool SPLIT = false, bool PREP = false>
+#ifndef GD_PREP_W0_STAGES
+#define GD_PREP_W0_STAGES 1   // prepared variants: 1 = wave 0 takes its share of the tile staging again (it has no context work to make
+                              // room for), 0 = the tile stays with the other seven waves
+#endif
 #ifndef GD_STEP_WAVES
 #define GD_STEP_WAVES 8      // waves per SIMD the tiled step kernel with byte-offset entries is compiled for: 8 = at most 64 VGPRs.  LDS
                              // admits three blocks per CU (6 waves per SIMD, 80 VGPRs would do), but the 64-register form -- four
@@ -566,8 +574,9 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
 {
     extern __shared__ __attribute__((aligned(16))) float4 s_tile[];
     __shared__ BondType s_bt[GD_MAX_BOND_TYPES];
-    __shared__ CtxF s_ctx;
+    __shared__ __attribute__((aligned(16))) CtxF s_ctx;
     __shared__ float s_red[GD_BLOCK / 64][4];
+    static_assert(!PREP || (MODE == GD_MODE_STEP && TILED && PK != 0), "prepared contexts: tiled stepping with a specialised pair form only");
     __shared__ double s_e[GD_BLOCK / 64];
 
     unsigned r, blk;
@@ -635,12 +644,15 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
             // Stepping: wave 0 stages the bond table only and leaves the tile to the other seven waves (pieces of 64 slots, stride
             // 448) -- it carries the block's context work in front of the barrier, and without its share of the DMA issue (and of
             // the DMAs in front of its context load) it no longer is the wave the others wait for.
-            constexpr bool W0_FREE = MODE == GD_MODE_STEP;
+            constexpr bool W0_FREE = MODE == GD_MODE_STEP && !(PREP && GD_PREP_W0_STAGES);
             const unsigned wq = (unsigned)__builtin_amdgcn_readfirstlane((int)((W0_FREE ? (wid == 0 ? 0x100000u : wid - 1u) : wid) * 64u));
             constexpr unsigned DMA_STRIDE = W0_FREE ? GD_BLOCK - 64u : GD_BLOCK;
             if (wid == 0 && lane < 2 * GD_MAX_BOND_TYPES)       // the bond-type table: 32 B per type, 16 B per lane (the buffer always holds the full table)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const uint4 *)p.btab + lane),
                                                  (__attribute__((address_space(3))) void *)s_bt, 16, 0, 0);
+            if (PREP && wid == 0 && lane < sizeof(CtxF) / 16u)      // the prepared context constants: 16 B per lane, like the bond table
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const uint4 *)(p.ctxf + r) + lane),
+                                                 (__attribute__((address_space(3))) void *)&s_ctx, 16, 0, 0);
             unsigned base = 0;
 #pragma unroll
 #ifdef GD_REPLAY
@@ -720,13 +732,14 @@ __global__ __launch_bounds__(GD_BLOCK, (TILED && MODE == GD_MODE_STEP) ? (S16 ? 
     // on top of what every wave does there; the other seven wait for it (section stamps: 12 % of a wave's life).  Its noise is needed
     // by the update at the very end only: wave 0 draws it behind the barrier, so that what it does in front of the barrier is about
     // what the others do (record, DMA issue, noise | record, DMA issue, context).
-    const bool noise_late = TILED && MODE == GD_MODE_STEP && wid == 0;
+    // (Prepared contexts: wave 0 has no such work and draws its noise with the others.)
+    const bool noise_late = TILED && MODE == GD_MODE_STEP && !PREP && wid == 0;
     if (!noise_late) draw_noise();
     GD_STAMP_USE3(z.x, z.y, z.z);
     GD_STAMP(10);     // noise
     // wave 0: pending callback + float copy of the context for the block.  After the noise: its vector loads sit behind the
     // DMAs in the vmcnt order, so this is where wave 0 waits for its share of the tile
-    if (wid == 0) {
+    if (!PREP && wid == 0) {
         DevCtx c = p.ctx_in[r];
         if (MODE == GD_MODE_STEP) {
             if (c.pending) apply_callback(c, p, r, lane);
@@ -1110,21 +1123,39 @@ __global__ __launch_bounds__(64) void k_ctx(const StepParams p, int mode)
     if (lane == 0) p.ctx_out[r] = c;
 }
 
-// The k_step instantiation of a launch: the one map from (MODE, SPLIT, periodic, tiled, pk, s16) to a variant, used by the launches
-// below and by the LDS opt-in (gd_kernels_init_device, which takes the tiled variants only).  A step split by tile class is tiled; the
-// generic path has plain-index lists only.
+// One wave per replica of a group, in front of the group's prepared k_step launch of the same StepParams: what wave 0 of every
+// stepping block does in front of the barrier otherwise -- pending callback (the same functions, the same lane-strided reduction),
+// the context as block 0 stores it, the float constants of the step -- once per replica instead of once per block.
+__global__ __launch_bounds__(64) void k_ctx_prep(const StepParams p)
+{
+    const unsigned r = p.r0 + blockIdx.x, lane = threadIdx.x;
+    DevCtx c = p.ctx_in[r];
+    if (c.pending) apply_callback(c, p, r, lane);
+    if (lane == 0) {
+        DevCtx o = c; o.pending = 1; p.ctx_out[r] = o;
+        CtxF f;
+        fill_ctxf(f, c, p);
+        p.ctxf[r] = f;
+    }
+}
+
+// The k_step instantiation of a launch: the one map from (MODE, SPLIT, PREP, periodic, tiled, pk, s16) to a variant, used by the
+// launches below and by the LDS opt-in (gd_kernels_init_device, which takes the tiled variants only).  A step split by tile class is
+// tiled; the generic path has plain-index lists only; prepared contexts exist for tiled stepping with a specialised pair form only.
 typedef void (*StepKernel)(StepParams);
-template <int MODE, bool SPLIT, bool PER, bool TIL, bool S16>
+template <int MODE, bool SPLIT, bool PER, bool TIL, bool S16, bool PREP = false>
 static StepKernel step_kernel_pk(int pk)
 {
-    return pk == 1 ? k_step<MODE, PER, TIL, 1, S16, SPLIT> : pk == 2 ? k_step<MODE, PER, TIL, 2, S16, SPLIT> : k_step<MODE, PER, TIL, 0, S16, SPLIT>;
+    if constexpr (PREP) return pk == 1 ? k_step<MODE, PER, TIL, 1, S16, SPLIT, true> : k_step<MODE, PER, TIL, 2, S16, SPLIT, true>;      // (pk != 0: the caller's)
+    else return pk == 1 ? k_step<MODE, PER, TIL, 1, S16, SPLIT> : pk == 2 ? k_step<MODE, PER, TIL, 2, S16, SPLIT> : k_step<MODE, PER, TIL, 0, S16, SPLIT>;
 }
-template <int MODE, bool SPLIT>
+template <int MODE, bool SPLIT, bool PREP = false>
 static StepKernel tiled_step_kernel(bool periodic, int pk, bool s16)
 {
     static_assert(!SPLIT || MODE == GD_MODE_STEP, "only stepping is split by tile class");
-    if (periodic) return s16 ? step_kernel_pk<MODE, SPLIT, true, true, true>(pk) : step_kernel_pk<MODE, SPLIT, true, true, false>(pk);
-    return s16 ? step_kernel_pk<MODE, SPLIT, false, true, true>(pk) : step_kernel_pk<MODE, SPLIT, false, true, false>(pk);
+    static_assert(!PREP || MODE == GD_MODE_STEP, "only stepping runs on prepared contexts");
+    if (periodic) return s16 ? step_kernel_pk<MODE, SPLIT, true, true, true, PREP>(pk) : step_kernel_pk<MODE, SPLIT, true, true, false, PREP>(pk);
+    return s16 ? step_kernel_pk<MODE, SPLIT, false, true, true, PREP>(pk) : step_kernel_pk<MODE, SPLIT, false, true, false, PREP>(pk);
 }
 template <int MODE>
 static StepKernel step_kernel(bool periodic, bool tiled, int pk, bool s16)
@@ -1149,8 +1180,11 @@ static void launch_step_mode(const StepParams &p, hipStream_t st)
     // (Plain-index lists -- tiles of 4 096 entries and more, the periodic 1 kb model -- split the same way at 3 312: their kernel fits
     // 80 registers, so the blocks with small tiles run three to a CU next to the few large ones.)
     const unsigned split_at = !p.tiled ? 0u : (s16 && p.tile_cap > 3312u) ? 3312u : (!s16 && p.tile_cap > 5072u) ? 5072u : (!s16 && p.tile_cap > 3312u) ? 3312u : 0u;
+    // prepared contexts (p.ctxf, set by gd_run's grouped spans only: tiled lists and a specialised pair form, gd::step_group_split):
+    // the variant without the context work; both launches of a split step read the one prepared context
+    const bool prep = MODE == GD_MODE_STEP && p.ctxf != nullptr;
     if (MODE == GD_MODE_STEP && split_at) {
-        const StepKernel k = tiled_step_kernel<GD_MODE_STEP, true>(p.periodic, p.pk, s16);
+        const StepKernel k = prep ? tiled_step_kernel<GD_MODE_STEP, true, true>(p.periodic, p.pk, s16) : tiled_step_kernel<GD_MODE_STEP, true>(p.periodic, p.pk, s16);
         StepParams q = p;
         for (int half = 0; half < 2; half++) {
             q.tile_cap = half ? p.tile_cap : split_at; q.tile_lo = half ? split_at : 0u; q.tile_hi = half ? 0xffffffffu : split_at;
@@ -1158,7 +1192,8 @@ static void launch_step_mode(const StepParams &p, hipStream_t st)
         }
         return;
     }
-    const StepKernel k = step_kernel<MODE>(p.periodic, p.tiled, p.pk, s16);
+    StepKernel k = step_kernel<MODE>(p.periodic, p.tiled, p.pk, s16);
+    if constexpr (MODE == GD_MODE_STEP) { if (prep) k = tiled_step_kernel<GD_MODE_STEP, false, true>(p.periodic, p.pk, s16); }
     hipLaunchKernelGGL(k, grid, block, lds, st, p);
 }
 
@@ -1172,6 +1207,11 @@ void gd_launch_step(const StepParams &p, int mode, hipStream_t st)
 void gd_launch_finalize(const StepParams &p, int mode, hipStream_t st)
 {
     hipLaunchKernelGGL(k_ctx, dim3(p.R), dim3(64), 0, st, p, mode);
+}
+
+void gd_launch_ctx_prep(const StepParams &p, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_ctx_prep, dim3(p.nrep), dim3(64), 0, st, p);
 }
 
 // --------------------------------------------------------- neighbour search
@@ -2683,6 +2723,11 @@ hipError_t gd_kernels_init_device(void)
                       tiled_step_kernel<GD_MODE_ENERGY, false>})
         for (int per = 0; per < 2; per++)
             for (int pk = 0; pk < 3; pk++)
+                for (int s16 = 0; s16 < 2; s16++) set(reinterpret_cast<const void *>(pick(per != 0, pk, s16 != 0)), 128 * 1024);
+    // ... and the variants that run on prepared contexts (specialised pair forms only)
+    for (auto pick : {tiled_step_kernel<GD_MODE_STEP, false, true>, tiled_step_kernel<GD_MODE_STEP, true, true>})
+        for (int per = 0; per < 2; per++)
+            for (int pk = 1; pk < 3; pk++)
                 for (int s16 = 0; s16 < 2; s16++) set(reinterpret_cast<const void *>(pick(per != 0, pk, s16 != 0)), 128 * 1024);
     for (int per = 0; per < 2; per++)
         for (int s16 = 0; s16 < 2; s16++)

@@ -107,6 +107,25 @@ inline uint32_t step_group_split(uint32_t mode, const StepGroupState &st, uint32
     return ra;
 }
 
+// ---- Prepared contexts (include/gdyn_prep.h).  In a span that runs in two groups, each step of each group may be
+// k_ctx_prep -> k_step on the group's stream: one wave per replica applies the pending callback and derives the step's float constants,
+// and the stepping blocks copy them instead of each computing them in front of its barrier.  The extra launch costs its stream a drain
+// and a launch per step, which only the other group's k_step can cover: never in a span that steps in one launch.  ra: what
+// step_group_split returned for the span.  prep: CTX_PREP_RULE in the product; the developer library's GDYN_CTX_PREP sets the others.
+enum : uint32_t { CTX_PREP_NEVER = 0, CTX_PREP_RULE = 1, CTX_PREP_ALWAYS = 2 };
+// blocks the smaller group must have under mode 0.  Measured (one handle, prepared against in-kernel contexts
+// alternating): groups of 1 888 blocks (30 000 beads x 64 replicas) gain 2.5 % of the wall time per step, groups of 944 lose 5 %, of 472
+// lose 17 %, of 240 lose 22 % -- the preparation launch is 8 us on its stream, and the shorter the other group's k_step, the less of it is
+// covered.  The threshold is the smallest size measured to win; the headline (128 replicas: groups of 3 776 blocks) gains 3.7 %.
+constexpr uint32_t CTX_PREP_MIN_BLOCKS = 1888u;
+inline bool ctx_prepared(uint32_t group_mode, uint32_t ra, const StepGroupState &st, uint32_t prep = CTX_PREP_RULE, uint32_t min_blocks = CTX_PREP_MIN_BLOCKS)
+{
+    if (ra == 0 || ra >= st.R || prep == CTX_PREP_NEVER) return false;      // one launch per step: the kernel as it was
+    if (prep == CTX_PREP_ALWAYS || group_mode == STEP_GROUPS_TWO) return true;
+    if (group_mode != STEP_GROUPS_RULE) return false;
+    return (uint64_t)std::min(ra, st.R - ra) * st.nblk >= min_blocks;
+}
+
 struct ListPolicy {
     // developer hooks (gd_create)
     std::vector<unsigned> tile_caps = {3312u, 4080u, 5072u, 8192u};      // (4080: the largest tile with byte-offset list entries)

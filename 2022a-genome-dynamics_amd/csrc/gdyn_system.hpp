@@ -14,6 +14,7 @@
 #include "../../include/gdyn_replica.h"
 #include "../../include/gdyn_ensemble.h"
 #include "../../include/gdyn_groups.h"
+#include "../../include/gdyn_prep.h"
 #include "../../include/gdyn_glue.h"
 
 #include "gdyn_types.h"
@@ -154,6 +155,10 @@ struct gd_system {
     // on it that the handle's stream does not wait for.
     hipStream_t stream2 = nullptr; hipEvent_t grp_fork = nullptr, grp_join = nullptr;
     uint32_t group_mode = gd::STEP_GROUPS_RULE, groups_last = 1;      // gd_set_step_groups; groups of the step launches of the last gd_run
+    // Prepared contexts of grouped spans (gdyn_prep.h, gd::ctx_prepared): the float constants k_ctx_prep leaves for the step kernels of
+    // the same step -- one buffer: stream order separates its writer from the previous step's readers
+    gd::dbuf<CtxF> ctxf;           // [R], allocated on first use
+    uint64_t prep_last = 0;        // preparation launches of the last gd_run
 
     // the features, each with the state and the buffers it owns (gd_destroy leaves the stream idle before they go)
     gd::Droplet sw;

@@ -95,6 +95,8 @@ struct CtxF {                   // float copy of DevCtx + block-uniform wall con
     float w_inv_q3;                             // 1 / (a^2 b^2 c^2)
     double w_q[4];                              // b^2c^2, a^2c^2, a^2b^2, a^2b^2c^2
 };
+// (the prepared k_step variants stage it with one LDS-DMA piece, 16 bytes per lane of one wave)
+static_assert(sizeof(CtxF) % 16 == 0 && sizeof(CtxF) <= 64 * 16, "CtxF is copied into LDS in 16-byte pieces by one wave");
 
 struct GridP {                  // per replica cell grid of the last list build
     float org[3];
@@ -224,6 +226,10 @@ struct StepParams {
     unsigned term_mask;
     float4 *fout;                       // [R][N] by bead index
     double *epart;                      // [R][nblk]
+    // prepared contexts (gd::ctx_prepared, gdyn_policy.hpp): non-NULL in the launches of a span whose steps are k_ctx_prep -> k_step.
+    // k_ctx_prep applies the replica's pending callback and writes ctx_out[r] and ctxf[r]; the prepared k_step variants copy ctxf[r]
+    // into LDS and touch neither the full context nor the reaction partials.  NULL: every stepping block does that work itself.
+    CtxF *ctxf;                         // [R]
 };
 
 struct BuildParams {
@@ -313,6 +319,7 @@ struct BuildParams {
 hipError_t gd_kernels_init_device(void);      // LDS opt-in of every kernel that needs it, on the current device (once per device: gd_create)
 void gd_launch_step(const StepParams &p, int mode, hipStream_t st);
 void gd_launch_finalize(const StepParams &p, int mode, hipStream_t st);     // k_ctx: 0 final callback, 1 fold reaction partials
+void gd_launch_ctx_prep(const StepParams &p, hipStream_t st);               // k_ctx_prep for replicas r0 .. r0 + nrep - 1, in front of their step (p.ctxf)
 void gd_launch_build(const BuildParams &p, hipStream_t st);
 // Droplet attraction among a small set of target beads (gd_set_pair_softwell): all pairs, one thread per target.
 struct SoftwellP {
