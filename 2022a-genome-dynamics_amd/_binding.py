@@ -1,5 +1,6 @@
 """What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap) share: loading libgdyn with a check of
-one module's symbols and ABI version, the life cycle of a ``gd_<x>`` handle, and the normalisation of frames."""
+one module's symbols and ABI version, the life cycle of a ``gd_<x>`` handle, the normalisation of frames, and the trajectory history
+that the msd, dcorr and dmap handles hold."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +22,14 @@ def load_library(prefix, symbols, abi_version, path=None):
     if version() != abi_version:
         raise OSError(f"{path}: {prefix} ABI version {version()}, this binding mirrors {abi_version}")
     d.gd_last_error.restype = C.c_char_p
+    return d
+
+
+def load_history_library(prefix, symbols, abi_version, path=None):
+    """load_library for a module whose handle holds a trajectory history (HistoryHandle); sets the argtypes of its two history calls."""
+    d = load_library(prefix, symbols, abi_version, path)
+    getattr(d, f"gd_{prefix}_set_history").argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
+    getattr(d, f"gd_{prefix}_set_history_live").argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     return d
 
 
@@ -53,6 +62,58 @@ class Handle:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class HistoryHandle(Handle):
+    """A ``gd_<prefix>`` handle that holds one trajectory history on the device (msd, dcorr, dmap).  ``shape`` is (F, N) of the
+    history, None before the first.  A subclass names its ``_prefix``, loads ``dll`` with load_history_library and overrides
+    ``_beads_changed``."""
+
+    _prefix = None
+
+    def __init__(self, dll):
+        super().__init__(dll)
+        self.shape = None
+
+    def _beads_changed(self, n_beads):
+        """The history has another N than the last: the library has dropped what the handle kept per bead."""
+
+    def _new_shape(self, shape):
+        if self.shape is None or self.shape[1] != shape[1]:
+            self._beads_changed(shape[1])
+        self.shape = shape
+
+    def set_history(self, frames):
+        """frames (F, N, 3), float32 or float64 (anything else becomes float32)."""
+        h = np.asarray(frames)
+        if h.ndim != 3 or h.shape[2] != 3:
+            raise ValueError(f"history must be (F, N, 3), got {h.shape}")
+        h, is64 = as_frames(h)
+        F, N, _ = h.shape
+        self._check(getattr(self.dll, f"gd_{self._prefix}_set_history")(self._h, h.ctypes.data, F, N, int(is64)))
+        self._new_shape((F, N))
+
+    def set_history_from(self, history, replica):
+        """The history becomes the frames that ``history`` (a live.History) recorded of ``replica``, float32 as recorded, going from
+        the recorder to this handle on the device."""
+        self._check(getattr(self.dll, f"gd_{self._prefix}_set_history_live")(self._h, history._h, int(replica)))
+        self._new_shape((history.frames, history.N))
+
+
+def _u32(values, what):
+    """``values`` as a contiguous uint32 array; ``what`` names them in the refusal of anything but integers in [0, 2^32)."""
+    v = np.asarray(values)
+    if v.size and (not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() > 0xFFFFFFFF):
+        raise ValueError(f"{what} must be integers in [0, 2^32)")
+    return np.ascontiguousarray(v, dtype=np.uint32)
+
+
+def _ratio(total, count):
+    """total / count with ``count`` broadcast to ``total``, NaN where count is 0."""
+    count = np.broadcast_to(count, total.shape)
+    out = np.full(total.shape, np.nan)
+    np.divide(total, count, out=out, where=count > 0)
+    return out
 
 
 def as_frames(x):

@@ -1,16 +1,20 @@
 // gdyn_analysis.hpp -- the host-side plumbing that the device analyses (gdyn_flow, gdyn_rdf, gdyn_lamina, gdyn_cmap,
-// gdyn_hic) share: error reporting, owned device and pinned host buffers, the device and stream of a handle with its create
-// prologue and destroy epilogue, and the grid size of a one-lane-per-element launch.  The stepper's host files (gdyn_system.hpp)
-// take the error reporting and the buffers from here too.  Nothing here is extern "C" or device code.
+// gdyn_hic, gdyn_msd, gdyn_dcorr, gdyn_dmap) and the recorder (gdyn_live) share: error reporting, owned device and pinned host
+// buffers, the device and stream of a handle with its create prologue and destroy epilogue, the grid size of a
+// one-lane-per-element launch and the opt-in to more than 64 KiB of dynamic LDS.  The stepper's host files (gdyn_system.hpp)
+// take the error reporting and the buffers from here too.  The trajectory history that gd_msd, gd_dcorr and gd_dmap hold is
+// gdyn_history.hpp's.  Nothing here is extern "C" or device code.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 #include <new>
 
 #include "../../include/gdyn.h"
+#include "gdyn_once.hpp"
 
 int gd_report_error(int code, const char *msg);      // gdyn_capi.hip: sets gd_last_error()
 
@@ -38,6 +42,22 @@ static int fail(int code, const char *fmt, ...)
 
 // blocks of `block` lanes for n elements; no caller comes near the cap, which keeps the count inside a grid dimension
 inline unsigned blocks_for(size_t n, unsigned block) { return (unsigned)std::min<size_t>((n + block - 1) / block, 1u << 30); }
+
+// The dynamic LDS a block of `kernels` may ask for on a device: all 160 KiB of a gfx950 CU where the opt-in is granted to every one
+// of them (once per device, gdyn_once.hpp), else 128 KiB, else the 64 KiB that need none.
+static inline int lds_opt_in(DeviceOnce<> &once, int device, std::initializer_list<const void *> kernels)
+{
+    int const bytes = once.run(device, [&](int) {
+        for (int want : {160 * 1024, 128 * 1024}) {
+            bool ok = true;
+            for (const void *k : kernels) ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess && ok;
+            if (ok) return want;
+            (void)hipGetLastError();
+        }
+        return 64 * 1024;
+    });
+    return bytes > 0 ? bytes : 64 * 1024;
+}
 
 // device memory of the current device, freed with its owner (the owner's device must be current then: gd::close)
 template <typename T>

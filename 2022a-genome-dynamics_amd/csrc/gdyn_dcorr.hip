@@ -1,6 +1,6 @@
 // gdyn_dcorr.hip -- the spatial correlation of bead displacements (include/gdyn_dcorr.h): per origin frame, pair class and
 // distance bin, the number of pairs and the fixed-point sum of D_i . D_j.  Beyond the reference, which has no such analysis.
-// The pair rules are gdyn_rdf.hip's, the history handling gdyn_msd.hip's.
+// The pair rules are gdyn_rdf.hip's, the history is gd::History's (gdyn_history.hpp).
 //
 // Per call:
 //   k_dcorr_tmax   the largest squared displacement t2 of the selected beads over all origins of the call (integer atomicMax on the
@@ -40,8 +40,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_dcorr.h"
 #include "gdyn_analysis.hpp"
-#include "gdyn_live.hpp"
-#include "gdyn_once.hpp"
+#include "gdyn_history.hpp"
 #include "gdyn_types.h"
 
 using namespace gd;
@@ -54,7 +53,6 @@ constexpr unsigned kTilePad = 2;             // words between the arrays of a ti
 constexpr unsigned kTileWords = 7;           // x y z Dx Dy Dz label|chain
 constexpr unsigned kUnroll = 4;              // partners of a lane whose positions are read together
 constexpr double kCellSlack = 1e-9;          // cells are this much wider than max_distance, against the rounding of the cell assignment
-constexpr unsigned long long kNoBadIndex = ~0ull;
 
 struct Rec {      // one selected bead of one origin
     double p[3];
@@ -420,32 +418,12 @@ __global__ void __launch_bounds__(kBlock) k_dcorr_pairs(const Rec *__restrict__ 
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(kBlock) k_dcorr_first_bad(const T *__restrict__ x, size_t n, unsigned long long *first_bad)
-{
-    unsigned long long bad = kNoBadIndex;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        if (!isfinite(x[i])) bad = min(bad, (unsigned long long)i);
-    if (bad != kNoBadIndex) atomicMin(first_bad, bad);
-}
-
-// The dynamic LDS a block of k_dcorr_pairs may ask for on a device: all 160 KiB of a gfx950 CU where the opt-in is granted (once per
-// device, gdyn_once.hpp), else 128 KiB, else the 64 KiB that need none.  A refusal only makes the tiles and the LDS histogram smaller.
+// the dynamic LDS a block of k_dcorr_pairs may ask for (gd::lds_opt_in).  A refusal only makes the tiles and the LDS histogram smaller.
 int lds_budget(int device)
 {
     static DeviceOnce<> once;
-    int const bytes = once.run(device, [](int) {
-        const void *kernels[] = {reinterpret_cast<const void *>(&k_dcorr_pairs<false, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<false, true>),
-                                 reinterpret_cast<const void *>(&k_dcorr_pairs<true, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<true, true>)};
-        for (int want : {160 * 1024, 128 * 1024}) {
-            bool ok = true;
-            for (const void *k : kernels) ok = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess && ok;
-            if (ok) return want;
-            (void)hipGetLastError();
-        }
-        return 64 * 1024;
-    });
-    return bytes > 0 ? bytes : 64 * 1024;
+    return lds_opt_in(once, device, {reinterpret_cast<const void *>(&k_dcorr_pairs<false, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<false, true>),
+                                     reinterpret_cast<const void *>(&k_dcorr_pairs<true, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<true, true>)});
 }
 
 size_t tile_bytes(unsigned tile) { return (size_t)kTileWords * (tile + kTilePad) * 8; }
@@ -475,12 +453,8 @@ bool scale_legal(uint64_t n, double M, int S)
 struct gd_dcorr : gd::handle {
     unsigned max_frames = 0;
     int lds_bytes = 64 * 1024;
-    unsigned F = 0, N = 0;         // F == 0: no history; N stays, for the labels and chains that belong to it
-    bool is_f64 = false;
-    dbuf<float> xf;
-    dbuf<double> xd;
-    dbuf<unsigned long long> first_bad;
-    // selection: labels and chains
+    History hist;
+    // selection: labels and chains, which belong to hist.beads()
     unsigned K = 1, n_sel = 0;
     bool have_labels = false, have_chains = false;
     std::vector<uint64_t> members;      // beads per label
@@ -499,7 +473,6 @@ struct gd_dcorr : gd::handle {
     dbuf<char> sort_tmp;
     dbuf<unsigned long long> counts, sums;
 
-    const void *x() const { return is_f64 ? (const void *)xd.p : (const void *)xf.p; }
     unsigned P() const { return K * (K + 1) / 2 * (have_chains ? 2u : 1u); }
 };
 
@@ -519,43 +492,23 @@ int select_all(gd_dcorr *h, unsigned N)
     return GD_OK;
 }
 
-// the history is on the device: the non-finite check, then the handle holds it (or none)
-int finish_history(gd_dcorr *h, const char *who, unsigned frames, unsigned n_beads, bool is_f64)
+History::Rebind rebind(gd_dcorr *h)
 {
-    size_t const n = (size_t)frames * n_beads * 3;
-    HIPCHK(h->first_bad.ensure(1));
-    HIPCHK(hipMemsetAsync(h->first_bad.p, 0xff, sizeof(unsigned long long), h->stream));
-    unsigned const blocks = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 8192);
-    if (is_f64) hipLaunchKernelGGL(k_dcorr_first_bad<double>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xd.p, n, h->first_bad.p);
-    else hipLaunchKernelGGL(k_dcorr_first_bad<float>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xf.p, n, h->first_bad.p);
-    HIPCHK(hipGetLastError());
-    unsigned long long bad = kNoBadIndex;
-    HIPCHK(hipMemcpyAsync(&bad, h->first_bad.p, sizeof bad, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (bad != kNoBadIndex) return fail(GD_EINVAL, "%s: non-finite coordinate at %llu", who, bad);
-    if (n_beads != h->N || !h->sel.p) {      // labels and chains belonged to another N
-        if (int rc = select_all(h, n_beads)) return rc;
-        h->have_chains = false;
-    }
-    h->F = frames;
-    h->N = n_beads;
-    h->is_f64 = is_f64;
-    return GD_OK;
-}
-
-int check_shape(const char *who, uint32_t frames, uint32_t n_beads)
-{
-    if (frames == 0 || n_beads == 0) return fail(GD_EINVAL, "%s: empty history (%u frames of %u beads)", who, frames, n_beads);
-    if (n_beads > (1u << 28)) return fail(GD_EINVAL, "%s: %u beads exceed 2^28", who, n_beads);
-    return GD_OK;
+    return [h](unsigned n_beads) -> int {
+        if (n_beads != h->hist.beads() || !h->sel.p) {      // labels and chains belonged to another N
+            GDCHK(select_all(h, n_beads));
+            h->have_chains = false;
+        }
+        return GD_OK;
+    };
 }
 
 uint32_t origins_of(const gd_dcorr *h, uint32_t lag, uint32_t first, uint32_t n_origins, uint32_t stride)
 {
-    if (!h || !h->F || !stride || !lag) return 0;
+    if (!h || !h->hist.frames() || !stride || !lag) return 0;
     if (n_origins) return n_origins;
-    if ((uint64_t)first + lag >= h->F) return 0;
-    return (h->F - lag - first - 1) / stride + 1;
+    if ((uint64_t)first + lag >= h->hist.frames()) return 0;
+    return (h->hist.frames() - lag - first - 1) / stride + 1;
 }
 
 struct Call {      // what a batch needs of its call
@@ -588,16 +541,16 @@ int run_batch(gd_dcorr *h, const Call &c, unsigned o0, unsigned B, uint64_t *cou
     HIPCHK(h->sums.ensure((size_t)B * cells));
     const int *label = h->have_labels ? h->label_dev.p : nullptr;
     const unsigned *chain = h->have_chains ? h->chain_dev.p : nullptr;
-    int const is64 = h->is_f64;
+    int const is64 = h->hist.is_f64;
     if (!c.sp.periodic) {
         std::vector<unsigned long long> init(6 * (size_t)B);
         for (size_t k = 0; k < init.size(); k++) init[k] = k % 6 < 3 ? ~0ull : 0ull;
         HIPCHK(hipMemcpyAsync(h->bbox.p, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));      // init is about to go out of scope
-        hipLaunchKernelGGL(k_dcorr_bbox, dim3(std::min(blocks_for(n, kBlock), 16u), B), dim3(kBlock), 0, st, h->x(), is64, h->N, h->sel.p, n, c.og, o0, h->bbox.p);
+        hipLaunchKernelGGL(k_dcorr_bbox, dim3(std::min(blocks_for(n, kBlock), 16u), B), dim3(kBlock), 0, st, h->hist.x(), is64, h->hist.beads(), h->sel.p, n, c.og, o0, h->bbox.p);
     }
     hipLaunchKernelGGL(k_dcorr_grid, dim3(blocks_for(B, kBlock)), dim3(kBlock), 0, st, h->bbox.p, B, c.sp, c.cap, h->grids.p);
-    hipLaunchKernelGGL(k_dcorr_disp, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->x(), is64, h->N, h->sel.p, label, chain, n, c.lag, c.og, o0, B,
+    hipLaunchKernelGGL(k_dcorr_disp, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, h->hist.beads(), h->sel.p, label, chain, n, c.lag, c.og, o0, B,
                        h->grids.p, c.sp.periodic, c.cap, h->keys[0].p, h->vals[0].p, h->grec.p);
     HIPCHK(hipGetLastError());
     unsigned bits = 1;
@@ -674,52 +627,31 @@ int gd_dcorr_destroy(gd_dcorr *h) { return gd::close(h); }
 int gd_dcorr_set_history(gd_dcorr *h, const void *xyz, uint32_t frames, uint32_t n_beads, int is_f64)
 {
     const char *who = "gd_dcorr_set_history";
-    if (!h || !xyz) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (int rc = check_shape(who, frames, n_beads)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    size_t const n = (size_t)frames * n_beads * 3;
-    h->F = 0;      // the buffer is about to be overwritten
-    if (is_f64) HIPCHK(h->xd.upload(static_cast<const double *>(xyz), n));
-    else HIPCHK(h->xf.upload(static_cast<const float *>(xyz), n));
-    return finish_history(h, who, frames, n_beads, is_f64 != 0);
+    if (!h) return fail(GD_EINVAL, "%s: NULL argument", who);
+    return h->hist.set_host(who, h->device, h->stream, xyz, frames, n_beads, is_f64 != 0, rebind(h));
 }
 
 int gd_dcorr_set_history_live(gd_dcorr *h, gd_live_history *history, uint32_t replica)
 {
     const char *who = "gd_dcorr_set_history_live";
-    if (!h || !history) return fail(GD_EINVAL, "%s: NULL handle", who);
-    gd_live_history_shape const v = gd_live_history_shape_of(history);
-    uint32_t slot = 0;
-    if (int rc = gd_live_history_slot(history, who, replica, &slot)) return rc;
-    if (v.device != h->device) return fail(GD_EINVAL, "%s: the recorder is on device %d, the analysis handle on device %d", who, v.device, h->device);
-    if (!v.frames) return fail(GD_ESTATE, "%s: no frame recorded", who);
-    if (int rc = check_shape(who, v.frames, v.N)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    size_t const M = (size_t)v.N * 3;
-    h->F = 0;
-    HIPCHK(h->xf.ensure((size_t)v.frames * M));
-    for (uint32_t f0 = 0; f0 < v.frames; f0 += v.frames_per_block) {      // one strided copy per block of the recorder
-        uint32_t const nf = std::min(v.frames_per_block, v.frames - f0);
-        HIPCHK(hipMemcpy2DAsync(h->xf.p + (size_t)f0 * M, M * sizeof(float), gd_live_history_frame(history, f0, slot), v.frame_stride * sizeof(float),
-                                M * sizeof(float), nf, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return finish_history(h, who, v.frames, v.N, false);
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    return h->hist.set_live(who, h->device, h->stream, history, replica, rebind(h));
 }
 
 int gd_dcorr_set_labels(gd_dcorr *h, const int32_t *label, uint32_t n_labels)
 {
     const char *who = "gd_dcorr_set_labels";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the labels are N values of its beads)", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the labels are N values of its beads)", who);
     if (!label) {
         if (n_labels > 1) return fail(GD_EINVAL, "%s: %u labels without a label array", who, n_labels);
         HIPCHK(hipSetDevice(h->device));
-        return select_all(h, h->N);
+        return select_all(h, h->hist.beads());
     }
     if (n_labels == 0 || n_labels > GD_DCORR_MAX_LABELS) return fail(GD_EINVAL, "%s: %u labels (1 to %d)", who, n_labels, GD_DCORR_MAX_LABELS);
     std::vector<unsigned> chosen;
     std::vector<uint64_t> members(n_labels, 0);
-    for (unsigned i = 0; i < h->N; i++) {
+    for (unsigned i = 0; i < h->hist.beads(); i++) {
         if (label[i] < -1 || label[i] >= (int64_t)n_labels) return fail(GD_EINVAL, "%s: label[%u] = %d is not in [-1, %u)", who, i, label[i], n_labels);
         if (label[i] >= 0) {
             chosen.push_back(i);
@@ -730,7 +662,7 @@ int gd_dcorr_set_labels(gd_dcorr *h, const int32_t *label, uint32_t n_labels)
     dbuf<unsigned> sel;
     dbuf<int> dev;
     HIPCHK(sel.upload(chosen.data(), chosen.size()));
-    HIPCHK(dev.upload(label, h->N));
+    HIPCHK(dev.upload(label, h->hist.beads()));
     h->sel = std::move(sel);
     h->label_dev = std::move(dev);
     h->n_sel = (unsigned)chosen.size();
@@ -744,14 +676,14 @@ int gd_dcorr_set_chains(gd_dcorr *h, const uint32_t *chain_id)
 {
     const char *who = "gd_dcorr_set_chains";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the chains are N values of its beads)", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the chains are N values of its beads)", who);
     if (!chain_id) {
         h->have_chains = false;
         return GD_OK;
     }
     HIPCHK(hipSetDevice(h->device));
     dbuf<unsigned> dev;
-    HIPCHK(dev.upload(chain_id, h->N));
+    HIPCHK(dev.upload(chain_id, h->hist.beads()));
     h->chain_dev = std::move(dev);
     h->have_chains = true;
     return GD_OK;
@@ -770,12 +702,12 @@ int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_
 {
     const char *who = "gd_dcorr_pairs";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set", who);
     if (lag == 0) return fail(GD_EINVAL, "%s: lag 0", who);
     if (origin_stride == 0) return fail(GD_EINVAL, "%s: origin stride 0", who);
-    if (n_origins && (uint64_t)first_origin + (uint64_t)(n_origins - 1) * origin_stride + lag >= h->F)
+    if (n_origins && (uint64_t)first_origin + (uint64_t)(n_origins - 1) * origin_stride + lag >= h->hist.frames())
         return fail(GD_EINVAL, "%s: origin %llu with lag %u lies beyond the %u frames", who,
-                    (unsigned long long)first_origin + (unsigned long long)(n_origins - 1) * origin_stride, lag, h->F);
+                    (unsigned long long)first_origin + (unsigned long long)(n_origins - 1) * origin_stride, lag, h->hist.frames());
     if (box)
         for (int a = 0; a < 3; a++)
             if (!(box[a] > 0.0) || !std::isfinite(box[a])) return fail(GD_EINVAL, "%s: box[%d] = %g is not positive and finite", who, a, box[a]);
@@ -800,7 +732,7 @@ int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_
     if (og.count && n) {
         HIPCHK(h->tmax.ensure(1));
         HIPCHK(hipMemsetAsync(h->tmax.p, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_dcorr_tmax, dim3(std::min(blocks_for((size_t)og.count * n, kBlock), 2048u)), dim3(kBlock), 0, st, h->x(), (int)h->is_f64, h->N, h->sel.p, n, lag,
+        hipLaunchKernelGGL(k_dcorr_tmax, dim3(std::min(blocks_for((size_t)og.count * n, kBlock), 2048u)), dim3(kBlock), 0, st, h->hist.x(), (int)h->hist.is_f64, h->hist.beads(), h->sel.p, n, lag,
                            og, h->tmax.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&M, h->tmax.p, sizeof M, hipMemcpyDeviceToHost, st));
@@ -826,8 +758,8 @@ int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_
             HIPCHK(h->self_sum.ensure((size_t)og.count * K));
             HIPCHK(hipMemsetAsync(h->self_sum.p, 0, (size_t)og.count * K * sizeof(unsigned long long), st));
             for (unsigned o0 = 0; o0 < og.count; o0 += 65535u)
-                hipLaunchKernelGGL(k_dcorr_self, dim3(blocks_for(n, kBlock), std::min(65535u, og.count - o0)), dim3(kBlock), 0, st, h->x(), (int)h->is_f64,
-                                   h->N, h->sel.p, label, n, lag, og, o0, scale, K, h->self_sum.p);
+                hipLaunchKernelGGL(k_dcorr_self, dim3(blocks_for(n, kBlock), std::min(65535u, og.count - o0)), dim3(kBlock), 0, st, h->hist.x(), (int)h->hist.is_f64,
+                                   h->hist.beads(), h->sel.p, label, n, lag, og, o0, scale, K, h->self_sum.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(self_sum_out, h->self_sum.p, (size_t)og.count * K * sizeof(int64_t), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));

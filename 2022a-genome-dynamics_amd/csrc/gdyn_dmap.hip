@@ -18,7 +18,7 @@
 //                    side, so that their reads and square roots overlap, and added one by one in ascending j.
 //   k_dmap_reduce    adds a cell's partial sums over the frame ranges in ascending order and writes the cell where the rectangle
 //                    holds it, and its mirror image where the rectangle holds that.
-//   k_dmap_first_bad the lowest index of a non-finite coordinate, as in gdyn_msd.hip
+// The history itself (upload, non-finite check) is gd::History's (gdyn_history.hpp).
 // Hit counters are 32-bit while one (u, v) pair of pieces is walked over one frame range: at most GD_DMAP_FRAME_RANGE *
 // GD_DMAP_PIECE_BEADS^2 = 2^16 terms, far below 2^32; they are added to 64-bit counters after each pair of pieces.
 // fp64 throughout, -ffp-contract=off (csrc/Makefile), no fast-math, no floating-point atomics.
@@ -33,8 +33,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_dmap.h"
 #include "gdyn_analysis.hpp"
-#include "gdyn_live.hpp"
-#include "gdyn_once.hpp"
+#include "gdyn_history.hpp"
 
 using namespace gd;
 
@@ -46,7 +45,6 @@ constexpr unsigned kRange = GD_DMAP_FRAME_RANGE;
 constexpr unsigned kPiece = GD_DMAP_PIECE_BEADS;
 constexpr unsigned kMaxT = GD_DMAP_MAX_THRESHOLDS;
 constexpr unsigned kWords = 2 + kMaxT;               // 8-byte words a lane leaves per frame range: sum1, sum2, hits[4]
-constexpr unsigned long long kNoBadIndex = ~0ull;
 constexpr size_t kPartialBytes = (size_t)1 << 30;    // tiles are walked in batches whose partial sums fit this
 constexpr size_t kAutoStageBytes = 40 * 1024;        // automatic chunk: four blocks per CU keep 16 waves resident
 constexpr size_t kStaticLds = 2 * kTB * 2 * sizeof(unsigned);      // the tile's bin table, next to the staged frames
@@ -219,39 +217,19 @@ __global__ void __launch_bounds__(kBlock) k_dmap_reduce(ReduceArgs p)
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(kBlock) k_dmap_first_bad(const T *__restrict__ x, size_t n, unsigned long long *first_bad)
-{
-    unsigned long long bad = kNoBadIndex;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        if (!isfinite(x[i])) bad = min(bad, (unsigned long long)i);
-    if (bad != kNoBadIndex) atomicMin(first_bad, bad);
-}
-
 template <typename T, bool BOX, bool SQRT>
-hipError_t opt_in(int bytes)
+const void *tile_kernel()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dmap_tile<T, BOX, SQRT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return reinterpret_cast<const void *>(&k_dmap_tile<T, BOX, SQRT>);
 }
 
-// The dynamic LDS a block of k_dmap_tile may ask for on a device: all 160 KiB of a gfx950 CU where the opt-in is granted (once per
-// device, gdyn_once.hpp), else 128 KiB, else the 64 KiB that need none.  A refusal only makes the chunks smaller.
+// the dynamic LDS a block of k_dmap_tile may ask for (gd::lds_opt_in).  A refusal only makes the chunks smaller.
 int lds_budget(int device)
 {
     static DeviceOnce<> once;
-    int const bytes = once.run(device, [](int) {
-        for (int want : {160 * 1024, 128 * 1024}) {
-            bool ok = true;
-            for (hipError_t e : {opt_in<float, false, false>(want), opt_in<float, false, true>(want), opt_in<float, true, false>(want),
-                                 opt_in<float, true, true>(want), opt_in<double, false, false>(want), opt_in<double, false, true>(want),
-                                 opt_in<double, true, false>(want), opt_in<double, true, true>(want)})
-                ok = ok && e == hipSuccess;
-            if (ok) return want;
-            (void)hipGetLastError();
-        }
-        return 64 * 1024;
-    });
-    return bytes > 0 ? bytes : 64 * 1024;
+    return lds_opt_in(once, device, {tile_kernel<float, false, false>(), tile_kernel<float, false, true>(), tile_kernel<float, true, false>(),
+                                     tile_kernel<float, true, true>(), tile_kernel<double, false, false>(), tile_kernel<double, false, true>(),
+                                     tile_kernel<double, true, false>(), tile_kernel<double, true, true>()});
 }
 
 template <typename T, bool BOX>
@@ -266,34 +244,18 @@ void launch_tile(bool want_sqrt, dim3 grid, size_t lds, hipStream_t stream, cons
 struct gd_dmap : gd::handle {
     unsigned knob = 0;
     int lds_bytes = 64 * 1024;
-    unsigned F = 0, N = 0;         // F == 0: no history; N stays, for the bins that belong to it
-    bool is_f64 = false;
-    dbuf<float> xf;
-    dbuf<double> xd;
-    dbuf<unsigned long long> first_bad;
+    History hist;
     bool have_bins = false;        // false: every bead is its own bin
-    std::vector<uint32_t> bins;    // (B, 2), the identity without bins of the caller's
+    std::vector<uint32_t> bins;    // (B, 2) ranges of hist.beads(), the identity without bins of the caller's
     dbuf<uint32_t> bins_dev;
     // per call
     dbuf<uint2> tiles_dev;
     dbuf<unsigned long long> partial, out;
 
-    const void *x() const { return is_f64 ? (const void *)xd.p : (const void *)xf.p; }
-    size_t elem() const { return is_f64 ? sizeof(double) : sizeof(float); }
     unsigned B() const { return (unsigned)(bins.size() / 2); }
 };
 
 namespace {
-
-int check_bins(const char *who, const uint32_t *r, unsigned B, unsigned N)
-{
-    for (unsigned b = 0; b < B; b++) {
-        if (r[2 * b] >= r[2 * b + 1]) return fail(GD_EINVAL, "%s: bin %u is empty or reversed: [%u, %u)", who, b, r[2 * b], r[2 * b + 1]);
-        if (r[2 * b + 1] > N) return fail(GD_EINVAL, "%s: bin %u ends at %u, beyond the %u beads", who, b, r[2 * b + 1], N);
-        if (b && r[2 * b] < r[2 * b - 1]) return fail(GD_EINVAL, "%s: bin %u starts at %u, before bin %u ends (%u)", who, b, r[2 * b], b - 1, r[2 * b - 1]);
-    }
-    return GD_OK;
-}
 
 // the bins of a handle become `ranges`; the device copy is replaced only when it has been made
 int install_bins(gd_dmap *h, std::vector<uint32_t> ranges, bool have)
@@ -316,33 +278,12 @@ std::vector<uint32_t> identity_bins(unsigned N)
     return r;
 }
 
-// the history is on the device: the non-finite check, then the handle holds it (or none)
-int finish_history(gd_dmap *h, const char *who, unsigned frames, unsigned n_beads, bool is_f64)
+History::Rebind rebind(gd_dmap *h)
 {
-    size_t const n = (size_t)frames * n_beads * 3;
-    HIPCHK(h->first_bad.ensure(1));
-    HIPCHK(hipMemsetAsync(h->first_bad.p, 0xff, sizeof(unsigned long long), h->stream));
-    unsigned const blocks = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 8192);
-    if (is_f64) hipLaunchKernelGGL(k_dmap_first_bad<double>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xd.p, n, h->first_bad.p);
-    else hipLaunchKernelGGL(k_dmap_first_bad<float>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xf.p, n, h->first_bad.p);
-    HIPCHK(hipGetLastError());
-    unsigned long long bad = kNoBadIndex;
-    HIPCHK(hipMemcpyAsync(&bad, h->first_bad.p, sizeof bad, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (bad != kNoBadIndex) return fail(GD_EINVAL, "%s: non-finite coordinate at %llu", who, bad);
-    if (n_beads != h->N || h->bins.empty())      // bins belonged to another N
-        if (int rc = install_bins(h, identity_bins(n_beads), false)) return rc;
-    h->F = frames;
-    h->N = n_beads;
-    h->is_f64 = is_f64;
-    return GD_OK;
-}
-
-int check_shape(const char *who, uint32_t frames, uint32_t n_beads)
-{
-    if (frames == 0 || n_beads == 0) return fail(GD_EINVAL, "%s: empty history (%u frames of %u beads)", who, frames, n_beads);
-    if (n_beads > (1u << 28)) return fail(GD_EINVAL, "%s: %u beads exceed 2^28", who, n_beads);
-    return GD_OK;
+    return [h](unsigned n_beads) -> int {
+        if (n_beads != h->hist.beads() || h->bins.empty()) GDCHK(install_bins(h, identity_bins(n_beads), false));      // bins belonged to another N
+        return GD_OK;
+    };
 }
 
 }  // namespace
@@ -364,47 +305,26 @@ int gd_dmap_destroy(gd_dmap *h) { return gd::close(h); }
 int gd_dmap_set_history(gd_dmap *h, const void *xyz, uint32_t frames, uint32_t n_beads, int is_f64)
 {
     const char *who = "gd_dmap_set_history";
-    if (!h || !xyz) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (int rc = check_shape(who, frames, n_beads)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    size_t const n = (size_t)frames * n_beads * 3;
-    h->F = 0;      // the buffer is about to be overwritten
-    if (is_f64) HIPCHK(h->xd.upload(static_cast<const double *>(xyz), n));
-    else HIPCHK(h->xf.upload(static_cast<const float *>(xyz), n));
-    return finish_history(h, who, frames, n_beads, is_f64 != 0);
+    if (!h) return fail(GD_EINVAL, "%s: NULL argument", who);
+    return h->hist.set_host(who, h->device, h->stream, xyz, frames, n_beads, is_f64 != 0, rebind(h));
 }
 
 int gd_dmap_set_history_live(gd_dmap *h, gd_live_history *history, uint32_t replica)
 {
     const char *who = "gd_dmap_set_history_live";
-    if (!h || !history) return fail(GD_EINVAL, "%s: NULL handle", who);
-    gd_live_history_shape const v = gd_live_history_shape_of(history);
-    uint32_t slot = 0;
-    if (int rc = gd_live_history_slot(history, who, replica, &slot)) return rc;
-    if (v.device != h->device) return fail(GD_EINVAL, "%s: the recorder is on device %d, the analysis handle on device %d", who, v.device, h->device);
-    if (!v.frames) return fail(GD_ESTATE, "%s: no frame recorded", who);
-    if (int rc = check_shape(who, v.frames, v.N)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    size_t const M = (size_t)v.N * 3;
-    h->F = 0;
-    HIPCHK(h->xf.ensure((size_t)v.frames * M));
-    for (uint32_t f0 = 0; f0 < v.frames; f0 += v.frames_per_block) {      // one strided copy per block of the recorder
-        uint32_t const nf = std::min(v.frames_per_block, v.frames - f0);
-        HIPCHK(hipMemcpy2DAsync(h->xf.p + (size_t)f0 * M, M * sizeof(float), gd_live_history_frame(history, f0, slot), v.frame_stride * sizeof(float),
-                                M * sizeof(float), nf, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return finish_history(h, who, v.frames, v.N, false);
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    return h->hist.set_live(who, h->device, h->stream, history, replica, rebind(h));
 }
 
 int gd_dmap_set_bins(gd_dmap *h, const uint32_t *ranges, uint32_t n_bins)
 {
     const char *who = "gd_dmap_set_bins";
     if (!h || (!ranges && n_bins)) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the bins are ranges of its beads)", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the bins are ranges of its beads)", who);
     if (n_bins > (1u << 28)) return fail(GD_EINVAL, "%s: %u bins exceed 2^28", who, n_bins);
     HIPCHK(hipSetDevice(h->device));
-    if (!n_bins) return install_bins(h, identity_bins(h->N), false);
-    if (int rc = check_bins(who, ranges, n_bins, h->N)) return rc;
+    if (!n_bins) return install_bins(h, identity_bins(h->hist.beads()), false);
+    if (int rc = check_ranges(who, "bin", false, ranges, n_bins, h->hist.beads())) return rc;
     return install_bins(h, std::vector<uint32_t>(ranges, ranges + 2 * (size_t)n_bins), true);
 }
 
@@ -413,14 +333,14 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
 {
     const char *who = "gd_dmap_map";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set", who);
     if (!count) return fail(GD_EINVAL, "%s: NULL argument", who);
     unsigned const B = h->B();
     if (n_rows == 0 || n_cols == 0 || (uint64_t)row_first + n_rows > B || (uint64_t)col_first + n_cols > B)
         return fail(GD_EINVAL, "%s: rows %u to %llu and columns %u to %llu of %u bins", who, row_first, (unsigned long long)row_first + n_rows, col_first,
                     (unsigned long long)col_first + n_cols, B);
-    if (n_frames == 0 || (uint64_t)first_frame + n_frames > h->F)
-        return fail(GD_EINVAL, "%s: frames %u to %llu of %u", who, first_frame, (unsigned long long)first_frame + n_frames, h->F);
+    if (n_frames == 0 || (uint64_t)first_frame + n_frames > h->hist.frames())
+        return fail(GD_EINVAL, "%s: frames %u to %llu of %u", who, first_frame, (unsigned long long)first_frame + n_frames, h->hist.frames());
     if (n_thresholds > kMaxT) return fail(GD_EINVAL, "%s: %u thresholds (at most %u)", who, n_thresholds, kMaxT);
     if (n_thresholds && !thresholds) return fail(GD_EINVAL, "%s: NULL argument", who);
     for (unsigned t = 0; t < n_thresholds; t++)
@@ -428,7 +348,7 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     if (box)
         for (int k = 0; k < 3; k++)
             if (!(box[k] > 0.0) || !std::isfinite(box[k])) return fail(GD_EINVAL, "%s: box period %d is %g (positive and finite)", who, k, box[k]);
-    if (int rc = check_bins(who, h->bins.data(), B, h->N)) return rc;
+    if (int rc = check_ranges(who, "bin", false, h->bins.data(), B, h->hist.beads())) return rc;
     HIPCHK(hipSetDevice(h->device));
 
     // the canonical tiles the rectangle touches, each once
@@ -453,16 +373,16 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     unsigned longest = 1;
     for (unsigned b = 0; b < B; b++) longest = std::max(longest, h->bins[2 * b + 1] - h->bins[2 * b]);
     MapArgs a{};
-    a.x = h->x();
+    a.x = h->hist.x();
     a.bins = h->bins_dev.p;
-    a.N = h->N;
+    a.N = h->hist.beads();
     a.B = B;
     a.f0 = first_frame;
     a.f1 = first_frame + n_frames;
     a.g0 = first_frame / kRange;
     a.L = std::min(longest, kPiece);
     a.S = a.L | 1u;
-    size_t const frame_bytes = (size_t)2 * 3 * kTB * a.S * h->elem();
+    size_t const frame_bytes = (size_t)2 * 3 * kTB * a.S * h->hist.elem();
     unsigned const fit = (unsigned)std::max<size_t>(((size_t)h->lds_bytes - kStaticLds) / frame_bytes, 1);
     a.chunk = h->knob ? std::min(h->knob, fit) : (unsigned)std::max<size_t>(kAutoStageBytes / frame_bytes, 1);
     a.chunk = std::min(a.chunk, kRange);
@@ -479,7 +399,7 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
         a.tiles = h->tiles_dev.p + t0;
         a.partial = h->partial.p;
         dim3 const grid(n, ranges);
-        if (h->is_f64) {
+        if (h->hist.is_f64) {
             if (box) launch_tile<double, true>(sum1 != nullptr, grid, lds, h->stream, a);
             else launch_tile<double, false>(sum1 != nullptr, grid, lds, h->stream, a);
         } else {

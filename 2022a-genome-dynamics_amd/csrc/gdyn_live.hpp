@@ -51,7 +51,7 @@ GD_SEAM int gd_flow_device(const gd_flow *h);
 GD_SEAM int gd_flow_history_begin(gd_flow *h, const char *who, uint32_t frames, uint32_t n_beads, double **x, hipStream_t *stream);
 GD_SEAM void gd_flow_history_end(gd_flow *h, uint32_t frames, uint32_t n_beads, bool ok);
 
-// ---- the recorder (gdyn_live.hip), for an analysis that takes its frames as recorded (gdyn_msd.hip): float32, frame f of a slot
+// ---- the recorder (gdyn_live.hip), for an analysis that takes its frames as recorded (gdyn_history.hip): float32, frame f of a slot
 // at gd_live_history_frame(h, f, slot), the frames of one block frame_stride floats apart.  The blocks are not written while the
 // recorder's stream is idle, which every gd_live_history_* call leaves it.
 struct gd_live_history_shape {

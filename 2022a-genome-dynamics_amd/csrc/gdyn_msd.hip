@@ -18,7 +18,7 @@
 //   k_msd_reduce1/2  the sums of a group: per fixed chunk of 256 sequences, serially over ascending sequences (each the serial sum
 //                    of its ranges), then serially over the chunks.  The order depends on the shapes alone.
 //   k_msd_per_seq    gd_msd_time_per_bead: the serial sum of a sequence's ranges.
-//   k_msd_first_bad  the lowest index of a non-finite coordinate (integer atomicMin, reached by no lane of a finite history)
+// The history itself (upload, non-finite check) is gd::History's (gdyn_history.hpp).
 // fp64 throughout, -ffp-contract=off (csrc/Makefile), no fast-math, no floating-point atomics.
 #include <hip/hip_runtime.h>
 
@@ -32,8 +32,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_msd.h"
 #include "gdyn_analysis.hpp"
-#include "gdyn_live.hpp"
-#include "gdyn_once.hpp"
+#include "gdyn_history.hpp"
 
 using namespace gd;
 
@@ -47,7 +46,6 @@ constexpr unsigned kSlots = kLagBlock / kSeqs;  // lags evaluated side by side
 constexpr unsigned kRow = 3 * kSeqs + 1;     // elements of an item row in LDS: odd, so consecutive items start on different banks
 constexpr unsigned kRange = 4096;            // origins of one serial sum: fixed, so that the order of summation is
 constexpr unsigned kChunk = 256;             // sequences of one serial group sum: likewise
-constexpr unsigned long long kNoBadIndex = ~0ull;
 constexpr size_t kPartialBytes = (size_t)1 << 30;      // lags are evaluated in batches whose partial sums fit this
 
 struct LagArgs {
@@ -236,30 +234,11 @@ __global__ void __launch_bounds__(kBlock) k_msd_per_seq(const double2 *__restric
     if (q < n_seqs) out[q] = sum_ranges(partial, ranges, n_seqs, 1, q, 0);
 }
 
-template <typename T>
-__global__ void __launch_bounds__(kBlock) k_msd_first_bad(const T *__restrict__ x, size_t n, unsigned long long *first_bad)
-{
-    unsigned long long bad = kNoBadIndex;
-    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock)
-        if (!isfinite(x[i])) bad = min(bad, (unsigned long long)i);
-    if (bad != kNoBadIndex) atomicMin(first_bad, bad);
-}
-
-// The dynamic LDS a block of k_msd_lag may ask for on a device: all 160 KiB of a gfx950 CU where the opt-in is granted (once per
-// device, gdyn_once.hpp), else 128 KiB, else the 64 KiB that need none.  A refusal only makes the windows smaller.
+// the dynamic LDS a block of k_msd_lag may ask for (gd::lds_opt_in).  A refusal only makes the windows smaller.
 int lds_budget(int device)
 {
     static DeviceOnce<> once;
-    int const bytes = once.run(device, [](int) {
-        for (int want : {160 * 1024, 128 * 1024}) {
-            hipError_t const a = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_lag<float>), hipFuncAttributeMaxDynamicSharedMemorySize, want);
-            hipError_t const b = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_msd_lag<double>), hipFuncAttributeMaxDynamicSharedMemorySize, want);
-            if (a == hipSuccess && b == hipSuccess) return want;
-            (void)hipGetLastError();
-        }
-        return 64 * 1024;
-    });
-    return bytes > 0 ? bytes : 64 * 1024;
+    return lds_opt_in(once, device, {reinterpret_cast<const void *>(&k_msd_lag<float>), reinterpret_cast<const void *>(&k_msd_lag<double>)});
 }
 
 }  // namespace
@@ -267,12 +246,8 @@ int lds_budget(int device)
 struct gd_msd : gd::handle {
     unsigned knob = 0;
     int lds_bytes = 64 * 1024;
-    unsigned F = 0, N = 0;         // F == 0: no history; N stays, for the groups and chains that belong to it
-    bool is_f64 = false;
-    dbuf<float> xf;
-    dbuf<double> xd;
-    dbuf<unsigned long long> first_bad;
-    // groups and chains
+    History hist;
+    // groups and chains, which belong to hist.beads()
     unsigned G = 1;
     bool have_groups = false;      // false: one group of all beads
     std::vector<int32_t> group;
@@ -282,9 +257,6 @@ struct gd_msd : gd::handle {
     // per call
     dbuf<uint32_t> lags_dev;
     dbuf<double2> partial, tmp, out;
-
-    const void *x() const { return is_f64 ? (const void *)xd.p : (const void *)xf.p; }
-    size_t elem() const { return is_f64 ? sizeof(double) : sizeof(float); }
 };
 
 namespace {
@@ -296,47 +268,17 @@ int check_groups(const char *who, const int32_t *group, unsigned N, unsigned G)
     return GD_OK;
 }
 
-int check_chains(const char *who, const uint32_t *r, unsigned C, unsigned N)
+History::Rebind rebind(gd_msd *h)
 {
-    for (unsigned c = 0; c < C; c++) {
-        if (r[2 * c] > r[2 * c + 1]) return fail(GD_EINVAL, "%s: chain %u is reversed: [%u, %u)", who, c, r[2 * c], r[2 * c + 1]);
-        if (r[2 * c + 1] > N) return fail(GD_EINVAL, "%s: chain %u ends at %u, beyond the %u beads", who, c, r[2 * c + 1], N);
-        if (c && r[2 * c] < r[2 * c - 1]) return fail(GD_EINVAL, "%s: chain %u starts at %u, before chain %u ends (%u)", who, c, r[2 * c], c - 1, r[2 * c - 1]);
-    }
-    return GD_OK;
-}
-
-// the history is on the device: the non-finite check, then the handle holds it (or none)
-int finish_history(gd_msd *h, const char *who, unsigned frames, unsigned n_beads, bool is_f64)
-{
-    size_t const n = (size_t)frames * n_beads * 3;
-    HIPCHK(h->first_bad.ensure(1));
-    HIPCHK(hipMemsetAsync(h->first_bad.p, 0xff, sizeof(unsigned long long), h->stream));
-    unsigned const blocks = (unsigned)std::min<size_t>((n + kBlock - 1) / kBlock, 8192);
-    if (is_f64) hipLaunchKernelGGL(k_msd_first_bad<double>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xd.p, n, h->first_bad.p);
-    else hipLaunchKernelGGL(k_msd_first_bad<float>, dim3(blocks), dim3(kBlock), 0, h->stream, h->xf.p, n, h->first_bad.p);
-    HIPCHK(hipGetLastError());
-    unsigned long long bad = kNoBadIndex;
-    HIPCHK(hipMemcpyAsync(&bad, h->first_bad.p, sizeof bad, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (bad != kNoBadIndex) return fail(GD_EINVAL, "%s: non-finite coordinate at %llu", who, bad);
-    if (n_beads != h->N) {      // groups and chains belonged to another N
-        h->have_groups = false;
-        h->G = 1;
-        h->group.clear();
-        h->chains.clear();
-    }
-    h->F = frames;
-    h->N = n_beads;
-    h->is_f64 = is_f64;
-    return GD_OK;
-}
-
-int check_shape(const char *who, uint32_t frames, uint32_t n_beads)
-{
-    if (frames == 0 || n_beads == 0) return fail(GD_EINVAL, "%s: empty history (%u frames of %u beads)", who, frames, n_beads);
-    if (n_beads > (1u << 28)) return fail(GD_EINVAL, "%s: %u beads exceed 2^28", who, n_beads);
-    return GD_OK;
+    return [h](unsigned n_beads) -> int {
+        if (n_beads != h->hist.beads()) {      // groups and chains belonged to another N
+            h->have_groups = false;
+            h->G = 1;
+            h->group.clear();
+            h->chains.clear();
+        }
+        return GD_OK;
+    };
 }
 
 // lags: distinct and >= 1; order: their indices by ascending lag
@@ -362,7 +304,7 @@ struct Plan {      // one axis of one call
 // evaluates the sorted lags [k0, k0 + nl) into h->partial ((ranges, n_seqs, nl), zero where nothing is summed)
 int run_lags(gd_msd *h, const Plan &pl, const uint32_t *sorted_lags_dev, unsigned nl)
 {
-    size_t const row = (size_t)kRow * h->elem();
+    size_t const row = (size_t)kRow * h->hist.elem();
     unsigned const fit = (unsigned)std::min<size_t>((size_t)h->lds_bytes / row, 1u << 28);
     unsigned W, windows;
     unsigned const want = h->knob ? std::min(h->knob, pl.longest) : pl.longest;
@@ -378,12 +320,12 @@ int run_lags(gd_msd *h, const Plan &pl, const uint32_t *sorted_lags_dev, unsigne
     HIPCHK(h->partial.ensure(cells));
     HIPCHK(hipMemsetAsync(h->partial.p, 0, cells * sizeof(double2), h->stream));
     LagArgs a;
-    a.x = h->x();
+    a.x = h->hist.x();
     a.chains = pl.along_chain ? h->chains_dev.p : nullptr;
     a.lags = sorted_lags_dev;
     a.partial = h->partial.p;
-    a.N = h->N;
-    a.F = h->F;
+    a.N = h->hist.beads();
+    a.F = h->hist.frames();
     a.C = (unsigned)(h->chains.size() / 2);
     a.f0 = pl.f0;
     a.nf = pl.nf;
@@ -394,7 +336,7 @@ int run_lags(gd_msd *h, const Plan &pl, const uint32_t *sorted_lags_dev, unsigne
     a.n_seqs = pl.n_seqs;
     dim3 const grid((unsigned)pl.tiles, std::min(pl.ranges, 65535u));
     size_t const lds = (size_t)windows * W * row;
-    if (h->is_f64) hipLaunchKernelGGL(k_msd_lag<double>, grid, dim3(kLagBlock), lds, h->stream, a);
+    if (h->hist.is_f64) hipLaunchKernelGGL(k_msd_lag<double>, grid, dim3(kLagBlock), lds, h->stream, a);
     else hipLaunchKernelGGL(k_msd_lag<float>, grid, dim3(kLagBlock), lds, h->stream, a);
     HIPCHK(hipGetLastError());
     return GD_OK;
@@ -437,10 +379,10 @@ Plan time_plan(const gd_msd *h)
 {
     Plan pl{};
     pl.along_chain = false;
-    pl.n_seqs = h->N;
-    pl.tiles = (h->N + kSeqs - 1) / kSeqs;
-    pl.longest = h->F;
-    pl.ranges = h->F > 1 ? (h->F - 1 + kRange - 1) / kRange : 1;
+    pl.n_seqs = h->hist.beads();
+    pl.tiles = (h->hist.beads() + kSeqs - 1) / kSeqs;
+    pl.longest = h->hist.frames();
+    pl.ranges = h->hist.frames() > 1 ? (h->hist.frames() - 1 + kRange - 1) / kRange : 1;
     return pl;
 }
 
@@ -463,43 +405,22 @@ int gd_msd_destroy(gd_msd *h) { return gd::close(h); }
 int gd_msd_set_history(gd_msd *h, const void *xyz, uint32_t frames, uint32_t n_beads, int is_f64)
 {
     const char *who = "gd_msd_set_history";
-    if (!h || !xyz) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (int rc = check_shape(who, frames, n_beads)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    size_t const n = (size_t)frames * n_beads * 3;
-    h->F = 0;      // the buffer is about to be overwritten
-    if (is_f64) HIPCHK(h->xd.upload(static_cast<const double *>(xyz), n));
-    else HIPCHK(h->xf.upload(static_cast<const float *>(xyz), n));
-    return finish_history(h, who, frames, n_beads, is_f64 != 0);
+    if (!h) return fail(GD_EINVAL, "%s: NULL argument", who);
+    return h->hist.set_host(who, h->device, h->stream, xyz, frames, n_beads, is_f64 != 0, rebind(h));
 }
 
 int gd_msd_set_history_live(gd_msd *h, gd_live_history *history, uint32_t replica)
 {
     const char *who = "gd_msd_set_history_live";
-    if (!h || !history) return fail(GD_EINVAL, "%s: NULL handle", who);
-    gd_live_history_shape const v = gd_live_history_shape_of(history);
-    uint32_t slot = 0;
-    if (int rc = gd_live_history_slot(history, who, replica, &slot)) return rc;
-    if (v.device != h->device) return fail(GD_EINVAL, "%s: the recorder is on device %d, the analysis handle on device %d", who, v.device, h->device);
-    if (!v.frames) return fail(GD_ESTATE, "%s: no frame recorded", who);
-    if (int rc = check_shape(who, v.frames, v.N)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    size_t const M = (size_t)v.N * 3;
-    h->F = 0;
-    HIPCHK(h->xf.ensure((size_t)v.frames * M));
-    for (uint32_t f0 = 0; f0 < v.frames; f0 += v.frames_per_block) {      // one strided copy per block of the recorder
-        uint32_t const nf = std::min(v.frames_per_block, v.frames - f0);
-        HIPCHK(hipMemcpy2DAsync(h->xf.p + (size_t)f0 * M, M * sizeof(float), gd_live_history_frame(history, f0, slot), v.frame_stride * sizeof(float),
-                                M * sizeof(float), nf, hipMemcpyDeviceToDevice, h->stream));
-    }
-    return finish_history(h, who, v.frames, v.N, false);
+    if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
+    return h->hist.set_live(who, h->device, h->stream, history, replica, rebind(h));
 }
 
 int gd_msd_set_groups(gd_msd *h, const int32_t *group, uint32_t n_groups)
 {
     const char *who = "gd_msd_set_groups";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the groups are N values of its beads)", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the groups are N values of its beads)", who);
     if (!group) {
         if (n_groups > 1) return fail(GD_EINVAL, "%s: %u groups without a group array", who, n_groups);
         h->have_groups = false;
@@ -508,12 +429,12 @@ int gd_msd_set_groups(gd_msd *h, const int32_t *group, uint32_t n_groups)
         return GD_OK;
     }
     if (n_groups == 0 || n_groups > (1u << 20)) return fail(GD_EINVAL, "%s: %u groups (1 to 2^20)", who, n_groups);
-    if (int rc = check_groups(who, group, h->N, n_groups)) return rc;
+    if (int rc = check_groups(who, group, h->hist.beads(), n_groups)) return rc;
     HIPCHK(hipSetDevice(h->device));
     dbuf<int32_t> dev;
-    HIPCHK(dev.upload(group, h->N));
+    HIPCHK(dev.upload(group, h->hist.beads()));
     h->group_dev = std::move(dev);
-    h->group.assign(group, group + h->N);
+    h->group.assign(group, group + h->hist.beads());
     h->G = n_groups;
     h->have_groups = true;
     return GD_OK;
@@ -523,9 +444,9 @@ int gd_msd_set_chains(gd_msd *h, const uint32_t *ranges, uint32_t n_chains)
 {
     const char *who = "gd_msd_set_chains";
     if (!h || (!ranges && n_chains)) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set (the chains are ranges of its beads)", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the chains are ranges of its beads)", who);
     if (n_chains > (1u << 24)) return fail(GD_EINVAL, "%s: %u chains exceed 2^24", who, n_chains);
-    if (int rc = check_chains(who, ranges, n_chains, h->N)) return rc;
+    if (int rc = check_ranges(who, "chain", true, ranges, n_chains, h->hist.beads())) return rc;
     HIPCHK(hipSetDevice(h->device));
     dbuf<uint32_t> dev;
     HIPCHK(dev.upload(ranges, 2 * (size_t)n_chains));
@@ -539,23 +460,23 @@ int gd_msd_time(gd_msd *h, const uint32_t *lags, uint32_t n_lags, double *sum2, 
     const char *who = "gd_msd_time";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
     if (n_lags && (!lags || !sum2 || !count)) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set", who);
     if (n_lags > (1u << 28)) return fail(GD_EINVAL, "%s: %u lags exceed 2^28", who, n_lags);
     std::vector<uint32_t> order;
     if (int rc = check_lags(who, "lag", lags, n_lags, order)) return rc;
     if (h->have_groups)
-        if (int rc = check_groups(who, h->group.data(), h->N, h->G)) return rc;
+        if (int rc = check_groups(who, h->group.data(), h->hist.beads(), h->G)) return rc;
     if (n_lags == 0) return GD_OK;
     HIPCHK(hipSetDevice(h->device));
     std::vector<double> s2((size_t)h->G * n_lags), s4((size_t)h->G * n_lags);
     GroupMap const m{h->have_groups ? h->group_dev.p : nullptr, 0};
     if (int rc = group_sums(h, time_plan(h), lags, order, m, h->G, s2.data(), s4.data())) return rc;
-    std::vector<uint64_t> members(h->G, h->have_groups ? 0 : h->N);
+    std::vector<uint64_t> members(h->G, h->have_groups ? 0 : h->hist.beads());
     if (h->have_groups)
         for (int32_t g : h->group)
             if (g >= 0) members[g]++;
     for (unsigned g = 0; g < h->G; g++)
-        for (unsigned l = 0; l < n_lags; l++) count[(size_t)g * n_lags + l] = members[g] * (lags[l] < h->F ? h->F - lags[l] : 0);
+        for (unsigned l = 0; l < n_lags; l++) count[(size_t)g * n_lags + l] = members[g] * (lags[l] < h->hist.frames() ? h->hist.frames() - lags[l] : 0);
     std::memcpy(sum2, s2.data(), s2.size() * sizeof(double));
     if (sum4) std::memcpy(sum4, s4.data(), s4.size() * sizeof(double));
     return GD_OK;
@@ -565,19 +486,19 @@ int gd_msd_time_per_bead(gd_msd *h, uint32_t lag, double *m2, double *m4)
 {
     const char *who = "gd_msd_time_per_bead";
     if (!h || !m2) return fail(GD_EINVAL, "%s: NULL argument", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
-    if (lag == 0 || lag >= h->F) return fail(GD_EINVAL, "%s: lag %u of %u frames (1 to F - 1)", who, lag, h->F);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set", who);
+    if (lag == 0 || lag >= h->hist.frames()) return fail(GD_EINVAL, "%s: lag %u of %u frames (1 to F - 1)", who, lag, h->hist.frames());
     HIPCHK(hipSetDevice(h->device));
     Plan const pl = time_plan(h);
     HIPCHK(h->lags_dev.upload(&lag, 1));
     if (int rc = run_lags(h, pl, h->lags_dev.p, 1)) return rc;
-    HIPCHK(h->out.ensure(h->N));
-    hipLaunchKernelGGL(k_msd_per_seq, dim3(blocks_for(h->N, kBlock)), dim3(kBlock), 0, h->stream, h->partial.p, pl.ranges, pl.n_seqs, h->out.p);
+    HIPCHK(h->out.ensure(h->hist.beads()));
+    hipLaunchKernelGGL(k_msd_per_seq, dim3(blocks_for(h->hist.beads(), kBlock)), dim3(kBlock), 0, h->stream, h->partial.p, pl.ranges, pl.n_seqs, h->out.p);
     HIPCHK(hipGetLastError());
-    std::vector<double2> host(h->N);
+    std::vector<double2> host(h->hist.beads());
     HIPCHK(hipMemcpyAsync(host.data(), h->out.p, host.size() * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (unsigned i = 0; i < h->N; i++) {
+    for (unsigned i = 0; i < h->hist.beads(); i++) {
         m2[i] = host[i].x;
         if (m4) m4[i] = host[i].y;
     }
@@ -589,15 +510,15 @@ int gd_msd_chain(gd_msd *h, const uint32_t *seps, uint32_t n_seps, uint32_t firs
 {
     const char *who = "gd_msd_chain";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
-    if (!h->F) return fail(GD_ESTATE, "%s: no history set", who);
+    if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set", who);
     unsigned const C = (unsigned)(h->chains.size() / 2);
     if (n_seps && C && (!seps || !sum2 || !count)) return fail(GD_EINVAL, "%s: NULL argument", who);
     if (n_seps > (1u << 28)) return fail(GD_EINVAL, "%s: %u separations exceed 2^28", who, n_seps);
-    if ((uint64_t)first_frame + n_frames > h->F)
-        return fail(GD_EINVAL, "%s: frames %u to %llu of %u", who, first_frame, (unsigned long long)first_frame + n_frames, h->F);
+    if ((uint64_t)first_frame + n_frames > h->hist.frames())
+        return fail(GD_EINVAL, "%s: frames %u to %llu of %u", who, first_frame, (unsigned long long)first_frame + n_frames, h->hist.frames());
     std::vector<uint32_t> order;
     if (int rc = check_lags(who, "separation", seps, n_seps, order)) return rc;
-    if (int rc = check_chains(who, h->chains.data(), C, h->N)) return rc;
+    if (int rc = check_ranges(who, "chain", true, h->chains.data(), C, h->hist.beads())) return rc;
     if (n_seps == 0 || C == 0) return GD_OK;
     size_t const cells = (size_t)C * n_seps;
     unsigned longest = 0;

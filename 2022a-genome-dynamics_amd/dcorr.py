@@ -22,7 +22,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._binding import GdynError, Handle, as_frames, load_library
+from ._binding import GdynError, HistoryHandle, _u32, load_history_library
 
 DCORR_ABI_VERSION = 1      # GD_DCORR_ABI_VERSION of the include/gdyn_dcorr.h this binding mirrors
 DCORR_SYMBOLS = ["gd_dcorr_abi_version", "gd_dcorr_create", "gd_dcorr_destroy", "gd_dcorr_set_history", "gd_dcorr_set_history_live",
@@ -42,11 +42,9 @@ class _DcorrDesc(C.Structure):
 
 def load_dcorr_library(path=None):
     """Loads libgdyn and checks the gd_dcorr_* symbols and their ABI version."""
-    d = load_library("dcorr", DCORR_SYMBOLS, DCORR_ABI_VERSION, path)
+    d = load_history_library("dcorr", DCORR_SYMBOLS, DCORR_ABI_VERSION, path)
     d.gd_dcorr_create.argtypes = [C.POINTER(_DcorrDesc), C.POINTER(C.c_void_p)]
     d.gd_dcorr_destroy.argtypes = [C.c_void_p]
-    d.gd_dcorr_set_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
-    d.gd_dcorr_set_history_live.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_dcorr_set_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_dcorr_set_chains.argtypes = [C.c_void_p, C.c_void_p]
     d.gd_dcorr_bins.argtypes = [C.c_double, C.c_double]
@@ -147,38 +145,20 @@ def curves(count, total, self_count, self_sum, scale_bits, n_labels, chains, bin
     return Correlation(0.5 * (edges[:-1] + edges[1:]), dot, normalised, np.array(n, dtype=np.uint64))
 
 
-class Dcorr(Handle):
+class Dcorr(HistoryHandle):
     """One device-side history with its bead labels and chains.  max_frames_per_launch: 0 = automatic (no result depends on it)."""
 
+    _prefix = "dcorr"
     _destroy = "gd_dcorr_destroy"
 
     def __init__(self, device=0, max_frames_per_launch=0, path=None):
         super().__init__(load_dcorr_library(path))
         self._check(self.dll.gd_dcorr_create(C.byref(_DcorrDesc(device, max_frames_per_launch)), C.byref(self._h)))
-        self.shape = None          # (F, N) of the history
         self.n_labels = 1
         self.chains = False
 
-    def _new_shape(self, shape):
-        if self.shape is None or self.shape[1] != shape[1]:      # the library drops labels and chains of another N
-            self.n_labels, self.chains = 1, False
-        self.shape = shape
-
-    def set_history(self, frames):
-        """frames (F, N, 3), float32 or float64 (anything else becomes float32)."""
-        h = np.asarray(frames)
-        if h.ndim != 3 or h.shape[2] != 3:
-            raise ValueError(f"history must be (F, N, 3), got {h.shape}")
-        h, is64 = as_frames(h)
-        F, N, _ = h.shape
-        self._check(self.dll.gd_dcorr_set_history(self._h, h.ctypes.data, F, N, int(is64)))
-        self._new_shape((F, N))
-
-    def set_history_from(self, history, replica):
-        """The history becomes the frames that ``history`` (a live.History) recorded of ``replica``, float32 as recorded, going from
-        the recorder to this handle on the device."""
-        self._check(self.dll.gd_dcorr_set_history_live(self._h, history._h, int(replica)))
-        self._new_shape((history.frames, history.N))
+    def _beads_changed(self, n_beads):      # the library drops labels and chains of another N
+        self.n_labels, self.chains = 1, False
 
     def set_labels(self, label, n_labels=None):
         """label: (N,) integers in [-1, n_labels), -1 for a bead that takes no part; None: one label of all beads.
@@ -203,9 +183,7 @@ class Dcorr(Handle):
         c = np.asarray(chain).reshape(-1)
         if self.shape is not None and len(c) != self.shape[1]:
             raise ValueError(f"chain must have one entry per bead ({self.shape[1]}), got {len(c)}")
-        if len(c) and (not np.issubdtype(c.dtype, np.integer) or c.min() < 0 or c.max() > 0xFFFFFFFF):
-            raise ValueError("chain ids must be integers in [0, 2^32)")
-        c = np.ascontiguousarray(c, dtype=np.uint32)
+        c = _u32(c, "chain ids")
         self._check(self.dll.gd_dcorr_set_chains(self._h, c.ctypes.data))
         self.chains = True
 

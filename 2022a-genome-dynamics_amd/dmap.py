@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._binding import GdynError, Handle, as_frames, load_library
+from ._binding import GdynError, HistoryHandle, _ratio, _u32, load_history_library
 
 DMAP_ABI_VERSION = 1      # GD_DMAP_ABI_VERSION of the include/gdyn_dmap.h this binding mirrors
 DMAP_MAX_THRESHOLDS = 4   # GD_DMAP_MAX_THRESHOLDS
@@ -34,60 +34,27 @@ class _DmapDesc(C.Structure):
 
 def load_dmap_library(path=None):
     """Loads libgdyn and checks the gd_dmap_* symbols and their ABI version."""
-    d = load_library("dmap", DMAP_SYMBOLS, DMAP_ABI_VERSION, path)
+    d = load_history_library("dmap", DMAP_SYMBOLS, DMAP_ABI_VERSION, path)
     d.gd_dmap_create.argtypes = [C.POINTER(_DmapDesc), C.POINTER(C.c_void_p)]
     d.gd_dmap_destroy.argtypes = [C.c_void_p]
-    d.gd_dmap_set_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
-    d.gd_dmap_set_history_live.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_dmap_set_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_dmap_map.argtypes = [C.c_void_p] + [C.c_uint32] * 6 + [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
     return d
 
 
-def _u32(values, what):
-    v = np.asarray(values)
-    if v.size and (not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() > 0xFFFFFFFF):
-        raise ValueError(f"{what} must be integers in [0, 2^32)")
-    return np.ascontiguousarray(v, dtype=np.uint32)
-
-
-def _ratio(total, count):
-    out = np.full(total.shape, np.nan)
-    np.divide(total, np.broadcast_to(count, total.shape), out=out, where=np.broadcast_to(count, total.shape) > 0)
-    return out
-
-
-class Dmap(Handle):
+class Dmap(HistoryHandle):
     """One device-side history with its bins.  max_frames_per_stage: 0 = automatic (no result depends on it)."""
 
+    _prefix = "dmap"
     _destroy = "gd_dmap_destroy"
 
     def __init__(self, device=0, max_frames_per_stage=0, path=None):
         super().__init__(load_dmap_library(path))
         self._check(self.dll.gd_dmap_create(C.byref(_DmapDesc(device, max_frames_per_stage)), C.byref(self._h)))
-        self.shape = None          # (F, N) of the history
         self.n_bins = 0            # B: N without bins of the caller's
 
-    def _new_shape(self, shape):
-        if self.shape is None or self.shape[1] != shape[1]:      # the library drops the bins of another N
-            self.n_bins = shape[1]
-        self.shape = shape
-
-    def set_history(self, frames):
-        """frames (F, N, 3), float32 or float64 (anything else becomes float32)."""
-        h = np.asarray(frames)
-        if h.ndim != 3 or h.shape[2] != 3:
-            raise ValueError(f"history must be (F, N, 3), got {h.shape}")
-        h, is64 = as_frames(h)
-        F, N, _ = h.shape
-        self._check(self.dll.gd_dmap_set_history(self._h, h.ctypes.data, F, N, int(is64)))
-        self._new_shape((F, N))
-
-    def set_history_from(self, history, replica):
-        """The history becomes the frames that ``history`` (a live.History) recorded of ``replica``, float32 as recorded, going from
-        the recorder to this handle on the device."""
-        self._check(self.dll.gd_dmap_set_history_live(self._h, history._h, int(replica)))
-        self._new_shape((history.frames, history.N))
+    def _beads_changed(self, n_beads):      # the library drops the bins of another N
+        self.n_bins = n_beads
 
     def set_bins(self, ranges):
         """ranges: (B, 2) [start, end) bead ranges, ascending, non-empty and not overlapping; None: every bead is its own bin."""

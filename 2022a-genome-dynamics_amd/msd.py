@@ -21,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._binding import GdynError, Handle, as_frames, load_library
+from ._binding import GdynError, HistoryHandle, _ratio, _u32, load_history_library
 
 MSD_ABI_VERSION = 1       # GD_MSD_ABI_VERSION of the include/gdyn_msd.h this binding mirrors
 MSD_SYMBOLS = ["gd_msd_abi_version", "gd_msd_create", "gd_msd_destroy", "gd_msd_set_history", "gd_msd_set_history_live",
@@ -34,11 +34,9 @@ class _MsdDesc(C.Structure):
 
 def load_msd_library(path=None):
     """Loads libgdyn and checks the gd_msd_* symbols and their ABI version."""
-    d = load_library("msd", MSD_SYMBOLS, MSD_ABI_VERSION, path)
+    d = load_history_library("msd", MSD_SYMBOLS, MSD_ABI_VERSION, path)
     d.gd_msd_create.argtypes = [C.POINTER(_MsdDesc), C.POINTER(C.c_void_p)]
     d.gd_msd_destroy.argtypes = [C.c_void_p]
-    d.gd_msd_set_history.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]
-    d.gd_msd_set_history_live.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_msd_set_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_msd_set_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     d.gd_msd_time.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -47,51 +45,20 @@ def load_msd_library(path=None):
     return d
 
 
-def _u32(values, what):
-    v = np.asarray(values)
-    if v.size and (not np.issubdtype(v.dtype, np.integer) or v.min() < 0 or v.max() > 0xFFFFFFFF):
-        raise ValueError(f"{what} must be integers in [0, 2^32)")
-    return np.ascontiguousarray(v, dtype=np.uint32)
-
-
-def _ratio(total, count):
-    out = np.full(total.shape, np.nan)
-    np.divide(total, count, out=out, where=count > 0)
-    return out
-
-
-class Msd(Handle):
+class Msd(HistoryHandle):
     """One device-side history with its bead groups and chains.  max_items_per_tile: 0 = automatic (no result depends on it)."""
 
+    _prefix = "msd"
     _destroy = "gd_msd_destroy"
 
     def __init__(self, device=0, max_items_per_tile=0, path=None):
         super().__init__(load_msd_library(path))
         self._check(self.dll.gd_msd_create(C.byref(_MsdDesc(device, max_items_per_tile)), C.byref(self._h)))
-        self.shape = None          # (F, N) of the history
         self.n_groups = 1
         self.n_chains = 0
 
-    def _new_shape(self, shape):
-        if self.shape is None or self.shape[1] != shape[1]:      # the library drops groups and chains of another N
-            self.n_groups, self.n_chains = 1, 0
-        self.shape = shape
-
-    def set_history(self, frames):
-        """frames (F, N, 3), float32 or float64 (anything else becomes float32)."""
-        h = np.asarray(frames)
-        if h.ndim != 3 or h.shape[2] != 3:
-            raise ValueError(f"history must be (F, N, 3), got {h.shape}")
-        h, is64 = as_frames(h)
-        F, N, _ = h.shape
-        self._check(self.dll.gd_msd_set_history(self._h, h.ctypes.data, F, N, int(is64)))
-        self._new_shape((F, N))
-
-    def set_history_from(self, history, replica):
-        """The history becomes the frames that ``history`` (a live.History) recorded of ``replica``, float32 as recorded, going from
-        the recorder to this handle on the device."""
-        self._check(self.dll.gd_msd_set_history_live(self._h, history._h, int(replica)))
-        self._new_shape((history.frames, history.N))
+    def _beads_changed(self, n_beads):      # the library drops groups and chains of another N
+        self.n_groups, self.n_chains = 1, 0
 
     def set_groups(self, group, n_groups=None):
         """group: (N,) integers in [-1, n_groups), -1 for a bead in no group; None: one group of all beads.
