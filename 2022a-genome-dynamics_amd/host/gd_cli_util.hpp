@@ -1,6 +1,7 @@
-// gd_cli_util.hpp -- what the analysis programs share whatever they analyse: strict number parsing, Python's repr of a
-// float, the sample name of a trajectory file, the HDF5 datasets and groups of an output file as h5py writes them
-// (put_dataset with its filters), the error check of a libgdyn call, and the read / compute / write stopwatch.
+// gd_cli_util.hpp -- what the analysis programs share whatever they analyse: the option scanner (gd_cli_args.hpp), Python's
+// repr of a float, the sample name of a trajectory file, the HDF5 datasets and groups of an output file as h5py writes them
+// (put_dataset with its filters, put typed on the data), the error check of a libgdyn call, the read / compute / write
+// stopwatch, the owner of a device handle (handle) and the one shape of a main (run).
 #pragma once
 #include <hdf5.h>
 
@@ -9,33 +10,22 @@
 #include <charconv>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/gdyn.h"
+#include "gd_cli_args.hpp"
 #include "gd_h5util.hpp"
 
 namespace gd {
 namespace cli {
-
-inline bool parse_int(std::string const &s, long &out)
-{
-    char *end = nullptr;
-    errno = 0;
-    out = std::strtol(s.c_str(), &end, 10);
-    return !s.empty() && errno == 0 && end && *end == '\0';
-}
-
-inline bool parse_float(std::string const &s, double &out)
-{
-    char *end = nullptr;
-    out = std::strtod(s.c_str(), &end);
-    return !s.empty() && end && *end == '\0';
-}
 
 // repr(float) of Python: the shortest round-trip digits, fixed notation for exponents in [-4, 16), else d.ddde+XX
 inline std::string py_float(double v)
@@ -109,6 +99,28 @@ inline void put_dataset(hid_t loc, std::string const &path, void const *data, st
     if (count) h5::check(H5Dwrite(ds, mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, data) >= 0, "cannot write " + path);
 }
 
+// the HDF5 types of an element type: {in memory, in the file as h5py stores a numpy array of it}
+template <typename T>
+std::pair<hid_t, hid_t> h5_types()
+{
+    if constexpr (std::is_same_v<T, float>) return {H5T_NATIVE_FLOAT, H5T_IEEE_F32LE};
+    else if constexpr (std::is_same_v<T, double>) return {H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE};
+    else if constexpr (std::is_same_v<T, int32_t>) return {H5T_NATIVE_INT32, H5T_STD_I32LE};
+    else if constexpr (std::is_same_v<T, uint32_t>) return {H5T_NATIVE_UINT32, H5T_STD_U32LE};
+    else if constexpr (std::is_same_v<T, int64_t>) return {H5T_NATIVE_INT64, H5T_STD_I64LE};
+    else {
+        static_assert(std::is_same_v<T, uint64_t>, "no HDF5 type for this element type: use put_dataset");
+        return {H5T_NATIVE_UINT64, H5T_STD_U64LE};
+    }
+}
+
+// put: put_dataset of an array whose file type is its element type's own
+template <typename T>
+void put(hid_t loc, std::string const &path, T const *data, std::vector<hsize_t> const &dims, filters const *f)
+{
+    put_dataset(loc, path, data, dims, sizeof(T), h5_types<T>().first, h5_types<T>().second, f);
+}
+
 inline hid_t open_output(std::string const &path)      // h5py.File(path, "a")
 {
     H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
@@ -146,6 +158,50 @@ struct stopwatch {
     }
     void report(char const *prog) const { std::fprintf(stderr, "%s: read %.3f s, compute %.3f s, write %.3f s\n", prog, read, compute, write); }
 };
+
+// one handle of a device module, owned.  open(create) makes it on first use, where create(&h) is the module's create call (a
+// program that opens it after its first read reports a missing input as such); every failure of the library ends the program
+template <typename H, auto Destroy>
+struct handle {
+    H *h = nullptr;
+    double startup = 0;      // seconds the create call took (the HIP runtime starts there), inside whichever lap the caller opens it in
+    handle() = default;
+    handle(handle const &) = delete;
+    handle &operator=(handle const &) = delete;
+    ~handle() { Destroy(h); }
+    template <typename Create>
+    void open(Create &&create)
+    {
+        if (h) return;
+        auto const t = std::chrono::steady_clock::now();
+        check(create(&h));
+        startup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    }
+    void report(char const *prog) const { std::fprintf(stderr, "%s: device start-up %.3f s\n", prog, startup); }
+};
+
+// the one main shape: a message of parse(err) after the usage text is status 2; plan() serves a --dry-run that needs no file and
+// says whether it did; then body() under the catch, where an exception is status 1 after `error_prefix`.  A program whose
+// --dry-run reads its inputs passes no_plan and serves it at the head of body
+inline bool no_plan() { return false; }
+
+template <typename Parse, typename Plan, typename Body>
+int run(std::string const &usage, char const *prog, char const *error_prefix, Parse &&parse, Plan &&plan, Body &&body)
+{
+    std::string err;
+    if (parse(err)) {
+        std::fprintf(stderr, "%s%s: error: %s\n", usage.c_str(), prog, err.c_str());
+        return 2;
+    }
+    if (plan()) return 0;
+    try {
+        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+        return body();
+    } catch (std::exception const &e) {
+        std::fprintf(stderr, "%s %s\n", error_prefix, e.what());
+        return 1;
+    }
+}
 
 }  // namespace cli
 }  // namespace gd

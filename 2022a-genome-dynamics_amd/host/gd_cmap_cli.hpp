@@ -73,46 +73,26 @@ inline std::vector<std::string> split(std::string const &s, char sep)      // st
 inline int parse(program p, int argc, char **argv, options &o, std::string &err)
 {
     bool const by_step = p == program::contact_map || p == program::nad_profile, gw = p == program::gw_contact_matrix;
+    using cli::kind;
+    static cli::table const by_step_options = {{"--dry-run", kind::flag}, {"--after", kind::value}, {"--before", kind::value}, {"--chroms", kind::value}},
+                            gw_options = {{"--dry-run", kind::flag}, {"--frame-range", kind::value}, {"--rebin-rate", kind::value}, {"--output", kind::value}, {"-o", kind::value}},
+                            power_law_options = {{"--dry-run", kind::flag}};
     bool has_chroms = false;
-    for (int k = 1; k < argc; k++) {
-        std::string const a = argv[k];
-        bool const is_short = gw && a == "-o";
-        if (!is_short && !(a.size() > 2 && a.compare(0, 2, "--") == 0)) {
-            o.inputs.push_back(a);
-            continue;
-        }
-        if (a == "--dry-run") { o.dry_run = true; continue; }
-        auto const eq = is_short ? std::string::npos : a.find('=');
-        std::string const key = eq == std::string::npos ? a : a.substr(0, eq);
-        bool const known = (by_step && (key == "--after" || key == "--before" || key == "--chroms")) ||
-                           (gw && (key == "--frame-range" || key == "--rebin-rate" || key == "--output" || key == "-o"));
-        if (!known) { err = "unrecognized arguments: " + a; return 2; }
-        std::string v;
-        if (eq != std::string::npos) v = a.substr(eq + 1);
-        else if (k + 1 < argc) v = argv[++k];
-        else { err = "argument " + key + ": expected one argument"; return 2; }
-        if (key == "--after" || key == "--before" || key == "--rebin-rate") {
-            long value = 0;
-            if (!cli::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
-            if (key == "--after") { o.has_after = true; o.after = value; }
-            else if (key == "--before") { o.has_before = true; o.before = value; }
-            else o.rebin_rate = value;
-        } else if (key == "--chroms") {
-            has_chroms = true;
-            o.chroms = split(v, ',');
-        } else if (key == "--frame-range") {
-            auto const tokens = split(v, ':');
-            // the reference leaves three tokens or more as a string, which fails in slice(*frame_range)
-            if (tokens.size() > 2) { err = "argument --frame-range: expected START[:END], got '" + v + "'"; return 2; }
-            o.range_tokens = (int)tokens.size();
-            if (!cli::parse_int(tokens[0], o.range_a) || (tokens.size() == 2 && !cli::parse_int(tokens[1], o.range_b))) {
-                err = "argument --frame-range: invalid int value in '" + v + "'";
-                return 2;
-            }
-        } else {
-            o.output = v;
-        }
-    }
+    err = cli::scan(argc, argv, by_step ? by_step_options : gw ? gw_options : power_law_options, [&](std::string const &key, std::string const &v) {
+        if (key == "--dry-run") return o.dry_run = true, std::string();
+        if (key == "--after") return cli::valid_if(o.has_after = cli::parse_int(v, o.after), v, "int");
+        if (key == "--before") return cli::valid_if(o.has_before = cli::parse_int(v, o.before), v, "int");
+        if (key == "--rebin-rate") return cli::to_int(v, o.rebin_rate, "int");
+        if (key == "--chroms") return has_chroms = true, o.chroms = split(v, ','), std::string();
+        if (key != "--frame-range") return o.output = v, std::string();
+        auto const tokens = split(v, ':');
+        // the reference leaves three tokens or more as a string, which fails in slice(*frame_range)
+        if (tokens.size() > 2) return "expected START[:END], got '" + v + "'";
+        o.range_tokens = (int)tokens.size();
+        bool const ok = cli::parse_int(tokens[0], o.range_a) && (tokens.size() < 2 || cli::parse_int(tokens[1], o.range_b));
+        return ok ? std::string() : "invalid int value in '" + v + "'";
+    }, o.inputs);
+    if (!err.empty()) return 2;
     if (by_step) {
         if (!has_chroms) { err = "the following arguments are required: --chroms"; return 2; }
         if (o.inputs.empty()) { err = "the following arguments are required: jobdir"; return 2; }
@@ -154,29 +134,21 @@ inline void print_plan(program p, options const &o)
     }
 }
 
-struct device {      // created when the first file has been read: a missing input is reported as such
-    gd_cmap *h = nullptr;
-    int ordinal = 0;         // HIP device
-    double startup = 0;      // seconds gd_cmap_create took (the HIP runtime starts there), inside whichever lap the caller opens it in
-    void open()
-    {
-        if (h) return;
-        auto const t = std::chrono::steady_clock::now();
-        gd_cmap_desc const d{ordinal, 0};
-        cli::check(gd_cmap_create(&d, &h));
-        startup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    }
-    ~device() { gd_cmap_destroy(h); }
-    void report(char const *prog) const { std::fprintf(stderr, "%s: device start-up %.3f s\n", prog, startup); }
-    std::vector<int32_t> fetch(int32_t target)
-    {
-        uint64_t count = 0;
-        cli::check(gd_cmap_target_size(h, target, &count));
-        std::vector<int32_t> out(count);
-        cli::check(gd_cmap_fetch(h, target, out.data()));
-        return out;
-    }
-};
+using device = cli::handle<gd_cmap, gd_cmap_destroy>;      // opened when the first file has been read: a missing input is reported as such
+
+inline void open(device &dev, int ordinal = 0)      // ordinal: the HIP device
+{
+    dev.open([ordinal](gd_cmap **h) { gd_cmap_desc const d{ordinal, 0}; return gd_cmap_create(&d, h); });
+}
+
+inline std::vector<int32_t> fetch(device &dev, int32_t target)
+{
+    uint64_t count = 0;
+    cli::check(gd_cmap_target_size(dev.h, target, &count));
+    std::vector<int32_t> out(count);
+    cli::check(gd_cmap_fetch(dev.h, target, out.data()));
+    return out;
+}
 
 // ---- what is read from one trajectory file
 
@@ -352,7 +324,7 @@ inline void run_by_step(program p, options const &o)
         trajectory t = pf.take();
         sw.read += sw.lap();
         if (nad && !t.nucleolus_member) throw std::runtime_error(files[k] + ": particle_types has no enum member 'nucleolus'");      // KeyError
-        dev.open();
+        open(dev);
         cli::check(gd_cmap_clear(dev.h));
         std::vector<int32_t> targets;
         for (auto const &c : o.chroms) {
@@ -367,7 +339,7 @@ inline void run_by_step(program p, options const &o)
         cli::check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
         for (auto id : targets) {
             if (!nad) cli::check(gd_cmap_finish(dev.h, id));
-            auto const part = dev.fetch(id);
+            auto const part = fetch(dev, id);
             if (first) {
                 sum.assign(part.begin(), part.end());
                 side = part.size();
@@ -444,11 +416,11 @@ inline void write_gw_matrix(std::string const &output, trajectory const &head, r
         H5Tenum_insert(names, kv.first.c_str(), &v);
     }
     cli::put_dataset(file, "/metadata/chromosome_ranges", rb.binned.data(), {rb.binned.size() / 2, 2}, 4, names, names, nullptr);
-    cli::put_dataset(file, "/metadata/rebin_map", rb.map.data(), {rb.map.size()}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, nullptr);
+    cli::put(file, "/metadata/rebin_map", rb.map.data(), {rb.map.size()}, nullptr);
     cli::filters f;
     f.scaleoffset_kind = H5Z_SO_INT;
     f.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;      // scaleoffset=0: integer scale-offset is lossless
-    cli::put_dataset(file, "/contact_matrix", matrix.data(), {rb.n_bins, rb.n_bins}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &f);
+    cli::put(file, "/contact_matrix", matrix.data(), {rb.n_bins, rb.n_bins}, &f);
     H5Fflush(file, H5F_SCOPE_GLOBAL);
 }
 
@@ -465,7 +437,7 @@ inline void run_gw(options const &o)
     prefetcher pf(o.inputs, rq);
     sw.read += sw.lap();
     device dev;
-    dev.open();
+    open(dev);
     int32_t id = -1;
     cli::check(gd_cmap_add_binned(dev.h, rb.map.data(), (uint32_t)rb.map.size(), rb.n_bins, &id));
     std::fputs("Loading: ", stderr);
@@ -479,7 +451,7 @@ inline void run_gw(options const &o)
         std::fflush(stderr);
     }
     std::fputs(" DONE\n", stderr);
-    auto const matrix = dev.fetch(id);
+    auto const matrix = fetch(dev, id);
     sw.compute += sw.lap();
     write_gw_matrix(o.output, head, rb, matrix);
     sw.write += sw.lap();
@@ -537,12 +509,12 @@ inline void run_power_law(options const &o)
             for (int b = t.ranges[c]; b < t.ranges[c + 1]; b++) chain[(std::size_t)b] = (int32_t)(c / 2);
             longest = std::max(longest, (uint32_t)(t.ranges[c + 1] - t.ranges[c]));
         }
-        dev.open();
+        open(dev);
         cli::check(gd_cmap_clear(dev.h));
         int32_t id = -1;
         cli::check(gd_cmap_add_separation_profile(dev.h, chain.data(), (uint32_t)chain.size(), longest, &id));
         cli::check(gd_cmap_accumulate(dev.h, t.rows.data(), t.rows.size() / 3));
-        auto const profile = dev.fetch(id);
+        auto const profile = fetch(dev, id);
         double const near = fit_exponent(profile, 3, 20), mid = fit_exponent(profile, 20, 100), far = fit_exponent(profile, 100, 1500);
         sw.compute += sw.lap();
         std::printf("%g\t%g\t%g\n", near, mid, far);
@@ -557,25 +529,13 @@ inline void run_power_law(options const &o)
 inline int main(program p, int argc, char **argv)
 {
     options o;
-    std::string err;
-    if (parse(p, argc, argv, o, err)) {
-        std::fprintf(stderr, "%s%s: error: %s\n", usage(p), name_of(p), err.c_str());
-        return 2;
-    }
-    if (o.dry_run) {
-        print_plan(p, o);
-        return 0;
-    }
-    try {
-        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    return cli::run(usage(p), name_of(p), "error:", [&](std::string &err) { return parse(p, argc, argv, o, err); },
+                    [&] { return o.dry_run && (print_plan(p, o), true); }, [&] {
         if (p == program::gw_contact_matrix) run_gw(o);
         else if (p == program::power_law) run_power_law(o);
         else run_by_step(p, o);
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 }  // namespace cmap

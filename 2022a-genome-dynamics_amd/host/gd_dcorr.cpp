@@ -33,49 +33,29 @@ struct options {
 
 int parse(int argc, char **argv, options &o, std::string &err)
 {
+    using gd::cli::kind;
+    static gd::cli::table const options = {{"--dry-run", kind::flag}, {"--split-chains", kind::flag}, {"--per-origin", kind::flag}, {"--name", kind::value},
+                                           {"--lags", kind::value}, {"--log-lags", kind::value}, {"--groups", kind::value}, {"--bin-width", kind::value},
+                                           {"--max-distance", kind::value}, {"--origin-stride", kind::value}, {"--box", kind::value}};
     std::vector<std::string> pos;
-    for (int k = 1; k < argc; k++) {
-        std::string a = argv[k], v;
-        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
-            if (a == "--dry-run") { o.dry_run = true; continue; }
-            if (a == "--split-chains") { o.split_chains = true; continue; }
-            if (a == "--per-origin") { o.per_origin = true; continue; }
-            auto eq = a.find('=');
-            bool const inline_value = eq != std::string::npos;
-            std::string const key = inline_value ? a.substr(0, eq) : a;
-            if (key != "--name" && key != "--lags" && key != "--log-lags" && key != "--groups" && key != "--bin-width" && key != "--max-distance" &&
-                key != "--origin-stride" && key != "--box") {
-                err = "unrecognized arguments: " + a;
-                return 2;
-            }
-            if (inline_value) v = a.substr(eq + 1);
-            else if (k + 1 < argc) v = argv[++k];
-            else { err = "argument " + key + ": expected one argument"; return 2; }
-            bool ok = true;
-            if (key == "--name") ok = !(o.name = v).empty() && v.find('/') == std::string::npos;
-            else if (key == "--groups") ok = (o.groups = v) == "all" || v == "types";
-            else if (key == "--lags") ok = o.lags.explicit_list = parse_list(v, o.lags.list);
-            else if (key == "--log-lags") {
-                ok = gd::cli::parse_int(v, o.lags.log_count) && o.lags.log_count >= 1 && o.lags.log_count <= (1l << 28);
-                o.lags.explicit_list = false;
-            } else if (key == "--bin-width") ok = gd::cli::parse_float(v, o.bin_width);
-            else if (key == "--max-distance") ok = gd::cli::parse_float(v, o.max_distance);
-            else if (key == "--origin-stride") ok = gd::cli::parse_int(v, o.origin_stride) && o.origin_stride >= 1 && o.origin_stride <= 0xffffffffl;
-            else ok = o.has_box = parse_box(v, o.box);
-            if (!ok) { err = "argument " + key + ": invalid value: '" + v + "'"; return 2; }
-        } else {
-            pos.push_back(a);
-        }
-    }
+    err = gd::cli::scan(argc, argv, options, [&o](std::string const &key, std::string const &v) {
+        if (key == "--dry-run") return o.dry_run = true, std::string();
+        if (key == "--split-chains") return o.split_chains = true, std::string();
+        if (key == "--per-origin") return o.per_origin = true, std::string();
+        if (key == "--name") return phase_name(v, o.name);
+        if (key == "--groups") return gd::cli::valid_if((o.groups = v) == "all" || v == "types", v);
+        if (key == "--lags" || key == "--log-lags") return lags_or_count(o.lags, key == "--lags", v);
+        if (key == "--bin-width") return gd::cli::to_float(v, o.bin_width);
+        if (key == "--max-distance") return gd::cli::to_float(v, o.max_distance);
+        if (key == "--origin-stride") return gd::cli::to_int(v, o.origin_stride, nullptr, 1, 0xffffffffl);
+        return gd::cli::valid_if(o.has_box = parse_box(v, o.box), v);
+    }, pos);
+    if (!err.empty()) return 2;
     if (!gd_dcorr_bins(o.bin_width, o.max_distance)) {
         err = "--bin-width and --max-distance are required, positive and finite, with at most " + std::to_string(GD_DCORR_MAX_BINS) + " bins";
         return 2;
     }
-    if (o.dry_run && pos.empty()) return 0;
-    if (pos.size() < 2) { err = "the following arguments are required: outfile, trajfiles"; return 2; }
-    o.outfile = pos[0];
-    o.trajfiles.assign(pos.begin() + 1, pos.end());
-    return 0;
+    return gd::flow::take_files(pos, o.dry_run, o.outfile, o.trajfiles, err);
 }
 
 // the chain of every bead: the index of its range; beads of no range share the index one past the last range
@@ -104,16 +84,6 @@ std::vector<std::string> class_names(std::vector<std::string> const &labels, boo
     return out;
 }
 
-struct device {      // one gd_dcorr handle; every failure of the library ends the program with its message
-    gd_dcorr *h = nullptr;
-    device()
-    {
-        gd_dcorr_desc d{0, 0};
-        gd::cli::check(gd_dcorr_create(&d, &h));
-    }
-    ~device() { gd_dcorr_destroy(h); }
-};
-
 // out[c] += in[o, c] over the origins, as 128-bit integers; then float64 of sum / 2^S
 template <typename T>
 void total(std::vector<T> const &in, std::size_t origins, std::size_t cells, std::vector<__int128> &acc)
@@ -128,16 +98,9 @@ void total(std::vector<T> const &in, std::size_t origins, std::size_t cells, std
 int main(int argc, char **argv)
 {
     options o;
-    std::string err;
-    if (parse(argc, argv, o, err)) {
-        std::fprintf(stderr,
-                     "usage: gd_dcorr [--name PHASE] --lags a,b,...|--log-lags K --bin-width W --max-distance R [--groups all|types] [--split-chains] "
-                     "[--origin-stride k] [--box Lx,Ly,Lz] [--per-origin] [--dry-run] outfile trajfiles ...\ngd_dcorr: error: %s\n",
-                     err.c_str());
-        return 2;
-    }
-    try {
-        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    char const *usage = "usage: gd_dcorr [--name PHASE] --lags a,b,...|--log-lags K --bin-width W --max-distance R [--groups all|types] [--split-chains] "
+                        "[--origin-stride k] [--box Lx,Ly,Lz] [--per-origin] [--dry-run] outfile trajfiles ...\n";
+    return gd::cli::run(usage, "gd_dcorr", "gd_dcorr: error:", [&](std::string &err) { return parse(argc, argv, o, err); }, gd::cli::no_plan, [&o] {
         uint32_t const n_bins = gd_dcorr_bins(o.bin_width, o.max_distance);
         if (o.dry_run) {
             std::printf("name\t%s\ngroups\t%s\nsplit chains\t%s\nlags\t%s\nbins\t%u of %s up to %s\norigin stride\t%ld\nbox\t%s\n", o.name.c_str(),
@@ -154,7 +117,8 @@ int main(int argc, char **argv)
             }
             return 0;
         }
-        device dev;
+        gd::cli::handle<gd_dcorr, gd_dcorr_destroy> dev;
+        dev.open([](gd_dcorr **h) { gd_dcorr_desc const d{0, 0}; return gd_dcorr_create(&d, h); });
         gd::h5::hid out(gd::cli::open_output(o.outfile));
         gd::cli::stopwatch sw;
         for (auto const &path : o.trajfiles) {
@@ -194,31 +158,28 @@ int main(int argc, char **argv)
                 for (std::size_t c = 0; c < K; c++) self_sum_total[k * K + c] = (double)acc[c] / unit;
                 if (o.per_origin) {
                     std::string const at = "per_origin/lag_" + std::to_string(lags[k]) + "/";
-                    gd::cli::put_dataset(group, at + "count", count.data(), {O, P, n_bins}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
-                    gd::cli::put_dataset(group, at + "sum", sum.data(), {O, P, n_bins}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, &f);
-                    gd::cli::put_dataset(group, at + "self_count", self_count.data(), {O, K}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
-                    gd::cli::put_dataset(group, at + "self_sum", self_sum.data(), {O, K}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, &f);
+                    gd::cli::put(group, at + "count", count.data(), {O, P, n_bins}, &f);
+                    gd::cli::put(group, at + "sum", sum.data(), {O, P, n_bins}, &f);
+                    gd::cli::put(group, at + "self_count", self_count.data(), {O, K}, &f);
+                    gd::cli::put(group, at + "self_sum", self_sum.data(), {O, K}, &f);
                     sw.write += sw.lap();
                 }
             }
             std::vector<double> edges(n_bins + 1);
             for (uint32_t b = 0; b <= n_bins; b++) edges[b] = std::min((double)b * o.bin_width, o.max_distance);
-            gd::cli::put_dataset(group, "lags", lags.data(), {L}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, nullptr);
-            gd::cli::put_dataset(group, "bin_edges", edges.data(), {n_bins + 1}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
-            gd::cli::put_dataset(group, "scale_bits", scale.data(), {L}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, nullptr);
-            gd::cli::put_dataset(group, "count", count_total.data(), {L, P, n_bins}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
-            gd::cli::put_dataset(group, "sum", sum_total.data(), {L, P, n_bins}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "self_count", self_count_total.data(), {L, K}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
-            gd::cli::put_dataset(group, "self_sum", self_sum_total.data(), {L, K}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
+            gd::cli::put(group, "lags", lags.data(), {L}, nullptr);
+            gd::cli::put(group, "bin_edges", edges.data(), {n_bins + 1}, nullptr);
+            gd::cli::put(group, "scale_bits", scale.data(), {L}, nullptr);
+            gd::cli::put(group, "count", count_total.data(), {L, P, n_bins}, &f);
+            gd::cli::put(group, "sum", sum_total.data(), {L, P, n_bins}, &f);
+            gd::cli::put(group, "self_count", self_count_total.data(), {L, K}, &f);
+            gd::cli::put(group, "self_sum", self_sum_total.data(), {L, K}, &f);
             gd::h5::unlink_if_present(group, "class_names");
             gd::h5::write_fixed_string_list(group, "class_names", class_names(l.group_names, o.split_chains));
             H5Fflush(out, H5F_SCOPE_GLOBAL);
             sw.write += sw.lap();
         }
         sw.report("gd_dcorr");
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "gd_dcorr: error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -70,40 +70,23 @@ bool parse_frames(std::string const &v, long &first, long &count)
 
 int parse(int argc, char **argv, options &o, std::string &err)
 {
+    using gd::cli::kind;
+    static gd::cli::table const options = {{"--dry-run", kind::flag}, {"--by-chain", kind::flag}, {"--name", kind::value}, {"--rebin-rate", kind::value},
+                                           {"--chains", kind::value}, {"--thresholds", kind::value}, {"--frames", kind::value}, {"--box", kind::value}};
     std::vector<std::string> pos;
-    for (int k = 1; k < argc; k++) {
-        std::string a = argv[k], v;
-        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
-            if (a == "--dry-run") { o.dry_run = true; continue; }
-            if (a == "--by-chain") { o.by_chain = true; continue; }
-            auto eq = a.find('=');
-            bool const inline_value = eq != std::string::npos;
-            std::string const key = inline_value ? a.substr(0, eq) : a;
-            if (key != "--name" && key != "--rebin-rate" && key != "--chains" && key != "--thresholds" && key != "--frames" && key != "--box") {
-                err = "unrecognized arguments: " + a;
-                return 2;
-            }
-            if (inline_value) v = a.substr(eq + 1);
-            else if (k + 1 < argc) v = argv[++k];
-            else { err = "argument " + key + ": expected one argument"; return 2; }
-            bool ok = true;
-            if (key == "--name") ok = !(o.name = v).empty() && v.find('/') == std::string::npos;
-            else if (key == "--rebin-rate") ok = gd::cli::parse_int(v, o.rate) && o.rate >= 1 && o.rate <= (1l << 28);
-            else if (key == "--chains") ok = parse_chains(v, o.chains);
-            else if (key == "--thresholds") ok = parse_thresholds(v, o.thresholds);
-            else if (key == "--frames") ok = o.has_frames = parse_frames(v, o.first_frame, o.n_frames);
-            else ok = o.has_box = parse_box(v, o.box);
-            if (!ok) { err = "argument " + key + ": invalid value: '" + v + "'"; return 2; }
-        } else {
-            pos.push_back(a);
-        }
-    }
+    err = gd::cli::scan(argc, argv, options, [&o](std::string const &key, std::string const &v) {
+        if (key == "--dry-run") return o.dry_run = true, std::string();
+        if (key == "--by-chain") return o.by_chain = true, std::string();
+        if (key == "--name") return phase_name(v, o.name);
+        if (key == "--rebin-rate") return gd::cli::to_int(v, o.rate, nullptr, 1, 1l << 28);
+        if (key == "--chains") return gd::cli::valid_if(parse_chains(v, o.chains), v);
+        if (key == "--thresholds") return gd::cli::valid_if(parse_thresholds(v, o.thresholds), v);
+        if (key == "--frames") return gd::cli::valid_if(o.has_frames = parse_frames(v, o.first_frame, o.n_frames), v);
+        return gd::cli::valid_if(o.has_box = parse_box(v, o.box), v);
+    }, pos);
+    if (!err.empty()) return 2;
     if (o.by_chain && o.rate != 1) { err = "argument --by-chain: not allowed with argument --rebin-rate"; return 2; }
-    if (o.dry_run && pos.empty()) return 0;
-    if (pos.size() < 2) { err = "the following arguments are required: outfile, trajfiles"; return 2; }
-    o.outfile = pos[0];
-    o.trajfiles.assign(pos.begin() + 1, pos.end());
-    return 0;
+    return gd::flow::take_files(pos, o.dry_run, o.outfile, o.trajfiles, err);
 }
 
 struct plan {      // the bins of one trajectory file and the ones selected
@@ -175,31 +158,14 @@ std::string join_doubles(std::vector<double> const &v)
     return s;
 }
 
-struct device {      // one gd_dmap handle; every failure of the library ends the program with its message
-    gd_dmap *h = nullptr;
-    device()
-    {
-        gd_dmap_desc d{0, 0};
-        gd::cli::check(gd_dmap_create(&d, &h));
-    }
-    ~device() { gd_dmap_destroy(h); }
-};
-
 }  // namespace
 
 int main(int argc, char **argv)
 {
     options o;
-    std::string err;
-    if (parse(argc, argv, o, err)) {
-        std::fprintf(stderr,
-                     "usage: gd_distance_map [--name PHASE] [--rebin-rate K] [--by-chain] [--chains a,b,...] [--thresholds t1,t2,...] [--frames FIRST:COUNT] "
-                     "[--box Lx,Ly,Lz] [--dry-run] outfile trajfiles ...\ngd_distance_map: error: %s\n",
-                     err.c_str());
-        return 2;
-    }
-    try {
-        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    char const *usage = "usage: gd_distance_map [--name PHASE] [--rebin-rate K] [--by-chain] [--chains a,b,...] [--thresholds t1,t2,...] [--frames FIRST:COUNT] "
+                        "[--box Lx,Ly,Lz] [--dry-run] outfile trajfiles ...\n";
+    return gd::cli::run(usage, "gd_distance_map", "gd_distance_map: error:", [&](std::string &err) { return parse(argc, argv, o, err); }, gd::cli::no_plan, [&o] {
         if (o.dry_run) {
             std::string chains;
             for (std::size_t k = 0; k < o.chains.size(); k++) chains += (k ? "," : "") + o.chains[k];
@@ -218,7 +184,8 @@ int main(int argc, char **argv)
             }
             return 0;
         }
-        device dev;
+        gd::cli::handle<gd_dmap, gd_dmap_destroy> dev;
+        dev.open([](gd_dmap **h) { gd_dmap_desc const d{0, 0}; return gd_dmap_create(&d, h); });
         gd::h5::hid out(gd::cli::open_output(o.outfile));
         gd::cli::stopwatch sw;
         for (auto const &path : o.trajfiles) {
@@ -260,22 +227,19 @@ int main(int argc, char **argv)
             gd::h5::hid group(gd::cli::require_group(out, "/dmap/" + o.name + "/" + gd::cli::sample_name(path)));
             gd::cli::filters const f;
             hsize_t const s = S, t = T;
-            gd::cli::put_dataset(group, "bins", bins.data(), {s, 2}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, &f);
-            gd::cli::put_dataset(group, "bin_chain", bin_chain.data(), {s}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, &f);
-            gd::cli::put_dataset(group, "thresholds", o.thresholds.data(), {t}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
-            gd::cli::put_dataset(group, "sum1", sum1.data(), {s, s}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "sum2", sum2.data(), {s, s}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "hits", hits.data(), {t, s, s}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
-            gd::cli::put_dataset(group, "count", count.data(), {s, s}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
+            gd::cli::put(group, "bins", bins.data(), {s, 2}, &f);
+            gd::cli::put(group, "bin_chain", bin_chain.data(), {s}, &f);
+            gd::cli::put(group, "thresholds", o.thresholds.data(), {t}, nullptr);
+            gd::cli::put(group, "sum1", sum1.data(), {s, s}, &f);
+            gd::cli::put(group, "sum2", sum2.data(), {s, s}, &f);
+            gd::cli::put(group, "hits", hits.data(), {t, s, s}, &f);
+            gd::cli::put(group, "count", count.data(), {s, s}, &f);
             gd::h5::unlink_if_present(group, "chain_names");
             gd::h5::write_fixed_string_list(group, "chain_names", l.chain_names);
             H5Fflush(out, H5F_SCOPE_GLOBAL);
             sw.write += sw.lap();
         }
         sw.report("gd_distance_map");
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "gd_distance_map: error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

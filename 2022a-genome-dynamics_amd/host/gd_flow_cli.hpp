@@ -1,7 +1,7 @@
 // gd_flow_cli.hpp -- what gd_particle_flow and gd_grid_flow share: the command line of the reference's
 // analyze_particle_flow / analyze_grid_flow (__main__.py), the stored config JSON as Python's json.dumps prints it and its
 // SHA-256 name (analysis.py: run), the input history (load_positions), the grid mesh, and the writers of the two output layouts
-// (put_dataset with h5py's filters).  The computation itself is libgdyn's (include/gdyn_flow.h).  gd_interphase writes the same
+// (cli::put with h5py's filters).  The computation itself is libgdyn's (include/gdyn_flow.h).  gd_interphase writes the same
 // outputs from frames recorded on the device (--particle-flow / --grid-flow) through the same writers.
 #pragma once
 #include <hdf5.h>
@@ -46,50 +46,50 @@ struct options {
     std::vector<std::string> trajfiles;
 };
 
+// the positionals "outfile trajfiles ..." of a trajectory analysis; --dry-run alone is served without them.  0 or 2 with a message
+inline int take_files(std::vector<std::string> const &pos, bool dry_run, std::string &outfile, std::vector<std::string> &trajfiles, std::string &err)
+{
+    if (dry_run && pos.empty()) return 0;
+    if (pos.size() < 2) { err = "the following arguments are required: outfile, trajfiles"; return 2; }
+    outfile = pos[0];
+    trajfiles.assign(pos.begin() + 1, pos.end());
+    return 0;
+}
+
 // argparse's conventions: "--opt value" or "--opt=value"; exit status 2 with a usage line on any error.  grid_options: the grid's
 // options are accepted (a particle analysis that shares its command line with a grid analysis ignores them)
 inline int parse(int argc, char **argv, bool grid, options &o, std::string &err, bool grid_options)
 {
+    using cli::kind;
+    static cli::table const particle = {{"--dry-run", kind::flag}, {"--name", kind::value}, {"--smoothing", kind::value}, {"--velocity-delay", kind::value},
+                                        {"--scan-radius", kind::value}, {"--jobs", kind::value}};
+    static cli::table const with_grid = [] {
+        cli::table t = particle;
+        for (char const *key : {"--grid-interval", "--x-range", "--y-range", "--z-range"}) t.push_back({key, kind::value});
+        return t;
+    }();
     std::vector<std::string> pos;
-    for (int k = 1; k < argc; k++) {
-        std::string a = argv[k], v;
-        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
-            if (a == "--dry-run") { o.dry_run = true; continue; }
-            auto eq = a.find('=');
-            bool const inline_value = eq != std::string::npos;
-            std::string const key = inline_value ? a.substr(0, eq) : a;
-            if (inline_value) v = a.substr(eq + 1);
-            else if (k + 1 < argc) v = argv[++k];
-            else { err = "argument " + key + ": expected one argument"; return 2; }
-            bool ok = true;
-            if (key == "--name") o.name = v;
-            else if (key == "--smoothing") ok = o.has_smoothing = cli::parse_int(v, o.smoothing);
-            else if (key == "--velocity-delay") ok = cli::parse_int(v, o.delay);
-            else if (key == "--scan-radius") ok = o.has_radius = cli::parse_float(v, o.radius);
-            else if (key == "--jobs") { long j; ok = cli::parse_int(v, j); }      // accepted; one device does the work
-            else if (grid_options && key == "--grid-interval") ok = o.has_interval = cli::parse_float(v, o.interval);
-            else if (grid_options && (key == "--x-range" || key == "--y-range" || key == "--z-range")) {
-                int const axis = key[2] - 'x';
-                auto comma = v.find(',');
-                ok = comma != std::string::npos && v.find(',', comma + 1) == std::string::npos &&
-                     cli::parse_float(v.substr(0, comma), o.range[axis][0]) && cli::parse_float(v.substr(comma + 1), o.range[axis][1]);
-                o.has_range[axis] = ok;
-            } else { err = "unrecognized arguments: " + a; return 2; }
-            if (!ok) { err = "argument " + key + ": invalid value: '" + v + "'"; return 2; }
-        } else {
-            pos.push_back(a);
-        }
-    }
+    err = cli::scan(argc, argv, grid_options ? with_grid : particle, [&o](std::string const &key, std::string const &v) {
+        if (key == "--dry-run") return o.dry_run = true, std::string();
+        if (key == "--name") return o.name = v, std::string();
+        if (key == "--smoothing") return cli::valid_if(o.has_smoothing = cli::parse_int(v, o.smoothing), v);
+        if (key == "--velocity-delay") return cli::to_int(v, o.delay);
+        if (key == "--scan-radius") return cli::valid_if(o.has_radius = cli::parse_float(v, o.radius), v);
+        if (key == "--jobs") { long j; return cli::to_int(v, j); }      // accepted; one device does the work
+        if (key == "--grid-interval") return cli::valid_if(o.has_interval = cli::parse_float(v, o.interval), v);
+        int const axis = key[2] - 'x';      // --x-range, --y-range, --z-range
+        auto const comma = v.find(',');
+        o.has_range[axis] = comma != std::string::npos && v.find(',', comma + 1) == std::string::npos &&
+                            cli::parse_float(v.substr(0, comma), o.range[axis][0]) && cli::parse_float(v.substr(comma + 1), o.range[axis][1]);
+        return cli::valid_if(o.has_range[axis], v);
+    }, pos);
+    if (!err.empty()) return 2;
     if (!o.has_radius) { err = "the following arguments are required: --scan-radius"; return 2; }
     if (grid && (!o.has_interval || !o.has_range[0] || !o.has_range[1] || !o.has_range[2])) {
         err = "the following arguments are required: --grid-interval, --x-range, --y-range, --z-range";
         return 2;
     }
-    if (o.dry_run && pos.empty()) return 0;
-    if (pos.size() < 2) { err = "the following arguments are required: outfile, trajfiles"; return 2; }
-    o.outfile = pos[0];
-    o.trajfiles.assign(pos.begin() + 1, pos.end());
-    return 0;
+    return take_files(pos, o.dry_run, o.outfile, o.trajfiles, err);
 }
 
 inline int parse(int argc, char **argv, bool grid, options &o, std::string &err) { return parse(argc, argv, grid, o, err, grid); }
@@ -174,41 +174,37 @@ inline std::vector<float> load_history(std::string const &path, uint32_t &frames
     return out;
 }
 
-struct device {      // one gd_flow handle; every failure of the library ends the program with its message
-    gd_flow *h = nullptr;
-    explicit device(int ordinal = 0)
-    {
-        gd_flow_desc d{ordinal, 0};
-        cli::check(gd_flow_create(&d, &h));
-    }
-    ~device() { gd_flow_destroy(h); }
-};
+using device = cli::handle<gd_flow, gd_flow_destroy>;      // one gd_flow handle
 
-// common front: parse, print the config for --dry-run; returns -1 to go on, else the exit status
-inline int front(int argc, char **argv, bool grid, options &o, std::string &config, std::string &name)
+inline void open(device &dev, int ordinal = 0)
 {
-    std::string err;
-    char const *prog = grid ? "gd_grid_flow" : "gd_particle_flow";
-    if (parse(argc, argv, grid, o, err)) {
-        std::fprintf(stderr, "usage: %s [--name NAME] [--smoothing W] [--velocity-delay D] --scan-radius R%s [--jobs J] [--dry-run] outfile trajfiles ...\n"
-                             "%s: error: %s\n",
-                     prog, grid ? " --grid-interval H --x-range A,B --y-range A,B --z-range A,B" : "", prog, err.c_str());
-        return 2;
-    }
-    config = config_json(o, grid);
-    name = analysis_name(o, config);
-    if (o.dry_run) {
-        std::printf("%s\n%s\n", config.c_str(), name.c_str());
-        return 0;
-    }
-    if (o.delay < 0 || o.smoothing < 0) {
-        std::fprintf(stderr, "%s: error: --velocity-delay and --smoothing must be >= 0\n", prog);
-        return 2;
-    }
-    return -1;
+    dev.open([ordinal](gd_flow **h) { gd_flow_desc const d{ordinal, 0}; return gd_flow_create(&d, h); });
 }
 
 inline bool smoothed(options const &o) { return o.has_smoothing && o.smoothing > 0; }
+
+// the main of both programs: parse, print the config for --dry-run, else body(o, config, name, prog) is the analysis
+template <typename Body>
+int main(int argc, char **argv, bool grid, Body &&body)
+{
+    std::string const prog = grid ? "gd_grid_flow" : "gd_particle_flow";
+    std::string const usage = "usage: " + prog + " [--name NAME] [--smoothing W] [--velocity-delay D] --scan-radius R" +
+                              (grid ? " --grid-interval H --x-range A,B --y-range A,B --z-range A,B" : "") + " [--jobs J] [--dry-run] outfile trajfiles ...\n";
+    options o;
+    return cli::run(usage, prog.c_str(), (prog + ": error:").c_str(), [&](std::string &err) { return parse(argc, argv, grid, o, err); }, cli::no_plan, [&] {
+        std::string const config = config_json(o, grid), name = analysis_name(o, config);
+        if (o.dry_run) {
+            std::printf("%s\n%s\n", config.c_str(), name.c_str());
+            return 0;
+        }
+        if (o.delay < 0 || o.smoothing < 0) {
+            std::fprintf(stderr, "%s: error: --velocity-delay and --smoothing must be >= 0\n", prog.c_str());
+            return 2;
+        }
+        body(o, config, name, prog.c_str());
+        return 0;
+    });
+}
 
 // ---- /particle_flow/<name> of the output file: .config, <sample>/{position,velocity}, and at the end .samples
 class particle_writer {
@@ -224,9 +220,9 @@ public:
         _samples.push_back(sample);
         cli::filters const f;
         std::vector<hsize_t> const dims = {F, N, 3};
-        if (smoothed_history) cli::put_dataset(_group, sample + "/position", smoothed_history, dims, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-        else cli::put_dataset(_group, sample + "/position", history, dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
-        cli::put_dataset(_group, sample + "/velocity", flows, dims, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+        if (smoothed_history) cli::put(_group, sample + "/position", smoothed_history, dims, &f);
+        else cli::put(_group, sample + "/position", history, dims, &f);
+        cli::put(_group, sample + "/velocity", flows, dims, &f);
     }
     void finish() { h5::write_fixed_string_list(_group, ".samples", _samples); }      // this run's samples only, as the reference does
 
@@ -306,9 +302,9 @@ public:
     {
         h5::write_string(_group, ".config", config);
         _samples = h5::read_string_list(_group, ".samples");      // incremental analysis: earlier samples stay listed
-        cli::put_dataset(_group, ".grid/shape", m.shape, {3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
-        cli::put_dataset(_group, ".grid/points", m.points.data(), {m.G, 3}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, nullptr);
-        cli::put_dataset(_group, ".grid/indices", m.indices.data(), {m.G, 3}, 8, H5T_NATIVE_INT64, H5T_STD_I64LE, nullptr);
+        cli::put(_group, ".grid/shape", m.shape, {3}, nullptr);
+        cli::put(_group, ".grid/points", m.points.data(), {m.G, 3}, nullptr);
+        cli::put(_group, ".grid/indices", m.indices.data(), {m.G, 3}, nullptr);
     }
     void put(std::string const &sample, uint32_t F, std::vector<float> const &flows, std::vector<int32_t> const &coverages, int factor)
     {
@@ -316,11 +312,11 @@ public:
         cli::filters ff;
         ff.scaleoffset_kind = H5Z_SO_FLOAT_DSCALE;
         ff.scaleoffset_factor = factor;
-        cli::put_dataset(_group, sample + "/flows", flows.data(), {F, _G, 3}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &ff);
+        cli::put(_group, sample + "/flows", flows.data(), {F, _G, 3}, &ff);
         cli::filters fc;
         fc.scaleoffset_kind = H5Z_SO_INT;
         fc.scaleoffset_factor = H5Z_SO_INT_MINBITS_DEFAULT;
-        cli::put_dataset(_group, sample + "/coverages", coverages.data(), {F, _G}, 4, H5T_NATIVE_INT32, H5T_STD_I32LE, &fc);
+        cli::put(_group, sample + "/coverages", coverages.data(), {F, _G}, &fc);
         H5Fflush(_file, H5F_SCOPE_GLOBAL);
     }
     void finish() { h5::write_fixed_string_list(_group, ".samples", remove_duplicates(_samples)); }

@@ -8,12 +8,10 @@
 int main(int argc, char **argv)
 {
     using namespace gd::flow;
-    options o;
-    std::string config, name;
-    if (int rc = front(argc, argv, true, o, config, name); rc >= 0) return rc;
-    try {
+    return gd::flow::main(argc, argv, true, [](options const &o, std::string const &config, std::string const &name, char const *prog) {
         mesh const m(o);
         device dev;
+        open(dev);
         grid_writer out(o.outfile, name, config, m);
         bool const smooth = smoothed(o);
         gd::cli::stopwatch sw;
@@ -33,10 +31,6 @@ int main(int argc, char **argv)
         }
         out.finish();
         sw.write += sw.lap();
-        sw.report("gd_grid_flow");
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "gd_grid_flow: error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        sw.report(prog);
+    });
 }

@@ -63,46 +63,23 @@ inline int parse(program p, int argc, char **argv, options &o, std::string &err)
 {
     bool const cooler_short = p == program::interactions || p == program::alpha;
     o.width = p == program::interactions ? 4 : 10;
+    using cli::kind;
+    static cli::table const cooler_options = {{"--dry-run", kind::flag}, {"-b", kind::value}, {"-w", kind::value}, {"-o", kind::value}},
+                            power_law_options = {{"--dry-run", kind::flag}, {"--binsize", kind::value}, {"--normalize", kind::value}},
+                            compartments_options = {{"--dry-run", kind::flag}, {"-b", kind::value}, {"-n", kind::value}, {"-k", kind::value}, {"--exclude", kind::value}, {"--chroms", kind::value}},
+                            downsample_options = {{"--dry-run", kind::flag}, {"--rate", kind::value}, {"--window", kind::value}, {"-o", kind::value}};
+    cli::table const &options = cooler_short ? cooler_options : p == program::power_law ? power_law_options : p == program::compartments ? compartments_options : downsample_options;
     std::vector<std::string> pos;
-    for (int k = 1; k < argc; k++) {
-        std::string const a = argv[k];
-        if (a == "--dry-run") { o.dry_run = true; continue; }
-        std::string key, v;
-        bool has_value = false;
-        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
-            auto const eq = a.find('=');
-            key = a.substr(0, eq);
-            if (eq != std::string::npos) { v = a.substr(eq + 1); has_value = true; }
-        } else if (a.size() >= 2 && a[0] == '-' && !(a[1] >= '0' && a[1] <= '9')) {
-            key = a.substr(0, 2);
-            if (a.size() > 2) { v = a.substr(2); has_value = true; }
-        } else {
-            pos.push_back(a);
-            continue;
-        }
-        bool const known = (cooler_short && (key == "-b" || key == "-w" || key == "-o")) ||
-                           (p == program::power_law && (key == "--binsize" || key == "--normalize")) ||
-                           (p == program::compartments && (key == "-b" || key == "-n" || key == "-k" || key == "--exclude" || key == "--chroms")) ||
-                           (p == program::downsample && (key == "--rate" || key == "--window" || key == "-o"));
-        if (!known) { err = "unrecognized arguments: " + a; return 2; }
-        if (!has_value) {
-            if (k + 1 >= argc) { err = "argument " + key + ": expected one argument"; return 2; }
-            v = argv[++k];
-        }
-        if (key == "-o") o.output = v;
-        else if (key == "--normalize" || key == "-n") o.normalize = v;
-        else if (key == "--exclude") o.exclude = v;
-        else if (key == "--chroms") o.chroms = v;
-        else {
-            long value = 0;
-            if (!cli::parse_int(v, value)) { err = "argument " + key + ": invalid int value: '" + v + "'"; return 2; }
-            if (key == "-b" || key == "--binsize") { o.binsize = value; o.has_binsize = true; }
-            else if (key == "-w") o.width = value;
-            else if (key == "-k") o.components = value;
-            else if (key == "--rate") o.rate = value;
-            else o.window = value;
-        }
-    }
+    err = cli::scan(argc, argv, options, [&o](std::string const &key, std::string const &v) {
+        if (key == "--dry-run") return o.dry_run = true, std::string();
+        if (key == "-o") return o.output = v, std::string();
+        if (key == "--normalize" || key == "-n") return o.normalize = v, std::string();
+        if (key == "--exclude") return o.exclude = v, std::string();
+        if (key == "--chroms") return o.chroms = v, std::string();
+        if (key == "-b" || key == "--binsize") return cli::valid_if(o.has_binsize = cli::parse_int(v, o.binsize), v, "int");
+        return cli::to_int(v, key == "-w" ? o.width : key == "-k" ? o.components : key == "--rate" ? o.rate : o.window, "int");
+    }, pos, cli::shorts::attached);
+    if (!err.empty()) return 2;
     char const *what = p == program::power_law ? "mcool" : p == program::downsample ? "infile" : p == program::compartments ? "coolfile" : "mcoolfile";
     if (p == program::interactions && !o.has_binsize) { err = "the following arguments are required: -b"; return 2; }
     if (pos.empty()) { err = std::string("the following arguments are required: ") + what; return 2; }
@@ -297,19 +274,12 @@ struct cooler {
     }
 };
 
-struct device {
-    gd_hic *h = nullptr;
-    double startup = 0;      // seconds gd_hic_create took (the HIP runtime starts there)
-    void open(bin_table const &bins)
-    {
-        auto const t = std::chrono::steady_clock::now();
-        gd_hic_desc const d{0, 0};
-        cli::check(gd_hic_create(&d, bins.chrom.data(), (uint32_t)bins.chrom.size(), &h));
-        startup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    }
-    ~device() { gd_hic_destroy(h); }
-    void report(char const *prog) const { std::fprintf(stderr, "%s: device start-up %.3f s\n", prog, startup); }
-};
+using device = cli::handle<gd_hic, gd_hic_destroy>;
+
+inline void open(device &dev, bin_table const &bins)
+{
+    dev.open([&bins](gd_hic **h) { gd_hic_desc const d{0, 0}; return gd_hic_create(&d, bins.chrom.data(), (uint32_t)bins.chrom.size(), h); });
+}
 
 // one pass: chunk k + 1 is read on a second thread while the device accumulates chunk k
 inline void stream_pixels(cooler const &c, device &dev, cli::stopwatch &sw)
@@ -374,7 +344,7 @@ inline void run_interactions(options const &o)
     output out(o.output);
     sw.read += sw.lap();
     device dev;
-    dev.open(bins);
+    open(dev, bins);
     int32_t band = -1;
     uint32_t const W = (uint32_t)o.width;
     cli::check(gd_hic_add_band(dev.h, W, &band));
@@ -425,7 +395,7 @@ inline void run_alpha(options const &o)
     output out(o.output);
     sw.read += sw.lap();
     device dev;
-    dev.open(bins);
+    open(dev, bins);
     int32_t band = -1;
     cli::check(gd_hic_add_band(dev.h, (uint32_t)o.width + 1, &band));
     sw.compute += sw.lap();
@@ -470,7 +440,7 @@ inline void run_power_law(options const &o)
     for (std::size_t b = 0; b < n; b++) size = std::max(size, ++sizes[bins.chrom[b]]);
     sw.read += sw.lap();
     device dev;
-    dev.open(bins);
+    open(dev, bins);
     int32_t profile = -1;
     cli::check(gd_hic_add_distance_profile(dev.h, excluded.data(), weighted ? weights.data() : nullptr, size, &profile));
     sw.compute += sw.lap();
@@ -528,7 +498,7 @@ inline void run_compartments(options const &o)
     }
     sw.read += sw.lap();
     device dev;
-    dev.open(bins);
+    open(dev, bins);
     int32_t dense = -1;
     cli::check(gd_hic_add_dense(dev.h, weighted ? weights.data() : nullptr, &dense));
     sw.compute += sw.lap();
@@ -651,27 +621,15 @@ inline void run_downsample(options const &o)
 inline int main(program p, int argc, char **argv)
 {
     options o;
-    std::string err;
-    if (parse(p, argc, argv, o, err)) {
-        std::fprintf(stderr, "%s%s: error: %s\n", usage(p), name_of(p), err.c_str());
-        return 2;
-    }
-    if (o.dry_run) {
-        print_plan(p, o);
-        return 0;
-    }
-    try {
-        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    return cli::run(usage(p), name_of(p), "error:", [&](std::string &err) { return parse(p, argc, argv, o, err); },
+                    [&] { return o.dry_run && (print_plan(p, o), true); }, [&] {
         if (p == program::interactions) run_interactions(o);
         else if (p == program::alpha) run_alpha(o);
         else if (p == program::power_law) run_power_law(o);
         else if (p == program::compartments) run_compartments(o);
         else run_downsample(o);
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 }  // namespace hic

@@ -131,12 +131,11 @@ struct ensemble_matrix {
     ensemble_matrix(std::string const &first_file, long rate, std::string const &out, int device)
         : output(out), head(gd::cmap::load_ranges(first_file)), rb(gd::cmap::rebin(head, rate))
     {
-        dev.ordinal = device;
-        dev.open();
+        gd::cmap::open(dev, device);
         gd::cli::check(gd_cmap_add_binned(dev.h, rb.map.data(), (uint32_t)rb.map.size(), rb.n_bins, &target));
     }
     void add(gd_system *sys, uint32_t replica) { gd::cli::check(gd_live_contacts(sys, replica, dev.h)); }
-    void write() { gd::cmap::write_gw_matrix(output, head, rb, dev.fetch(target)); }
+    void write() { gd::cmap::write_gw_matrix(output, head, rb, gd::cmap::fetch(dev, target)); }
 };
 
 // The models of a batch: files whose /metadata/ab_factors are equal, numbered by first appearance in file order
@@ -243,7 +242,8 @@ struct flow_outputs {
         uint32_t const F = frames(), N = beads;
         options const &o = particle.outfile.empty() ? grid : particle;      // (the velocity options are the same in both)
         bool const smooth = smoothed(o);
-        gd::flow::device dev(ordinal);
+        gd::flow::device dev;
+        gd::flow::open(dev, ordinal);
         std::unique_ptr<particle_writer> pw;
         std::unique_ptr<grid_writer> gw;
         std::unique_ptr<mesh> m;

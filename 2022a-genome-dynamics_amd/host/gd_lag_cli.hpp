@@ -32,6 +32,15 @@ inline bool parse_list(std::string const &v, std::vector<uint32_t> &out)
     return !out.empty();
 }
 
+// the handlers of the options the three programs share (gd_cli_args.hpp): "" or why the value will not do
+inline std::string lags_or_count(lag_option &l, bool list, std::string const &v)      // --lags a,b,... / --log-lags K, K of 1 to 2^28
+{
+    l.explicit_list = list && parse_list(v, l.list);
+    return list ? gd::cli::valid_if(l.explicit_list, v) : gd::cli::to_int(v, l.log_count, nullptr, 1, 1l << 28);
+}
+
+inline std::string phase_name(std::string const &v, std::string &name) { return gd::cli::valid_if(!(name = v).empty() && v.find('/') == std::string::npos, v); }
+
 // --box Lx,Ly,Lz: three positive finite periods
 inline bool parse_box(std::string const &v, double box[3])
 {

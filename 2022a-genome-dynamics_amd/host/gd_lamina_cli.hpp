@@ -33,28 +33,19 @@ inline const char *usage()
 // argparse's conventions: "--opt value" or "--opt=value"; 0 or 2 with a message
 inline int parse(int argc, char **argv, options &o, std::string &err)
 {
+    using cli::kind;
+    static cli::table const before_contact = {{"--dry-run", kind::flag}},
+                            after_contact = {{"--dry-run", kind::flag}, {"--name", kind::value}, {"--contact-distance", kind::value}};
     std::vector<std::string> pos;
-    for (int k = 1; k < argc; k++) {
-        std::string const a = argv[k];
-        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
-            if (a == "--dry-run") { o.dry_run = true; continue; }
-            auto const eq = a.find('=');
-            std::string const key = eq == std::string::npos ? a : a.substr(0, eq);
-            bool const contact = !pos.empty() && pos[0] == "contact";
-            if (!contact || (key != "--name" && key != "--contact-distance")) { err = "unrecognized arguments: " + a; return 2; }
-            std::string v;
-            if (eq != std::string::npos) v = a.substr(eq + 1);
-            else if (k + 1 < argc) v = argv[++k];
-            else { err = "argument " + key + ": expected one argument"; return 2; }
-            if (key == "--name") o.name = v;
-            else if (!(o.has_contact_distance = cli::parse_float(v, o.contact_distance))) {
-                err = "argument --contact-distance: invalid float value: '" + v + "'";
-                return 2;
-            }
-        } else {
-            pos.push_back(a);
-        }
-    }
+    err = cli::scan_by(
+        argc, argv, cli::shorts::exact, [](std::vector<std::string> const &p) -> cli::table const & { return !p.empty() && p[0] == "contact" ? after_contact : before_contact; },
+        [&o](std::string const &key, std::string const &v) {
+            if (key == "--dry-run") return o.dry_run = true, std::string();
+            if (key == "--name") return o.name = v, std::string();
+            return cli::valid_if(o.has_contact_distance = cli::parse_float(v, o.contact_distance), v, "float");
+        },
+        pos);
+    if (!err.empty()) return 2;
     if (pos.empty()) { err = "the following arguments are required: command"; return 2; }
     o.command = pos[0];
     if (o.command != "distance" && o.command != "contact") {
@@ -90,15 +81,12 @@ inline void print_plan(options const &o)
     }
 }
 
-struct device {
-    gd_lamina *h = nullptr;
-    device()
-    {
-        gd_lamina_desc const d{0, 0};
-        cli::check(gd_lamina_create(&d, &h));
-    }
-    ~device() { gd_lamina_destroy(h); }
-};
+using device = cli::handle<gd_lamina, gd_lamina_destroy>;
+
+inline void open(device &dev)
+{
+    dev.open([](gd_lamina **h) { gd_lamina_desc const d{0, 0}; return gd_lamina_create(&d, h); });
+}
 
 struct history {
     uint32_t frames = 0, beads = 0;
@@ -162,13 +150,14 @@ inline void copy_metadata(std::string const &path, hid_t output)
     h5::hid ds(H5Dcreate2(out, "particle_types", ttype, tspace, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT));
     h5::check(ds >= 0, "cannot create metadata/particle_types");
     if (nt > 0) h5::check(H5Dwrite(ds, ttype, H5S_ALL, H5S_ALL, H5P_DEFAULT, tdata.data()) >= 0, "cannot write metadata/particle_types");
-    cli::put_dataset(out, "chromosome_ranges", ranges.data(), {rows, 2}, 4, H5T_NATIVE_INT, H5T_STD_I32LE, nullptr);
+    cli::put(out, "chromosome_ranges", ranges.data(), {rows, 2}, nullptr);
     h5::write_fixed_string_list(out, "chromosome_names", names);
 }
 
 inline void run_distance(options const &o)
 {
     device dev;
+    open(dev);
     h5::hid file(cli::open_output(o.outfile));
     cli::stopwatch sw;
     copy_metadata(o.trajfiles[0], file);
@@ -186,8 +175,7 @@ inline void run_distance(options const &o)
         sw.compute += sw.lap();
         history following = next.valid() ? next.get() : history{};      // (a std::async future joins its thread when it is dropped)
         sw.read += sw.lap();
-        cli::put_dataset(file, "/distance/" + cli::sample_name(o.trajfiles[k]), dist.data(), {cur.frames, cur.beads}, 4, H5T_NATIVE_FLOAT,
-                          H5T_IEEE_F32LE, &f);
+        cli::put(file, "/distance/" + cli::sample_name(o.trajfiles[k]), dist.data(), {cur.frames, cur.beads}, &f);
         sw.write += sw.lap();
         cur = std::move(following);
     }
@@ -203,6 +191,7 @@ inline herr_t collect_name(hid_t, const char *name, const H5L_info_t *, void *da
 inline void run_contact(options const &o)
 {
     device dev;
+    open(dev);
     h5::hid file(cli::open_output(o.outfile));
     cli::stopwatch sw;
     h5::hid group(H5Gopen2(file, "/distance", H5P_DEFAULT));
@@ -235,7 +224,7 @@ inline void run_contact(options const &o)
     std::vector<float> average(dims[0] * dims[1]);
     cli::check(gd_lamina_average(dev.h, average.data()));
     sw.compute += sw.lap();
-    cli::put_dataset(file, "/average_contact/" + o.name, average.data(), {dims[0], dims[1]}, 4, H5T_NATIVE_FLOAT, H5T_IEEE_F32LE, &f);
+    cli::put(file, "/average_contact/" + o.name, average.data(), {dims[0], dims[1]}, &f);
     sw.write += sw.lap();
     sw.report("gd_analyze_lamina contact");
 }
@@ -244,24 +233,12 @@ inline void run_contact(options const &o)
 inline int main(int argc, char **argv)
 {
     options o;
-    std::string err;
-    if (parse(argc, argv, o, err)) {
-        std::fprintf(stderr, "%sgd_analyze_lamina: error: %s\n", usage(), err.c_str());
-        return 2;
-    }
-    if (o.dry_run) {
-        print_plan(o);
-        return 0;
-    }
-    try {
-        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    return cli::run(usage(), "gd_analyze_lamina", "error:", [&](std::string &err) { return parse(argc, argv, o, err); },
+                    [&o] { return o.dry_run && (print_plan(o), true); }, [&o] {
         if (o.command == "distance") run_distance(o);
         else run_contact(o);
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 }  // namespace lamina

@@ -26,69 +26,28 @@ struct options {
 
 int parse(int argc, char **argv, options &o, std::string &err)
 {
+    using gd::cli::kind;
+    static gd::cli::table const options = {{"--dry-run", kind::flag}, {"--name", kind::value}, {"--lags", kind::value}, {"--log-lags", kind::value},
+                                           {"--seps", kind::value}, {"--log-seps", kind::value}, {"--groups", kind::value}};
     std::vector<std::string> pos;
-    for (int k = 1; k < argc; k++) {
-        std::string a = argv[k], v;
-        if (a.size() > 2 && a.compare(0, 2, "--") == 0) {
-            if (a == "--dry-run") { o.dry_run = true; continue; }
-            auto eq = a.find('=');
-            bool const inline_value = eq != std::string::npos;
-            std::string const key = inline_value ? a.substr(0, eq) : a;
-            if (key != "--name" && key != "--lags" && key != "--log-lags" && key != "--seps" && key != "--log-seps" && key != "--groups") {
-                err = "unrecognized arguments: " + a;
-                return 2;
-            }
-            if (inline_value) v = a.substr(eq + 1);
-            else if (k + 1 < argc) v = argv[++k];
-            else { err = "argument " + key + ": expected one argument"; return 2; }
-            bool ok = true;
-            if (key == "--name") ok = !(o.name = v).empty() && v.find('/') == std::string::npos;
-            else if (key == "--groups") ok = (o.groups = v) == "all" || v == "types" || v == "chains";
-            else {
-                lag_option &l = key == "--lags" || key == "--log-lags" ? o.lags : o.seps;
-                if (key == "--lags" || key == "--seps") ok = l.explicit_list = parse_list(v, l.list);
-                else {
-                    ok = gd::cli::parse_int(v, l.log_count) && l.log_count >= 1 && l.log_count <= (1l << 28);
-                    l.explicit_list = false;
-                }
-            }
-            if (!ok) { err = "argument " + key + ": invalid value: '" + v + "'"; return 2; }
-        } else {
-            pos.push_back(a);
-        }
-    }
-    if (o.dry_run && pos.empty()) return 0;
-    if (pos.size() < 2) { err = "the following arguments are required: outfile, trajfiles"; return 2; }
-    o.outfile = pos[0];
-    o.trajfiles.assign(pos.begin() + 1, pos.end());
-    return 0;
+    err = gd::cli::scan(argc, argv, options, [&o](std::string const &key, std::string const &v) {
+        if (key == "--dry-run") return o.dry_run = true, std::string();
+        if (key == "--name") return phase_name(v, o.name);
+        if (key == "--groups") return gd::cli::valid_if((o.groups = v) == "all" || v == "types" || v == "chains", v);
+        return lags_or_count(key == "--lags" || key == "--log-lags" ? o.lags : o.seps, key == "--lags" || key == "--seps", v);
+    }, pos);
+    if (!err.empty()) return 2;
+    return gd::flow::take_files(pos, o.dry_run, o.outfile, o.trajfiles, err);
 }
-
-struct device {      // one gd_msd handle; every failure of the library ends the program with its message
-    gd_msd *h = nullptr;
-    device()
-    {
-        gd_msd_desc d{0, 0};
-        gd::cli::check(gd_msd_create(&d, &h));
-    }
-    ~device() { gd_msd_destroy(h); }
-};
 
 }  // namespace
 
 int main(int argc, char **argv)
 {
     options o;
-    std::string err;
-    if (parse(argc, argv, o, err)) {
-        std::fprintf(stderr,
-                     "usage: gd_msd [--name PHASE] [--lags a,b,...|--log-lags K] [--seps a,b,...|--log-seps K] [--groups all|types|chains] [--dry-run] "
-                     "outfile trajfiles ...\ngd_msd: error: %s\n",
-                     err.c_str());
-        return 2;
-    }
-    try {
-        H5Eset_auto2(H5E_DEFAULT, nullptr, nullptr);
+    char const *usage = "usage: gd_msd [--name PHASE] [--lags a,b,...|--log-lags K] [--seps a,b,...|--log-seps K] [--groups all|types|chains] [--dry-run] "
+                        "outfile trajfiles ...\n";
+    return gd::cli::run(usage, "gd_msd", "gd_msd: error:", [&](std::string &err) { return parse(argc, argv, o, err); }, gd::cli::no_plan, [&o] {
         if (o.dry_run) {
             std::printf("name\t%s\ngroups\t%s\nlags\t%s\nseps\t%s\n", o.name.c_str(), o.groups.c_str(), describe(o.lags).c_str(), describe(o.seps).c_str());
             for (auto const &path : o.trajfiles) {
@@ -102,7 +61,8 @@ int main(int argc, char **argv)
             }
             return 0;
         }
-        device dev;
+        gd::cli::handle<gd_msd, gd_msd_destroy> dev;
+        dev.open([](gd_msd **h) { gd_msd_desc const d{0, 0}; return gd_msd_create(&d, h); });
         gd::h5::hid out(gd::cli::open_output(o.outfile));
         gd::cli::stopwatch sw;
         for (auto const &path : o.trajfiles) {
@@ -123,23 +83,20 @@ int main(int argc, char **argv)
             gd::h5::hid group(gd::cli::require_group(out, "/msd/" + o.name + "/" + gd::cli::sample_name(path)));
             gd::cli::filters const f;
             hsize_t const L = lags.size(), S = seps.size();
-            gd::cli::put_dataset(group, "lags", lags.data(), {L}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, nullptr);
-            gd::cli::put_dataset(group, "time_sum2", t2.data(), {G, L}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "time_sum4", t4.data(), {G, L}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "time_count", tn.data(), {G, L}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
-            gd::cli::put_dataset(group, "seps", seps.data(), {S}, 4, H5T_NATIVE_UINT32, H5T_STD_U32LE, nullptr);
-            gd::cli::put_dataset(group, "chain_sum2", c2.data(), {C, S}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "chain_sum4", c4.data(), {C, S}, 8, H5T_NATIVE_DOUBLE, H5T_IEEE_F64LE, &f);
-            gd::cli::put_dataset(group, "chain_count", cn.data(), {C, S}, 8, H5T_NATIVE_UINT64, H5T_STD_U64LE, &f);
+            gd::cli::put(group, "lags", lags.data(), {L}, nullptr);
+            gd::cli::put(group, "time_sum2", t2.data(), {G, L}, &f);
+            gd::cli::put(group, "time_sum4", t4.data(), {G, L}, &f);
+            gd::cli::put(group, "time_count", tn.data(), {G, L}, &f);
+            gd::cli::put(group, "seps", seps.data(), {S}, nullptr);
+            gd::cli::put(group, "chain_sum2", c2.data(), {C, S}, &f);
+            gd::cli::put(group, "chain_sum4", c4.data(), {C, S}, &f);
+            gd::cli::put(group, "chain_count", cn.data(), {C, S}, &f);
             gd::h5::unlink_if_present(group, "group_names");
             gd::h5::write_fixed_string_list(group, "group_names", l.group_names);
             H5Fflush(out, H5F_SCOPE_GLOBAL);
             sw.write += sw.lap();
         }
         sw.report("gd_msd");
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "gd_msd: error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

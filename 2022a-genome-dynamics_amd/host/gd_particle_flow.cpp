@@ -7,11 +7,9 @@
 int main(int argc, char **argv)
 {
     using namespace gd::flow;
-    options o;
-    std::string config, name;
-    if (int rc = front(argc, argv, false, o, config, name); rc >= 0) return rc;
-    try {
+    return gd::flow::main(argc, argv, false, [](options const &o, std::string const &config, std::string const &name, char const *prog) {
         device dev;
+        open(dev);
         particle_writer out(o.outfile, name, config);
         bool const smooth = smoothed(o);
         gd::cli::stopwatch sw;
@@ -30,10 +28,6 @@ int main(int argc, char **argv)
         }
         out.finish();
         sw.write += sw.lap();
-        sw.report("gd_particle_flow");
-    } catch (std::exception const &e) {
-        std::fprintf(stderr, "gd_particle_flow: error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        sw.report(prog);
+    });
 }
