@@ -1,4 +1,4 @@
-// gd_lag_cli.hpp -- what gd_msd, gd_dcorr and gd_distance_map share: the lag lists of their command lines (--lags a,b,... /
+// gd_lag_cli.hpp -- what gd_msd, gd_dcorr, gd_distance_map and gd_structure_factor share: the lag lists of their command lines (--lags a,b,... /
 // --log-lags K), the periods of --box, and what a trajectory file says about its beads (the chains of chromosome_ranges, the groups
 // of particle_types).
 #pragma once
