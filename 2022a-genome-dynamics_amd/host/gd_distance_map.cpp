@@ -12,35 +12,22 @@
 // --by-chain every non-empty chain as one bin.  --chains restricts rows and columns to the bins of the chains named.  --dry-run prints
 // the plan and, for every trajectory file given, its shape and bins; no device is used.
 #include "../../include/gdyn_dmap.h"
-#include "gd_lag_cli.hpp"
+#include "gd_bins_cli.hpp"
 
 using namespace gd::lagcli;
+using namespace gd::binscli;
 
 namespace {
 
-struct options {
+struct options : bin_options {
     std::string name = "interphase";
-    long rate = 1;
-    bool by_chain = false, has_box = false, has_frames = false, dry_run = false;
-    std::vector<std::string> chains;
+    bool has_box = false, has_frames = false, dry_run = false;
     std::vector<double> thresholds;
     long first_frame = 0, n_frames = 0;
     double box[3] = {0, 0, 0};
     std::string outfile;
     std::vector<std::string> trajfiles;
 };
-
-std::vector<std::string> split(std::string const &v)
-{
-    std::vector<std::string> out;
-    std::size_t at = 0;
-    while (at <= v.size()) {
-        auto const comma = std::min(v.find(',', at), v.size());
-        out.push_back(v.substr(at, comma - at));
-        at = comma + 1;
-    }
-    return out;
-}
 
 bool parse_thresholds(std::string const &v, std::vector<double> &out)
 {
@@ -51,21 +38,6 @@ bool parse_thresholds(std::string const &v, std::vector<double> &out)
         out.push_back(t);
     }
     return out.size() <= GD_DMAP_MAX_THRESHOLDS;
-}
-
-bool parse_chains(std::string const &v, std::vector<std::string> &out)
-{
-    out = split(v);
-    for (auto const &s : out)
-        if (s.empty() || std::count(out.begin(), out.end(), s) != 1) return false;
-    return true;
-}
-
-bool parse_frames(std::string const &v, long &first, long &count)
-{
-    auto const colon = v.find(':');
-    return colon != std::string::npos && gd::cli::parse_int(v.substr(0, colon), first) && gd::cli::parse_int(v.substr(colon + 1), count) && first >= 0 &&
-           count >= 1 && first <= 0xffffffffl && count <= 0xffffffffl;
 }
 
 int parse(int argc, char **argv, options &o, std::string &err)
@@ -85,70 +57,23 @@ int parse(int argc, char **argv, options &o, std::string &err)
         return gd::cli::valid_if(o.has_box = parse_box(v, o.box), v);
     }, pos);
     if (!err.empty()) return 2;
-    if (o.by_chain && o.rate != 1) { err = "argument --by-chain: not allowed with argument --rebin-rate"; return 2; }
+    if (!(err = conflict(o)).empty()) return 2;
     return gd::flow::take_files(pos, o.dry_run, o.outfile, o.trajfiles, err);
 }
 
-struct plan {      // the bins of one trajectory file and the ones selected
-    std::vector<uint32_t> bins, bin_chain;      // (B, 2), (B)
-    std::vector<uint32_t> selected;             // ascending bin indices
+struct plan : bin_plan {
     uint32_t first_frame = 0, n_frames = 0;
 };
-
-// `rate` consecutive beads per bin within each chain; the last bin of a chain is shorter (Dmap.bins_from_chains)
-void bins_from_chains(std::vector<uint32_t> const &chains, uint32_t rate, plan &p)
-{
-    for (std::size_t c = 0; c < chains.size() / 2; c++)
-        for (uint32_t a = chains[2 * c]; a < chains[2 * c + 1]; a += rate) {
-            p.bins.push_back(a);
-            p.bins.push_back(std::min<uint64_t>((uint64_t)a + rate, chains[2 * c + 1]));
-            p.bin_chain.push_back((uint32_t)c);
-        }
-}
 
 plan make_plan(options const &o, layout const &l, std::string const &path, uint32_t F)
 {
     plan p;
-    if (o.by_chain) {
-        for (std::size_t c = 0; c < l.chains.size() / 2; c++)
-            if (l.chains[2 * c] < l.chains[2 * c + 1]) {
-                p.bins.push_back(l.chains[2 * c]);
-                p.bins.push_back(l.chains[2 * c + 1]);
-                p.bin_chain.push_back((uint32_t)c);
-            }
-    } else {
-        bins_from_chains(l.chains, (uint32_t)o.rate, p);
-    }
-    std::vector<char> wanted(l.chain_names.size(), o.chains.empty());
-    for (auto const &name : o.chains) {
-        auto const it = std::find(l.chain_names.begin(), l.chain_names.end(), name);
-        gd::h5::check(it != l.chain_names.end(), path + ": no chain named " + name);
-        wanted[it - l.chain_names.begin()] = 1;
-    }
-    for (uint32_t b = 0; b < p.bin_chain.size(); b++)
-        if (wanted[p.bin_chain[b]]) p.selected.push_back(b);
-    gd::h5::check(!p.selected.empty(), path + ": no bin selected");
+    plan_bins(o, l, path, p);
     p.first_frame = o.has_frames ? (uint32_t)o.first_frame : 0;
     p.n_frames = o.has_frames ? (uint32_t)o.n_frames : F;
     gd::h5::check((uint64_t)p.first_frame + p.n_frames <= F, path + ": --frames " + std::to_string(p.first_frame) + ":" + std::to_string(p.n_frames) + " of " +
                                                                  std::to_string(F) + " frames");
     return p;
-}
-
-// the runs of consecutive bin indices of `selected`: (place in selected, first bin, length)
-struct run {
-    std::size_t at;
-    uint32_t first, n;
-};
-
-std::vector<run> runs_of(std::vector<uint32_t> const &selected)
-{
-    std::vector<run> out;
-    for (std::size_t k = 0; k < selected.size(); k++) {
-        if (!out.empty() && out.back().first + out.back().n == selected[k]) out.back().n++;
-        else out.push_back({k, selected[k], 1});
-    }
-    return out;
 }
 
 std::string join_doubles(std::vector<double> const &v)
@@ -167,8 +92,7 @@ int main(int argc, char **argv)
                         "[--box Lx,Ly,Lz] [--dry-run] outfile trajfiles ...\n";
     return gd::cli::run(usage, "gd_distance_map", "gd_distance_map: error:", [&](std::string &err) { return parse(argc, argv, o, err); }, gd::cli::no_plan, [&o] {
         if (o.dry_run) {
-            std::string chains;
-            for (std::size_t k = 0; k < o.chains.size(); k++) chains += (k ? "," : "") + o.chains[k];
+            std::string const chains = join_names(o.chains);
             std::printf("name\t%s\nbins\t%s\nchains\t%s\nthresholds\t%s\nframes\t%s\nbox\t%s\n", o.name.c_str(),
                         o.by_chain ? "by chain" : ("rate " + std::to_string(o.rate)).c_str(), o.chains.empty() ? "all" : chains.c_str(),
                         o.thresholds.empty() ? "none" : join_doubles(o.thresholds).c_str(),
@@ -218,24 +142,15 @@ int main(int argc, char **argv)
                         }
                 }
             sw.compute += sw.lap();
-            std::vector<uint32_t> bins(2 * S), bin_chain(S);
-            for (std::size_t k = 0; k < S; k++) {
-                bins[2 * k] = p.bins[2 * (std::size_t)p.selected[k]];
-                bins[2 * k + 1] = p.bins[2 * (std::size_t)p.selected[k] + 1];
-                bin_chain[k] = p.bin_chain[p.selected[k]];
-            }
             gd::h5::hid group(gd::cli::require_group(out, "/dmap/" + o.name + "/" + gd::cli::sample_name(path)));
             gd::cli::filters const f;
             hsize_t const s = S, t = T;
-            gd::cli::put(group, "bins", bins.data(), {s, 2}, &f);
-            gd::cli::put(group, "bin_chain", bin_chain.data(), {s}, &f);
+            put_selected(group, p, l.chain_names, f);
             gd::cli::put(group, "thresholds", o.thresholds.data(), {t}, nullptr);
             gd::cli::put(group, "sum1", sum1.data(), {s, s}, &f);
             gd::cli::put(group, "sum2", sum2.data(), {s, s}, &f);
             gd::cli::put(group, "hits", hits.data(), {t, s, s}, &f);
             gd::cli::put(group, "count", count.data(), {s, s}, &f);
-            gd::h5::unlink_if_present(group, "chain_names");
-            gd::h5::write_fixed_string_list(group, "chain_names", l.chain_names);
             H5Fflush(out, H5F_SCOPE_GLOBAL);
             sw.write += sw.lap();
         }
