@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap, sq, cluster, dcov) share: loading libgdyn with a check of
+"""What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap, sq, cluster, dcov, gyr) share: loading libgdyn with a check of
 one module's symbols and ABI version, the life cycle of a ``gd_<x>`` handle, the normalisation of frames, and the trajectory history
-that the msd, dcorr, dmap, sq, cluster and dcov handles hold."""
+that the msd, dcorr, dmap, sq, cluster, dcov and gyr handles hold."""
 from __future__ import annotations
 
 import ctypes as C
@@ -65,7 +65,7 @@ class Handle:
 
 
 class HistoryHandle(Handle):
-    """A ``gd_<prefix>`` handle that holds one trajectory history on the device (msd, dcorr, dmap, sq, cluster, dcov).  ``shape`` is (F, N) of the
+    """A ``gd_<prefix>`` handle that holds one trajectory history on the device (msd, dcorr, dmap, sq, cluster, dcov, gyr).  ``shape`` is (F, N) of the
     history, None before the first.  A subclass names its ``_prefix``, loads ``dll`` with load_history_library and overrides
     ``_beads_changed``."""
 

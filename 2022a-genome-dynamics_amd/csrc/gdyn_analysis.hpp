@@ -1,8 +1,8 @@
 // gdyn_analysis.hpp -- the host-side plumbing that the device analyses (gdyn_flow, gdyn_rdf, gdyn_lamina, gdyn_cmap,
-// gdyn_hic, gdyn_msd, gdyn_dcorr, gdyn_dmap, gdyn_sq, gdyn_cluster, gdyn_dcov) and the recorder (gdyn_live) share: error reporting, owned device and pinned host
+// gdyn_hic, gdyn_msd, gdyn_dcorr, gdyn_dmap, gdyn_sq, gdyn_cluster, gdyn_dcov, gdyn_gyr) and the recorder (gdyn_live) share: error reporting, owned device and pinned host
 // buffers, the device and stream of a handle with its create prologue and destroy epilogue, the grid size of a
 // one-lane-per-element launch and the opt-in to more than 64 KiB of dynamic LDS.  The stepper's host files (gdyn_system.hpp)
-// take the error reporting and the buffers from here too.  The trajectory history that gd_msd, gd_dcorr, gd_dmap, gd_sq, gd_cluster and gd_dcov hold is
+// take the error reporting and the buffers from here too.  The trajectory history that gd_msd, gd_dcorr, gd_dmap, gd_sq, gd_cluster, gd_dcov and gd_gyr hold is
 // gdyn_history.hpp's.  Nothing here is extern "C" or device code.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// gdyn_history.hpp -- the trajectory history of an analysis handle (gd_msd, gd_dcorr, gd_dmap, gd_sq, gd_cluster, gd_dcov): (F, N, 3) coordinates on the
+// gdyn_history.hpp -- the trajectory history of an analysis handle (gd_msd, gd_dcorr, gd_dmap, gd_sq, gd_cluster, gd_dcov, gd_gyr): (F, N, 3) coordinates on the
 // device in the precision they came in, fed from the host or from a recorder (gdyn_live.hip), and held only when every
 // coordinate is finite.  gdyn_history.hip; C++ linkage and hidden, like the seams of gdyn_live.hpp: none of it is exported.
 #pragma once

@@ -1,4 +1,4 @@
-// gd_bins_cli.hpp -- what gd_distance_map and gd_covariance_map share: the bins of their maps (--rebin-rate K, --by-chain, --chains
+// gd_bins_cli.hpp -- what gd_distance_map, gd_covariance_map and gd_gyration share: the bins of their maps (--rebin-rate K, --by-chain, --chains
 // a,b,...), the --frames FIRST:COUNT window, and the runs of consecutive selected bins that one rectangle call each serves.
 #pragma once
 #include "gd_lag_cli.hpp"

@@ -20,7 +20,8 @@
  * [first_frame, first_frame + n_frames):
  *     c2[c, s] = sum over the frames f and i = start_c .. end_c-1-s of t2(X[f,i], X[f,i+s]);   c4 likewise of t4;
  *     count[c, s] = n_frames * max(0, len_c - s)   (a separation at least as long as the chain: count 0, sums 0).
- *   Rg^2 of a chain follows from all its separations (sum over i<j of r_ij^2 / n^2); there is no separate call.
+ *   Rg^2 of a chain follows from all its separations (sum over i<j of r_ij^2 / n^2), averaged over the frames; there is no separate call
+ *   here.  Per frame, with the tensor, and for sliding windows: include/gdyn_gyr.h.
  *
  * Nothing is subtracted: no drift, no centroid.  Periodic systems store unwrapped coordinates, so MSD across box images is
  * already right.
