@@ -1,6 +1,6 @@
 """What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap, sq, cluster, dcov, gyr) share: loading libgdyn with a check of
 one module's symbols and ABI version, the life cycle of a ``gd_<x>`` handle, the normalisation of frames, and the trajectory history
-that the msd, dcorr, dmap, sq, cluster, dcov and gyr handles hold."""
+that the msd, dcorr, dmap, sq, cluster, dcov and gyr handles hold, with the bodies of their label, range and timing methods."""
 from __future__ import annotations
 
 import ctypes as C
@@ -98,6 +98,48 @@ class HistoryHandle(Handle):
         the recorder to this handle on the device."""
         self._check(getattr(self.dll, f"gd_{self._prefix}_set_history_live")(self._h, history._h, int(replica)))
         self._new_shape((history.frames, history.N))
+
+    # ---- what the history modules' setters and getters share; a subclass keeps its public method and its own attributes
+
+    def _set_labels(self, label, n_labels):
+        """The body of set_labels: label (N,) integers in [-1, n_labels) or None, n_labels None: the largest label + 1.  Returns
+        (K, the labels as int32 or None)."""
+        call = getattr(self.dll, f"gd_{self._prefix}_set_labels")
+        if label is None:
+            self._check(call(self._h, None, 1))
+            return 1, None
+        l = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
+        if self.shape is not None and len(l) != self.shape[1]:
+            raise ValueError(f"label must have one entry per bead ({self.shape[1]}), got {len(l)}")
+        K = int(n_labels) if n_labels is not None else max(int(l.max()) + 1, 1) if len(l) else 1
+        self._check(call(self._h, l.ctypes.data, K))
+        return K, l
+
+    def _set_ranges(self, call, ranges, what, empty, default):
+        """The body of a setter of (R, 2) [start, end) bead ranges (``what``: "bin ranges"; ``empty``: the refusal of an empty list).
+        Returns them as uint32, or ``default`` for ``ranges`` None, which makes the library's own default."""
+        if ranges is None:
+            self._check(call(self._h, None, 0))
+            return default
+        r = _u32(ranges, what).reshape(-1, 2)
+        if not len(r):
+            raise ValueError(empty)
+        self._check(call(self._h, r.ctypes.data, len(r)))
+        return r
+
+    def _last_times(self, *names):
+        """The three device times of gd_<prefix>_last_times under ``names``."""
+        t = [C.c_double() for _ in range(3)]
+        self._check(getattr(self.dll, f"gd_{self._prefix}_last_times")(self._h, *[C.byref(v) for v in t]))
+        return {name: v.value for name, v in zip(names, t)}
+
+
+def box3(box):
+    """A period or three as the three doubles of a ``const double *box`` argument: (their address or None, the array to keep alive)."""
+    if box is None:
+        return None, None
+    b = (C.c_double * 3)(*np.broadcast_to(np.asarray(box, dtype=np.float64), (3,)))
+    return C.addressof(b), b
 
 
 def _u32(values, what):

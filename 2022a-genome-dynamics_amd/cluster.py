@@ -20,7 +20,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._binding import GdynError, HistoryHandle, load_history_library
+from ._binding import GdynError, HistoryHandle, box3, load_history_library
 
 CLUSTER_ABI_VERSION = 1      # GD_CLUSTER_ABI_VERSION of the include/gdyn_cluster.h this binding mirrors
 CLUSTER_SYMBOLS = ["gd_cluster_abi_version", "gd_cluster_create", "gd_cluster_destroy", "gd_cluster_set_history", "gd_cluster_set_history_live",
@@ -120,16 +120,7 @@ class Clusters(HistoryHandle):
     def set_labels(self, label, n_labels=None):
         """label: (N,) integers in [-1, n_labels), -1 for a bead that takes no part; None: one label of all beads.
         n_labels=None: the largest label + 1.  The link mask becomes "all"."""
-        if label is None:
-            self._check(self.dll.gd_cluster_set_labels(self._h, None, 1))
-            self.n_labels = 1
-            return
-        l = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
-        if self.shape is not None and len(l) != self.shape[1]:
-            raise ValueError(f"label must have one entry per bead ({self.shape[1]}), got {len(l)}")
-        K = int(n_labels) if n_labels is not None else max(int(l.max()) + 1, 1) if len(l) else 1
-        self._check(self.dll.gd_cluster_set_labels(self._h, l.ctypes.data, K))
-        self.n_labels = K
+        self.n_labels, _ = self._set_labels(label, n_labels)
 
     def set_links(self, links):
         """Which label pairs may link: "all", "same" (a with a only), a list [(a, b), ...], or the 64-bit mask itself."""
@@ -147,7 +138,7 @@ class Clusters(HistoryHandle):
         frames first_frame + k frame_stride (n_frames 0: all that fit).  box: a period or three, None: open.  root[f, i]: the
         smallest bead index of bead i's cluster, -1 for a bead that takes no part.  histogram[f, b]: clusters of size b + 1, the last
         bin those of size_bins and more."""
-        b = None if box is None else (C.c_double * 3)(*np.broadcast_to(np.asarray(box, dtype=np.float64), (3,)))
+        box_at, _keep = box3(box)
         F = int(self.dll.gd_cluster_frames(self._h, int(first_frame), int(n_frames), int(frame_stride)))
         N = self.shape[1] if self.shape is not None else 0
         nb = int(size_bins)
@@ -156,6 +147,6 @@ class Clusters(HistoryHandle):
         keep = 0 < nb <= MAX_SIZE_BINS
         root = np.full((F, N), -1, np.int32) if roots else None
         summary, hist = np.zeros((F, 4), np.uint64), np.zeros((F, nb if keep else 1), np.uint64)
-        self._check(self.dll.gd_cluster_components(self._h, int(first_frame), int(n_frames), int(frame_stride), None if b is None else C.addressof(b),
+        self._check(self.dll.gd_cluster_components(self._h, int(first_frame), int(n_frames), int(frame_stride), box_at,
                                                    float(distance), nb, root.ctypes.data if roots else None, summary.ctypes.data, hist.ctypes.data))
         return Components(root, summary[:, 0].copy(), summary[:, 1].copy(), summary[:, 2].copy(), summary[:, 3].copy(), hist)

@@ -1,7 +1,7 @@
 // gdyn_analysis.hpp -- the host-side plumbing that the device analyses (gdyn_flow, gdyn_rdf, gdyn_lamina, gdyn_cmap,
 // gdyn_hic, gdyn_msd, gdyn_dcorr, gdyn_dmap, gdyn_sq, gdyn_cluster, gdyn_dcov, gdyn_gyr) and the recorder (gdyn_live) share: error reporting, owned device and pinned host
 // buffers, the device and stream of a handle with its create prologue and destroy epilogue, the grid size of a
-// one-lane-per-element launch and the opt-in to more than 64 KiB of dynamic LDS.  The stepper's host files (gdyn_system.hpp)
+// one-lane-per-element launch, the opt-in to more than 64 KiB of dynamic LDS and the stage timer of gd_dcov and gd_gyr.  The stepper's host files (gdyn_system.hpp)
 // take the error reporting and the buffers from here too.  The trajectory history that gd_msd, gd_dcorr, gd_dmap, gd_sq, gd_cluster, gd_dcov and gd_gyr hold is
 // gdyn_history.hpp's.  Nothing here is extern "C" or device code.
 #pragma once
@@ -170,6 +170,39 @@ struct handle {
     ~handle()
     {
         if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// The device times of a handle's last calls (gd_<x>_last_times): three events for the marks on its stream, three stages to report.
+struct StageTimer {
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    double ms[3] = {0.0, 0.0, 0.0};
+
+    ~StageTimer()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create()
+    {
+        for (hipEvent_t &e : ev)
+            if (hipError_t const rc = hipEventCreate(&e)) return rc;
+        return hipSuccess;
+    }
+    hipError_t mark(int i, hipStream_t st) { return hipEventRecord(ev[i], st); }
+    // the milliseconds from mark `from` to mark `to`, both reached
+    hipError_t between(int from, int to, double *out) const
+    {
+        float f = 0.0f;
+        hipError_t const rc = hipEventElapsedTime(&f, ev[from], ev[to]);
+        *out = f;
+        return rc;
+    }
+    void report(double *a, double *b, double *c) const
+    {
+        if (a) *a = ms[0];
+        if (b) *b = ms[1];
+        if (c) *c = ms[2];
     }
 };
 

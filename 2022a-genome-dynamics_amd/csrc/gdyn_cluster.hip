@@ -1,17 +1,15 @@
 // gdyn_cluster.hip -- the connected clusters of a history (include/gdyn_cluster.h): per frame, the connected components of the
 // graph whose edges are the pairs of selected beads closer than a distance, as the smallest bead index of every bead's component,
 // with the number of clusters, the largest, the sum of squared sizes and the histogram of sizes.  Beyond the reference, which has
-// no such analysis.  The pair rules are gdyn_rdf.hip's, the cell walk is gdyn_dcorr.hip's, the history is gd::History's
-// (gdyn_history.hpp).  Unlike every other analysis here the result is not a sum of independent terms but a fixed point: a
+// no such analysis.  The pair rules and the cell grid are gdyn_cells.hpp's, the walk over the grid is that of gdyn_dcorr.hip, the
+// history is gd::History's (gdyn_history.hpp).  Unlike every other analysis here the result is not a sum of independent terms but a fixed point: a
 // concurrent union-find over the pair graph.
 //
 // Per batch of frames (max_frames_per_launch; no result depends on it):
-//   k_cluster_bbox, k_cluster_grid   as gdyn_dcorr.hip: the bounding box of each frame's selected beads in an open box; cells of
-//                    side >= distance (1 + kCellSlack) of the periodic box or of that bounding box, coarsened until a frame has
-//                    at most `cap` = n / 16 cells, so that a cell holds 16 beads or so and a block's lanes have centres to serve
-//   k_cluster_keys   gathers the selected beads of each frame as 32-byte records (position, bead index, label) keyed (frame, cell)
-//   gd_sort_contacts, k_cluster_sorted, k_cluster_starts, k_cluster_work   as gdyn_dcorr.hip: the records in key order, the first
-//                    sorted index of every cell, one work item per kChunk centres of a non-empty cell
+//   gd::CellIndex    (gdyn_cells.hpp) as in gdyn_dcorr.hip: cells of side >= distance (1 + kCellSlack), coarsened until a frame has
+//                    at most `cap` = n / 16 of them, so that a cell holds 16 beads or so and a block's lanes have centres to serve;
+//                    the records in (frame, cell) order, the cell starts, one work item per kChunk centres of a non-empty cell
+//   k_cluster_keys   between its steps: gathers the selected beads of each frame as 32-byte records (position, bead index, label)
 //   k_cluster_init   parent[b, i] = i: every bead is the root of its own tree (uint32, bead-index space, one array per frame)
 //   k_cluster_link   the hot path.  A block owns one work item: up to kChunk centres of one cell, held in registers.  It stages
 //                    the partner cells (27, fewer at an open edge, every cell once where an axis has fewer than 3) through LDS in
@@ -50,12 +48,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_cluster.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_cells.hpp"
+#include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
 #include "gdyn_types.h"
 
@@ -63,14 +62,13 @@ using namespace gd;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr unsigned kChunk = kBlock;          // centres of one work item
+constexpr int kBlock = kCellBlock;
+constexpr unsigned kChunk = kCellChunk;      // centres of one work item
 constexpr unsigned kTile = 512;              // records of a partner tile
 constexpr unsigned kTilePad = 2;             // words between the arrays of a tile
 constexpr unsigned kTileWords = 4;           // x y z bead|label
 constexpr unsigned kUnroll = 4;              // partners of a lane whose positions are read together
 constexpr unsigned kLdsBins = 2048;          // size bins a block of k_cluster_summary counts in LDS
-constexpr double kCellSlack = 1e-9;          // cells are this much wider than the distance, against the rounding of the cell assignment
 
 enum : unsigned { kErrLink = 1u, kErrFlatten = 2u };      // bits of the error word
 
@@ -81,140 +79,8 @@ struct Rec {      // one selected bead of one frame
 };
 static_assert(sizeof(Rec) == 32, "a record is 32 bytes");
 
-struct Grid {      // the cells of one frame
-    double lo[3];            // open: the low corner of the bounding box; periodic: 0
-    double box[3];           // periodic: the periods
-    double inv_side[3];      // cells per unit length (0 along an axis of zero extent)
-    int n[3];                // cells per axis (>= 1)
-    unsigned cells;
-};
-
-struct Frames {      // first + k * stride, k < count
-    unsigned first, stride, count;
-};
-
-struct Space {
-    int periodic;
-    double box[3];
-    double cell_side;        // distance (1 + kCellSlack)
-};
-
-// ---- the helpers of gdyn_dcorr.hip, copied: its object stays as it is
-
-// an image of a double under which unsigned order is numeric order
-__device__ inline unsigned long long ordered(double x)
-{
-    unsigned long long const u = (unsigned long long)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ inline double unordered(unsigned long long o)
-{
-    return __longlong_as_double((long long)((o >> 63) ? (o & ~(1ull << 63)) : ~o));
-}
-
-__device__ inline double wave_min(double v)
-{
-    for (int m = 32; m; m >>= 1) v = fmin(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ inline double wave_max(double v)
-{
-    for (int m = 32; m; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    return v;
-}
-
-// the same over the block (every lane calls; sh: kBlock / 64 doubles)
-__device__ inline double block_min(double v, double *sh)
-{
-    v = wave_min(v);
-    __syncthreads();      // sh is free again
-    if (threadIdx.x % 64 == 0) sh[threadIdx.x / 64] = v;
-    __syncthreads();
-    for (int w = 0; w < kBlock / 64; w++) v = fmin(v, sh[w]);
-    return v;
-}
-__device__ inline double block_max(double v, double *sh)
-{
-    v = wave_max(v);
-    __syncthreads();
-    if (threadIdx.x % 64 == 0) sh[threadIdx.x / 64] = v;
-    __syncthreads();
-    for (int w = 0; w < kBlock / 64; w++) v = fmax(v, sh[w]);
-    return v;
-}
-
-__device__ inline double wrap(double x, double L)      // gdyn_rdf.hip
-{
-    double const w = fmod(x, L);
-    return w < 0.0 ? w + L : w;
-}
-
-__device__ inline int cell_of(double w, double inv_side, int n) { return (int)fmin(fmax(floor(w * inv_side), 0.0), (double)(n - 1)); }
-
-__device__ inline double min_image(double d, double L)     // DESIGN.md 7b; |d| <= L/2 already gives nearbyint(d/L) = 0
-{
-    return fabs(d) > 0.5 * L ? d - L * nearbyint(d / L) : d;
-}
-
-__device__ inline void load3(const void *__restrict__ xyz, int is_f64, size_t at, double p[3])
-{
-    for (int a = 0; a < 3; a++) p[a] = is_f64 ? static_cast<const double *>(xyz)[at + a] : (double)static_cast<const float *>(xyz)[at + a];
-}
-
-// bbox[o]: ordered images of (min x, y, z, max x, y, z), preset to (~0, ~0, ~0, 0, 0, 0); grid (a few blocks that stride over the selection, B)
-__global__ void __launch_bounds__(kBlock) k_cluster_bbox(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                         unsigned n_sel, Frames fr, unsigned o0, unsigned long long *__restrict__ bbox)
-{
-    __shared__ double sh[kBlock / 64];
-    unsigned const o = blockIdx.y;
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (unsigned k = blockIdx.x * kBlock + threadIdx.x; k < n_sel; k += gridDim.x * kBlock) {
-        double p[3];
-        load3(xyz, is_f64, ((size_t)(fr.first + (o0 + o) * fr.stride) * N + sel[k]) * 3, p);
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fmin(lo[a], p[a]);
-            hi[a] = fmax(hi[a], p[a]);
-        }
-    }
-    for (int a = 0; a < 3; a++) {
-        lo[a] = block_min(lo[a], sh);
-        hi[a] = block_max(hi[a], sh);
-    }
-    if (threadIdx.x == 0 && lo[0] <= hi[0])
-        for (int a = 0; a < 3; a++) {
-            atomicMin(&bbox[6 * (size_t)o + a], ordered(lo[a]));
-            atomicMax(&bbox[6 * (size_t)o + 3 + a], ordered(hi[a]));
-        }
-}
-
-__global__ void __launch_bounds__(kBlock) k_cluster_grid(const unsigned long long *__restrict__ bbox, unsigned B, Space sp, unsigned cap,
-                                                         Grid *__restrict__ grids)
-{
-    unsigned const o = blockIdx.x * kBlock + threadIdx.x;
-    if (o >= B) return;
-    Grid g;
-    double n[3], ext[3];
-    for (int a = 0; a < 3; a++) {
-        g.lo[a] = sp.periodic ? 0.0 : unordered(bbox[6 * (size_t)o + a]);
-        g.box[a] = sp.periodic ? sp.box[a] : 0.0;
-        ext[a] = sp.periodic ? sp.box[a] : unordered(bbox[6 * (size_t)o + 3 + a]) - g.lo[a];
-        n[a] = fmin(fmax(1.0, floor(ext[a] / sp.cell_side)), 1048576.0);
-    }
-    while (n[0] * n[1] * n[2] > (double)cap) {
-        int const a = (n[0] >= n[1] && n[0] >= n[2]) ? 0 : (n[1] >= n[2] ? 1 : 2);
-        n[a] = fmax(1.0, floor(n[a] * 0.9));
-    }
-    g.cells = 1;
-    for (int a = 0; a < 3; a++) {
-        g.n[a] = (int)n[a];
-        g.inv_side[a] = ext[a] > 0.0 ? n[a] / ext[a] : 0.0;
-        g.cells *= (unsigned)g.n[a];
-    }
-    grids[o] = g;
-}
-
 __global__ void __launch_bounds__(kBlock) k_cluster_keys(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                         const int *__restrict__ label, unsigned n_sel, Frames fr, unsigned o0, unsigned B,
+                                                         const int *__restrict__ label, unsigned n_sel, FrameSel fr, unsigned o0, unsigned B,
                                                          const Grid *__restrict__ grids, int periodic, unsigned cap, unsigned long long *__restrict__ keys,
                                                          unsigned *__restrict__ vals, Rec *__restrict__ grec)
 {
@@ -226,55 +92,9 @@ __global__ void __launch_bounds__(kBlock) k_cluster_keys(const void *__restrict_
     r.bead = bead;
     r.label = label ? label[bead] : 0;
     Grid const g = grids[o];
-    int c[3];
-    for (int a = 0; a < 3; a++) c[a] = cell_of(periodic ? wrap(r.p[a], g.box[a]) : r.p[a] - g.lo[a], g.inv_side[a], g.n[a]);
-    unsigned const cell = ((unsigned)c[2] * (unsigned)g.n[1] + (unsigned)c[1]) * (unsigned)g.n[0] + (unsigned)c[0];
-    keys[idx] = (unsigned long long)o * cap + cell;
+    keys[idx] = cell_key(g, r.p, periodic, o, cap);
     vals[idx] = (unsigned)idx;
     grec[idx] = r;
-}
-
-__global__ void __launch_bounds__(kBlock) k_cluster_sorted(const Rec *__restrict__ grec, const unsigned *__restrict__ vals, size_t n, Rec *__restrict__ srec)
-{
-    size_t const s = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s < n) srec[s] = grec[vals[s]];
-}
-
-// starts[t] = first sorted index whose key >= t, t in [0, count)
-__global__ void __launch_bounds__(kBlock) k_cluster_starts(const unsigned long long *__restrict__ keys, size_t n, size_t count, unsigned *__restrict__ starts)
-{
-    size_t const t = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= count) return;
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        size_t const mid = (lo + hi) / 2;
-        if (keys[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    starts[t] = (unsigned)lo;
-}
-
-// work items (cell slot, chunk of kChunk centres) of the non-empty cells; slots = B * cap
-__global__ void __launch_bounds__(kBlock) k_cluster_work(const unsigned *__restrict__ starts, size_t slots, uint2 *__restrict__ work, unsigned *__restrict__ n_work)
-{
-    size_t const t = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= slots) return;
-    unsigned const c = starts[t + 1] - starts[t];
-    if (!c) return;
-    unsigned const items = (c + kChunk - 1) / kChunk, base = atomicAdd(n_work, items);
-    for (unsigned k = 0; k < items; k++) work[base + k] = make_uint2((unsigned)t, k);
-}
-
-// the distinct cells of one axis that the neighbours of cell c lie in: first and count
-__device__ inline void axis_cells(int c, int n, int periodic, int &first, int &count)
-{
-    if (periodic) {
-        first = n < 3 ? 0 : (c + n - 1) % n;
-        count = n < 3 ? n : 3;
-    } else {
-        first = max(c - 1, 0);
-        count = min(c + 1, n - 1) - first + 1;
-    }
 }
 
 // ---- the union-find
@@ -484,49 +304,29 @@ struct gd_cluster : gd::handle {
     unsigned max_frames = 0;
     History hist;
     // selection: labels and link mask, which belong to hist.beads()
-    unsigned K = 1, n_sel = 0;
-    bool have_labels = false;
+    LabelSelection ls;
     uint64_t mask = 1;
-    dbuf<unsigned> sel;                 // the selected beads, ascending
-    dbuf<int> label_dev;
     // per batch
-    dbuf<unsigned long long> bbox;
-    dbuf<Grid> grids;
-    dbuf<Rec> grec, srec;
-    dbuf<unsigned long long> keys[2];
-    dbuf<unsigned> vals[2], starts, n_work, err;
-    dbuf<uint2> work;
-    dbuf<char> sort_tmp;
-    dbuf<unsigned> parent, members;
+    CellIndex<Rec> cells;
+    dbuf<unsigned> err, parent, members;
     dbuf<int> root;
     dbuf<unsigned long long> summary, sizes;
 
-    unsigned P() const { return K * (K + 1) / 2; }
+    unsigned P() const { return ls.K * (ls.K + 1) / 2; }
 };
 
 namespace {
 
 uint64_t all_classes(unsigned K) { return (1ull << (K * (K + 1) / 2)) - 1; }      // P <= 36
 
-int select_all(gd_cluster *h, unsigned N)
-{
-    std::vector<unsigned> all(N);
-    std::iota(all.begin(), all.end(), 0u);
-    dbuf<unsigned> dev;
-    HIPCHK(dev.upload(all.data(), N));
-    h->sel = std::move(dev);
-    h->n_sel = N;
-    h->K = 1;
-    h->have_labels = false;
-    h->mask = all_classes(1);
-    return GD_OK;
-}
-
 History::Rebind rebind(gd_cluster *h, const char *who)
 {
     return [h, who](unsigned n_beads) -> int {
         if (n_beads >= (1u << 31)) return fail(GD_EINVAL, "%s: %u beads (fewer than 2^31)", who, n_beads);
-        if (n_beads != h->hist.beads() || !h->sel.p) GDCHK(select_all(h, n_beads));      // labels and mask belonged to another N
+        if (n_beads != h->hist.beads() || !h->ls.sel.p) {      // labels and mask belonged to another N
+            GDCHK(h->ls.select_all(n_beads));
+            h->mask = all_classes(1);
+        }
         return GD_OK;
     };
 }
@@ -534,13 +334,11 @@ History::Rebind rebind(gd_cluster *h, const char *who)
 uint32_t frames_of(const gd_cluster *h, uint32_t first, uint32_t count, uint32_t stride)
 {
     if (!h || !h->hist.frames() || !stride) return 0;
-    if (count) return count;
-    if (first >= h->hist.frames()) return 0;
-    return (h->hist.frames() - first - 1) / stride + 1;
+    return (uint32_t)frames_served(frames_fit(h->hist.frames(), first, stride), count);
 }
 
 struct Call {      // what a batch needs of its call
-    Frames fr;
+    FrameSel fr;
     Space sp;
     double distance;
     unsigned n_bins, cap;
@@ -549,48 +347,23 @@ struct Call {      // what a batch needs of its call
 int run_batch(gd_cluster *h, const Call &c, unsigned o0, unsigned B, int32_t *root_out, uint64_t *summary_out, uint64_t *hist_out)
 {
     hipStream_t st = h->stream;
-    unsigned const n = h->n_sel, N = h->hist.beads();
+    CellIndex<Rec> &ci = h->cells;
+    unsigned const n = h->ls.n_sel, N = h->hist.beads();
     size_t const nb = (size_t)B * n, nB = (size_t)B * N, slots = (size_t)B * c.cap;
-    HIPCHK(h->bbox.ensure(6 * (size_t)B));
-    HIPCHK(h->grids.ensure(B));
-    HIPCHK(h->grec.ensure(nb));
-    HIPCHK(h->srec.ensure(nb));
-    for (int k = 0; k < 2; k++) {
-        HIPCHK(h->keys[k].ensure(nb));
-        HIPCHK(h->vals[k].ensure(nb));
-    }
-    HIPCHK(h->starts.ensure(slots + 1));
-    HIPCHK(h->work.ensure(nb / kChunk + std::min(nb, slots) + 1));
-    HIPCHK(h->n_work.ensure(1));
+    GDCHK(ci.room(B, n, c.cap));
     HIPCHK(h->err.ensure(1));
     HIPCHK(h->parent.ensure(nB));
     HIPCHK(h->members.ensure(nB));
     HIPCHK(h->root.ensure(nB));
     HIPCHK(h->summary.ensure(4 * (size_t)B));
     if (hist_out) HIPCHK(h->sizes.ensure((size_t)B * c.n_bins));
-    const int *label = h->have_labels ? h->label_dev.p : nullptr;
+    const int *label = h->ls.labels();
     int const is64 = h->hist.is_f64;
-    if (!c.sp.periodic) {
-        std::vector<unsigned long long> init(6 * (size_t)B);
-        for (size_t k = 0; k < init.size(); k++) init[k] = k % 6 < 3 ? ~0ull : 0ull;
-        HIPCHK(hipMemcpyAsync(h->bbox.p, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));      // init is about to go out of scope
-        hipLaunchKernelGGL(k_cluster_bbox, dim3(std::min(blocks_for(n, kBlock), 16u), B), dim3(kBlock), 0, st, h->hist.x(), is64, N, h->sel.p, n, c.fr, o0, h->bbox.p);
-    }
-    hipLaunchKernelGGL(k_cluster_grid, dim3(blocks_for(B, kBlock)), dim3(kBlock), 0, st, h->bbox.p, B, c.sp, c.cap, h->grids.p);
-    hipLaunchKernelGGL(k_cluster_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, N, h->sel.p, label, n, c.fr, o0, B, h->grids.p,
-                       c.sp.periodic, c.cap, h->keys[0].p, h->vals[0].p, h->grec.p);
+    GDCHK(ci.make_grids(st, h->hist.x(), is64, N, h->ls.sel.p, n, c.fr, o0, B, c.sp, c.cap));
+    hipLaunchKernelGGL(k_cluster_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, N, h->ls.sel.p, label, n, c.fr, o0, B, ci.grids.p,
+                       c.sp.periodic, c.cap, ci.keys[0].p, ci.vals[0].p, ci.grec.p);
     HIPCHK(hipGetLastError());
-    unsigned bits = 1;
-    while (bits < 64 && ((unsigned long long)slots >> bits)) bits++;
-    size_t tmp_bytes = 0;
-    HIPCHK(gd_sort_contacts(nullptr, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
-    HIPCHK(h->sort_tmp.ensure(tmp_bytes));
-    HIPCHK(gd_sort_contacts(h->sort_tmp.p, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
-    hipLaunchKernelGGL(k_cluster_sorted, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->grec.p, h->vals[1].p, nb, h->srec.p);
-    hipLaunchKernelGGL(k_cluster_starts, dim3(blocks_for(slots + 1, kBlock)), dim3(kBlock), 0, st, h->keys[1].p, nb, slots + 1, h->starts.p);
-    HIPCHK(hipMemsetAsync(h->n_work.p, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(k_cluster_work, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, st, h->starts.p, slots, h->work.p, h->n_work.p);
+    GDCHK(ci.sort(st, nb, slots));
     hipLaunchKernelGGL(k_cluster_init, dim3(blocks_for(nB, kBlock)), dim3(kBlock), 0, st, h->parent.p, N, nB);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(h->err.p, 0, sizeof(unsigned), st));
@@ -598,22 +371,20 @@ int run_batch(gd_cluster *h, const Call &c, unsigned o0, unsigned B, int32_t *ro
     HIPCHK(hipMemsetAsync(h->summary.p, 0, 4 * (size_t)B * sizeof(unsigned long long), st));
     if (hist_out) HIPCHK(hipMemsetAsync(h->sizes.p, 0, (size_t)B * c.n_bins * sizeof(unsigned long long), st));
     unsigned n_work = 0;
-    HIPCHK(hipMemcpyAsync(&n_work, h->n_work.p, sizeof n_work, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (n_work > h->work.n) return fail(GD_EHIP, "gd_cluster_components: %u work items for %zu", n_work, h->work.n);
+    GDCHK(ci.work_items("gd_cluster_components", st, &n_work));
     if (n_work) {
         LinkArgs a;
         a.d2 = c.distance * c.distance;
         a.mask = h->mask;
-        a.K = h->K;
+        a.K = h->ls.K;
         a.N = N;
         a.cap = c.cap;
         a.bound = (unsigned)std::min<uint64_t>(2 * (uint64_t)N + 2, 0xffffffffu);
         a.parent = h->parent.p;
         a.err = h->err.p;
         dim3 const grid(n_work), block(kBlock);
-        if (c.sp.periodic) hipLaunchKernelGGL(k_cluster_link<true>, grid, block, 0, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
-        else hipLaunchKernelGGL(k_cluster_link<false>, grid, block, 0, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+        if (c.sp.periodic) hipLaunchKernelGGL(k_cluster_link<true>, grid, block, 0, st, ci.srec.p, ci.starts.p, ci.work.p, ci.grids.p, a);
+        else hipLaunchKernelGGL(k_cluster_link<false>, grid, block, 0, st, ci.srec.p, ci.starts.p, ci.work.p, ci.grids.p, a);
         HIPCHK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_cluster_flatten, dim3(blocks_for(nB, kBlock)), dim3(kBlock), 0, st, h->parent.p, label, N, nB, h->root.p, h->err.p);
@@ -668,28 +439,8 @@ int gd_cluster_set_labels(gd_cluster *h, const int32_t *label, uint32_t n_labels
     const char *who = "gd_cluster_set_labels";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the labels are N values of its beads)", who);
-    if (!label) {
-        if (n_labels > 1) return fail(GD_EINVAL, "%s: %u labels without a label array", who, n_labels);
-        HIPCHK(hipSetDevice(h->device));
-        return select_all(h, h->hist.beads());
-    }
-    if (n_labels == 0 || n_labels > GD_CLUSTER_MAX_LABELS) return fail(GD_EINVAL, "%s: %u labels (1 to %d)", who, n_labels, GD_CLUSTER_MAX_LABELS);
-    std::vector<unsigned> chosen;
-    for (unsigned i = 0; i < h->hist.beads(); i++) {
-        if (label[i] < -1 || label[i] >= (int64_t)n_labels) return fail(GD_EINVAL, "%s: label[%u] = %d is not in [-1, %u)", who, i, label[i], n_labels);
-        if (label[i] >= 0) chosen.push_back(i);
-    }
-    HIPCHK(hipSetDevice(h->device));
-    dbuf<unsigned> sel;
-    dbuf<int> dev;
-    HIPCHK(sel.upload(chosen.data(), chosen.size()));
-    HIPCHK(dev.upload(label, h->hist.beads()));
-    h->sel = std::move(sel);
-    h->label_dev = std::move(dev);
-    h->n_sel = (unsigned)chosen.size();
-    h->K = n_labels;
-    h->have_labels = true;
-    h->mask = all_classes(n_labels);
+    GDCHK(h->ls.set(who, h->device, label, n_labels, GD_CLUSTER_MAX_LABELS, h->hist.beads()));
+    h->mask = all_classes(h->ls.K);
     return GD_OK;
 }
 
@@ -699,8 +450,8 @@ int gd_cluster_set_links(gd_cluster *h, uint64_t link_mask)
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the classes are those of its beads' labels)", who);
     if (!link_mask) return fail(GD_EINVAL, "%s: an empty mask links nothing", who);
-    if (link_mask & ~all_classes(h->K))
-        return fail(GD_EINVAL, "%s: mask 0x%llx has a bit at or past the %u classes of %u labels", who, (unsigned long long)link_mask, h->P(), h->K);
+    if (link_mask & ~all_classes(h->ls.K))
+        return fail(GD_EINVAL, "%s: mask 0x%llx has a bit at or past the %u classes of %u labels", who, (unsigned long long)link_mask, h->P(), h->ls.K);
     h->mask = link_mask;
     return GD_OK;
 }
@@ -728,10 +479,10 @@ int gd_cluster_components(gd_cluster *h, uint32_t first_frame, uint32_t n_frames
     if (!(distance > 0.0) || !std::isfinite(distance)) return fail(GD_EINVAL, "%s: distance %g is not positive and finite", who, distance);
     if (n_size_bins == 0 || n_size_bins > GD_CLUSTER_MAX_SIZE_BINS)
         return fail(GD_EINVAL, "%s: %u size bins (1 to %u)", who, n_size_bins, GD_CLUSTER_MAX_SIZE_BINS);
-    Frames const fr{first_frame, frame_stride, frames_of(h, first_frame, n_frames, frame_stride)};
+    FrameSel const fr{first_frame, frame_stride, frames_of(h, first_frame, n_frames, frame_stride)};
     if (!fr.count) return GD_OK;
     if (!summary_out) return fail(GD_EINVAL, "%s: NULL summary output", who);
-    unsigned const n = h->n_sel, N = h->hist.beads();
+    unsigned const n = h->ls.n_sel, N = h->hist.beads();
     if (n == 0) {      // nobody takes part
         if (root_out) std::fill(root_out, root_out + (size_t)fr.count * N, -1);
         std::memset(summary_out, 0, (size_t)fr.count * 4 * sizeof(uint64_t));

@@ -1,6 +1,6 @@
 // gdyn_dcorr.hip -- the spatial correlation of bead displacements (include/gdyn_dcorr.h): per origin frame, pair class and
 // distance bin, the number of pairs and the fixed-point sum of D_i . D_j.  Beyond the reference, which has no such analysis.
-// The pair rules are gdyn_rdf.hip's, the history is gd::History's (gdyn_history.hpp).
+// The pair rules and the cell grid are gdyn_cells.hpp's, the history is gd::History's (gdyn_history.hpp).
 //
 // Per call:
 //   k_dcorr_tmax   the largest squared displacement t2 of the selected beads over all origins of the call (integer atomicMax on the
@@ -8,14 +8,10 @@
 //                  any pair is walked.
 //   k_dcorr_self   per origin and label, the sum of llrint(t2 * 2^S) (LDS integer atomics per block, one global one per label).
 // Per batch of origins (max_frames_per_launch; no result depends on it):
-//   k_dcorr_bbox   open box: the bounding box of each origin frame's selected beads (block reduction, integer atomicMin / atomicMax
-//                  on an order-preserving image of the double)
-//   k_dcorr_grid   the cells of each origin: of side >= max_distance (1 + kCellSlack), of the periodic box or of the frame's own
-//                  bounding box, coarsened until an origin has at most `cap` cells.  An axis of zero extent has one cell.
-//   k_dcorr_disp   gathers the selected beads of each origin, computes D in fp64 and keys the bead (origin, cell)
-//   gd_sort_contacts, k_dcorr_sorted, k_dcorr_starts   as gdyn_rdf.hip: the beads in key order as 64-byte records (position, D,
-//                  label, chain) and the first sorted index of every cell
-//   k_dcorr_work   one work item per kChunk centres of a non-empty cell (their order is arbitrary: the sums are integers)
+//   gd::CellIndex  (gdyn_cells.hpp) the cells of each origin, of side >= max_distance (1 + kCellSlack) and at most `cap` a frame, the
+//                  beads in (origin, cell) order as 64-byte records (position, D, label, chain), the first sorted index of every cell
+//                  and one work item per kChunk centres of a non-empty cell (their order is arbitrary: the sums are integers)
+//   k_dcorr_disp   between its steps: gathers the selected beads of each origin, computes D in fp64 and keys the bead (origin, cell)
 //   k_dcorr_pairs  the hot path.  A block owns one work item: up to kChunk centres of one cell, held in registers.  Every bead of a
 //                  cell wants the same 27 cells (fewer at an open edge, every cell once where an axis has fewer than 3), so the
 //                  block stages them through LDS in tiles, one x-row span at a time, as seven arrays of 8-byte words (structure of
@@ -34,12 +30,13 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_dcorr.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_cells.hpp"
+#include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
 #include "gdyn_types.h"
 
@@ -47,12 +44,11 @@ using namespace gd;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr unsigned kChunk = kBlock;          // centres of one work item
+constexpr int kBlock = kCellBlock;
+constexpr unsigned kChunk = kCellChunk;      // centres of one work item
 constexpr unsigned kTilePad = 2;             // words between the arrays of a tile: staging writes 8 fields of 2 records per 16 lanes
 constexpr unsigned kTileWords = 7;           // x y z Dx Dy Dz label|chain
 constexpr unsigned kUnroll = 4;              // partners of a lane whose positions are read together
-constexpr double kCellSlack = 1e-9;          // cells are this much wider than max_distance, against the rounding of the cell assignment
 
 struct Rec {      // one selected bead of one origin
     double p[3];
@@ -62,84 +58,6 @@ struct Rec {      // one selected bead of one origin
     unsigned pad[2];
 };
 static_assert(sizeof(Rec) == 64, "a record is 64 bytes");
-
-struct Grid {      // the cells of one origin
-    double lo[3];            // open: the low corner of the bounding box; periodic: 0
-    double box[3];           // periodic: the periods
-    double inv_side[3];      // cells per unit length (0 along an axis of zero extent)
-    int n[3];                // cells per axis (>= 1)
-    unsigned cells;
-};
-
-struct Origins {      // first + k * stride, k < count
-    unsigned first, stride, count;
-};
-
-struct Space {
-    int periodic;
-    double box[3];
-    double cell_side;        // max_distance (1 + kCellSlack)
-};
-
-// an image of a double under which unsigned order is numeric order
-__device__ inline unsigned long long ordered(double x)
-{
-    unsigned long long const u = (unsigned long long)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ inline double unordered(unsigned long long o)
-{
-    return __longlong_as_double((long long)((o >> 63) ? (o & ~(1ull << 63)) : ~o));
-}
-
-__device__ inline double wave_min(double v)
-{
-    for (int m = 32; m; m >>= 1) v = fmin(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ inline double wave_max(double v)
-{
-    for (int m = 32; m; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    return v;
-}
-
-// the same over the block (every lane calls; sh: kBlock / 64 doubles)
-__device__ inline double block_min(double v, double *sh)
-{
-    v = wave_min(v);
-    __syncthreads();      // sh is free again
-    if (threadIdx.x % 64 == 0) sh[threadIdx.x / 64] = v;
-    __syncthreads();
-    for (int w = 0; w < kBlock / 64; w++) v = fmin(v, sh[w]);
-    return v;
-}
-__device__ inline double block_max(double v, double *sh)
-{
-    v = wave_max(v);
-    __syncthreads();
-    if (threadIdx.x % 64 == 0) sh[threadIdx.x / 64] = v;
-    __syncthreads();
-    for (int w = 0; w < kBlock / 64; w++) v = fmax(v, sh[w]);
-    return v;
-}
-
-__device__ inline double wrap(double x, double L)      // gdyn_rdf.hip
-{
-    double const w = fmod(x, L);
-    return w < 0.0 ? w + L : w;
-}
-
-__device__ inline int cell_of(double w, double inv_side, int n) { return (int)fmin(fmax(floor(w * inv_side), 0.0), (double)(n - 1)); }
-
-__device__ inline double min_image(double d, double L)     // DESIGN.md 7b; |d| <= L/2 already gives nearbyint(d/L) = 0
-{
-    return fabs(d) > 0.5 * L ? d - L * nearbyint(d / L) : d;
-}
-
-__device__ inline void load3(const void *__restrict__ xyz, int is_f64, size_t at, double p[3])
-{
-    for (int a = 0; a < 3; a++) p[a] = is_f64 ? static_cast<const double *>(xyz)[at + a] : (double)static_cast<const float *>(xyz)[at + a];
-}
 
 // t2 of selected bead k at origin o (and D)
 __device__ inline double disp_of(const void *__restrict__ xyz, int is_f64, unsigned N, unsigned bead, unsigned f, unsigned lag, double p[3], double d[3])
@@ -152,7 +70,7 @@ __device__ inline double disp_of(const void *__restrict__ xyz, int is_f64, unsig
 }
 
 __global__ void __launch_bounds__(kBlock) k_dcorr_tmax(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                       unsigned n_sel, unsigned lag, Origins og, unsigned long long *__restrict__ tmax)
+                                                       unsigned n_sel, unsigned lag, FrameSel og, unsigned long long *__restrict__ tmax)
 {
     __shared__ double sh[kBlock / 64];
     double t2 = 0.0;
@@ -167,7 +85,7 @@ __global__ void __launch_bounds__(kBlock) k_dcorr_tmax(const void *__restrict__ 
 
 // self_sum[o, label] += llrint(t2 * scale); grid (blocks over the selection, origins of this launch)
 __global__ void __launch_bounds__(kBlock) k_dcorr_self(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                       const int *__restrict__ label, unsigned n_sel, unsigned lag, Origins og, unsigned o0,
+                                                       const int *__restrict__ label, unsigned n_sel, unsigned lag, FrameSel og, unsigned o0,
                                                        double scale, unsigned K, unsigned long long *__restrict__ self_sum)
 {
     __shared__ unsigned long long acc[GD_DCORR_MAX_LABELS];
@@ -184,61 +102,9 @@ __global__ void __launch_bounds__(kBlock) k_dcorr_self(const void *__restrict__ 
     if (threadIdx.x < K && acc[threadIdx.x]) atomicAdd(&self_sum[(size_t)o * K + threadIdx.x], acc[threadIdx.x]);
 }
 
-// bbox[o]: ordered images of (min x, y, z, max x, y, z), preset to (~0, ~0, ~0, 0, 0, 0); grid (a few blocks that stride over the selection, B)
-__global__ void __launch_bounds__(kBlock) k_dcorr_bbox(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                       unsigned n_sel, Origins og, unsigned o0, unsigned long long *__restrict__ bbox)
-{
-    __shared__ double sh[kBlock / 64];
-    unsigned const o = blockIdx.y;
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (unsigned k = blockIdx.x * kBlock + threadIdx.x; k < n_sel; k += gridDim.x * kBlock) {
-        double p[3];
-        load3(xyz, is_f64, ((size_t)(og.first + (o0 + o) * og.stride) * N + sel[k]) * 3, p);
-        for (int a = 0; a < 3; a++) {
-            lo[a] = fmin(lo[a], p[a]);
-            hi[a] = fmax(hi[a], p[a]);
-        }
-    }
-    for (int a = 0; a < 3; a++) {
-        lo[a] = block_min(lo[a], sh);
-        hi[a] = block_max(hi[a], sh);
-    }
-    if (threadIdx.x == 0 && lo[0] <= hi[0])
-        for (int a = 0; a < 3; a++) {
-            atomicMin(&bbox[6 * (size_t)o + a], ordered(lo[a]));
-            atomicMax(&bbox[6 * (size_t)o + 3 + a], ordered(hi[a]));
-        }
-}
-
-__global__ void __launch_bounds__(kBlock) k_dcorr_grid(const unsigned long long *__restrict__ bbox, unsigned B, Space sp, unsigned cap,
-                                                       Grid *__restrict__ grids)
-{
-    unsigned const o = blockIdx.x * kBlock + threadIdx.x;
-    if (o >= B) return;
-    Grid g;
-    double n[3], ext[3];
-    for (int a = 0; a < 3; a++) {
-        g.lo[a] = sp.periodic ? 0.0 : unordered(bbox[6 * (size_t)o + a]);
-        g.box[a] = sp.periodic ? sp.box[a] : 0.0;
-        ext[a] = sp.periodic ? sp.box[a] : unordered(bbox[6 * (size_t)o + 3 + a]) - g.lo[a];
-        n[a] = fmin(fmax(1.0, floor(ext[a] / sp.cell_side)), 1048576.0);
-    }
-    while (n[0] * n[1] * n[2] > (double)cap) {
-        int const a = (n[0] >= n[1] && n[0] >= n[2]) ? 0 : (n[1] >= n[2] ? 1 : 2);
-        n[a] = fmax(1.0, floor(n[a] * 0.9));
-    }
-    g.cells = 1;
-    for (int a = 0; a < 3; a++) {
-        g.n[a] = (int)n[a];
-        g.inv_side[a] = ext[a] > 0.0 ? n[a] / ext[a] : 0.0;
-        g.cells *= (unsigned)g.n[a];
-    }
-    grids[o] = g;
-}
-
 __global__ void __launch_bounds__(kBlock) k_dcorr_disp(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
                                                        const int *__restrict__ label, const unsigned *__restrict__ chain, unsigned n_sel,
-                                                       unsigned lag, Origins og, unsigned o0, unsigned B, const Grid *__restrict__ grids, int periodic,
+                                                       unsigned lag, FrameSel og, unsigned o0, unsigned B, const Grid *__restrict__ grids, int periodic,
                                                        unsigned cap, unsigned long long *__restrict__ keys, unsigned *__restrict__ vals,
                                                        Rec *__restrict__ grec)
 {
@@ -251,55 +117,9 @@ __global__ void __launch_bounds__(kBlock) k_dcorr_disp(const void *__restrict__ 
     r.chain = chain ? chain[bead] : 0u;
     r.pad[0] = r.pad[1] = 0u;
     Grid const g = grids[o];
-    int c[3];
-    for (int a = 0; a < 3; a++) c[a] = cell_of(periodic ? wrap(r.p[a], g.box[a]) : r.p[a] - g.lo[a], g.inv_side[a], g.n[a]);
-    unsigned const cell = ((unsigned)c[2] * (unsigned)g.n[1] + (unsigned)c[1]) * (unsigned)g.n[0] + (unsigned)c[0];
-    keys[idx] = (unsigned long long)o * cap + cell;
+    keys[idx] = cell_key(g, r.p, periodic, o, cap);
     vals[idx] = (unsigned)idx;
     grec[idx] = r;
-}
-
-__global__ void __launch_bounds__(kBlock) k_dcorr_sorted(const Rec *__restrict__ grec, const unsigned *__restrict__ vals, size_t n, Rec *__restrict__ srec)
-{
-    size_t const s = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s < n) srec[s] = grec[vals[s]];
-}
-
-// starts[t] = first sorted index whose key >= t, t in [0, count)
-__global__ void __launch_bounds__(kBlock) k_dcorr_starts(const unsigned long long *__restrict__ keys, size_t n, size_t count, unsigned *__restrict__ starts)
-{
-    size_t const t = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= count) return;
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        size_t const mid = (lo + hi) / 2;
-        if (keys[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    starts[t] = (unsigned)lo;
-}
-
-// work items (cell slot, chunk of kChunk centres) of the non-empty cells; slots = B * cap
-__global__ void __launch_bounds__(kBlock) k_dcorr_work(const unsigned *__restrict__ starts, size_t slots, uint2 *__restrict__ work, unsigned *__restrict__ n_work)
-{
-    size_t const t = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= slots) return;
-    unsigned const c = starts[t + 1] - starts[t];
-    if (!c) return;
-    unsigned const items = (c + kChunk - 1) / kChunk, base = atomicAdd(n_work, items);
-    for (unsigned k = 0; k < items; k++) work[base + k] = make_uint2((unsigned)t, k);
-}
-
-// the distinct cells of one axis that the neighbours of cell c lie in: first and count
-__device__ inline void axis_cells(int c, int n, int periodic, int &first, int &count)
-{
-    if (periodic) {
-        first = n < 3 ? 0 : (c + n - 1) % n;
-        count = n < 3 ? n : 3;
-    } else {
-        first = max(c - 1, 0);
-        count = min(c + 1, n - 1) - first + 1;
-    }
 }
 
 struct PairArgs {
@@ -455,48 +275,25 @@ struct gd_dcorr : gd::handle {
     int lds_bytes = 64 * 1024;
     History hist;
     // selection: labels and chains, which belong to hist.beads()
-    unsigned K = 1, n_sel = 0;
-    bool have_labels = false, have_chains = false;
-    std::vector<uint64_t> members;      // beads per label
-    dbuf<unsigned> sel;                 // the selected beads, ascending
-    dbuf<int> label_dev;
+    LabelSelection ls;
+    bool have_chains = false;
     dbuf<unsigned> chain_dev;
     // per call
     dbuf<unsigned long long> tmax, self_sum;
     // per batch
-    dbuf<unsigned long long> bbox;
-    dbuf<Grid> grids;
-    dbuf<Rec> grec, srec;
-    dbuf<unsigned long long> keys[2];
-    dbuf<unsigned> vals[2], starts, n_work;
-    dbuf<uint2> work;
-    dbuf<char> sort_tmp;
+    CellIndex<Rec> cells;
     dbuf<unsigned long long> counts, sums;
 
-    unsigned P() const { return K * (K + 1) / 2 * (have_chains ? 2u : 1u); }
+    unsigned P() const { return ls.K * (ls.K + 1) / 2 * (have_chains ? 2u : 1u); }
 };
 
 namespace {
 
-int select_all(gd_dcorr *h, unsigned N)
-{
-    std::vector<unsigned> all(N);
-    std::iota(all.begin(), all.end(), 0u);
-    dbuf<unsigned> dev;
-    HIPCHK(dev.upload(all.data(), N));
-    h->sel = std::move(dev);
-    h->n_sel = N;
-    h->K = 1;
-    h->have_labels = false;
-    h->members.assign(1, N);
-    return GD_OK;
-}
-
 History::Rebind rebind(gd_dcorr *h)
 {
     return [h](unsigned n_beads) -> int {
-        if (n_beads != h->hist.beads() || !h->sel.p) {      // labels and chains belonged to another N
-            GDCHK(select_all(h, n_beads));
+        if (n_beads != h->hist.beads() || !h->ls.sel.p) {      // labels and chains belonged to another N
+            GDCHK(h->ls.select_all(n_beads));
             h->have_chains = false;
         }
         return GD_OK;
@@ -506,14 +303,12 @@ History::Rebind rebind(gd_dcorr *h)
 uint32_t origins_of(const gd_dcorr *h, uint32_t lag, uint32_t first, uint32_t n_origins, uint32_t stride)
 {
     if (!h || !h->hist.frames() || !stride || !lag) return 0;
-    if (n_origins) return n_origins;
-    if ((uint64_t)first + lag >= h->hist.frames()) return 0;
-    return (h->hist.frames() - lag - first - 1) / stride + 1;
+    return (uint32_t)frames_served(frames_fit(h->hist.frames(), first, stride, lag), n_origins);
 }
 
 struct Call {      // what a batch needs of its call
     unsigned lag;
-    Origins og;
+    FrameSel og;
     Space sp;
     double bin_width, md, scale;
     unsigned n_bins, cap;
@@ -524,59 +319,31 @@ struct Call {      // what a batch needs of its call
 int run_batch(gd_dcorr *h, const Call &c, unsigned o0, unsigned B, uint64_t *count_out, int64_t *sum_out)
 {
     hipStream_t st = h->stream;
-    unsigned const n = h->n_sel;
+    CellIndex<Rec> &ci = h->cells;
+    unsigned const n = h->ls.n_sel;
     size_t const nb = (size_t)B * n, slots = (size_t)B * c.cap, cells = (size_t)h->P() * c.n_bins;
-    HIPCHK(h->bbox.ensure(6 * (size_t)B));
-    HIPCHK(h->grids.ensure(B));
-    HIPCHK(h->grec.ensure(nb));
-    HIPCHK(h->srec.ensure(nb));
-    for (int k = 0; k < 2; k++) {
-        HIPCHK(h->keys[k].ensure(nb));
-        HIPCHK(h->vals[k].ensure(nb));
-    }
-    HIPCHK(h->starts.ensure(slots + 1));
-    HIPCHK(h->work.ensure(nb / kChunk + std::min(nb, slots) + 1));
-    HIPCHK(h->n_work.ensure(1));
+    GDCHK(ci.room(B, n, c.cap));
     HIPCHK(h->counts.ensure((size_t)B * cells));
     HIPCHK(h->sums.ensure((size_t)B * cells));
-    const int *label = h->have_labels ? h->label_dev.p : nullptr;
     const unsigned *chain = h->have_chains ? h->chain_dev.p : nullptr;
     int const is64 = h->hist.is_f64;
-    if (!c.sp.periodic) {
-        std::vector<unsigned long long> init(6 * (size_t)B);
-        for (size_t k = 0; k < init.size(); k++) init[k] = k % 6 < 3 ? ~0ull : 0ull;
-        HIPCHK(hipMemcpyAsync(h->bbox.p, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));      // init is about to go out of scope
-        hipLaunchKernelGGL(k_dcorr_bbox, dim3(std::min(blocks_for(n, kBlock), 16u), B), dim3(kBlock), 0, st, h->hist.x(), is64, h->hist.beads(), h->sel.p, n, c.og, o0, h->bbox.p);
-    }
-    hipLaunchKernelGGL(k_dcorr_grid, dim3(blocks_for(B, kBlock)), dim3(kBlock), 0, st, h->bbox.p, B, c.sp, c.cap, h->grids.p);
-    hipLaunchKernelGGL(k_dcorr_disp, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, h->hist.beads(), h->sel.p, label, chain, n, c.lag, c.og, o0, B,
-                       h->grids.p, c.sp.periodic, c.cap, h->keys[0].p, h->vals[0].p, h->grec.p);
+    GDCHK(ci.make_grids(st, h->hist.x(), is64, h->hist.beads(), h->ls.sel.p, n, c.og, o0, B, c.sp, c.cap));
+    hipLaunchKernelGGL(k_dcorr_disp, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, h->hist.beads(), h->ls.sel.p, h->ls.labels(), chain, n, c.lag, c.og,
+                       o0, B, ci.grids.p, c.sp.periodic, c.cap, ci.keys[0].p, ci.vals[0].p, ci.grec.p);
     HIPCHK(hipGetLastError());
-    unsigned bits = 1;
-    while (bits < 64 && ((unsigned long long)slots >> bits)) bits++;
-    size_t tmp_bytes = 0;
-    HIPCHK(gd_sort_contacts(nullptr, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
-    HIPCHK(h->sort_tmp.ensure(tmp_bytes));
-    HIPCHK(gd_sort_contacts(h->sort_tmp.p, &tmp_bytes, h->keys[0].p, h->keys[1].p, h->vals[0].p, h->vals[1].p, nb, bits, st));
-    hipLaunchKernelGGL(k_dcorr_sorted, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->grec.p, h->vals[1].p, nb, h->srec.p);
-    hipLaunchKernelGGL(k_dcorr_starts, dim3(blocks_for(slots + 1, kBlock)), dim3(kBlock), 0, st, h->keys[1].p, nb, slots + 1, h->starts.p);
-    HIPCHK(hipMemsetAsync(h->n_work.p, 0, sizeof(unsigned), st));
-    hipLaunchKernelGGL(k_dcorr_work, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, st, h->starts.p, slots, h->work.p, h->n_work.p);
+    GDCHK(ci.sort(st, nb, slots));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(h->counts.p, 0, (size_t)B * cells * sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(h->sums.p, 0, (size_t)B * cells * sizeof(unsigned long long), st));
     unsigned n_work = 0;
-    HIPCHK(hipMemcpyAsync(&n_work, h->n_work.p, sizeof n_work, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (n_work > h->work.n) return fail(GD_EHIP, "gd_dcorr_pairs: %u work items for %zu", n_work, h->work.n);
+    GDCHK(ci.work_items("gd_dcorr_pairs", st, &n_work));
     if (n_work) {
         PairArgs a;
         a.md2 = c.md * c.md;
         a.inv_bw = 1 / c.bin_width;
         a.scale = c.scale;
         a.n_bins = c.n_bins;
-        a.K = h->K;
+        a.K = h->ls.K;
         a.split = h->have_chains;
         a.cells = (unsigned)cells;
         a.tile = c.tile;
@@ -586,13 +353,13 @@ int run_batch(gd_dcorr *h, const Call &c, unsigned o0, unsigned B, uint64_t *cou
         size_t const shmem = tile_bytes(c.tile) + (c.lds ? cells * 12 : 0);
         dim3 const grid(n_work), block(kBlock);
         if (c.sp.periodic && c.lds)
-            hipLaunchKernelGGL((k_dcorr_pairs<true, true>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+            hipLaunchKernelGGL((k_dcorr_pairs<true, true>), grid, block, shmem, st, ci.srec.p, ci.starts.p, ci.work.p, ci.grids.p, a);
         else if (c.sp.periodic)
-            hipLaunchKernelGGL((k_dcorr_pairs<true, false>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+            hipLaunchKernelGGL((k_dcorr_pairs<true, false>), grid, block, shmem, st, ci.srec.p, ci.starts.p, ci.work.p, ci.grids.p, a);
         else if (c.lds)
-            hipLaunchKernelGGL((k_dcorr_pairs<false, true>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+            hipLaunchKernelGGL((k_dcorr_pairs<false, true>), grid, block, shmem, st, ci.srec.p, ci.starts.p, ci.work.p, ci.grids.p, a);
         else
-            hipLaunchKernelGGL((k_dcorr_pairs<false, false>), grid, block, shmem, st, h->srec.p, h->starts.p, h->work.p, h->grids.p, a);
+            hipLaunchKernelGGL((k_dcorr_pairs<false, false>), grid, block, shmem, st, ci.srec.p, ci.starts.p, ci.work.p, ci.grids.p, a);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(count_out, h->counts.p, (size_t)B * cells * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -643,33 +410,7 @@ int gd_dcorr_set_labels(gd_dcorr *h, const int32_t *label, uint32_t n_labels)
     const char *who = "gd_dcorr_set_labels";
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the labels are N values of its beads)", who);
-    if (!label) {
-        if (n_labels > 1) return fail(GD_EINVAL, "%s: %u labels without a label array", who, n_labels);
-        HIPCHK(hipSetDevice(h->device));
-        return select_all(h, h->hist.beads());
-    }
-    if (n_labels == 0 || n_labels > GD_DCORR_MAX_LABELS) return fail(GD_EINVAL, "%s: %u labels (1 to %d)", who, n_labels, GD_DCORR_MAX_LABELS);
-    std::vector<unsigned> chosen;
-    std::vector<uint64_t> members(n_labels, 0);
-    for (unsigned i = 0; i < h->hist.beads(); i++) {
-        if (label[i] < -1 || label[i] >= (int64_t)n_labels) return fail(GD_EINVAL, "%s: label[%u] = %d is not in [-1, %u)", who, i, label[i], n_labels);
-        if (label[i] >= 0) {
-            chosen.push_back(i);
-            members[label[i]]++;
-        }
-    }
-    HIPCHK(hipSetDevice(h->device));
-    dbuf<unsigned> sel;
-    dbuf<int> dev;
-    HIPCHK(sel.upload(chosen.data(), chosen.size()));
-    HIPCHK(dev.upload(label, h->hist.beads()));
-    h->sel = std::move(sel);
-    h->label_dev = std::move(dev);
-    h->n_sel = (unsigned)chosen.size();
-    h->K = n_labels;
-    h->have_labels = true;
-    h->members = std::move(members);
-    return GD_OK;
+    return h->ls.set(who, h->device, label, n_labels, GD_DCORR_MAX_LABELS, h->hist.beads());
 }
 
 int gd_dcorr_set_chains(gd_dcorr *h, const uint32_t *chain_id)
@@ -719,20 +460,20 @@ int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_
         return fail(GD_EINVAL, "%s: scale_bits %d (0: automatic, 1 to %d, or GD_DCORR_SCALE_UNIT)", who, scale_bits, GD_DCORR_MAX_SCALE_BITS);
     size_t const cells = (size_t)h->P() * n_bins;
     if (cells > (1u << 30)) return fail(GD_EINVAL, "%s: %u classes of %u bins exceed 2^30 cells", who, h->P(), n_bins);
-    Origins const og{first_origin, origin_stride, origins_of(h, lag, first_origin, n_origins, origin_stride)};
+    FrameSel const og{first_origin, origin_stride, origins_of(h, lag, first_origin, n_origins, origin_stride)};
     if (og.count && (!count_out || !sum_out)) return fail(GD_EINVAL, "%s: NULL output", who);
     if ((self_count_out == nullptr) != (self_sum_out == nullptr)) return fail(GD_EINVAL, "%s: one self output without the other", who);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    unsigned const n = h->n_sel, K = h->K;
-    const int *label = h->have_labels ? h->label_dev.p : nullptr;
+    unsigned const n = h->ls.n_sel, K = h->ls.K;
+    const int *label = h->ls.labels();
 
     // the largest t2 of the call, then the scale
     double M = 0.0;
     if (og.count && n) {
         HIPCHK(h->tmax.ensure(1));
         HIPCHK(hipMemsetAsync(h->tmax.p, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_dcorr_tmax, dim3(std::min(blocks_for((size_t)og.count * n, kBlock), 2048u)), dim3(kBlock), 0, st, h->hist.x(), (int)h->hist.is_f64, h->hist.beads(), h->sel.p, n, lag,
+        hipLaunchKernelGGL(k_dcorr_tmax, dim3(std::min(blocks_for((size_t)og.count * n, kBlock), 2048u)), dim3(kBlock), 0, st, h->hist.x(), (int)h->hist.is_f64, h->hist.beads(), h->ls.sel.p, n, lag,
                            og, h->tmax.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&M, h->tmax.p, sizeof M, hipMemcpyDeviceToHost, st));
@@ -752,14 +493,14 @@ int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_
 
     if (self_sum_out) {
         for (unsigned o = 0; o < og.count; o++)
-            for (unsigned l = 0; l < K; l++) self_count_out[(size_t)o * K + l] = h->members[l];
+            for (unsigned l = 0; l < K; l++) self_count_out[(size_t)o * K + l] = h->ls.members[l];
         std::memset(self_sum_out, 0, (size_t)og.count * K * sizeof(int64_t));
         if (n) {
             HIPCHK(h->self_sum.ensure((size_t)og.count * K));
             HIPCHK(hipMemsetAsync(h->self_sum.p, 0, (size_t)og.count * K * sizeof(unsigned long long), st));
             for (unsigned o0 = 0; o0 < og.count; o0 += 65535u)
                 hipLaunchKernelGGL(k_dcorr_self, dim3(blocks_for(n, kBlock), std::min(65535u, og.count - o0)), dim3(kBlock), 0, st, h->hist.x(), (int)h->hist.is_f64,
-                                   h->hist.beads(), h->sel.p, label, n, lag, og, o0, scale, K, h->self_sum.p);
+                                   h->hist.beads(), h->ls.sel.p, label, n, lag, og, o0, scale, K, h->self_sum.p);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(self_sum_out, h->self_sum.p, (size_t)og.count * K * sizeof(int64_t), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));

@@ -32,6 +32,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_dcov.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
 
 using namespace gd;
@@ -239,9 +240,7 @@ struct gd_dcov : gd::handle {
     unsigned knob = 0;
     int lds_bytes = 64 * 1024;
     History hist;
-    bool have_bins = false;        // false: every bead is its own bin
-    std::vector<uint32_t> bins;    // (B, 2) ranges of hist.beads(), the identity without bins of the caller's
-    dbuf<uint32_t> bins_dev;
+    BeadRanges bins;               // of hist.beads(); every bead its own bin without bins of the caller's
     // the preparation: columns == 0 without one
     unsigned columns = 0, K = 0, Bp = 0;
     dbuf<double> At;
@@ -249,47 +248,18 @@ struct gd_dcov : gd::handle {
     dbuf<double> mean, drift, rows_out;
     dbuf<uint2> tiles_dev;
     dbuf<double> partial, out;
-    // device times of the last calls (gd_dcov_last_times), between events on the handle's stream
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double stage1_ms = 0.0, product_ms = 0.0, merge_ms = 0.0;
+    StageTimer timer;              // gd_dcov_last_times: stage 1, product, merge
 
-    unsigned B() const { return (unsigned)(bins.size() / 2); }
-    ~gd_dcov()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    unsigned B() const { return bins.count(); }
 };
 
 namespace {
-
-// the bins of a handle become `ranges`; the device copy is replaced only when it has been made.  The preparation was of the old bins
-int install_bins(gd_dcov *h, std::vector<uint32_t> ranges, bool have)
-{
-    dbuf<uint32_t> dev;
-    HIPCHK(dev.upload(ranges.data(), ranges.size()));
-    h->bins_dev = std::move(dev);
-    h->bins = std::move(ranges);
-    h->have_bins = have;
-    h->columns = 0;
-    return GD_OK;
-}
-
-std::vector<uint32_t> identity_bins(unsigned N)
-{
-    std::vector<uint32_t> r(2 * (size_t)N);
-    for (unsigned i = 0; i < N; i++) {
-        r[2 * (size_t)i] = i;
-        r[2 * (size_t)i + 1] = i + 1;
-    }
-    return r;
-}
 
 History::Rebind rebind(gd_dcov *h)
 {
     return [h](unsigned n_beads) -> int {
         h->columns = 0;      // the preparation was of the last history
-        if (n_beads != h->hist.beads() || h->bins.empty()) GDCHK(install_bins(h, identity_bins(n_beads), false));      // bins belonged to another N
+        if (n_beads != h->hist.beads() || h->bins.host.empty()) GDCHK(h->bins.every_bead(n_beads));      // bins belonged to another N
         return GD_OK;
     };
 }
@@ -305,13 +275,10 @@ int gd_dcov_create(const gd_dcov_desc *desc, gd_dcov **out)
     if (int rc = gd::open("gd_dcov_create", desc, out)) return rc;
     (*out)->knob = desc->columns_per_stage;
     (*out)->lds_bytes = lds_budget(desc->device);
-    for (hipEvent_t &e : (*out)->ev) {
-        hipError_t const rc = hipEventCreate(&e);
-        if (rc != hipSuccess) {
-            gd::close(*out);
-            *out = nullptr;
-            return fail(GD_EHIP, "gd_dcov_create: hipEventCreate failed: %s", hipGetErrorString(rc));
-        }
+    if (hipError_t const rc = (*out)->timer.create()) {
+        gd::close(*out);
+        *out = nullptr;
+        return fail(GD_EHIP, "gd_dcov_create: hipEventCreate failed: %s", hipGetErrorString(rc));
     }
     return GD_OK;
 }
@@ -341,11 +308,9 @@ int gd_dcov_set_bins(gd_dcov *h, const uint32_t *ranges, uint32_t n_bins)
     const char *who = "gd_dcov_set_bins";
     if (!h || (!ranges && n_bins)) return fail(GD_EINVAL, "%s: NULL argument", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the bins are ranges of its beads)", who);
-    if (n_bins > (1u << 28)) return fail(GD_EINVAL, "%s: %u bins exceed 2^28", who, n_bins);
-    HIPCHK(hipSetDevice(h->device));
-    if (!n_bins) return install_bins(h, identity_bins(h->hist.beads()), false);
-    if (int rc = check_ranges(who, "bin", false, ranges, n_bins, h->hist.beads())) return rc;
-    return install_bins(h, std::vector<uint32_t>(ranges, ranges + 2 * (size_t)n_bins), true);
+    GDCHK(h->bins.set(who, "bin", h->device, ranges, n_bins, 28, h->hist.beads()));
+    h->columns = 0;      // the preparation was of the old bins
+    return GD_OK;
 }
 
 int gd_dcov_prepare(gd_dcov *h, uint32_t lag, uint32_t first, uint32_t stride, uint32_t count, int remove_drift)
@@ -356,14 +321,14 @@ int gd_dcov_prepare(gd_dcov *h, uint32_t lag, uint32_t first, uint32_t stride, u
     if (!F) return fail(GD_ESTATE, "%s: no history set", who);
     if (stride == 0) return fail(GD_EINVAL, "%s: stride 0", who);
     // the frames f with f + lag < F from `first` on, `stride` apart
-    uint64_t const fit = (uint64_t)first + lag < F ? ((uint64_t)F - 1 - lag - first) / stride + 1 : 0;
+    uint64_t const fit = frames_fit(F, first, stride, lag);
     if (count > fit || fit == 0)
         return fail(GD_EINVAL, "%s: %s from frame %u with stride %u and lag %u: %llu fit in %u frames", who, count ? "the origins asked for" : "no origin",
                     first, stride, lag, (unsigned long long)fit, F);
-    uint64_t const origins = count ? count : fit;
+    uint64_t const origins = frames_served(fit, count);
     if (origins > (1u << 28)) return fail(GD_EINVAL, "%s: %llu origins exceed 2^28", who, (unsigned long long)origins);
     if ((B + kBlock - 1) / kBlock > 65535) return fail(GD_EINVAL, "%s: %u bins exceed %u", who, B, 65535 * kBlock);      // a grid dimension of stage 1
-    if (int rc = check_ranges(who, "bin", false, h->bins.data(), B, h->hist.beads())) return rc;
+    GDCHK(h->bins.check(who, "bin", h->hist.beads()));
     HIPCHK(hipSetDevice(h->device));
 
     unsigned const columns = 3 * (unsigned)origins, K = (columns + 3) / 4 * 4, Bp = (B + kTile - 1) / kTile * kTile;
@@ -372,9 +337,9 @@ int gd_dcov_prepare(gd_dcov *h, uint32_t lag, uint32_t first, uint32_t stride, u
         (void)hipGetLastError();
         return fail(GD_ENOMEM, "%s: %u bins x %u columns do not fit on the device", who, B, columns);
     }
-    HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h->timer.mark(0, h->stream));
     HIPCHK(hipMemsetAsync(At.p, 0, (size_t)K * Bp * sizeof(double), h->stream));
-    RowArgs a{h->hist.x(), h->bins_dev.p, nullptr, At.p, h->hist.beads(), B, Bp, lag, first, stride, (unsigned)origins};
+    RowArgs a{h->hist.x(), h->bins.dev.p, nullptr, At.p, h->hist.beads(), B, Bp, lag, first, stride, (unsigned)origins};
     bool const f64 = h->hist.is_f64;
     if (lag == 0) {
         HIPCHK(h->mean.ensure(3 * a.N));
@@ -390,18 +355,16 @@ int gd_dcov_prepare(gd_dcov *h, uint32_t lag, uint32_t first, uint32_t stride, u
     HIPCHK(hipGetLastError());
     if (remove_drift) {
         uint64_t binned = 0;
-        for (unsigned b = 0; b < B; b++) binned += h->bins[2 * (size_t)b + 1] - h->bins[2 * (size_t)b];
+        for (unsigned b = 0; b < B; b++) binned += h->bins.length(b);
         HIPCHK(h->drift.ensure(columns));
         hipLaunchKernelGGL(k_dcov_drift, dim3(blocks_for(columns, kBlock)), dim3(kBlock), 0, h->stream, At.p, h->drift.p, columns, B, Bp, (double)binned);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_dcov_apply, grid, dim3(kBlock), 0, h->stream, At.p, h->drift.p, h->bins_dev.p, B, Bp);
+        hipLaunchKernelGGL(k_dcov_apply, grid, dim3(kBlock), 0, h->stream, At.p, h->drift.p, h->bins.dev.p, B, Bp);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h->timer.mark(1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->stage1_ms = ms;
+    HIPCHK(h->timer.between(0, 1, &h->timer.ms[0]));
     h->At = std::move(At);      // the last preparation's block goes with `At`
     h->columns = columns;
     h->K = K;
@@ -414,9 +377,7 @@ uint32_t gd_dcov_columns(const gd_dcov *h) { return h && h->hist.frames() ? h->c
 int gd_dcov_last_times(const gd_dcov *h, double *stage1_ms, double *product_ms, double *merge_ms)
 {
     if (!h) return fail(GD_EINVAL, "gd_dcov_last_times: NULL handle");
-    if (stage1_ms) *stage1_ms = h->stage1_ms;
-    if (product_ms) *product_ms = h->product_ms;
-    if (merge_ms) *merge_ms = h->merge_ms;
+    h->timer.report(stage1_ms, product_ms, merge_ms);
     return GD_OK;
 }
 
@@ -457,21 +418,9 @@ int gd_dcov_map(gd_dcov *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     HIPCHK(hipSetDevice(h->device));
 
     // the canonical tiles the rectangle touches, each once, and the diagonal tiles of its bins where their cells are asked for
-    unsigned const ti0 = row_first / kTile, ti1 = (row_first + n_rows - 1) / kTile, tj0 = col_first / kTile, tj1 = (col_first + n_cols - 1) / kTile;
-    std::vector<uint64_t> keys;
-    if (sum) {
-        keys.reserve((size_t)(ti1 - ti0 + 1) * (tj1 - tj0 + 1));
-        for (unsigned ti = ti0; ti <= ti1; ti++)
-            for (unsigned tj = tj0; tj <= tj1; tj++) keys.push_back((uint64_t)std::min(ti, tj) << 32 | std::max(ti, tj));
-    }
-    if (diag_rows)
-        for (unsigned t = ti0; t <= ti1; t++) keys.push_back((uint64_t)t << 32 | t);
-    if (diag_cols)
-        for (unsigned t = tj0; t <= tj1; t++) keys.push_back((uint64_t)t << 32 | t);
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    std::vector<uint2> tiles(keys.size());
-    for (size_t k = 0; k < keys.size(); k++) tiles[k] = make_uint2((unsigned)(keys[k] >> 32), (unsigned)keys[k]);
+    auto const cover = tile_cover(kTile, row_first, n_rows, col_first, n_cols, sum != nullptr, diag_rows != nullptr, diag_cols != nullptr);
+    std::vector<uint2> tiles(cover.size());
+    for (size_t k = 0; k < cover.size(); k++) tiles[k] = make_uint2(cover[k].first, cover[k].second);
 
     size_t const plane = (size_t)n_rows * n_cols;
     if (!tiles.empty()) {
@@ -492,28 +441,27 @@ int gd_dcov_map(gd_dcov *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
             (void)hipGetLastError();
             return fail(GD_ENOMEM, "%s: the partial sums of %zu tiles do not fit on the device", who, batch);
         }
-        double product_ms = 0.0, merge_ms = 0.0;
+        double product_ms = 0.0, merge_ms = 0.0, ms = 0.0;
         for (size_t t0 = 0; t0 < tiles.size(); t0 += batch) {
             unsigned const n = (unsigned)std::min(batch, tiles.size() - t0);
             a.tiles = h->tiles_dev.p + t0;
             a.partial = h->partial.p;
-            HIPCHK(hipEventRecord(h->ev[0], h->stream));
+            HIPCHK(h->timer.mark(0, h->stream));
             hipLaunchKernelGGL(k_dcov_product, dim3(n, ranges), dim3(kBlock), lds, h->stream, a);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(h->ev[1], h->stream));
+            HIPCHK(h->timer.mark(1, h->stream));
             MergeArgs m{h->partial.p, a.tiles, h->out.p, h->out.p + plane, h->out.p + plane + n_rows, ranges, n, B, row_first, n_rows, col_first, n_cols};
             hipLaunchKernelGGL(k_dcov_merge, dim3(n), dim3(kBlock), 0, h->stream, m);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(h->ev[2], h->stream));
-            HIPCHK(hipEventSynchronize(h->ev[2]));      // the events serve the next batch
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+            HIPCHK(h->timer.mark(2, h->stream));
+            HIPCHK(hipEventSynchronize(h->timer.ev[2]));      // the events serve the next batch
+            HIPCHK(h->timer.between(0, 1, &ms));
             product_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+            HIPCHK(h->timer.between(1, 2, &ms));
             merge_ms += ms;
         }
-        h->product_ms = product_ms;
-        h->merge_ms = merge_ms;
+        h->timer.ms[1] = product_ms;
+        h->timer.ms[2] = merge_ms;
         if (sum) HIPCHK(hipMemcpyAsync(sum, h->out.p, plane * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (diag_rows) HIPCHK(hipMemcpyAsync(diag_rows, h->out.p + plane, n_rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (diag_cols) HIPCHK(hipMemcpyAsync(diag_cols, h->out.p + plane + n_rows, n_cols * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -522,9 +470,9 @@ int gd_dcov_map(gd_dcov *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     if (count) {
         uint64_t const origins = h->columns / 3;
         for (unsigned i = 0; i < n_rows; i++) {
-            uint64_t const li = h->bins[2 * (size_t)(row_first + i) + 1] - h->bins[2 * (size_t)(row_first + i)];
+            uint64_t const li = h->bins.length(row_first + i);
             for (unsigned j = 0; j < n_cols; j++)
-                count[(size_t)i * n_cols + j] = origins * li * (h->bins[2 * (size_t)(col_first + j) + 1] - h->bins[2 * (size_t)(col_first + j)]);
+                count[(size_t)i * n_cols + j] = origins * li * h->bins.length(col_first + j);
         }
     }
     return GD_OK;

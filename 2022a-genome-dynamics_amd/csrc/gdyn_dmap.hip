@@ -33,6 +33,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_dmap.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
 
 using namespace gd;
@@ -245,43 +246,20 @@ struct gd_dmap : gd::handle {
     unsigned knob = 0;
     int lds_bytes = 64 * 1024;
     History hist;
-    bool have_bins = false;        // false: every bead is its own bin
-    std::vector<uint32_t> bins;    // (B, 2) ranges of hist.beads(), the identity without bins of the caller's
-    dbuf<uint32_t> bins_dev;
+    BeadRanges bins;               // of hist.beads(); every bead its own bin without bins of the caller's
     // per call
     dbuf<uint2> tiles_dev;
     dbuf<unsigned long long> partial, out;
 
-    unsigned B() const { return (unsigned)(bins.size() / 2); }
+    unsigned B() const { return bins.count(); }
 };
 
 namespace {
 
-// the bins of a handle become `ranges`; the device copy is replaced only when it has been made
-int install_bins(gd_dmap *h, std::vector<uint32_t> ranges, bool have)
-{
-    dbuf<uint32_t> dev;
-    HIPCHK(dev.upload(ranges.data(), ranges.size()));
-    h->bins_dev = std::move(dev);
-    h->bins = std::move(ranges);
-    h->have_bins = have;
-    return GD_OK;
-}
-
-std::vector<uint32_t> identity_bins(unsigned N)
-{
-    std::vector<uint32_t> r(2 * (size_t)N);
-    for (unsigned i = 0; i < N; i++) {
-        r[2 * (size_t)i] = i;
-        r[2 * (size_t)i + 1] = i + 1;
-    }
-    return r;
-}
-
 History::Rebind rebind(gd_dmap *h)
 {
     return [h](unsigned n_beads) -> int {
-        if (n_beads != h->hist.beads() || h->bins.empty()) GDCHK(install_bins(h, identity_bins(n_beads), false));      // bins belonged to another N
+        if (n_beads != h->hist.beads() || h->bins.host.empty()) GDCHK(h->bins.every_bead(n_beads));      // bins belonged to another N
         return GD_OK;
     };
 }
@@ -321,11 +299,7 @@ int gd_dmap_set_bins(gd_dmap *h, const uint32_t *ranges, uint32_t n_bins)
     const char *who = "gd_dmap_set_bins";
     if (!h || (!ranges && n_bins)) return fail(GD_EINVAL, "%s: NULL argument", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the bins are ranges of its beads)", who);
-    if (n_bins > (1u << 28)) return fail(GD_EINVAL, "%s: %u bins exceed 2^28", who, n_bins);
-    HIPCHK(hipSetDevice(h->device));
-    if (!n_bins) return install_bins(h, identity_bins(h->hist.beads()), false);
-    if (int rc = check_ranges(who, "bin", false, ranges, n_bins, h->hist.beads())) return rc;
-    return install_bins(h, std::vector<uint32_t>(ranges, ranges + 2 * (size_t)n_bins), true);
+    return h->bins.set(who, "bin", h->device, ranges, n_bins, 28, h->hist.beads());
 }
 
 int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_first, uint32_t n_cols, uint32_t first_frame, uint32_t n_frames,
@@ -348,19 +322,12 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     if (box)
         for (int k = 0; k < 3; k++)
             if (!(box[k] > 0.0) || !std::isfinite(box[k])) return fail(GD_EINVAL, "%s: box period %d is %g (positive and finite)", who, k, box[k]);
-    if (int rc = check_ranges(who, "bin", false, h->bins.data(), B, h->hist.beads())) return rc;
+    GDCHK(h->bins.check(who, "bin", h->hist.beads()));
     HIPCHK(hipSetDevice(h->device));
 
-    // the canonical tiles the rectangle touches, each once
-    unsigned const ti0 = row_first / kTB, ti1 = (row_first + n_rows - 1) / kTB, tj0 = col_first / kTB, tj1 = (col_first + n_cols - 1) / kTB;
-    std::vector<uint64_t> keys;
-    keys.reserve((size_t)(ti1 - ti0 + 1) * (tj1 - tj0 + 1));
-    for (unsigned ti = ti0; ti <= ti1; ti++)
-        for (unsigned tj = tj0; tj <= tj1; tj++) keys.push_back((uint64_t)std::min(ti, tj) << 32 | std::max(ti, tj));
-    std::sort(keys.begin(), keys.end());
-    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-    std::vector<uint2> tiles(keys.size());
-    for (size_t k = 0; k < keys.size(); k++) tiles[k] = make_uint2((unsigned)(keys[k] >> 32), (unsigned)keys[k]);
+    auto const cover = tile_cover(kTB, row_first, n_rows, col_first, n_cols);
+    std::vector<uint2> tiles(cover.size());
+    for (size_t k = 0; k < cover.size(); k++) tiles[k] = make_uint2(cover[k].first, cover[k].second);
 
     size_t const plane = (size_t)n_rows * n_cols;
     unsigned const nt = hits ? n_thresholds : 0;
@@ -371,10 +338,10 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     HIPCHK(h->tiles_dev.upload(tiles.data(), tiles.size()));
 
     unsigned longest = 1;
-    for (unsigned b = 0; b < B; b++) longest = std::max(longest, h->bins[2 * b + 1] - h->bins[2 * b]);
+    for (unsigned b = 0; b < B; b++) longest = std::max(longest, h->bins.length(b));
     MapArgs a{};
     a.x = h->hist.x();
-    a.bins = h->bins_dev.p;
+    a.bins = h->bins.dev.p;
     a.N = h->hist.beads();
     a.B = B;
     a.f0 = first_frame;
@@ -416,9 +383,9 @@ int gd_dmap_map(gd_dmap *h, uint32_t row_first, uint32_t n_rows, uint32_t col_fi
     if (nt) HIPCHK(hipMemcpyAsync(hits, h->out.p + 2 * plane, nt * plane * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (unsigned i = 0; i < n_rows; i++) {
-        uint64_t const li = h->bins[2 * (size_t)(row_first + i) + 1] - h->bins[2 * (size_t)(row_first + i)];
+        uint64_t const li = h->bins.length(row_first + i);
         for (unsigned j = 0; j < n_cols; j++) {
-            uint64_t const lj = h->bins[2 * (size_t)(col_first + j) + 1] - h->bins[2 * (size_t)(col_first + j)];
+            uint64_t const lj = h->bins.length(col_first + j);
             count[(size_t)i * n_cols + j] = (uint64_t)n_frames * (li * lj - (row_first + i == col_first + j ? li : 0));
         }
     }

@@ -30,6 +30,7 @@
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_gyr.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
 
 using namespace gd;
@@ -217,16 +218,9 @@ struct gd_gyr : gd::handle {
     // per call
     dbuf<double> partial, partial_sq, out;
     dbuf<Tile> tiles;
-    // device times of the last calls (gd_gyr_last_times), between events on the handle's stream
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double tensors_ms = 0.0, windows_ms = 0.0, merge_ms = 0.0;
+    StageTimer timer;                                     // gd_gyr_last_times: tensors, windows, merge
 
     unsigned S() const { return (unsigned)(segments.size() / 2); }
-    ~gd_gyr()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 namespace {
@@ -270,11 +264,11 @@ History::Rebind rebind(gd_gyr *h)
 int select_frames(const char *who, unsigned F, uint32_t first, uint32_t stride, uint32_t count, unsigned *K)
 {
     if (stride == 0) return fail(GD_EINVAL, "%s: stride 0", who);
-    uint64_t const fit = first < F ? ((uint64_t)F - 1 - first) / stride + 1 : 0;
+    uint64_t const fit = frames_fit(F, first, stride);
     if (count > fit || fit == 0)
         return fail(GD_EINVAL, "%s: %s from frame %u with stride %u: %llu fit in %u frames", who, count ? "the frames asked for" : "no frame", first, stride,
                     (unsigned long long)fit, F);
-    *K = count ? count : (unsigned)fit;
+    *K = (unsigned)frames_served(fit, count);
     return GD_OK;
 }
 
@@ -359,7 +353,7 @@ int run_windows(const char *who, gd_gyr *h, const uint32_t *windows, uint32_t n_
     a.first = first;
     a.stride = stride;
     a.n_windows = n_windows;
-    HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h->timer.mark(0, h->stream));
     // entries of windows that are not valid stay +0
     if (FRAMES) HIPCHK(hipMemsetAsync(h->out.p, 0, cells * sizeof(double), h->stream));
     else {
@@ -370,7 +364,7 @@ int run_windows(const char *who, gd_gyr *h, const uint32_t *windows, uint32_t n_
         unsigned const asked = h->frames_per_launch ? std::max(h->frames_per_launch / kRange, 1u) : 65535u;
         GDCHK(launch_windows<FRAMES>(h, a, windows, (unsigned)tiles.size(), ranges, std::min(asked, 65535u)));
     }
-    HIPCHK(hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h->timer.mark(1, h->stream));
     *K_out = K;
     *ranges_out = ranges;
     return GD_OK;
@@ -389,13 +383,10 @@ int gd_gyr_create(const gd_gyr_desc *desc, gd_gyr **out)
     if (int rc = gd::open(who, desc, out)) return rc;
     (*out)->tile = desc->beads_per_tile ? desc->beads_per_tile : kAutoTile;
     (*out)->frames_per_launch = desc->frames_per_launch;
-    for (hipEvent_t &e : (*out)->ev) {
-        hipError_t const rc = hipEventCreate(&e);
-        if (rc != hipSuccess) {
-            gd::close(*out);
-            *out = nullptr;
-            return fail(GD_EHIP, "%s: hipEventCreate failed: %s", who, hipGetErrorString(rc));
-        }
+    if (hipError_t const rc = (*out)->timer.create()) {
+        gd::close(*out);
+        *out = nullptr;
+        return fail(GD_EHIP, "%s: hipEventCreate failed: %s", who, hipGetErrorString(rc));
     }
     return GD_OK;
 }
@@ -462,7 +453,7 @@ int gd_gyr_tensors(gd_gyr *h, uint32_t first, uint32_t stride, uint32_t count, d
     double *const d_sum = h->out.p, *const d_centre = h->out.p + plane, *const d_moment = h->out.p + 2 * plane;
     PieceArgs a{h->hist.x(), h->pieces.p, d_centre, h->partial.p, h->hist.beads(), P, S, first, stride, 0};
     bool const f64 = h->hist.is_f64;
-    HIPCHK(hipEventRecord(h->ev[0], h->stream));
+    HIPCHK(h->timer.mark(0, h->stream));
     for (unsigned k0 = 0; k0 < K; k0 += per_launch) {
         unsigned const n = std::min(per_launch, K - k0);
         dim3 const grid((P + kRun - 1) / kRun, n);
@@ -481,14 +472,12 @@ int gd_gyr_tensors(gd_gyr *h, uint32_t first, uint32_t stride, uint32_t count, d
                            h->segments_dev.p, d_moment, (double *)nullptr, P, S, k0, n);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h->timer.mark(1, h->stream));
     if (centre_sum) HIPCHK(hipMemcpyAsync(centre_sum, d_sum, plane * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (centre) HIPCHK(hipMemcpyAsync(centre, d_centre, plane * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (moment) HIPCHK(hipMemcpyAsync(moment, d_moment, 2 * plane * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->tensors_ms = ms;
+    HIPCHK(h->timer.between(0, 1, &h->timer.ms[0]));
     return GD_OK;
 }
 
@@ -503,15 +492,12 @@ int gd_gyr_profile(gd_gyr *h, const uint32_t *windows, uint32_t n_windows, uint3
     hipLaunchKernelGGL(k_gyr_ranges, dim3(blocks_for(cells, kBlock)), dim3(kBlock), 0, h->stream, h->partial.p, h->partial_sq.p, h->out.p, h->out.p + cells, cells,
                        ranges);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h->timer.mark(2, h->stream));
     if (sum) HIPCHK(hipMemcpyAsync(sum, h->out.p, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (sum_sq) HIPCHK(hipMemcpyAsync(sum_sq, h->out.p + cells, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->windows_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
-    h->merge_ms = ms;
+    HIPCHK(h->timer.between(0, 1, &h->timer.ms[1]));
+    HIPCHK(h->timer.between(1, 2, &h->timer.ms[2]));
     if (count_out) {
         std::fill(count_out, count_out + cells, (uint64_t)0);
         for (uint32_t m = 0; m < n_windows; m++)
@@ -529,19 +515,15 @@ int gd_gyr_profile_frames(gd_gyr *h, uint32_t window, uint32_t first, uint32_t s
     GDCHK(run_windows<true>(who, h, &window, 1, first, stride, count, &K, &ranges));
     HIPCHK(hipMemcpyAsync(out, h->out.p, (size_t)K * h->hist.beads() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->windows_ms = ms;
-    h->merge_ms = 0.0;
+    HIPCHK(h->timer.between(0, 1, &h->timer.ms[1]));
+    h->timer.ms[2] = 0.0;
     return GD_OK;
 }
 
 int gd_gyr_last_times(const gd_gyr *h, double *tensors_ms, double *windows_ms, double *merge_ms)
 {
     if (!h) return fail(GD_EINVAL, "gd_gyr_last_times: NULL handle");
-    if (tensors_ms) *tensors_ms = h->tensors_ms;
-    if (windows_ms) *windows_ms = h->windows_ms;
-    if (merge_ms) *merge_ms = h->merge_ms;
+    h->timer.report(tensors_ms, windows_ms, merge_ms);
     return GD_OK;
 }
 

@@ -2,6 +2,8 @@
 //   k_history_first_bad  the lowest index of a non-finite coordinate (integer atomicMin, reached by no lane of a finite history)
 #include "gdyn_history.hpp"
 
+#include <numeric>
+
 using namespace gd;
 
 namespace {
@@ -94,6 +96,87 @@ int check_ranges(const char *who, const char *noun, bool empty_allowed, const ui
             return fail(GD_EINVAL, "%s: %s %u starts at %u, before %s %u ends (%u)", who, noun, c, r[2 * c], noun, c - 1, r[2 * c - 1]);
     }
     return GD_OK;
+}
+
+int check_labels(const char *who, const char *noun, const int32_t *label, unsigned N, unsigned K)
+{
+    if (!label) return K > 1 ? fail(GD_EINVAL, "%s: %u %ss without a %s array", who, K, noun, noun) : GD_OK;
+    for (unsigned i = 0; i < N; i++)
+        if (label[i] < -1 || label[i] >= (int64_t)K) return fail(GD_EINVAL, "%s: %s[%u] = %d is not in [-1, %u)", who, noun, i, label[i], K);
+    return GD_OK;
+}
+
+int LabelSelection::select_all(unsigned N)
+{
+    std::vector<unsigned> all(N);
+    std::iota(all.begin(), all.end(), 0u);
+    dbuf<unsigned> dev;
+    HIPCHK(dev.upload(all.data(), N));
+    sel = std::move(dev);
+    n_sel = N;
+    K = 1;
+    have_labels = false;
+    members.assign(1, N);
+    return GD_OK;
+}
+
+int LabelSelection::set(const char *who, int device, const int32_t *label, uint32_t n_labels, unsigned max_labels, unsigned N)
+{
+    if (!label) {
+        GDCHK(check_labels(who, "label", nullptr, N, n_labels));
+        HIPCHK(hipSetDevice(device));
+        return select_all(N);
+    }
+    if (n_labels == 0 || n_labels > max_labels) return fail(GD_EINVAL, "%s: %u labels (1 to %u)", who, n_labels, max_labels);
+    GDCHK(check_labels(who, "label", label, N, n_labels));
+    std::vector<unsigned> chosen;
+    std::vector<uint64_t> count(n_labels, 0);
+    for (unsigned i = 0; i < N; i++)
+        if (label[i] >= 0) {
+            chosen.push_back(i);
+            count[label[i]]++;
+        }
+    HIPCHK(hipSetDevice(device));
+    dbuf<unsigned> s;
+    dbuf<int> dev;
+    HIPCHK(s.upload(chosen.data(), chosen.size()));
+    HIPCHK(dev.upload(label, N));
+    sel = std::move(s);
+    label_dev = std::move(dev);
+    n_sel = (unsigned)chosen.size();
+    K = n_labels;
+    have_labels = true;
+    members = std::move(count);
+    return GD_OK;
+}
+
+int BeadRanges::install(std::vector<uint32_t> ranges, bool have_now)
+{
+    dbuf<uint32_t> d;
+    HIPCHK(d.upload(ranges.data(), ranges.size()));
+    dev = std::move(d);
+    host = std::move(ranges);
+    have = have_now;
+    return GD_OK;
+}
+
+int BeadRanges::every_bead(unsigned N)
+{
+    std::vector<uint32_t> r(2 * (size_t)N);
+    for (unsigned i = 0; i < N; i++) {
+        r[2 * (size_t)i] = i;
+        r[2 * (size_t)i + 1] = i + 1;
+    }
+    return install(std::move(r), false);
+}
+
+int BeadRanges::set(const char *who, const char *noun, int device, const uint32_t *ranges, uint32_t n, unsigned limit_bits, unsigned N)
+{
+    if (n > (1u << limit_bits)) return fail(GD_EINVAL, "%s: %u %ss exceed 2^%u", who, n, noun, limit_bits);
+    HIPCHK(hipSetDevice(device));
+    if (!n) return every_bead(N);
+    GDCHK(check_ranges(who, noun, false, ranges, n, N));
+    return install(std::vector<uint32_t>(ranges, ranges + 2 * (size_t)n), true);
 }
 
 }  // namespace gd

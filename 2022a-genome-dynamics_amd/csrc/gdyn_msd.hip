@@ -261,13 +261,6 @@ struct gd_msd : gd::handle {
 
 namespace {
 
-int check_groups(const char *who, const int32_t *group, unsigned N, unsigned G)
-{
-    for (unsigned i = 0; i < N; i++)
-        if (group[i] < -1 || group[i] >= (int64_t)G) return fail(GD_EINVAL, "%s: group[%u] = %d is not in [-1, %u)", who, i, group[i], G);
-    return GD_OK;
-}
-
 History::Rebind rebind(gd_msd *h)
 {
     return [h](unsigned n_beads) -> int {
@@ -422,14 +415,14 @@ int gd_msd_set_groups(gd_msd *h, const int32_t *group, uint32_t n_groups)
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the groups are N values of its beads)", who);
     if (!group) {
-        if (n_groups > 1) return fail(GD_EINVAL, "%s: %u groups without a group array", who, n_groups);
+        GDCHK(check_labels(who, "group", nullptr, h->hist.beads(), n_groups));
         h->have_groups = false;
         h->G = 1;
         h->group.clear();
         return GD_OK;
     }
     if (n_groups == 0 || n_groups > (1u << 20)) return fail(GD_EINVAL, "%s: %u groups (1 to 2^20)", who, n_groups);
-    if (int rc = check_groups(who, group, h->hist.beads(), n_groups)) return rc;
+    GDCHK(check_labels(who, "group", group, h->hist.beads(), n_groups));
     HIPCHK(hipSetDevice(h->device));
     dbuf<int32_t> dev;
     HIPCHK(dev.upload(group, h->hist.beads()));
@@ -465,7 +458,7 @@ int gd_msd_time(gd_msd *h, const uint32_t *lags, uint32_t n_lags, double *sum2, 
     std::vector<uint32_t> order;
     if (int rc = check_lags(who, "lag", lags, n_lags, order)) return rc;
     if (h->have_groups)
-        if (int rc = check_groups(who, h->group.data(), h->hist.beads(), h->G)) return rc;
+        if (int rc = check_labels(who, "group", h->group.data(), h->hist.beads(), h->G)) return rc;
     if (n_lags == 0) return GD_OK;
     HIPCHK(hipSetDevice(h->device));
     std::vector<double> s2((size_t)h->G * n_lags), s4((size_t)h->G * n_lags);

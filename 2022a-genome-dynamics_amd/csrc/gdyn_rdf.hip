@@ -29,6 +29,7 @@
 #include "../../include/gdyn_rdf.h"
 #include "gdyn_analysis.hpp"
 #include "gdyn_live.hpp"
+#include "gdyn_pair_rules.hpp"
 #include "gdyn_types.h"
 
 using namespace gd;
@@ -45,24 +46,6 @@ struct RdfGrid {
     int n[3];                // cells per axis (>= 1)
     unsigned cells;
 };
-
-// position in [0, L]: fmod is exact, so the error is at most half an ulp of L whatever the magnitude of x (unwrapped input)
-__device__ inline double wrap(double x, double L)
-{
-    double const w = fmod(x, L);
-    return w < 0.0 ? w + L : w;
-}
-
-__device__ inline int cell_of(double w, double inv_side, int n)
-{
-    return (int)fmin(fmax(floor(w * inv_side), 0.0), (double)(n - 1));      // (NaN -> 0)
-}
-
-__device__ inline double min_image(double d, double L)     // DESIGN.md 7b; |d| <= L/2 already gives nearbyint(d/L) = 0
-{
-#pragma clang fp contract(off)
-    return fabs(d) > 0.5 * L ? d - L * nearbyint(d / L) : d;
-}
 
 __global__ void __launch_bounds__(kBlock) k_rdf_keys(const void *__restrict__ xyz, int is_f64, unsigned n_points, const unsigned *__restrict__ sel,
                                                      unsigned n_sel, unsigned n_center, unsigned B, RdfGrid g, unsigned long long *__restrict__ keys,

@@ -338,13 +338,12 @@ int gd_sq_set_labels(gd_sq *h, const int32_t *label, uint32_t n_labels)
     if (!h) return fail(GD_EINVAL, "%s: NULL handle", who);
     if (!h->hist.frames()) return fail(GD_ESTATE, "%s: no history set (the labels are N values of its beads)", who);
     if (!label) {
-        if (n_labels > 1) return fail(GD_EINVAL, "%s: %u labels without a label array", who, n_labels);
+        GDCHK(check_labels(who, "label", nullptr, h->hist.beads(), n_labels));
         HIPCHK(hipSetDevice(h->device));
         return install_labels(h, nullptr, 1, h->hist.beads());
     }
     if (n_labels == 0 || n_labels > kMaxK) return fail(GD_EINVAL, "%s: %u labels (1 to %u)", who, n_labels, kMaxK);
-    for (unsigned i = 0; i < h->hist.beads(); i++)
-        if (label[i] < -1 || label[i] >= (int64_t)n_labels) return fail(GD_EINVAL, "%s: label[%u] = %d is not in [-1, %u)", who, i, label[i], n_labels);
+    GDCHK(check_labels(who, "label", label, h->hist.beads(), n_labels));
     HIPCHK(hipSetDevice(h->device));
     return install_labels(h, label, n_labels, h->hist.beads());
 }

@@ -22,7 +22,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._binding import GdynError, HistoryHandle, _u32, load_history_library
+from ._binding import GdynError, HistoryHandle, _u32, box3, load_history_library
 
 DCORR_ABI_VERSION = 1      # GD_DCORR_ABI_VERSION of the include/gdyn_dcorr.h this binding mirrors
 DCORR_SYMBOLS = ["gd_dcorr_abi_version", "gd_dcorr_create", "gd_dcorr_destroy", "gd_dcorr_set_history", "gd_dcorr_set_history_live",
@@ -163,16 +163,7 @@ class Dcorr(HistoryHandle):
     def set_labels(self, label, n_labels=None):
         """label: (N,) integers in [-1, n_labels), -1 for a bead that takes no part; None: one label of all beads.
         n_labels=None: the largest label + 1."""
-        if label is None:
-            self._check(self.dll.gd_dcorr_set_labels(self._h, None, 1))
-            self.n_labels = 1
-            return
-        l = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
-        if self.shape is not None and len(l) != self.shape[1]:
-            raise ValueError(f"label must have one entry per bead ({self.shape[1]}), got {len(l)}")
-        K = int(n_labels) if n_labels is not None else max(int(l.max()) + 1, 1) if len(l) else 1
-        self._check(self.dll.gd_dcorr_set_labels(self._h, l.ctypes.data, K))
-        self.n_labels = K
+        self.n_labels, _ = self._set_labels(label, n_labels)
 
     def set_chains(self, chain):
         """chain: (N,) non-negative integers below 2^32, the chain of every bead; None: classes are not split by chain."""
@@ -195,7 +186,7 @@ class Dcorr(HistoryHandle):
         """The tables of one lag: Pairs(count (O, P, n_bins) uint64, sum (O, P, n_bins) int64, self_count (O, K) uint64,
         self_sum (O, K) int64, scale_bits).  box: a period or three, None: open.  scale_bits 0: automatic, SCALE_UNIT: quantum 1.
         Origins first_origin + k origin_stride; n_origins 0: all that fit."""
-        b = None if box is None else (C.c_double * 3)(*np.broadcast_to(np.asarray(box, dtype=np.float64), (3,)))
+        box_at, _keep = box3(box)
         nb = int(self.dll.gd_dcorr_bins(float(bin_width), float(max_distance)))
         O = int(self.dll.gd_dcorr_origins(self._h, int(lag), int(first_origin), int(n_origins), int(origin_stride)))
         P, K = self.n_classes, self.n_labels
@@ -203,7 +194,7 @@ class Dcorr(HistoryHandle):
         self_count, self_sum = np.zeros((O, K), np.uint64), np.zeros((O, K), np.int64)
         used = C.c_int32(0)
         self._check(self.dll.gd_dcorr_pairs(self._h, int(lag), int(first_origin), int(n_origins), int(origin_stride),
-                                            None if b is None else C.addressof(b), float(bin_width), float(max_distance), int(scale_bits), C.byref(used),
+                                            box_at, float(bin_width), float(max_distance), int(scale_bits), C.byref(used),
                                             count.ctypes.data, total.ctypes.data, self_count.ctypes.data, self_sum.ctypes.data))
         return Pairs(count[:, :, :nb], total[:, :, :nb], self_count, self_sum, int(used.value))
 

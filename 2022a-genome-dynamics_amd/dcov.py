@@ -21,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._binding import GdynError, HistoryHandle, _ratio, _u32, load_history_library
+from ._binding import GdynError, HistoryHandle, _ratio, load_history_library
 from .dmap import Dmap
 
 DCOV_ABI_VERSION = 1      # GD_DCOV_ABI_VERSION of the include/gdyn_dcov.h this binding mirrors
@@ -72,22 +72,13 @@ class Dcov(HistoryHandle):
 
     def last_times(self):
         """Device milliseconds of the last prepare (stage 1) and of the product and the merge kernel of the last map."""
-        t = [C.c_double() for _ in range(3)]
-        self._check(self.dll.gd_dcov_last_times(self._h, *[C.byref(v) for v in t]))
-        return {"stage1_ms": t[0].value, "product_ms": t[1].value, "merge_ms": t[2].value}
+        return self._last_times("stage1_ms", "product_ms", "merge_ms")
 
     def set_bins(self, ranges):
         """ranges: (B, 2) [start, end) bead ranges, ascending, non-empty and not overlapping; None: every bead is its own bin.
         The preparation is dropped."""
-        if ranges is None:
-            self._check(self.dll.gd_dcov_set_bins(self._h, None, 0))
-            self.n_bins = (self.shape or (0, 0))[1]
-            return
-        r = _u32(ranges, "bin ranges").reshape(-1, 2)
-        if not len(r):
-            raise ValueError("no bins (None makes every bead its own bin)")
-        self._check(self.dll.gd_dcov_set_bins(self._h, r.ctypes.data, len(r)))
-        self.n_bins = len(r)
+        every_bead = range((self.shape or (0, 0))[1])
+        self.n_bins = len(self._set_ranges(self.dll.gd_dcov_set_bins, ranges, "bin ranges", "no bins (None makes every bead its own bin)", every_bead))
 
     def prepare(self, lag, first=0, stride=1, count=0, remove_drift=False):
         """Builds the rows on the device.  lag >= 1: the displacements over ``lag`` frames from the origins first + k stride, k < count

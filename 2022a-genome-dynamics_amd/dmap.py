@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._binding import GdynError, HistoryHandle, _ratio, _u32, load_history_library
+from ._binding import GdynError, HistoryHandle, _ratio, load_history_library
 
 DMAP_ABI_VERSION = 1      # GD_DMAP_ABI_VERSION of the include/gdyn_dmap.h this binding mirrors
 DMAP_MAX_THRESHOLDS = 4   # GD_DMAP_MAX_THRESHOLDS
@@ -58,15 +58,8 @@ class Dmap(HistoryHandle):
 
     def set_bins(self, ranges):
         """ranges: (B, 2) [start, end) bead ranges, ascending, non-empty and not overlapping; None: every bead is its own bin."""
-        if ranges is None:
-            self._check(self.dll.gd_dmap_set_bins(self._h, None, 0))
-            self.n_bins = (self.shape or (0, 0))[1]
-            return
-        r = _u32(ranges, "bin ranges").reshape(-1, 2)
-        if not len(r):
-            raise ValueError("no bins (None makes every bead its own bin)")
-        self._check(self.dll.gd_dmap_set_bins(self._h, r.ctypes.data, len(r)))
-        self.n_bins = len(r)
+        every_bead = range((self.shape or (0, 0))[1])
+        self.n_bins = len(self._set_ranges(self.dll.gd_dmap_set_bins, ranges, "bin ranges", "no bins (None makes every bead its own bin)", every_bead))
 
     @staticmethod
     def bins_from_chains(chain_ranges, rate):

@@ -78,27 +78,19 @@ class Gyration(HistoryHandle):
 
     def last_times(self):
         """Device milliseconds of the last tensors call, and of the window kernel and the merge kernel of the last profile call."""
-        t = [C.c_double() for _ in range(3)]
-        self._check(self.dll.gd_gyr_last_times(self._h, *[C.byref(v) for v in t]))
-        return {"tensors_ms": t[0].value, "windows_ms": t[1].value, "merge_ms": t[2].value}
+        return self._last_times("tensors_ms", "windows_ms", "merge_ms")
 
-    def _set_ranges(self, call, ranges, what):
-        if ranges is None:
-            self._check(call(self._h, None, 0))
-            return np.array([[0, (self.shape or (0, 0))[1]]], np.uint32)
-        r = _u32(ranges, what).reshape(-1, 2)
-        if not len(r):
-            raise ValueError(f"no {what} (None makes one range of all beads)")
-        self._check(call(self._h, r.ctypes.data, len(r)))
-        return r.copy()
+    def _bead_ranges(self, call, ranges, what):
+        whole = np.array([[0, (self.shape or (0, 0))[1]]], np.uint32)
+        return self._set_ranges(call, ranges, what, f"no {what} (None makes one range of all beads)", whole).copy()
 
     def set_segments(self, ranges):
         """ranges: (S, 2) [start, end) bead ranges, ascending, non-empty and not overlapping; None: one segment of all beads."""
-        self.segments = self._set_ranges(self.dll.gd_gyr_set_segments, ranges, "segment ranges")
+        self.segments = self._bead_ranges(self.dll.gd_gyr_set_segments, ranges, "segment ranges")
 
     def set_chains(self, ranges):
         """ranges: (C, 2) [start, end) bead ranges, ascending and not overlapping, empty ones allowed; None: one chain of all beads."""
-        self.chains = self._set_ranges(self.dll.gd_gyr_set_chains, ranges, "chain ranges")
+        self.chains = self._bead_ranges(self.dll.gd_gyr_set_chains, ranges, "chain ranges")
 
     def selected(self, first=0, stride=1, count=0):
         """The frames a call with this selection takes (count 0: all from ``first`` on, ``stride`` apart)."""

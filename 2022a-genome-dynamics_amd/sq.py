@@ -71,16 +71,11 @@ class Sq(HistoryHandle):
     def set_labels(self, label, n_labels=None):
         """label: (N,) integers in [-1, n_labels), -1 for a bead that takes no part; None: one label of all beads.
         n_labels=None: the largest label + 1."""
-        if label is None:
-            self._check(self.dll.gd_sq_set_labels(self._h, None, 1))
+        K, l = self._set_labels(label, n_labels)
+        if l is None:
             self._beads_changed(self.shape[1])
-            return
-        l = np.ascontiguousarray(label, dtype=np.int32).reshape(-1)
-        if self.shape is not None and len(l) != self.shape[1]:
-            raise ValueError(f"label must have one entry per bead ({self.shape[1]}), got {len(l)}")
-        K = int(n_labels) if n_labels is not None else max(int(l.max()) + 1, 1) if len(l) else 1
-        self._check(self.dll.gd_sq_set_labels(self._h, l.ctypes.data, K))
-        self.n_labels, self.label_sizes = K, np.bincount(l[l >= 0], minlength=K).astype(np.uint64)
+        else:
+            self.n_labels, self.label_sizes = K, np.bincount(l[l >= 0], minlength=K).astype(np.uint64)
 
     def set_vectors(self, q):
         """q: (Q, 3) finite wave vectors, the zero vector allowed."""
