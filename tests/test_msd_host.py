@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import msd_edge_cases as ec
 import msd_restatement as mr
 from conftest import ROOT
 
@@ -111,6 +112,33 @@ def test_restatement_against_closed_forms():
     c2, _, cn = mr.chain(frames, [(0, 1000)], seps)
     assert np.array_equal(c2[0], [2 * (1000 - s) * 6 * s * s if s < 1000 else 0 for s in seps])
     assert np.array_equal(cn[0], [2 * max(0, 1000 - s) for s in seps])
+
+
+def test_edge_cases_hold_their_restatement_and_their_shapes():
+    """The reference of test_msd_edges_gpu.py is itself held: the restatement of every integer case equals int64 sums of the same
+    terms and the closed-form counts, in both precisions, and every case reaches the path of gdyn_msd.hip it is there for."""
+    ec.assert_shape_facts()
+    for name in ec.CASES:
+        sum2, sum4, count = ec.int_sums(name)
+        assert 0 < sum2.max() < 2 ** 53 and 0 < sum4.max() < 2 ** 53
+        for dtype in ec.DTYPES:
+            c = ec.case(name, "integer", dtype)
+            assert c.x.dtype == dtype and np.array_equal(c.x, ec.case(name, "integer", np.float64).x)
+            want2, want4, wantn = c.want
+            assert want2.dtype == want4.dtype == np.float64 and wantn.dtype == np.uint64
+            assert np.array_equal(want2, sum2) and np.array_equal(want4, sum4) and np.array_equal(wantn.astype(np.int64), count), name
+            assert ((sum2 == 0) == (count == 0)).all() and ((sum4 == 0) == (count == 0)).all(), name
+        assert ec.case(name, "walk", np.float32).x.shape == ec.case(name, "integer", np.float32).x.shape
+    # what the issue of these cases states of them
+    b, d = ec.case("B", "integer", np.float64), ec.case("D", "integer", np.float64)
+    assert b.want[2][2, -4:].tolist() == [171, 152, 19, 0] and (b.want[2][0] == 0).all()
+    assert d.want[2][:, 0].tolist() == [160, 0, 1320, 40, 1560, 1560, 1600]
+    a = ec.case("A", "integer", np.float32)
+    for lag in a.per_bead:      # per bead: the columns of x, summed as integers
+        x = a.x.astype(np.int64)
+        t2 = ((x[lag:] - x[:-lag]) ** 2).sum(axis=-1)
+        m2, m4 = ec.per_bead("A", "integer", np.float32, lag)
+        assert np.array_equal(m2, t2.sum(axis=0)) and np.array_equal(m4, (t2 * t2).sum(axis=0))
 
 
 # ---- the program
