@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap, sq, cluster, dcov, gyr, dwell) share: loading libgdyn with a check of
+"""What the ctypes bindings of the device analyses (flow, rdf, lamina, cmap, hic, msd, dcorr, dmap, sq, cluster, dcov, gyr, dwell, vanhove) share: loading libgdyn with a check of
 one module's symbols and ABI version, the life cycle of a ``gd_<x>`` handle, the normalisation of frames, and the trajectory history
-that the msd, dcorr, dmap, sq, cluster, dcov, gyr and dwell handles hold, with the bodies of their label, range and timing methods."""
+that the msd, dcorr, dmap, sq, cluster, dcov, gyr, dwell and vanhove handles hold, with the bodies of their label, range and timing methods."""
 from __future__ import annotations
 
 import ctypes as C
