@@ -1,22 +1,20 @@
 // gdyn_cluster.hip -- the connected clusters of a history (include/gdyn_cluster.h): per frame, the connected components of the
 // graph whose edges are the pairs of selected beads closer than a distance, as the smallest bead index of every bead's component,
 // with the number of clusters, the largest, the sum of squared sizes and the histogram of sizes.  Beyond the reference, which has
-// no such analysis.  The pair rules and the cell grid are gdyn_cells.hpp's, the walk over the grid is that of gdyn_dcorr.hip, the
+// no such analysis.  The pair rules, the cell grid and the walk over it are gdyn_cells.hpp's, which gdyn_dcorr.hip shares, the
 // history is gd::History's (gdyn_history.hpp).  Unlike every other analysis here the result is not a sum of independent terms but a fixed point: a
 // concurrent union-find over the pair graph.
 //
 // Per batch of frames (max_frames_per_launch; no result depends on it):
 //   gd::CellIndex    (gdyn_cells.hpp) as in gdyn_dcorr.hip: cells of side >= distance (1 + kCellSlack), coarsened until a frame has
 //                    at most `cap` = n / 16 of them, so that a cell holds 16 beads or so and a block's lanes have centres to serve;
-//                    the records in (frame, cell) order, the cell starts, one work item per kChunk centres of a non-empty cell
-//   k_cluster_keys   between its steps: gathers the selected beads of each frame as 32-byte records (position, bead index, label)
+//                    the records in (frame, cell) order, the cell starts, one work item per kCellChunk centres of a non-empty cell
+//   PositionFill     (gdyn_cells.hpp) between its steps: the selected beads of each frame as 32-byte records (position, bead, label)
 //   k_cluster_init   parent[b, i] = i: every bead is the root of its own tree (uint32, bead-index space, one array per frame)
-//   k_cluster_link   the hot path.  A block owns one work item: up to kChunk centres of one cell, held in registers.  It stages
-//                    the partner cells (27, fewer at an open edge, every cell once where an axis has fewer than 3) through LDS in
-//                    tiles of kTile records as four arrays of 8-byte words (x y z and bead|label).  Lane = (centre, slice) as in
-//                    k_dcorr_pairs; only partners later in sorted order count, so every unordered pair is seen once.  A pair
-//                    inside the cutoff whose class may link is an edge, and the lane calls unite() on its frame's parent array,
-//                    unless both ends already report the same parent.
+//   k_cluster_link   the hot path: the tile walk of gdyn_cells.hpp in tiles of kTile records in static LDS (x y z and bead|label as
+//                    four arrays of 8-byte words); only partners later in sorted order count, so every unordered pair is seen once.
+//                    The body: a pair inside the cutoff whose class may link is an edge, and the lane calls unite() on its frame's
+//                    parent array, unless both ends already report the same parent.
 //   k_cluster_flatten   a launch of its own, so that every write of the link kernel is visible to it: root[b, i] = the root of
 //                    bead i's tree (-1 for a bead that is not selected).  parent is read-only here and root is another array.
 //   k_cluster_sizes  members per root (uint32 integer atomics; the lanes of a wave that count for one root add once, for the root of
@@ -63,9 +61,7 @@ using namespace gd;
 namespace {
 
 constexpr int kBlock = kCellBlock;
-constexpr unsigned kChunk = kCellChunk;      // centres of one work item
 constexpr unsigned kTile = 512;              // records of a partner tile
-constexpr unsigned kTilePad = 2;             // words between the arrays of a tile
 constexpr unsigned kTileWords = 4;           // x y z bead|label
 constexpr unsigned kUnroll = 4;              // partners of a lane whose positions are read together
 constexpr unsigned kLdsBins = 2048;          // size bins a block of k_cluster_summary counts in LDS
@@ -78,24 +74,6 @@ struct Rec {      // one selected bead of one frame
     int label;
 };
 static_assert(sizeof(Rec) == 32, "a record is 32 bytes");
-
-__global__ void __launch_bounds__(kBlock) k_cluster_keys(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                         const int *__restrict__ label, unsigned n_sel, FrameSel fr, unsigned o0, unsigned B,
-                                                         const Grid *__restrict__ grids, int periodic, unsigned cap, unsigned long long *__restrict__ keys,
-                                                         unsigned *__restrict__ vals, Rec *__restrict__ grec)
-{
-    size_t const idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= (size_t)B * n_sel) return;
-    unsigned const o = (unsigned)(idx / n_sel), k = (unsigned)(idx % n_sel), bead = sel[k];
-    Rec r;
-    load3(xyz, is_f64, ((size_t)(fr.first + (o0 + o) * fr.stride) * N + bead) * 3, r.p);
-    r.bead = bead;
-    r.label = label ? label[bead] : 0;
-    Grid const g = grids[o];
-    keys[idx] = cell_key(g, r.p, periodic, o, cap);
-    vals[idx] = (unsigned)idx;
-    grec[idx] = r;
-}
 
 // ---- the union-find
 
@@ -147,79 +125,47 @@ template <bool kPeriodic>
 __global__ void __launch_bounds__(kBlock) k_cluster_link(const Rec *__restrict__ srec, const unsigned *__restrict__ starts, const uint2 *__restrict__ work,
                                                          const Grid *__restrict__ grids, LinkArgs a)
 {
-    constexpr unsigned stride = kTile + kTilePad;
+    constexpr unsigned stride = kTile + kCellTilePad;
     __shared__ __attribute__((aligned(16))) unsigned long long smem[kTileWords * stride];
     double *tx = reinterpret_cast<double *>(smem);      // [3][stride]
     unsigned long long *tmeta = smem + 3 * stride;
 
-    uint2 const w = work[blockIdx.x];
-    unsigned const o = w.x / a.cap, cell = w.x % a.cap;
-    Grid const g = grids[o];
-    const unsigned *st = starts + (size_t)o * a.cap;
-    unsigned const s_begin = st[cell] + w.y * kChunk, nc = min(st[cell + 1] - s_begin, kChunk);
-    unsigned gs = 1;      // lanes per centre
-    while (2 * gs * nc <= (unsigned)kBlock) gs *= 2;
-    unsigned const ci = threadIdx.x / gs, sl = threadIdx.x % gs;
-    bool const active = ci < nc;
-    unsigned const s = s_begin + ci;
+    CellWork const cw = cell_work(work[blockIdx.x], starts, a.cap);
+    Grid const g = grids[cw.o];
+    unsigned const s = cw.s_begin + cw.ci, gs = cw.gs;
     Rec q;
-    if (active) q = srec[s];
-    unsigned *parent = a.parent + (size_t)o * a.N;
+    if (cw.active) q = srec[s];
+    unsigned *parent = a.parent + (size_t)cw.o * a.N;
     bool failed = false;
 
-    int const cx = (int)(cell % (unsigned)g.n[0]), cy = (int)(cell / (unsigned)g.n[0] % (unsigned)g.n[1]),
-              cz = (int)(cell / ((unsigned)g.n[0] * (unsigned)g.n[1]));
-    int x0, nx, y0, ny, z0, nz;
-    axis_cells(cx, g.n[0], kPeriodic, x0, nx);
-    axis_cells(cy, g.n[1], kPeriodic, y0, ny);
-    axis_cells(cz, g.n[2], kPeriodic, z0, nz);
-    int const xa1 = min(x0 + nx, g.n[0]), xb1 = x0 + nx - xa1;      // [x0, x0 + nx) split where it wraps past the last cell
-    for (int iz = 0; iz < nz; iz++) {
-        int const pz = (z0 + iz) % g.n[2];
-        for (int iy = 0; iy < ny; iy++) {
-            int const py = (y0 + iy) % g.n[1];
-            unsigned const row = ((unsigned)pz * (unsigned)g.n[1] + (unsigned)py) * (unsigned)g.n[0];
-            for (int span = 0; span < 2; span++) {
-                unsigned const j_begin = max(span ? st[row] : st[row + x0], s_begin + 1u);      // partners later in sorted order only
-                unsigned const j_end = span ? st[row + xb1] : st[row + xa1];
-                for (unsigned j0 = j_begin; j0 < j_end; j0 += kTile) {
-                    unsigned const nt = min(kTile, j_end - j0);
-                    __syncthreads();      // the last tile has been read
-                    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(srec + j0);
-                    for (unsigned e = threadIdx.x; e < nt * kTileWords; e += kBlock) smem[(e % kTileWords) * stride + e / kTileWords] = src[e];
-                    __syncthreads();
-                    if (!active) continue;
-                    for (unsigned k0 = sl; k0 < nt; k0 += kUnroll * gs) {
-                        // the positions of kUnroll partners first, so that their LDS reads are in flight together
-                        double r2[kUnroll];
+    // partners later in sorted order only
+    cell_tile_walk<kPeriodic, kTileWords, kTileWords>(g, cw.cell, starts + (size_t)cw.o * a.cap, cw.s_begin + 1u, srec, smem, std::integral_constant<unsigned, kTile>{}, cw.active, [&](unsigned j0, unsigned nt) {
+        for (unsigned k0 = cw.sl; k0 < nt; k0 += kUnroll * gs) {
+            // the positions of kUnroll partners first, so that their LDS reads are in flight together
+            double r2[kUnroll];
 #pragma unroll
-                        for (unsigned u = 0; u < kUnroll; u++) {
-                            unsigned const k = k0 + u * gs, kc = min(k, nt - 1u);
-                            double dx = q.p[0] - tx[kc], dy = q.p[1] - tx[stride + kc], dz = q.p[2] - tx[2 * stride + kc];
-                            if (kPeriodic) {
-                                dx = min_image(dx, g.box[0]);
-                                dy = min_image(dy, g.box[1]);
-                                dz = min_image(dz, g.box[2]);
-                            }
-                            r2[u] = k < nt && j0 + k > s ? (dx * dx + dy * dy) + dz * dz : INFINITY;
-                        }
-#pragma unroll
-                        for (unsigned u = 0; u < kUnroll; u++) {
-                            if (!(r2[u] < a.d2)) continue;
-                            unsigned long long const meta = tmeta[k0 + u * gs];
-                            unsigned const bj = (unsigned)(meta & 0xffffffffu), lj = (unsigned)(meta >> 32);
-                            unsigned const la = min((unsigned)q.label, lj), lb = max((unsigned)q.label, lj);
-                            unsigned const p = la * a.K - la * (la - 1u) / 2u + (lb - la);      // (la = 0: 0 * 0xffffffff / 2 = 0)
-                            if (!((a.mask >> p) & 1ull)) continue;
-                            unsigned const pi = peek(parent + q.bead), pj = peek(parent + bj);
-                            if (pi == pj) continue;      // one tree already
-                            if (!unite(parent, pi, pj, a.bound)) failed = true;
-                        }
-                    }
+            for (unsigned u = 0; u < kUnroll; u++) {
+                unsigned const k = k0 + u * gs, kc = min(k, nt - 1u);
+                double dx = q.p[0] - tx[kc], dy = q.p[1] - tx[stride + kc], dz = q.p[2] - tx[2 * stride + kc];
+                if (kPeriodic) {
+                    dx = min_image(dx, g.box[0]);
+                    dy = min_image(dy, g.box[1]);
+                    dz = min_image(dz, g.box[2]);
                 }
+                r2[u] = k < nt && j0 + k > s ? (dx * dx + dy * dy) + dz * dz : INFINITY;
+            }
+#pragma unroll
+            for (unsigned u = 0; u < kUnroll; u++) {
+                if (!(r2[u] < a.d2)) continue;
+                unsigned long long const meta = tmeta[k0 + u * gs];
+                unsigned const bj = (unsigned)(meta & 0xffffffffu), lj = (unsigned)(meta >> 32);
+                if (!((a.mask >> pair_class((unsigned)q.label, lj, a.K)) & 1ull)) continue;
+                unsigned const pi = peek(parent + q.bead), pj = peek(parent + bj);
+                if (pi == pj) continue;      // one tree already
+                if (!unite(parent, pi, pj, a.bound)) failed = true;
             }
         }
-    }
+    });
     if (failed) atomicOr(a.err, kErrLink);
 }
 
@@ -359,10 +305,9 @@ int run_batch(gd_cluster *h, const Call &c, unsigned o0, unsigned B, int32_t *ro
     if (hist_out) HIPCHK(h->sizes.ensure((size_t)B * c.n_bins));
     const int *label = h->ls.labels();
     int const is64 = h->hist.is_f64;
-    GDCHK(ci.make_grids(st, h->hist.x(), is64, N, h->ls.sel.p, n, c.fr, o0, B, c.sp, c.cap));
-    hipLaunchKernelGGL(k_cluster_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, N, h->ls.sel.p, label, n, c.fr, o0, B, ci.grids.p,
-                       c.sp.periodic, c.cap, ci.keys[0].p, ci.vals[0].p, ci.grec.p);
-    HIPCHK(hipGetLastError());
+    BatchFrames const fr{c.fr, o0};
+    GDCHK(ci.make_grids(st, h->hist.x(), is64, N, h->ls.sel.p, n, fr, B, c.sp, c.cap));
+    GDCHK(ci.make_keys(st, PositionFill<BatchFrames>{h->hist.x(), is64, N, label, fr, 0}, h->ls.sel.p, n, B, ci.grids.p, c.sp.periodic, c.cap));
     GDCHK(ci.sort(st, nb, slots));
     hipLaunchKernelGGL(k_cluster_init, dim3(blocks_for(nB, kBlock)), dim3(kBlock), 0, st, h->parent.p, N, nB);
     HIPCHK(hipGetLastError());

@@ -1,6 +1,6 @@
 // gdyn_dcorr.hip -- the spatial correlation of bead displacements (include/gdyn_dcorr.h): per origin frame, pair class and
 // distance bin, the number of pairs and the fixed-point sum of D_i . D_j.  Beyond the reference, which has no such analysis.
-// The pair rules and the cell grid are gdyn_cells.hpp's, the history is gd::History's (gdyn_history.hpp).
+// The pair rules, the cell grid and the walk over it are gdyn_cells.hpp's, the history is gd::History's (gdyn_history.hpp).
 //
 // Per call:
 //   k_dcorr_tmax   the largest squared displacement t2 of the selected beads over all origins of the call (integer atomicMax on the
@@ -10,19 +10,14 @@
 // Per batch of origins (max_frames_per_launch; no result depends on it):
 //   gd::CellIndex  (gdyn_cells.hpp) the cells of each origin, of side >= max_distance (1 + kCellSlack) and at most `cap` a frame, the
 //                  beads in (origin, cell) order as 64-byte records (position, D, label, chain), the first sorted index of every cell
-//                  and one work item per kChunk centres of a non-empty cell (their order is arbitrary: the sums are integers)
-//   k_dcorr_disp   between its steps: gathers the selected beads of each origin, computes D in fp64 and keys the bead (origin, cell)
-//   k_dcorr_pairs  the hot path.  A block owns one work item: up to kChunk centres of one cell, held in registers.  Every bead of a
-//                  cell wants the same 27 cells (fewer at an open edge, every cell once where an axis has fewer than 3), so the
-//                  block stages them through LDS in tiles, one x-row span at a time, as seven arrays of 8-byte words (structure of
-//                  arrays: x y z Dx Dy Dz and label|chain).  Lane = (centre, slice): the kBlock / centres (a power of two) lanes of
-//                  a centre walk the tile interleaved, so the lanes of a wave read a few consecutive words of an array (no bank
-//                  conflict for 8-byte reads, identical addresses broadcast) and small cells still fill the block.  Only partners
-//                  later in sorted order count, so every unordered pair is seen once.  The positions are read first and D and the
-//                  labels only for the ~15 % of partners inside the cutoff.  Pairs go to a block histogram in LDS (uint32 counts,
-//                  64-bit sums, ds integer atomics) whose non-zero cells are flushed with one 64-bit integer global atomic each (a
-//                  signed sum added as two's complement through the unsigned atomic is exact); above GD_DCORR_LDS_BINS cells every
-//                  pair goes to global memory directly.
+//                  and one work item per kCellChunk centres of a non-empty cell (their order is arbitrary: the sums are integers)
+//   Fill           between its steps, for k_cells_keys: gathers the selected beads of each origin and computes D in fp64
+//   k_dcorr_pairs  the hot path: the tile walk of gdyn_cells.hpp over seven of a record's eight words (x y z Dx Dy Dz and label|chain),
+//                  from the sorted index after the block's first centre on: only partners later in sorted order count, so every
+//                  unordered pair is seen once.  The body reads the positions of four partners first and D and the labels only for
+//                  the ~15 % of partners inside the cutoff.  Pairs go to a block histogram in LDS (uint32 counts, 64-bit sums) whose
+//                  non-zero cells are flushed with one 64-bit integer global atomic each (a signed sum added as two's complement
+//                  through the unsigned atomic is exact); above GD_DCORR_LDS_BINS cells every pair goes to global memory directly.
 // fp64 throughout, -ffp-contract=off (csrc/Makefile), no fast-math, no floating-point atomics: every table is an integer sum.
 #include <hip/hip_runtime.h>
 
@@ -45,9 +40,7 @@ using namespace gd;
 namespace {
 
 constexpr int kBlock = kCellBlock;
-constexpr unsigned kChunk = kCellChunk;      // centres of one work item
-constexpr unsigned kTilePad = 2;             // words between the arrays of a tile: staging writes 8 fields of 2 records per 16 lanes
-constexpr unsigned kTileWords = 7;           // x y z Dx Dy Dz label|chain
+constexpr unsigned kTileWords = 7;           // words of a record that are staged: x y z Dx Dy Dz label|chain
 constexpr unsigned kUnroll = 4;              // partners of a lane whose positions are read together
 
 struct Rec {      // one selected bead of one origin
@@ -102,25 +95,22 @@ __global__ void __launch_bounds__(kBlock) k_dcorr_self(const void *__restrict__ 
     if (threadIdx.x < K && acc[threadIdx.x]) atomicAdd(&self_sum[(size_t)o * K + threadIdx.x], acc[threadIdx.x]);
 }
 
-__global__ void __launch_bounds__(kBlock) k_dcorr_disp(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                       const int *__restrict__ label, const unsigned *__restrict__ chain, unsigned n_sel,
-                                                       unsigned lag, FrameSel og, unsigned o0, unsigned B, const Grid *__restrict__ grids, int periodic,
-                                                       unsigned cap, unsigned long long *__restrict__ keys, unsigned *__restrict__ vals,
-                                                       Rec *__restrict__ grec)
-{
-    size_t const idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= (size_t)B * n_sel) return;
-    unsigned const o = (unsigned)(idx / n_sel), k = (unsigned)(idx % n_sel), bead = sel[k];
-    Rec r;
-    (void)disp_of(xyz, is_f64, N, bead, og.first + (o0 + o) * og.stride, lag, r.p, r.d);
-    r.label = label ? label[bead] : 0;
-    r.chain = chain ? chain[bead] : 0u;
-    r.pad[0] = r.pad[1] = 0u;
-    Grid const g = grids[o];
-    keys[idx] = cell_key(g, r.p, periodic, o, cap);
-    vals[idx] = (unsigned)idx;
-    grec[idx] = r;
-}
+struct Fill {      // k_cells_keys: the record of a bead at origin o0 + o of the batch
+    const void *xyz;
+    int is_f64;
+    unsigned N;
+    const int *label;
+    const unsigned *chain;
+    unsigned lag;
+    BatchFrames fr;
+    __device__ void operator()(unsigned o, unsigned bead, Rec &r) const
+    {
+        (void)disp_of(xyz, is_f64, N, bead, fr.frame(o, 0), lag, r.p, r.d);
+        r.label = label ? label[bead] : 0;
+        r.chain = chain ? chain[bead] : 0u;
+        r.pad[0] = r.pad[1] = 0u;
+    }
+};
 
 struct PairArgs {
     double md2, inv_bw, scale;
@@ -134,98 +124,64 @@ __global__ void __launch_bounds__(kBlock) k_dcorr_pairs(const Rec *__restrict__ 
                                                         const Grid *__restrict__ grids, PairArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
-    unsigned const stride = a.tile + kTilePad;
+    unsigned const stride = a.tile + kCellTilePad;
     double *tx = reinterpret_cast<double *>(smem);      // [kTileWords][stride]
     unsigned long long *tmeta = smem + 6 * (size_t)stride;
     unsigned long long *hsum = smem + kTileWords * (size_t)stride;
     unsigned *hcount = reinterpret_cast<unsigned *>(hsum + (kLds ? a.cells : 0));
 
-    uint2 const w = work[blockIdx.x];
-    unsigned const o = w.x / a.cap, cell = w.x % a.cap;
-    Grid const g = grids[o];
-    const unsigned *st = starts + (size_t)o * a.cap;
-    unsigned const s_begin = st[cell] + w.y * kChunk, nc = min(st[cell + 1] - s_begin, kChunk);
-    unsigned gs = 1;      // lanes per centre
-    while (2 * gs * nc <= (unsigned)kBlock) gs *= 2;
-    unsigned const ci = threadIdx.x / gs, sl = threadIdx.x % gs;
-    bool const active = ci < nc;
-    unsigned const s = s_begin + ci;
+    CellWork const cw = cell_work(work[blockIdx.x], starts, a.cap);
+    Grid const g = grids[cw.o];
+    unsigned const s = cw.s_begin + cw.ci, gs = cw.gs;
     Rec q;
-    if (active) q = srec[s];
+    if (cw.active) q = srec[s];
     if (kLds) {
         for (unsigned e = threadIdx.x; e < a.cells; e += kBlock) {
             hsum[e] = 0ull;
             hcount[e] = 0u;
         }
     }
-    unsigned long long *gcount = a.counts + (size_t)o * a.cells, *gsum = a.sums + (size_t)o * a.cells;
+    unsigned long long *gcount = a.counts + (size_t)cw.o * a.cells, *gsum = a.sums + (size_t)cw.o * a.cells;
 
-    int const cx = (int)(cell % (unsigned)g.n[0]), cy = (int)(cell / (unsigned)g.n[0] % (unsigned)g.n[1]),
-              cz = (int)(cell / ((unsigned)g.n[0] * (unsigned)g.n[1]));
-    int x0, nx, y0, ny, z0, nz;
-    axis_cells(cx, g.n[0], kPeriodic, x0, nx);
-    axis_cells(cy, g.n[1], kPeriodic, y0, ny);
-    axis_cells(cz, g.n[2], kPeriodic, z0, nz);
-    int const xa1 = min(x0 + nx, g.n[0]), xb1 = x0 + nx - xa1;      // [x0, x0 + nx) split where it wraps past the last cell
-    for (int iz = 0; iz < nz; iz++) {
-        int const pz = (z0 + iz) % g.n[2];
-        for (int iy = 0; iy < ny; iy++) {
-            int const py = (y0 + iy) % g.n[1];
-            unsigned const row = ((unsigned)pz * (unsigned)g.n[1] + (unsigned)py) * (unsigned)g.n[0];
-            for (int span = 0; span < 2; span++) {
-                unsigned const j_begin = max(span ? st[row] : st[row + x0], s_begin + 1u);      // partners later in sorted order only
-                unsigned const j_end = span ? st[row + xb1] : st[row + xa1];
-                for (unsigned j0 = j_begin; j0 < j_end; j0 += a.tile) {
-                    unsigned const nt = min(a.tile, j_end - j0);
-                    __syncthreads();      // the last tile has been read (and, the first time, the histogram is clear)
-                    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(srec + j0);
-                    for (unsigned e = threadIdx.x; e < nt * 8; e += kBlock) {
-                        unsigned const field = e % 8;
-                        if (field < kTileWords) smem[field * stride + e / 8] = src[e];
-                    }
-                    __syncthreads();
-                    if (!active) continue;
-                    for (unsigned k0 = sl; k0 < nt; k0 += kUnroll * gs) {
-                        // the positions of kUnroll partners first, so that their LDS reads are in flight together
-                        double r2[kUnroll];
+    // partners later in sorted order only
+    cell_tile_walk<kPeriodic, kTileWords, 8>(g, cw.cell, starts + (size_t)cw.o * a.cap, cw.s_begin + 1u, srec, smem, a.tile, cw.active, [&](unsigned j0, unsigned nt) {
+        for (unsigned k0 = cw.sl; k0 < nt; k0 += kUnroll * gs) {
+            // the positions of kUnroll partners first, so that their LDS reads are in flight together
+            double r2[kUnroll];
 #pragma unroll
-                        for (unsigned u = 0; u < kUnroll; u++) {
-                            unsigned const k = k0 + u * gs, kc = min(k, nt - 1u);
-                            double dx = q.p[0] - tx[kc], dy = q.p[1] - tx[stride + kc], dz = q.p[2] - tx[2 * stride + kc];
-                            if (kPeriodic) {
-                                dx = min_image(dx, g.box[0]);
-                                dy = min_image(dy, g.box[1]);
-                                dz = min_image(dz, g.box[2]);
-                            }
-                            r2[u] = k < nt && j0 + k > s ? (dx * dx + dy * dy) + dz * dz : INFINITY;
-                        }
+            for (unsigned u = 0; u < kUnroll; u++) {
+                unsigned const k = k0 + u * gs, kc = min(k, nt - 1u);
+                double dx = q.p[0] - tx[kc], dy = q.p[1] - tx[stride + kc], dz = q.p[2] - tx[2 * stride + kc];
+                if (kPeriodic) {
+                    dx = min_image(dx, g.box[0]);
+                    dy = min_image(dy, g.box[1]);
+                    dz = min_image(dz, g.box[2]);
+                }
+                r2[u] = k < nt && j0 + k > s ? (dx * dx + dy * dy) + dz * dz : INFINITY;
+            }
 #pragma unroll
-                        for (unsigned u = 0; u < kUnroll; u++) {
-                            if (!(r2[u] < a.md2)) continue;
-                            unsigned const k = k0 + u * gs;
-                            unsigned long long const bin = (unsigned long long)(sqrt(r2[u]) * a.inv_bw);
-                            if (bin >= a.n_bins) continue;
-                            double const dot = (q.d[0] * tx[3 * stride + k] + q.d[1] * tx[4 * stride + k]) + q.d[2] * tx[5 * stride + k];
-                            unsigned long long const term = (unsigned long long)llrint(dot * a.scale);
-                            unsigned long long const meta = tmeta[k];
-                            unsigned const lj = (unsigned)(meta & 0xffffffffu), chj = (unsigned)(meta >> 32);
-                            unsigned const la = min((unsigned)q.label, lj), lb = max((unsigned)q.label, lj);
-                            unsigned p = la * a.K - la * (la - 1u) / 2u + (lb - la);      // (la = 0: 0 * 0xffffffff / 2 = 0)
-                            if (a.split) p = 2u * p + (q.chain != chj ? 1u : 0u);
-                            unsigned const e = p * a.n_bins + (unsigned)bin;
-                            if (kLds) {
-                                atomicAdd(&hcount[e], 1u);
-                                atomicAdd(&hsum[e], term);
-                            } else {
-                                atomicAdd(&gcount[e], 1ull);
-                                atomicAdd(&gsum[e], term);
-                            }
-                        }
-                    }
+            for (unsigned u = 0; u < kUnroll; u++) {
+                if (!(r2[u] < a.md2)) continue;
+                unsigned const k = k0 + u * gs;
+                unsigned long long const bin = (unsigned long long)(sqrt(r2[u]) * a.inv_bw);
+                if (bin >= a.n_bins) continue;
+                double const dot = (q.d[0] * tx[3 * stride + k] + q.d[1] * tx[4 * stride + k]) + q.d[2] * tx[5 * stride + k];
+                unsigned long long const term = (unsigned long long)llrint(dot * a.scale);
+                unsigned long long const meta = tmeta[k];
+                unsigned const lj = (unsigned)(meta & 0xffffffffu), chj = (unsigned)(meta >> 32);
+                unsigned p = pair_class((unsigned)q.label, lj, a.K);
+                if (a.split) p = 2u * p + (q.chain != chj ? 1u : 0u);
+                unsigned const e = p * a.n_bins + (unsigned)bin;
+                if (kLds) {
+                    atomicAdd(&hcount[e], 1u);
+                    atomicAdd(&hsum[e], term);
+                } else {
+                    atomicAdd(&gcount[e], 1ull);
+                    atomicAdd(&gsum[e], term);
                 }
             }
         }
-    }
+    });
     if (kLds) {
         __syncthreads();
         for (unsigned e = threadIdx.x; e < a.cells; e += kBlock) {
@@ -246,7 +202,7 @@ int lds_budget(int device)
                                      reinterpret_cast<const void *>(&k_dcorr_pairs<true, false>), reinterpret_cast<const void *>(&k_dcorr_pairs<true, true>)});
 }
 
-size_t tile_bytes(unsigned tile) { return (size_t)kTileWords * (tile + kTilePad) * 8; }
+size_t tile_bytes(unsigned tile) { return (size_t)kTileWords * (tile + kCellTilePad) * 8; }
 
 // max(n (n - 1) / 2, 1) * (M * 2^S + 1) < 2^62, exactly (M = m * 2^e with a 53-bit integer m)
 bool scale_legal(uint64_t n, double M, int S)
@@ -327,10 +283,9 @@ int run_batch(gd_dcorr *h, const Call &c, unsigned o0, unsigned B, uint64_t *cou
     HIPCHK(h->sums.ensure((size_t)B * cells));
     const unsigned *chain = h->have_chains ? h->chain_dev.p : nullptr;
     int const is64 = h->hist.is_f64;
-    GDCHK(ci.make_grids(st, h->hist.x(), is64, h->hist.beads(), h->ls.sel.p, n, c.og, o0, B, c.sp, c.cap));
-    hipLaunchKernelGGL(k_dcorr_disp, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, h->hist.beads(), h->ls.sel.p, h->ls.labels(), chain, n, c.lag, c.og,
-                       o0, B, ci.grids.p, c.sp.periodic, c.cap, ci.keys[0].p, ci.vals[0].p, ci.grec.p);
-    HIPCHK(hipGetLastError());
+    BatchFrames const fr{c.og, o0};
+    GDCHK(ci.make_grids(st, h->hist.x(), is64, h->hist.beads(), h->ls.sel.p, n, fr, B, c.sp, c.cap));
+    GDCHK(ci.make_keys(st, Fill{h->hist.x(), is64, h->hist.beads(), h->ls.labels(), chain, c.lag, fr}, h->ls.sel.p, n, B, ci.grids.p, c.sp.periodic, c.cap));
     GDCHK(ci.sort(st, nb, slots));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(h->counts.p, 0, (size_t)B * cells * sizeof(unsigned long long), st));
@@ -523,7 +478,7 @@ int gd_dcorr_pairs(gd_dcorr *h, uint32_t lag, uint32_t first_origin, uint32_t n_
     c.scale = scale;
     c.n_bins = n_bins;
     c.cap = std::max(4096u, n);
-    // the histogram in LDS: a block adds at most kChunk * n to one uint32 counter; the tile takes what the table leaves, 64 to 256 records
+    // the histogram in LDS: a block adds at most kCellChunk * n to one uint32 counter; the tile takes what the table leaves, 64 to 256 records
     c.tile = 256;
     c.lds = cells <= GD_DCORR_LDS_BINS && n < (1u << 24) && cells * 12 + tile_bytes(64) <= (size_t)h->lds_bytes;
     while (c.tile > 64 && tile_bytes(c.tile) + (c.lds ? cells * 12 : 0) > (size_t)h->lds_bytes) c.tile /= 2;

@@ -1,9 +1,11 @@
 // gdyn_frames.hpp -- the arithmetic that the history analyses share and that needs no device: which frames of a history a call
-// selects (gd_dcorr, gd_cluster, gd_dcov, gd_gyr) and which tiles of a symmetric map a rectangle of it touches (gd_dmap, gd_dcov).
+// selects (gd_dcorr, gd_cluster, gd_dcov, gd_gyr), which tiles of a symmetric map a rectangle of it touches (gd_dmap, gd_dcov), the
+// windows of the lag walk (gdyn_lagwalk.hpp) that an LDS budget holds and the order of a call's lags (gd_msd, gd_vanhove).
 // Plain C++ in the manner of gdyn_policy.hpp: no HIP call, no handle, no error reporting; tests/native/test_frames.cpp drives it.
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <numeric>
 #include <utility>
 #include <vector>
 
@@ -40,6 +42,43 @@ inline std::vector<std::pair<uint32_t, uint32_t>> tile_cover(uint32_t tile, uint
     std::sort(tiles.begin(), tiles.end());
     tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
     return tiles;
+}
+
+struct LagWindows {
+    unsigned W, windows;      // items of a window; 1: the longest sequence fits in one window and partners lie in it, else 2
+};
+
+// The windows of the lag walk in `budget` bytes of LDS of which `fixed` lie in front of them: `row` bytes an item, sequences of at most
+// `longest` items, W at most `knob` (0: no bound).  Where fewer than two rows fit, W = 1 with two windows.
+inline LagWindows lag_windows(size_t budget, size_t fixed, size_t row, unsigned longest, unsigned knob)
+{
+    unsigned const fit = (unsigned)std::min<size_t>((budget > fixed ? budget - fixed : 0) / row, 1u << 28);
+    unsigned const want = knob ? std::min(knob, longest) : longest;
+    if (want > fit) return {std::max(fit / 2, 1u), 2};
+    unsigned const W = std::max(want, 1u);
+    if (W >= longest) return {W, 1};
+    return {2 * (size_t)W > fit ? std::max(fit / 2, 1u) : W, 2};
+}
+
+struct LagOrder {      // the indices of a call's lags by ascending lag, the least lag (none: 2^32 - 1) and, if one is listed twice, the least such
+    std::vector<uint32_t> order;
+    uint32_t least = 0xffffffffu, repeated = 0;
+    bool twice = false;
+};
+
+inline LagOrder sort_lags(const uint32_t *lags, uint32_t n)
+{
+    LagOrder r;
+    r.order.resize(n);
+    std::iota(r.order.begin(), r.order.end(), 0u);
+    std::sort(r.order.begin(), r.order.end(), [&](uint32_t a, uint32_t b) { return lags[a] < lags[b]; });
+    if (n) r.least = lags[r.order[0]];
+    for (uint32_t k = 1; k < n && !r.twice; k++)
+        if (lags[r.order[k]] == lags[r.order[k - 1]]) {
+            r.twice = true;
+            r.repeated = lags[r.order[k]];
+        }
+    return r;
 }
 
 }  // namespace gd

@@ -4,17 +4,12 @@
 // A *sequence* is a run of items (3 coordinates each) a fixed stride apart: along time one bead's trajectory (item stride 3 N
 // elements, neighbouring beads 3 elements apart), along the chain one chain in one frame (item stride 3, the same chain in the
 // next frame 3 N elements on).  A *tile* is kSeqs = 16 sequences that lie side by side: 16 consecutive beads, or one chain in 16
-// consecutive frames of the window.
+// consecutive frames of the window.  The walk over the windows of a tile is gdyn_lagwalk.hpp's, which van Hove's self part shares.
 //
-//   k_msd_lag<T>     one block per (tile, origin range of kRange = 4096 origins).  It stages windows of W items of its 16 sequences
-//                    in LDS, [item][sequence][3] in the stored type T with one element of padding per item row, and evaluates
-//                    every requested lag from there: lane = (sequence, lag), 16 x 64 per block, so the 16 lanes of a lag read
-//                    items 3 elements apart (conflict-free) and run the same trip count.  When the whole sequence fits (F <= W:
-//                    835 float32 items in 160 KiB) the history is read from HBM once per call whatever the number of lags.
-//                    Otherwise the block walks origin windows A and, for each, only the partner windows B = A + d W that a
-//                    requested lag connects (lags are sorted, so the lags of one d are a range found by bisection).
-//                    Every (sequence, lag, range) sum is ONE lane's serial sum over ascending origins, carried from window
-//                    pair to window pair in its slot of `partial` (always the same lane's): no bit depends on W.
+//   k_msd_lag<T>     one block per (tile, origin range of kRange = 4096 origins): the lag walk with the body LagSums.  Lane =
+//                    (sequence, lag), 16 x 64 per block, so the 16 lanes of a lag read items 3 elements apart (conflict-free) and run
+//                    the same trip count.  Every (sequence, lag, range) sum is ONE lane's serial sum over ascending origins, carried
+//                    from window pair to window pair in its slot of `partial` (always the same lane's): no bit depends on W.
 //   k_msd_reduce1/2  the sums of a group: per fixed chunk of 256 sequences, serially over ascending sequences (each the serial sum
 //                    of its ranges), then serially over the chunks.  The order depends on the shapes alone.
 //   k_msd_per_seq    gd_msd_time_per_bead: the serial sum of a sequence's ranges.
@@ -26,26 +21,21 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "../../include/gdyn.h"
 #include "../../include/gdyn_msd.h"
 #include "gdyn_analysis.hpp"
+#include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
+#include "gdyn_lagwalk.hpp"
 
 using namespace gd;
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kLagBlock = 1024;              // k_msd_lag: a tile of F = 701 float32 frames leaves room for one block per CU, so the
-                                             // block brings the waves that hide the LDS latency itself (four per SIMD)
-constexpr unsigned kSeqs = 16;               // sequences of a tile
-constexpr unsigned kSlots = kLagBlock / kSeqs;  // lags evaluated side by side
-constexpr unsigned kRow = 3 * kSeqs + 1;     // elements of an item row in LDS: odd, so consecutive items start on different banks
-constexpr unsigned kRange = 4096;            // origins of one serial sum: fixed, so that the order of summation is
-constexpr unsigned kChunk = 256;             // sequences of one serial group sum: likewise
+constexpr unsigned kChunk = 256;             // sequences of one serial group sum: fixed, like kRange, so that the order of summation is
 constexpr size_t kPartialBytes = (size_t)1 << 30;      // lags are evaluated in batches whose partial sums fit this
 
 struct LagArgs {
@@ -59,34 +49,36 @@ struct LagArgs {
     size_t n_seqs;
 };
 
-__device__ inline unsigned lower_bound_dev(const uint32_t *__restrict__ v, unsigned n, unsigned long long key)      // first index with v[i] >= key
-{
-    unsigned lo = 0, hi = n;
-    while (lo < hi) {
-        unsigned const mid = (lo + hi) / 2;
-        if (v[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// items [i0, i0 + n) of the tile's sequences into dst ([item][sequence][3]); sequences beyond `valid` read as zeros
+// The body of the lag walk: lane = (sequence, lag slot).  Lag k is always the same lane's, and its sum over the origins of a window pair
+// goes on serially from where the last pair left it in `mine`.
 template <typename T>
-__device__ inline void stage(T *dst, const T *__restrict__ base, size_t seq_stride, size_t item_stride, unsigned valid, size_t i0, unsigned n)
-{
-    unsigned const total = n * kSeqs * 3;
-    if (item_stride >= seq_stride) {      // along time: an item row of the tile is contiguous in memory
-        for (unsigned idx = threadIdx.x; idx < total; idx += kLagBlock) {
-            unsigned const w = idx / (3 * kSeqs), e = idx % (3 * kSeqs), s = e / 3;
-            dst[w * kRow + e] = s < valid ? base[(i0 + w) * item_stride + (size_t)s * seq_stride + e % 3] : T(0);
-        }
-    } else {      // along the chain: the items of a sequence are contiguous
-        for (unsigned idx = threadIdx.x; idx < total; idx += kLagBlock) {
-            unsigned const s = idx / (3 * n), e = idx % (3 * n), w = e / 3;
-            dst[w * kRow + 3 * s + e % 3] = s < valid ? base[(size_t)s * seq_stride + (i0 + w) * item_stride + e % 3] : T(0);
-        }
+struct LagSums {
+    const uint32_t *lags;
+    double2 *mine;      // this lane's sequence's row of `partial` in this range
+    unsigned s, slot, valid;
+
+    __device__ bool wants(long long, long long) const { return true; }
+    __device__ void operator()(const LagPair &w, const T *A, const T *Bw) const
+    {
+        if (s < valid)
+            for (unsigned k = w.lo / kSlots * kSlots + slot; k < w.hi; k += kSlots) {      // lag k is always this lane's
+                if (k < w.lo) continue;
+                long long const shift = (long long)lags[k] - w.d * w.W;      // partner's place in B = origin's place in A + shift
+                long long const r0 = max(0ll, -shift), r1 = min(w.nO, w.nB - shift);
+                if (r1 <= r0) continue;
+                const T *pa = A + r0 * kRow + 3 * s, *pb = Bw + (r0 + shift) * kRow + 3 * s;
+                double2 acc = mine[k];
+#pragma unroll 4
+                for (long long r = r0; r < r1; r++, pa += kRow, pb += kRow) {
+                    double const dx = (double)pb[0] - (double)pa[0], dy = (double)pb[1] - (double)pa[1], dz = (double)pb[2] - (double)pa[2];
+                    double const t2 = (dx * dx + dy * dy) + dz * dz;
+                    acc.x += t2;
+                    acc.y += t2 * t2;
+                }
+                mine[k] = acc;
+            }
     }
-}
+};
 
 template <typename T>
 __global__ void __launch_bounds__(kLagBlock) k_msd_lag(LagArgs p)
@@ -94,79 +86,36 @@ __global__ void __launch_bounds__(kLagBlock) k_msd_lag(LagArgs p)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     T *A = reinterpret_cast<T *>(smem);
     T *B = A + (size_t)(p.windows - 1) * p.W * kRow;      // one window: partners lie in A
-    const T *x = static_cast<const T *>(p.x);
 
     // the tile: where its sequences lie, how long they are, and which rows of `partial` are theirs
-    size_t base, seq_stride, item_stride, q0, q_stride;
-    unsigned valid, L;
+    LagTile t;
+    size_t q0, q_stride;
     if (p.chains) {
         unsigned const c = blockIdx.x / p.ftiles, ft = blockIdx.x % p.ftiles;
         unsigned const start = p.chains[2 * c];
-        L = p.chains[2 * c + 1] - start;
-        base = ((size_t)p.f0 + (size_t)ft * kSeqs) * p.N * 3 + (size_t)start * 3;
-        seq_stride = (size_t)p.N * 3;
-        item_stride = 3;
-        valid = min(kSeqs, p.nf - ft * kSeqs);
+        t.L = p.chains[2 * c + 1] - start;
+        t.base = ((size_t)p.f0 + (size_t)ft * kSeqs) * p.N * 3 + (size_t)start * 3;
+        t.seq_stride = (size_t)p.N * 3;
+        t.item_stride = 3;
+        t.valid = min(kSeqs, p.nf - ft * kSeqs);
         q0 = (size_t)ft * kSeqs * p.C + c;
         q_stride = p.C;
     } else {
-        L = p.F;
-        base = (size_t)blockIdx.x * kSeqs * 3;
-        seq_stride = 3;
-        item_stride = (size_t)p.N * 3;
-        valid = min(kSeqs, p.N - blockIdx.x * kSeqs);
+        t.L = p.F;
+        t.base = (size_t)blockIdx.x * kSeqs * 3;
+        t.seq_stride = 3;
+        t.item_stride = (size_t)p.N * 3;
+        t.valid = min(kSeqs, p.N - blockIdx.x * kSeqs);
         q0 = (size_t)blockIdx.x * kSeqs;
         q_stride = 1;
     }
     unsigned const s = threadIdx.x % kSeqs, slot = threadIdx.x / kSeqs;
-    long long const W = p.W;
-    if (L < 2) return;
-    unsigned const ranges = (L - 1 + kRange - 1) / kRange;      // origins 0 .. L-2
+    if (t.L < 2) return;
+    unsigned const ranges = (t.L - 1 + kRange - 1) / kRange;      // origins 0 .. L-2
     for (unsigned g = blockIdx.y; g < ranges; g += gridDim.y) {
-        long long const O0 = (long long)g * kRange, O1 = min(O0 + (long long)kRange, (long long)L - 1);
-        double2 *mine = p.partial + ((size_t)g * p.n_seqs + q0 + (size_t)s * q_stride) * p.n_lags;
-        for (long long A0 = O0; A0 < O1; A0 += W) {
-            long long const nO = min(W, O1 - A0), nA = min(W, (long long)L - A0);      // origins; items staged
-            __syncthreads();      // the last window pair has been read
-            stage(A, x + base, seq_stride, item_stride, valid, (size_t)A0, (unsigned)nA);
-            for (long long d = 0;;) {      // partner windows [A0 + d W, A0 + (d + 1) W): the lags of d lie in ((d - 1) W, (d + 1) W)
-                unsigned const lo = d ? lower_bound_dev(p.lags, p.n_lags, (unsigned long long)((d - 1) * W + 1)) : 0;
-                unsigned const hi = lower_bound_dev(p.lags, p.n_lags, (unsigned long long)((d + 1) * W));
-                if (lo == hi) {
-                    if (hi >= p.n_lags) break;
-                    d = p.lags[hi] / W;      // >= d + 1
-                    continue;
-                }
-                long long const B0 = A0 + d * W;
-                if (B0 >= (long long)L) break;
-                long long const nB = d ? min(W, (long long)L - B0) : nA;
-                const T *Bw = A;
-                if (d) {
-                    __syncthreads();      // the last partner window has been read
-                    stage(B, x + base, seq_stride, item_stride, valid, (size_t)B0, (unsigned)nB);
-                    Bw = B;
-                }
-                __syncthreads();
-                if (s < valid)
-                    for (unsigned k = lo / kSlots * kSlots + slot; k < hi; k += kSlots) {      // lag k is always this lane's
-                        if (k < lo) continue;
-                        long long const shift = (long long)p.lags[k] - d * W;      // partner's place in B = origin's place in A + shift
-                        long long const r0 = max(0ll, -shift), r1 = min(nO, nB - shift);
-                        if (r1 <= r0) continue;
-                        const T *pa = A + r0 * kRow + 3 * s, *pb = Bw + (r0 + shift) * kRow + 3 * s;
-                        double2 acc = mine[k];
-#pragma unroll 4
-                        for (long long r = r0; r < r1; r++, pa += kRow, pb += kRow) {
-                            double const dx = (double)pb[0] - (double)pa[0], dy = (double)pb[1] - (double)pa[1], dz = (double)pb[2] - (double)pa[2];
-                            double const t2 = (dx * dx + dy * dy) + dz * dz;
-                            acc.x += t2;
-                            acc.y += t2 * t2;
-                        }
-                        mine[k] = acc;
-                    }
-                d++;
-            }
-        }
+        long long const O0 = (long long)g * kRange, O1 = min(O0 + (long long)kRange, (long long)t.L - 1);
+        LagSums<T> body{p.lags, p.partial + ((size_t)g * p.n_seqs + q0 + (size_t)s * q_stride) * p.n_lags, s, slot, t.valid};
+        lag_walk(static_cast<const T *>(p.x), t, p.lags, p.n_lags, (long long)p.W, O0, O1, A, B, body);
     }
 }
 
@@ -277,12 +226,10 @@ History::Rebind rebind(gd_msd *h)
 // lags: distinct and >= 1; order: their indices by ascending lag
 int check_lags(const char *who, const char *what, const uint32_t *lags, uint32_t n, std::vector<uint32_t> &order)
 {
-    order.resize(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lags[a] < lags[b]; });
-    if (n && lags[order[0]] == 0) return fail(GD_EINVAL, "%s: %s 0", who, what);
-    for (uint32_t k = 1; k < n; k++)
-        if (lags[order[k]] == lags[order[k - 1]]) return fail(GD_EINVAL, "%s: %s %u is listed twice", who, what, lags[order[k]]);
+    LagOrder lo = sort_lags(lags, n);
+    if (lo.least == 0) return fail(GD_EINVAL, "%s: %s 0", who, what);
+    if (lo.twice) return fail(GD_EINVAL, "%s: %s %u is listed twice", who, what, lo.repeated);
+    order = std::move(lo.order);
     return GD_OK;
 }
 
@@ -298,17 +245,7 @@ struct Plan {      // one axis of one call
 int run_lags(gd_msd *h, const Plan &pl, const uint32_t *sorted_lags_dev, unsigned nl)
 {
     size_t const row = (size_t)kRow * h->hist.elem();
-    unsigned const fit = (unsigned)std::min<size_t>((size_t)h->lds_bytes / row, 1u << 28);
-    unsigned W, windows;
-    unsigned const want = h->knob ? std::min(h->knob, pl.longest) : pl.longest;
-    if (want <= fit) {
-        W = std::max(want, 1u);
-        windows = W >= pl.longest ? 1 : 2;
-        if (windows == 2 && 2 * (size_t)W > fit) W = std::max(fit / 2, 1u);
-    } else {
-        W = std::max(fit / 2, 1u);
-        windows = 2;
-    }
+    LagWindows const lw = lag_windows((size_t)h->lds_bytes, 0, row, pl.longest, h->knob);
     size_t const cells = (size_t)pl.ranges * pl.n_seqs * nl;
     HIPCHK(h->partial.ensure(cells));
     HIPCHK(hipMemsetAsync(h->partial.p, 0, cells * sizeof(double2), h->stream));
@@ -324,11 +261,11 @@ int run_lags(gd_msd *h, const Plan &pl, const uint32_t *sorted_lags_dev, unsigne
     a.nf = pl.nf;
     a.ftiles = pl.ftiles;
     a.n_lags = nl;
-    a.W = W;
-    a.windows = windows;
+    a.W = lw.W;
+    a.windows = lw.windows;
     a.n_seqs = pl.n_seqs;
     dim3 const grid((unsigned)pl.tiles, std::min(pl.ranges, 65535u));
-    size_t const lds = (size_t)windows * W * row;
+    size_t const lds = (size_t)lw.windows * lw.W * row;
     if (h->hist.is_f64) hipLaunchKernelGGL(k_msd_lag<double>, grid, dim3(kLagBlock), lds, h->stream, a);
     else hipLaunchKernelGGL(k_msd_lag<float>, grid, dim3(kLagBlock), lds, h->stream, a);
     HIPCHK(hipGetLastError());

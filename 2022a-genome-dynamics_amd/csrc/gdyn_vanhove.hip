@@ -2,35 +2,29 @@
 // displacements per lag and label (self part) and the histogram of the distances from where a bead was to where the OTHER beads are a
 // lag later, per ordered label pair (distinct part).  Beyond the reference, which has neither.  Every output is an integer count.
 //
-//   k_vh_self<T, LDS>      the walk of k_msd_lag (gdyn_msd.hip): one block per (tile of kSeqs = 16 consecutive beads, range of kRange
-//                          origin frames).  It stages windows of W frames of its beads in LDS, [frame][bead][3] in the stored type T
-//                          with one element of padding per row, and evaluates every requested lag from there; when the whole history
-//                          of the tile fits (835 float32 frames in 160 KiB less the histogram) the history is read from HBM once per
-//                          call whatever the number of lags.  Otherwise it walks origin windows A and, for each, only the partner
-//                          windows A + d W that a requested lag connects (the lags are sorted).  Lane = (bead, slot); the kSlots = 64
-//                          slots share out the (lag, origin) pairs of a window pair, whose order does not matter: every count is an
-//                          integer.  The squared edges (fp64, squared on the host) sit in LDS and a lane finds its cell by bisection
-//                          over them; cell 0 of a (lag, label) row is `below`, cells 1 .. B the bins, cell B + 1 `above`.  LDS: counts
-//                          go to a block histogram of uint32 (a block adds at most kSeqs * kRange = 2^16 to a cell before it is
-//                          flushed, once per range, with one 64-bit atomic per non-zero cell); else (more than GD_VANHOVE_LDS_CELLS
-//                          cells) straight to the global table.  per_origin is added to directly in global memory: its cells are
-//                          (lag, origin, label, bin), so a tile's 16 beads of one origin are all that ever meet in one of them.
-//   k_vh_bbox, k_vh_keys   distinct part, per batch of (origin, lag) frame pairs: the bounding box of the selected beads over BOTH
-//                          frames of a pair (open box), and the records (position, label, bead) of the centres (frame f) and of the
-//                          partners (frame f + tau) keyed by (pair, cell) on the one grid of the pair (gdyn_cells.hpp)
-//   k_vh_pairs<PERIODIC, LDS>   k_dcorr_pairs' walk with two sets of records: a block owns up to kChunk centres of one cell of the
-//                          centres' index and stages the cells around it of the PARTNERS' index through LDS in tiles (x y z and
-//                          label|bead as four arrays of 8-byte words).  Every ordered pair of different beads is seen once.  Block
-//                          histogram in LDS (class, bin) or, above GD_VANHOVE_LDS_CELLS cells, global atomics.
+//   k_vh_self<T, LDS>      the lag walk of gdyn_lagwalk.hpp, which gdyn_msd.hip shares, with the body SelfCount; an origin window that
+//                          holds no selected origin is not staged.  Lane = (bead, slot); the kSlots = 64 slots share out the (lag,
+//                          origin) pairs of a window pair, whose order does not matter: every count is an integer.  A lane finds its
+//                          cell by bisection over the squared edges (fp64, squared on the host) in LDS; cell 0 of a (lag, label) row
+//                          is `below`, cells 1 .. B the bins, cell B + 1 `above`.  LDS: counts go to a block histogram of uint32 (a
+//                          block adds at most kSeqs * kRange = 2^16 to a cell before it is flushed, once per range around the walk,
+//                          with one 64-bit atomic per non-zero cell); else (more than GD_VANHOVE_LDS_CELLS cells) straight to the
+//                          global table.  per_origin is added to directly in global memory: a tile's 16 beads of one origin are all
+//                          that ever meet in one of its cells (lag, origin, label, bin).
+//   PairFrames             distinct part, for gdyn_cells.hpp's kernels and its PositionFill: both frames of an (origin, lag) pair for the bounding box,
+//                          and the records (position, label, bead) of the centres (frame f) and of the partners (frame f + tau)
+//   k_vh_pairs<PERIODIC, LDS>   the tile walk of gdyn_cells.hpp with two sets of records: the centres are those of a cell of the centres'
+//                          index, the cells around it those of the PARTNERS' index on the one grid of the pair, from their first
+//                          record on: every ordered pair of different beads is seen once.  The body bins a partner by bisection.
+//                          Block histogram in LDS (class, bin) or, above GD_VANHOVE_LDS_CELLS cells, global atomics.
 // Only integer atomics.  fp64 throughout, -ffp-contract=off (csrc/Makefile), no fast-math.  The history is gd::History's, the labels
-// gd::LabelSelection's (gdyn_history.hpp), the grid, the sort and the pair rules gdyn_cells.hpp's.
+// gd::LabelSelection's (gdyn_history.hpp), the grid, the sort, the tile walk and the pair rules gdyn_cells.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "../../include/gdyn.h"
@@ -39,6 +33,7 @@
 #include "gdyn_cells.hpp"
 #include "gdyn_frames.hpp"
 #include "gdyn_history.hpp"
+#include "gdyn_lagwalk.hpp"
 #include "gdyn_types.h"
 
 using namespace gd;
@@ -48,15 +43,10 @@ namespace {
 typedef unsigned long long u64;
 static_assert(sizeof(u64) == sizeof(uint64_t), "the outputs are uint64");
 
-constexpr int kSelfBlock = 1024;             // as k_msd_lag: one block per CU when the window is the whole history
-constexpr unsigned kSeqs = 16;               // beads of a tile
-constexpr unsigned kSlots = kSelfBlock / kSeqs;
-constexpr unsigned kRow = 3 * kSeqs + 1;     // elements of a frame row in LDS: odd, so consecutive frames start on different banks
-constexpr unsigned kRange = 4096;            // origin frames of one block: kSeqs * kRange < 2^32 bounds a uint32 cell
+constexpr int kSelfBlock = kLagBlock;        // the lag walk's: a tile is kSeqs beads, and kSeqs * kRange < 2^32 bounds a uint32 cell
 constexpr unsigned kMaxLags = GD_VANHOVE_MAX_LAGS, kMaxBins = GD_VANHOVE_MAX_BINS, kLdsCells = GD_VANHOVE_LDS_CELLS;
 constexpr int kBlock = kCellBlock;
-constexpr unsigned kChunk = kCellChunk;      // centres of one work item
-constexpr unsigned kTilePad = 2, kTileWords = 4;      // x y z label|bead
+constexpr unsigned kTileWords = 4;           // x y z label|bead
 
 // the number of edges2[0 .. B] that are <= r2: 0 below, B + 1 above, else 1 + bin
 __device__ inline unsigned cell_of_r2(const double *e2, unsigned B, double r2)
@@ -102,27 +92,56 @@ struct SelfArgs {
     u64 *per_origin;            // (n_lags, O, K, B) or nullptr
 };
 
-__device__ inline unsigned lower_bound_dev(const uint32_t *__restrict__ v, unsigned n, u64 key)      // first index with v[i] >= key
-{
-    unsigned lo = 0, hi = n;
-    while (lo < hi) {
-        unsigned const mid = (lo + hi) / 2;
-        if (v[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
+// The body of the lag walk: lane = (bead, slot).  The slots share out the (lag, origin) pairs of a window pair and count each
+// displacement in its cell of the histogram.
+template <typename T, bool LDS>
+struct SelfCount {
+    const SelfArgs &p;
+    const double *e2;
+    unsigned *hist;
+    unsigned s, slot;
+    int lab;
+    long long k_lo;      // the selected origins of the window: k_lo + [0, nk)
+    unsigned nk;
 
-// frames [i0, i0 + n) of the tile's beads into dst ([frame][bead][3]); beads beyond `valid` read as zeros
-template <typename T>
-__device__ inline void stage(T *dst, const T *__restrict__ base, size_t frame_stride, unsigned valid, size_t i0, unsigned n)
-{
-    unsigned const total = n * kSeqs * 3;
-    for (unsigned idx = threadIdx.x; idx < total; idx += kSelfBlock) {
-        unsigned const w = idx / (3 * kSeqs), e = idx % (3 * kSeqs);
-        dst[w * kRow + e] = e / 3 < valid ? base[(i0 + w) * frame_stride + e] : T(0);
+    __device__ bool wants(long long A0, long long nO)
+    {
+        // the origins k with A0 <= first + k stride < A0 + nO
+        k_lo = A0 <= (long long)p.first ? 0 : (A0 - p.first + p.stride - 1) / p.stride;
+        long long const k_hi = A0 + nO <= (long long)p.first ? 0 : min((long long)p.O, (A0 + nO - p.first + p.stride - 1) / p.stride);
+        nk = (unsigned)(k_hi - k_lo);
+        return k_lo < k_hi;
     }
-}
+    __device__ void operator()(const LagPair &w, const T *A, const T *Bw) const
+    {
+        unsigned const B = p.B;
+        bool const ax = p.axes & 1u, ay = p.axes & 2u, az = p.axes & 4u;
+        unsigned const total = (w.hi - w.lo) * nk;      // <= 32 * 4096
+        for (unsigned i0 = 0; i0 < total; i0 += kSlots) {      // the same trip count for every lane of the block
+            unsigned const idx = i0 + slot;
+            bool ok = lab >= 0 && idx < total;
+            unsigned cell = 0, li = 0, k = 0;
+            if (ok) {
+                li = w.lo + idx / nk;
+                k = (unsigned)k_lo + idx % nk;
+                long long const r = (long long)p.first + (long long)k * p.stride - w.A0;      // in [0, nO)
+                long long const rb = r + (long long)p.lags[li] - w.d * w.W;
+                ok = rb >= 0 && rb < w.nB;
+                if (ok) {
+                    const T *pa = A + r * kRow + 3 * s, *pb = Bw + rb * kRow + 3 * s;
+                    double const dx = (double)pb[0] - (double)pa[0], dy = (double)pb[1] - (double)pa[1], dz = (double)pb[2] - (double)pa[2];
+                    double const tx = ax ? dx * dx : 0.0, ty = ay ? dy * dy : 0.0, tz = az ? dz * dz : 0.0;
+                    cell = cell_of_r2(e2, B, (tx + ty) + tz);
+                }
+            }
+            unsigned const at = (li * p.K + (unsigned)lab) * (B + 2) + cell;
+            if (LDS) lds_count(hist, at, ok);
+            else if (ok) atomicAdd(&p.table[at], 1ull);
+            if (ok && p.per_origin && cell >= 1 && cell <= B)
+                atomicAdd(&p.per_origin[(((size_t)li * p.O + k) * p.K + (unsigned)lab) * B + (cell - 1)], 1ull);
+        }
+    }
+};
 
 template <typename T, bool LDS>
 __global__ void __launch_bounds__(kSelfBlock) k_vh_self(SelfArgs p)
@@ -132,75 +151,20 @@ __global__ void __launch_bounds__(kSelfBlock) k_vh_self(SelfArgs p)
     unsigned *hist = reinterpret_cast<unsigned *>(e2 + p.B + 1);
     T *A = reinterpret_cast<T *>(hist + (LDS ? (p.cells + 1u) / 2u * 2u : 0u));
     T *Bw0 = A + (size_t)(p.windows - 1) * p.W * kRow;      // one window: partners lie in A
-    const T *x = static_cast<const T *>(p.x) + (size_t)blockIdx.x * kSeqs * 3;
-    size_t const frame_stride = (size_t)p.N * 3;
-    unsigned const valid = min(kSeqs, p.N - blockIdx.x * kSeqs);
-    unsigned const s = threadIdx.x % kSeqs, slot = threadIdx.x / kSeqs, B = p.B;
-    int const lab = s < valid ? (p.label ? p.label[blockIdx.x * kSeqs + s] : 0) : -1;
-    bool const ax = p.axes & 1u, ay = p.axes & 2u, az = p.axes & 4u;
-    long long const W = p.W, F = p.F;
-    for (unsigned e = threadIdx.x; e <= B; e += kSelfBlock) e2[e] = p.edges2[e];
+    __builtin_assume(p.N >= 1);      // item_stride >= seq_stride: only the along-time half of stage() is this kernel's
+    LagTile const t{(size_t)blockIdx.x * kSeqs * 3, 3, (size_t)p.N * 3, min(kSeqs, p.N - blockIdx.x * kSeqs), p.F};
+    unsigned const s = threadIdx.x % kSeqs, slot = threadIdx.x / kSeqs;
+    int const lab = s < t.valid ? (p.label ? p.label[blockIdx.x * kSeqs + s] : 0) : -1;
+    SelfCount<T, LDS> body{p, e2, hist, s, slot, lab, 0, 0};
+    for (unsigned e = threadIdx.x; e <= p.B; e += kSelfBlock) e2[e] = p.edges2[e];
     unsigned const ranges = (p.F + kRange - 1) / kRange;
     for (unsigned g = blockIdx.y; g < ranges; g += gridDim.y) {
-        long long const O0 = (long long)g * kRange, O1 = min(O0 + (long long)kRange, F);
+        long long const O0 = (long long)g * kRange, O1 = min(O0 + (long long)kRange, (long long)p.F);
         if (LDS) {
             __syncthreads();      // the last range has been flushed
             for (unsigned c = threadIdx.x; c < p.cells; c += kSelfBlock) hist[c] = 0u;
         }
-        for (long long A0 = O0; A0 < O1; A0 += W) {
-            long long const nO = min(W, O1 - A0), nA = min(W, F - A0);      // origin frames; frames staged
-            // the origins k with A0 <= first + k stride < A0 + nO
-            long long const k_lo = A0 <= (long long)p.first ? 0 : (A0 - p.first + p.stride - 1) / p.stride;
-            long long const k_hi = A0 + nO <= (long long)p.first ? 0 : min((long long)p.O, (A0 + nO - p.first + p.stride - 1) / p.stride);
-            if (k_lo >= k_hi) continue;
-            unsigned const nk = (unsigned)(k_hi - k_lo);
-            __syncthreads();      // the last window pair has been read
-            stage(A, x, frame_stride, valid, (size_t)A0, (unsigned)nA);
-            for (long long d = 0;;) {      // partner windows [A0 + d W, A0 + (d + 1) W): the lags of d lie in ((d - 1) W, (d + 1) W)
-                unsigned const lo = d ? lower_bound_dev(p.lags, p.n_lags, (u64)((d - 1) * W + 1)) : 0;
-                unsigned const hi = lower_bound_dev(p.lags, p.n_lags, (u64)((d + 1) * W));
-                if (lo == hi) {
-                    if (hi >= p.n_lags) break;
-                    d = p.lags[hi] / W;      // >= d + 1
-                    continue;
-                }
-                long long const B0 = A0 + d * W;
-                if (B0 >= F) break;
-                long long const nB = d ? min(W, F - B0) : nA;
-                const T *Bw = A;
-                if (d) {
-                    __syncthreads();      // the last partner window has been read
-                    stage(Bw0, x, frame_stride, valid, (size_t)B0, (unsigned)nB);
-                    Bw = Bw0;
-                }
-                __syncthreads();
-                unsigned const total = (hi - lo) * nk;      // <= 32 * 4096
-                for (unsigned i0 = 0; i0 < total; i0 += kSlots) {      // the same trip count for every lane of the block
-                    unsigned const idx = i0 + slot;
-                    bool ok = lab >= 0 && idx < total;
-                    unsigned cell = 0, li = 0, k = 0;
-                    if (ok) {
-                        li = lo + idx / nk;
-                        k = (unsigned)k_lo + idx % nk;
-                        long long const r = (long long)p.first + (long long)k * p.stride - A0;      // in [0, nO)
-                        long long const rb = r + (long long)p.lags[li] - d * W;
-                        ok = rb >= 0 && rb < nB;
-                        if (ok) {
-                            const T *pa = A + r * kRow + 3 * s, *pb = Bw + rb * kRow + 3 * s;
-                            double const dx = (double)pb[0] - (double)pa[0], dy = (double)pb[1] - (double)pa[1], dz = (double)pb[2] - (double)pa[2];
-                            double const tx = ax ? dx * dx : 0.0, ty = ay ? dy * dy : 0.0, tz = az ? dz * dz : 0.0;
-                            cell = cell_of_r2(e2, B, (tx + ty) + tz);
-                        }
-                    }
-                    unsigned const at = (li * p.K + (unsigned)lab) * (B + 2) + cell;
-                    if (LDS) lds_count(hist, at, ok);
-                    else if (ok) atomicAdd(&p.table[at], 1ull);
-                    if (ok && p.per_origin && cell >= 1 && cell <= B)
-                        atomicAdd(&p.per_origin[(((size_t)li * p.O + k) * p.K + (unsigned)lab) * B + (cell - 1)], 1ull);
-                }
-                d++;
-            }
-        }
+        lag_walk(static_cast<const T *>(p.x), t, p.lags, p.n_lags, (long long)p.W, O0, O1, A, Bw0, body);
         if (LDS) {
             __syncthreads();
             for (unsigned c = threadIdx.x; c < p.cells; c += kSelfBlock) {
@@ -232,53 +196,11 @@ struct Item {      // one (origin, lag) frame pair: the centres' frame, the part
     unsigned fo, fp, l;
 };
 
-// bbox[o] over both frames of item o of the batch; preset and layout as k_cells_bbox; grid (a few blocks, B)
-__global__ void __launch_bounds__(kBlock) k_vh_bbox(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel, unsigned n_sel,
-                                                    const Item *__restrict__ items, u64 *__restrict__ bbox)
-{
-    __shared__ double sh[kBlock / 64];
-    unsigned const o = blockIdx.y;
-    Item const it = items[o];
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (unsigned k = blockIdx.x * kBlock + threadIdx.x; k < n_sel; k += gridDim.x * kBlock)
-        for (int which = 0; which < 2; which++) {
-            double p[3];
-            load3(xyz, is_f64, ((size_t)(which ? it.fp : it.fo) * N + sel[k]) * 3, p);
-            for (int a = 0; a < 3; a++) {
-                lo[a] = fmin(lo[a], p[a]);
-                hi[a] = fmax(hi[a], p[a]);
-            }
-        }
-    for (int a = 0; a < 3; a++) {
-        lo[a] = block_min(lo[a], sh);
-        hi[a] = block_max(hi[a], sh);
-    }
-    if (threadIdx.x == 0 && lo[0] <= hi[0])
-        for (int a = 0; a < 3; a++) {
-            atomicMin(&bbox[6 * (size_t)o + a], ordered(lo[a]));
-            atomicMax(&bbox[6 * (size_t)o + 3 + a], ordered(hi[a]));
-        }
-}
-
-// the records of the centres (partner == 0: frame fo) or the partners (frame fp) of every item of the batch, keyed (item, cell)
-__global__ void __launch_bounds__(kBlock) k_vh_keys(const void *__restrict__ xyz, int is_f64, unsigned N, const unsigned *__restrict__ sel,
-                                                    const int *__restrict__ label, unsigned n_sel, const Item *__restrict__ items, int partner, unsigned B,
-                                                    const Grid *__restrict__ grids, int periodic, unsigned cap, u64 *__restrict__ keys,
-                                                    unsigned *__restrict__ vals, Rec *__restrict__ grec)
-{
-    size_t const idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (idx >= (size_t)B * n_sel) return;
-    unsigned const o = (unsigned)(idx / n_sel), k = (unsigned)(idx % n_sel), bead = sel[k];
-    Item const it = items[o];
-    Rec r;
-    load3(xyz, is_f64, ((size_t)(partner ? it.fp : it.fo) * N + bead) * 3, r.p);
-    r.label = label ? label[bead] : 0;
-    r.bead = bead;
-    Grid const g = grids[o];
-    keys[idx] = cell_key(g, r.p, periodic, o, cap);
-    vals[idx] = (unsigned)idx;
-    grec[idx] = r;
-}
+struct PairFrames {      // k_cells_bbox: both frames of item o of the batch
+    const Item *items;
+    static constexpr int kFrames = 2;
+    __device__ unsigned frame(unsigned o, int which) const { return which ? items[o].fp : items[o].fo; }
+};
 
 struct PairArgs {
     const double *edges2;      // (B + 1)
@@ -293,70 +215,40 @@ __global__ void __launch_bounds__(kBlock) k_vh_pairs(const Rec *__restrict__ cre
                                                      const Rec *__restrict__ prec, const unsigned *__restrict__ pstarts, const Grid *__restrict__ grids, PairArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) u64 smem2[];
-    unsigned const stride = a.tile + kTilePad, B = a.B;
+    unsigned const stride = a.tile + kCellTilePad, B = a.B;
     double *tx = reinterpret_cast<double *>(smem2);      // [kTileWords][stride]
     u64 *tmeta = smem2 + 3 * (size_t)stride;
     double *e2 = reinterpret_cast<double *>(smem2 + kTileWords * (size_t)stride);
     unsigned *hist = reinterpret_cast<unsigned *>(e2 + B + 1);
 
-    uint2 const w = work[blockIdx.x];
-    unsigned const o = w.x / a.cap, cell = w.x % a.cap;
-    Grid const g = grids[o];
-    const unsigned *sc = cstarts + (size_t)o * a.cap, *sp = pstarts + (size_t)o * a.cap;
-    unsigned const s_begin = sc[cell] + w.y * kChunk, nc = min(sc[cell + 1] - s_begin, kChunk);
-    unsigned gs = 1;      // lanes per centre
-    while (2 * gs * nc <= (unsigned)kBlock) gs *= 2;
-    unsigned const ci = threadIdx.x / gs, sl = threadIdx.x % gs;
-    bool const active = ci < nc;
+    CellWork const cw = cell_work(work[blockIdx.x], cstarts, a.cap);
+    Grid const g = grids[cw.o];
     Rec q;
-    if (active) q = crec[s_begin + ci];
+    if (cw.active) q = crec[cw.s_begin + cw.ci];
     for (unsigned e = threadIdx.x; e <= B; e += kBlock) e2[e] = a.edges2[e];
     if (kLds)
         for (unsigned e = threadIdx.x; e < a.cells; e += kBlock) hist[e] = 0u;
-    u64 *gtable = a.table + (size_t)a.items[o].l * a.cells;
+    u64 *gtable = a.table + (size_t)a.items[cw.o].l * a.cells;
 
-    int const cx = (int)(cell % (unsigned)g.n[0]), cy = (int)(cell / (unsigned)g.n[0] % (unsigned)g.n[1]),
-              cz = (int)(cell / ((unsigned)g.n[0] * (unsigned)g.n[1]));
-    int x0, nx, y0, ny, z0, nz;
-    axis_cells(cx, g.n[0], kPeriodic, x0, nx);
-    axis_cells(cy, g.n[1], kPeriodic, y0, ny);
-    axis_cells(cz, g.n[2], kPeriodic, z0, nz);
-    int const xa1 = min(x0 + nx, g.n[0]), xb1 = x0 + nx - xa1;      // [x0, x0 + nx) split where it wraps past the last cell
-    for (int iz = 0; iz < nz; iz++) {
-        int const pz = (z0 + iz) % g.n[2];
-        for (int iy = 0; iy < ny; iy++) {
-            int const py = (y0 + iy) % g.n[1];
-            unsigned const row = ((unsigned)pz * (unsigned)g.n[1] + (unsigned)py) * (unsigned)g.n[0];
-            for (int span = 0; span < 2; span++) {
-                unsigned const j_begin = span ? sp[row] : sp[row + x0];
-                unsigned const j_end = span ? sp[row + xb1] : sp[row + xa1];
-                for (unsigned j0 = j_begin; j0 < j_end; j0 += a.tile) {
-                    unsigned const nt = min(a.tile, j_end - j0);
-                    __syncthreads();      // the last tile has been read (and, the first time, the edges and the histogram are set)
-                    const u64 *src = reinterpret_cast<const u64 *>(prec + j0);
-                    for (unsigned e = threadIdx.x; e < nt * kTileWords; e += kBlock) smem2[(e % kTileWords) * stride + e / kTileWords] = src[e];
-                    __syncthreads();
-                    if (!active) continue;
-                    for (unsigned k = sl; k < nt; k += gs) {
-                        double dx = tx[k] - q.p[0], dy = tx[stride + k] - q.p[1], dz = tx[2 * stride + k] - q.p[2];
-                        if (kPeriodic) {
-                            dx = min_image(dx, g.box[0]);
-                            dy = min_image(dy, g.box[1]);
-                            dz = min_image(dz, g.box[2]);
-                        }
-                        double const r2 = (dx * dx + dy * dy) + dz * dz;
-                        if (!(r2 < e2[B]) || r2 < e2[0]) continue;
-                        u64 const meta = tmeta[k];
-                        if ((unsigned)(meta >> 32) == q.bead) continue;      // the bead itself is the self part's
-                        unsigned const bin = cell_of_r2(e2, B, r2) - 1u;    // in [0, B)
-                        unsigned const e = ((unsigned)q.label * a.K + (unsigned)(meta & 0xffffffffu)) * B + bin;
-                        if (kLds) atomicAdd(&hist[e], 1u);
-                        else atomicAdd(&gtable[e], 1ull);
-                    }
-                }
+    // every partner of the cells around: the index is another, so no pair is seen twice
+    cell_tile_walk<kPeriodic, kTileWords, kTileWords>(g, cw.cell, pstarts + (size_t)cw.o * a.cap, 0u, prec, smem2, a.tile, cw.active, [&](unsigned, unsigned nt) {
+        for (unsigned k = cw.sl; k < nt; k += cw.gs) {
+            double dx = tx[k] - q.p[0], dy = tx[stride + k] - q.p[1], dz = tx[2 * stride + k] - q.p[2];
+            if (kPeriodic) {
+                dx = min_image(dx, g.box[0]);
+                dy = min_image(dy, g.box[1]);
+                dz = min_image(dz, g.box[2]);
             }
+            double const r2 = (dx * dx + dy * dy) + dz * dz;
+            if (!(r2 < e2[B]) || r2 < e2[0]) continue;
+            u64 const meta = tmeta[k];
+            if ((unsigned)(meta >> 32) == q.bead) continue;      // the bead itself is the self part's
+            unsigned const bin = cell_of_r2(e2, B, r2) - 1u;    // in [0, B)
+            unsigned const e = ((unsigned)q.label * a.K + (unsigned)(meta & 0xffffffffu)) * B + bin;
+            if (kLds) atomicAdd(&hist[e], 1u);
+            else atomicAdd(&gtable[e], 1ull);
         }
-    }
+    });
     if (kLds) {
         __syncthreads();
         for (unsigned e = threadIdx.x; e < a.cells; e += kBlock) {
@@ -366,7 +258,7 @@ __global__ void __launch_bounds__(kBlock) k_vh_pairs(const Rec *__restrict__ cre
     }
 }
 
-size_t tile_bytes(unsigned tile) { return (size_t)kTileWords * (tile + kTilePad) * 8; }
+size_t tile_bytes(unsigned tile) { return (size_t)kTileWords * (tile + kCellTilePad) * 8; }
 
 }  // namespace
 
@@ -425,12 +317,10 @@ int check_spec(const char *who, const gd_vanhove *h, const gd_vanhove_spec *s, u
     if (!pl.O)
         return fail(GD_EINVAL, "%s: %u origins from frame %u with stride %u: %llu fit in %u frames", who, s->count, s->first, s->stride,
                     (unsigned long long)frames_fit(F, s->first, s->stride), F);
-    pl.order.resize(s->n_lags);
-    std::iota(pl.order.begin(), pl.order.end(), 0u);
-    std::sort(pl.order.begin(), pl.order.end(), [&](uint32_t a, uint32_t b) { return s->lags[a] < s->lags[b]; });
-    if (s->lags[pl.order[0]] < least_lag) return fail(GD_EINVAL, "%s: lag %u (at least %u)", who, s->lags[pl.order[0]], least_lag);
-    for (uint32_t k = 1; k < s->n_lags; k++)
-        if (s->lags[pl.order[k]] == s->lags[pl.order[k - 1]]) return fail(GD_EINVAL, "%s: lag %u is listed twice", who, s->lags[pl.order[k]]);
+    LagOrder lo = sort_lags(s->lags, s->n_lags);
+    if (lo.least < least_lag) return fail(GD_EINVAL, "%s: lag %u (at least %u)", who, lo.least, least_lag);
+    if (lo.twice) return fail(GD_EINVAL, "%s: lag %u is listed twice", who, lo.repeated);
+    pl.order = std::move(lo.order);
     pl.B = s->n_bins;
     pl.origins.resize(s->n_lags);
     for (uint32_t l = 0; l < s->n_lags; l++) pl.origins[l] = std::min<uint64_t>(pl.O, frames_fit(F, s->first, s->stride, s->lags[l]));
@@ -531,17 +421,7 @@ int gd_vanhove_self(gd_vanhove *h, const gd_vanhove_spec *spec, uint32_t axes, c
         HIPCHK(h->edges_dev.upload(pl.edges2.data(), B + 1));
         bool const lds = cells <= kLdsCells;
         size_t const fixed = (size_t)(B + 1) * 8 + (lds ? (cells + 1) / 2 * 8 : 0), row = (size_t)kRow * h->hist.elem();
-        unsigned const fit = (unsigned)std::min<size_t>(((size_t)h->lds_bytes - fixed) / row, 1u << 28);
-        unsigned const want = h->frames_per_tile ? std::min(h->frames_per_tile, F) : F;
-        unsigned W, windows;
-        if (want <= fit) {
-            W = std::max(want, 1u);
-            windows = W >= F ? 1 : 2;
-            if (windows == 2 && 2 * (size_t)W > fit) W = std::max(fit / 2, 1u);
-        } else {
-            W = std::max(fit / 2, 1u);
-            windows = 2;
-        }
+        LagWindows const lw = lag_windows((size_t)h->lds_bytes, fixed, row, F, h->frames_per_tile);
         SelfArgs a{};
         a.x = h->hist.x();
         a.label = h->ls.labels();
@@ -552,8 +432,8 @@ int gd_vanhove_self(gd_vanhove *h, const gd_vanhove_spec *spec, uint32_t axes, c
         a.n_lags = nl;
         a.B = B;
         a.K = K;
-        a.W = W;
-        a.windows = windows;
+        a.W = lw.W;
+        a.windows = lw.windows;
         a.first = spec->first;
         a.stride = spec->stride;
         a.O = O;
@@ -566,7 +446,7 @@ int gd_vanhove_self(gd_vanhove *h, const gd_vanhove_spec *spec, uint32_t axes, c
         if (out->per_origin) HIPCHK(hipMemsetAsync(h->per_origin.p, 0, nl * po_row * sizeof(u64), st));
         HIPCHK(h->timer.mark(1, st));
         dim3 const grid((N + kSeqs - 1) / kSeqs, std::min((F + kRange - 1) / kRange, 65535u));
-        size_t const shmem = fixed + (size_t)windows * W * row;
+        size_t const shmem = fixed + (size_t)lw.windows * lw.W * row;
         if (h->hist.is_f64) launch_self<double>(h, grid, shmem, lds, a);
         else launch_self<float>(h, grid, shmem, lds, a);
         HIPCHK(hipGetLastError());
@@ -631,7 +511,7 @@ int gd_vanhove_distinct(gd_vanhove *h, const gd_vanhove_spec *spec, const double
         for (int a = 0; a < 3; a++) sp.box[a] = box ? box[a] : 0.0;
         sp.cell_side = spec->edges[B] * (1.0 + kCellSlack);
         unsigned const cap = std::max(4096u, n);
-        // the histogram in LDS: a block adds at most kChunk * n to one uint32 counter
+        // the histogram in LDS: a block adds at most kCellChunk * n to one uint32 counter
         bool const lds = cells <= kLdsCells && n < (1u << 24);
         unsigned const tile = 256;
         size_t const shmem = tile_bytes(tile) + (size_t)(B + 1) * 8 + (lds ? cells * 4 : 0);      // < 64 KiB
@@ -648,21 +528,11 @@ int gd_vanhove_distinct(gd_vanhove *h, const gd_vanhove_spec *spec, const double
             GDCHK(cc.room(nb_items, n, cap));
             GDCHK(pp.room(nb_items, n, cap));
             HIPCHK(h->timer.mark(0, st));
-            if (sp.periodic) {      // the grid of the box, whatever the frames
-                GDCHK(pp.make_grids(st, h->hist.x(), is64, N, h->ls.sel.p, n, FrameSel{0, 1, nb_items}, 0, nb_items, sp, cap));
-            } else {
-                std::vector<u64> init(6 * (size_t)nb_items);
-                for (size_t k = 0; k < init.size(); k++) init[k] = k % 6 < 3 ? ~0ull : 0ull;
-                HIPCHK(hipMemcpyAsync(pp.bbox.p, init.data(), init.size() * sizeof(u64), hipMemcpyHostToDevice, st));
-                HIPCHK(hipStreamSynchronize(st));      // init is about to go out of scope
-                hipLaunchKernelGGL(k_vh_bbox, dim3(std::min(blocks_for(n, kBlock), 16u), nb_items), dim3(kBlock), 0, st, h->hist.x(), is64, N, h->ls.sel.p, n, batch, pp.bbox.p);
-                hipLaunchKernelGGL(k_cells_grid, dim3(blocks_for(nb_items, kBlock)), dim3(kBlock), 0, st, pp.bbox.p, nb_items, sp, cap, pp.grids.p);
-            }
+            PairFrames const fr{batch};
+            GDCHK(pp.make_grids(st, h->hist.x(), is64, N, h->ls.sel.p, n, fr, nb_items, sp, cap));      // one grid for both frames of an item
             for (int partner = 0; partner < 2; partner++) {
                 CellIndex<Rec> &ci = partner ? pp : cc;
-                hipLaunchKernelGGL(k_vh_keys, dim3(blocks_for(nb, kBlock)), dim3(kBlock), 0, st, h->hist.x(), is64, N, h->ls.sel.p, h->ls.labels(), n, batch, partner,
-                                   nb_items, pp.grids.p, sp.periodic, cap, ci.keys[0].p, ci.vals[0].p, ci.grec.p);
-                HIPCHK(hipGetLastError());
+                GDCHK(ci.make_keys(st, PositionFill<PairFrames>{h->hist.x(), is64, N, h->ls.labels(), fr, partner}, h->ls.sel.p, n, nb_items, pp.grids.p, sp.periodic, cap));
                 GDCHK(ci.sort(st, nb, slots));
                 HIPCHK(hipGetLastError());
             }

@@ -1,5 +1,6 @@
 // test_frames.cpp -- csrc/gdyn_frames.hpp on the CPU against brute-force loops: how many frames of a history a selection holds and
-// serves, and which tiles of a symmetric map a rectangle touches.  Prints "frames: ok" and returns 0 when every check holds.
+// serves, which tiles of a symmetric map a rectangle touches, the windows of the lag walk that an LDS budget holds, and the order
+// of a call's lags.  Prints "frames: ok" and returns 0 when every check holds.
 #include <cstdint>
 #include <cstdio>
 #include <set>
@@ -123,12 +124,93 @@ void test_tile_cover()
     CHECK(gd::tile_cover(16, 49, 1, 0, 1, true, false, true) == std::vector<Tile>({{0, 0}, {0, 3}}), "the last cell against the first");
 }
 
+// the windows by search: the largest W <= the knob and the longest sequence whose one window (W >= longest) or two fit the rows that
+// the budget holds after `fixed`; (1, 2) where nothing fits
+gd::LagWindows brute_windows(size_t budget, size_t fixed, size_t row, unsigned longest, unsigned knob)
+{
+    size_t const fit = budget > fixed ? (budget - fixed) / row : 0;
+    for (unsigned W = knob ? std::min(knob, longest) : longest; W >= 1; W--) {
+        unsigned const windows = W >= longest ? 1 : 2;
+        if ((size_t)windows * W <= fit) return {W, windows};
+    }
+    return {1, 2};
+}
+
+void check_windows(size_t budget, size_t fixed, size_t row, unsigned longest)
+{
+    size_t const fit = budget > fixed ? (budget - fixed) / row : 0;
+    gd::LagWindows const free = gd::lag_windows(budget, fixed, row, longest, 0);
+    for (unsigned knob : {0u, 1u, 2u, 3u, 8u, 36u, 37u, 416u, 417u, 418u, 834u, 835u, 836u, 5000u}) {
+        gd::LagWindows const got = gd::lag_windows(budget, fixed, row, longest, knob), want = brute_windows(budget, fixed, row, longest, knob);
+        CHECK(got.W == want.W && got.windows == want.windows, "budget %zu fixed %zu row %zu longest %u knob %u: (%u, %u), by search (%u, %u)", budget, fixed, row,
+              longest, knob, got.W, got.windows, want.W, want.windows);
+        CHECK(got.W >= 1 && (got.windows == 1 || got.windows == 2), "budget %zu longest %u knob %u: W %u windows %u", budget, longest, knob, got.W, got.windows);
+        CHECK(got.W <= free.W, "budget %zu longest %u: knob %u raises W from %u to %u", budget, longest, knob, free.W, got.W);
+        if (knob) CHECK(got.W <= knob, "budget %zu longest %u: W %u beyond the knob %u", budget, longest, got.W, knob);
+        if (fit < 2 && !(fit == 1 && longest == 1)) {      // less than two rows: one item a window and two of them, whatever the budget
+            CHECK(got.W == 1 && got.windows == 2, "budget %zu fixed %zu row %zu longest %u knob %u: (%u, %u) where %zu rows fit", budget, fixed, row, longest, knob,
+                  got.W, got.windows, fit);
+            continue;
+        }
+        CHECK((got.windows == 1) == (got.W >= longest), "budget %zu longest %u knob %u: W %u with %u windows", budget, longest, knob, got.W, got.windows);
+        CHECK((size_t)got.windows * got.W * row + fixed <= budget, "budget %zu fixed %zu row %zu longest %u knob %u: %u windows of %u rows", budget, fixed, row, longest,
+              knob, got.windows, got.W);
+    }
+}
+
+void test_lag_windows()
+{
+    // small budgets, every one: rows of 3 and 7 bytes, with and without bytes in front, budgets below `fixed` and below one and two rows
+    for (size_t row : {3u, 7u})
+        for (size_t fixed : {0u, 5u})
+            for (size_t budget = 0; budget <= 80; budget++)
+                for (unsigned longest = 1; longest <= 30; longest++) check_windows(budget, fixed, row, longest);
+    // the two real cases: 160 KiB of rows of 49 float32 or float64
+    size_t const lds = 160 * 1024;
+    CHECK(lds / (49 * 4) == 835 && lds / (49 * 8) == 417, "the rows of 160 KiB");
+    for (size_t row : {49u * 4u, 49u * 8u})
+        for (size_t fixed : {(size_t)0, (size_t)(65 * 8 + 1024 * 4)})
+            for (unsigned longest : {1u, 2u, 200u, 408u, 409u, 416u, 417u, 418u, 701u, 811u, 812u, 834u, 835u, 836u, 1670u, 8199u, 100000u})
+                check_windows(lds, fixed, row, longest);
+    gd::LagWindows w = gd::lag_windows(lds, 0, 49 * 4, 835, 0);
+    CHECK(w.W == 835 && w.windows == 1, "835 float32 items are one window");
+    w = gd::lag_windows(lds, 0, 49 * 4, 836, 0);
+    CHECK(w.W == 417 && w.windows == 2, "836 float32 items are walked in windows of 417");
+    w = gd::lag_windows(lds, 0, 49 * 8, 417, 0);
+    CHECK(w.W == 417 && w.windows == 1, "417 float64 items are one window");
+    w = gd::lag_windows(lds, 0, 49 * 8, 8199, 0);
+    CHECK(w.W == 208 && w.windows == 2, "a long float64 history is walked in windows of 208");
+    w = gd::lag_windows(lds, 0, 49 * 8, 8199, 37);
+    CHECK(w.W == 37 && w.windows == 2, "the knob bounds the window");
+    // fewer than two rows
+    w = gd::lag_windows(49 * 8 + 100, 0, 49 * 8, 701, 0);
+    CHECK(w.W == 1 && w.windows == 2, "one row fits: (%u, %u)", w.W, w.windows);
+    w = gd::lag_windows(100, 0, 49 * 8, 701, 0);
+    CHECK(w.W == 1 && w.windows == 2, "no row fits: (%u, %u)", w.W, w.windows);
+    w = gd::lag_windows(100, 200, 49 * 8, 701, 5);
+    CHECK(w.W == 1 && w.windows == 2, "the fixed bytes alone exceed the budget: (%u, %u)", w.W, w.windows);
+}
+
+void test_sort_lags()
+{
+    uint32_t const lags[] = {7, 1, 4096, 3, 2};
+    gd::LagOrder lo = gd::sort_lags(lags, 5);
+    CHECK(lo.order == std::vector<uint32_t>({1, 4, 3, 0, 2}) && lo.least == 1 && !lo.twice, "five distinct lags in ascending order");
+    uint32_t const twice[] = {9, 0, 5, 9, 5};
+    lo = gd::sort_lags(twice, 5);
+    CHECK(lo.least == 0 && lo.twice && lo.repeated == 5, "the least lag and the least repeated one: %u, %u", lo.least, lo.repeated);
+    lo = gd::sort_lags(nullptr, 0);
+    CHECK(lo.order.empty() && lo.least == kMax && !lo.twice, "no lags");
+}
+
 }  // namespace
 
 int main()
 {
     test_frame_counts();
     test_tile_cover();
+    test_lag_windows();
+    test_sort_lags();
     if (failures) {
         std::printf("frames: %d checks failed\n", failures);
         return 1;

@@ -1,7 +1,8 @@
 """The frame selection and the tile cover of the history analyses (csrc/gdyn_frames.hpp) on the CPU: tests/native/test_frames.cpp holds
 gd::frames_fit, gd::frames_served and gd::tile_cover to brute-force loops at their edges (one frame, selections past the history, exactly
 one frame that fits, 2^32 - 1 without wrap-around; rectangles inside a tile, across a boundary, above their columns, with and without
-diagonal tiles, the last partial tile)."""
+diagonal tiles, the last partial tile), gd::lag_windows to a search over small budgets and at the two real ones (160 KiB of float32 and
+float64 rows, and budgets that hold fewer than two rows), and gd::sort_lags on a few lists."""
 import os
 import subprocess
 

@@ -5,7 +5,8 @@ history.  Then the program gd_van_hove end to end.  Every output is an integer c
 
 The shapes are chosen to break the kernels, not to resemble a genome.  Self part: 75 beads (five tiles of 16, the last of 11), three
 labels with beads in none, 41 frames walked in windows of 41, 8 and 13 frames, so that the lags 1 to 40 lie inside a window, connect
-neighbouring windows and skip windows; lag 40 has one origin, 41 and 60 none.  Distinct part: 150 selected beads of 170 in periodic
+neighbouring windows and skip windows; lag 40 has one origin, 41 and 60 none; and 8199 frames of 20 beads, three ranges of 4096
+origin frames, with lags up to the last origin.  Distinct part: 150 selected beads of 170 in periodic
 boxes with and without three cells on every axis, in open and planar sets, 300 beads in one cell (two work chunks of 256), beads that
 jump a period, and a bead that lands exactly where another sat."""
 import ctypes as C
@@ -119,6 +120,41 @@ def test_both_paths_and_the_axes(walk, dtype):
                 assert alone[k][0].tobytes() == want[k][l].tobytes(), (k, l)
         for axes in ("xy", "z", "xz", "y"):
             assert _equal(v.self_part([1, 9, 40], OUTSIDE, axes=axes), vr.self_part(x, [1, 9, 40], OUTSIDE, label, K, axes), SELF_KEYS[:3]), axes
+
+
+LONG_F, LONG_N = 4096 + 4096 + 7, 20
+LONG_LAGS = [1, 417, 418, 835, 836, 4095, 4096, 4097, 8192, 8198]
+LONG_EDGES = np.linspace(0.05, 12.0, 33)      # 32 linear bins; a step of the walk is 0.1 an axis: some of lag 1 below, of the long lags above
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_self_beyond_one_range(dtype):
+    """The lag walk of k_vh_self beyond one range of kRange = 4096 origin frames, on the shape of case A of test_msd_edges_gpu.py:
+    4096 + 4096 + 7 frames, so three ranges (O0 != 0), and 20 beads, so two tiles, the last of 4.  Lags at, around and beyond the
+    window of either precision (417, 835), the range, twice the range and the last origin: partner windows that cross a range
+    boundary and window jumps d > 1.  With windows of 36 and 37 frames the history is a few hundred windows long.  Every origin, and
+    the origins 5 + 3 k, of which lag 8198 has none."""
+    rng = np.random.default_rng(20)
+    x = np.cumsum(rng.standard_normal((LONG_F, LONG_N, 3)) * 0.1, axis=0).astype(dtype)
+    label = rng.integers(-1, 3, LONG_N).astype(np.int32)
+    label[[0, 17]] = -1      # one bead in none in either tile
+    label[[1, 2, 3, 18]] = [0, 1, 2, 1]
+    for selection, per_origin in (((0, 1, 0), False), ((5, 3, 0), True)):
+        want = vr.self_part(x, LONG_LAGS, LONG_EDGES, label, 3, "xyz", *selection)
+        if selection[0]:
+            assert want["origins"][[0, 6, 9]].tolist() == [2731, 1366, 0]
+        keys = SELF_KEYS if per_origin else ("counts", "below", "above", "origins")
+        first = None
+        for tile in (0, 36, 37):
+            with VanHove(0, tile) as v:
+                v.set_history(x)
+                v.set_labels(label, 3)
+                got = v.self_part(LONG_LAGS, LONG_EDGES, first=selection[0], stride=selection[1], count=selection[2], per_origin=per_origin)
+            assert ("per_origin" in got) == per_origin
+            assert _equal(got, want, keys), (selection, tile)
+            first = first or _bytes(got, keys)
+            assert _bytes(got, keys) == first, (selection, tile)
+    assert want["below"].any() and want["above"].any()
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
